@@ -20,6 +20,13 @@ their output through — or the launcher form the driver uses,
  --master-port P bench.py --gpus N --steps K --warmup W`.
 Either way rank 0 prints ONE JSON line.  `--plumbing-only` runs launch, process group (gloo),
 sharding and the all-gather on stand-in vectors without a GPU: the CPU test of this plumbing.
+
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`, the
+per-kernel HIP-event times of the timed steps and the roofline arithmetic on them).  `--full` adds
+everything measured or checked beside it after the timed region: the oracle check of `--verify`
+songs, the FIR mode 0 steps, BASELINE configs[1] / configs[4], the 10 000 x 10 000 matrices, the
+PMC traffic passes and the CPU baseline.  `--dump-outputs DIR` writes what the last timed step
+computed (rank 0's share) as DIR/<name>.npy, for comparing two builds output for output.
 """
 import argparse
 import ctypes as C
@@ -638,16 +645,16 @@ def main():
     ap.add_argument("--songs-per-gpu", type=int, default=0,
                     help="0 = configs[2] shard (8192) if it fits in HBM, else the largest count that does")
     ap.add_argument("--seconds", type=int, default=SONG_SECONDS, help="song length (default 180)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out the CPU baseline")
     ap.add_argument("--no-mode0-pass", action="store_true",
-                    help="skip the untimed extra pass in FIR mode 0 (profiling runs: one envelope launch per step)")
+                    help="--full: skip the untimed extra pass in FIR mode 0 (profiling runs: one envelope launch per step)")
     ap.add_argument("--cpu-ladder", default="1,8,32,64,128,256",
-                    help="concurrent oracle processes per rung of the CPU baseline (tests shorten it)")
+                    help="concurrent oracle processes per rung of the CPU baseline of --full (tests shorten it)")
     ap.add_argument("--no-live-traffic", action="store_true",
-                    help="do not collect roofline.traffic in this run (two rocprofv3 --pmc passes over 1 024 songs, N = 1 "
+                    help="--full: do not collect roofline.traffic in this run (two rocprofv3 --pmc passes over 1 024 songs, N = 1 "
                          "only, ~20 s): take the committed profile's figure")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the untimed-for-value legs on BASELINE configs[1] and configs[4] (profiling runs)")
+                    help="--full: skip the untimed-for-value legs on BASELINE configs[1] and configs[4] (profiling runs)")
     ap.add_argument("--verbose", action="store_true",
                     help="leave stdout / stderr of the rank alone (default: library chatter goes to a log file in the temp "
                          "directory, replayed on failure, so that stdout is the JSON line and stderr stays short)")
@@ -655,7 +662,7 @@ def main():
                     help="where the full record goes (verification per song, per-kernel times, CPU ladder, traffic by "
                          "kernel ...; default: bench_details.json next to this script); stdout carries the compact line only")
     ap.add_argument("--verify", type=int, default=32,
-                    help="songs of the resident batch re-analysed by the CPU oracle after the timed region")
+                    help="--full: songs of the resident batch re-analysed by the CPU oracle after the timed region")
     ap.add_argument("--emulate-world", type=int, default=0,
                     help="diagnostic: size the gather buffer and this rank's row block as for a job of W ranks "
                          "(all_vecs = W x songs vectors, rows = songs x W*songs floats; the other ranks' vectors "
@@ -669,7 +676,16 @@ def main():
                     help="start the ranks through the self-launcher even for --gpus 1 (RCCL group of one)")
     ap.add_argument("--plumbing-only", action="store_true",
                     help="no GPU: launch, gloo process group, sharding and all-gather on stand-in vectors")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the oracle check (--verify), the FIR mode 0 steps, "
+                         "BASELINE configs[1] / configs[4], the 10 000 x 10 000 matrices, the PMC traffic passes and the "
+                         "CPU baseline (the --no-* options leave parts of it out); a plain run does none of these")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed (rank 0's song records, the gathered force vectors, "
+                         "a seeded sample of its distance rows) as DIR/<name>.npy, float32 / float64, under 64 MB")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     under_launcher = "RANK" in os.environ and "WORLD_SIZE" in os.environ
     if not under_launcher and (args.gpus > 1 or args.launch):
@@ -686,6 +702,83 @@ def main():
             quiet.replay()
         raise
     quiet.done()
+
+
+DUMP_SONGS_MAX = 1 << 17          # per-song records written whole up to this many songs (116 B each), else a sample
+DUMP_VECS_MAX = 1 << 18           # gathered force vectors (16 B each)
+DUMP_COLS_MAX = 1 << 20           # columns of one sampled distance row (4 B each)
+DUMP_ROWS_BYTES = 16 << 20        # the sampled distance rows together
+
+
+def _dump_sample(n, cap, seed):
+    """Sorted indices of a fixed, seeded sample of `cap` out of range(n); all of them when n <= cap."""
+    import numpy as np
+    if n <= cap:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, cap, replace=False))
+
+
+def dump_outputs(path, res, first, all_vecs, rows):
+    """--dump-outputs: what a caller of the timed step receives, as DIR/<name>.npy in float32 / float64 (under
+    48 MB): every field of this rank's song records (integers as float64, exact), the gathered force vectors and the
+    distance row block, each with the global song indices it holds (`*_index`); a seeded sample where the output is
+    larger than the DUMP_* caps.  Same arguments, same inputs (seeds = global song index): same files."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+
+    def save(name, a):
+        a = np.asarray(a)
+        np.save(os.path.join(path, name + ".npy"), a if a.dtype in (np.float32, np.float64) else a.astype(np.float64))
+
+    songs = _dump_sample(len(res), DUMP_SONGS_MAX, 1)
+    save("song_index", first + songs)
+    for k in res.dtype.names:
+        save(k, res[k][songs])
+    vi = _dump_sample(all_vecs.shape[0], DUMP_VECS_MAX, 2)
+    save("force_vectors_index", vi)
+    save("force_vectors", all_vecs[torch.from_numpy(vi).to(all_vecs.device)].cpu().numpy())
+    ci = _dump_sample(rows.shape[1], DUMP_COLS_MAX, 3)
+    ri = _dump_sample(rows.shape[0], max(1, DUMP_ROWS_BYTES // (4 * len(ci))), 4)
+    block = rows.index_select(0, torch.from_numpy(ri).to(rows.device))
+    if len(ci) < rows.shape[1]:
+        block = block.index_select(1, torch.from_numpy(ci).to(rows.device))
+    save("distance_rows_index", first + ri)
+    save("distance_cols_index", ci)
+    save("distance_rows", block.cpu().numpy())
+
+
+def matrices_10k(lib, dev, stream):
+    """--full: BASELINE config 4, the standalone 10 000 x 10 000 bl_distance matrix on one GPU, and its sibling
+    bl_cosine_similarity matrix on the same vectors.  Returns the seconds of each (mean of 10 launches)."""
+    import torch
+    g = torch.Generator(device="cpu").manual_seed(4)
+    v10 = (torch.randn((10000, 4), generator=g) * 8).to(dev)
+    m10 = torch.empty((10000, 10000), dtype=torch.float32, device=dev)
+    for _ in range(2):
+        lib.bl_amd_distance_matrix_device(C.c_void_p(v10.data_ptr()), 10000, 0, 10000,
+                                          C.c_void_p(m10.data_ptr()), stream)
+    torch.cuda.synchronize(dev)
+    reps = 10
+    t1 = time.perf_counter()
+    for _ in range(reps):
+        lib.bl_amd_distance_matrix_device(C.c_void_p(v10.data_ptr()), 10000, 0, 10000,
+                                          C.c_void_p(m10.data_ptr()), stream)
+    torch.cuda.synchronize(dev)
+    dm_s = (time.perf_counter() - t1) / reps
+    # its sibling on the same vectors: the 10 000 x 10 000 bl_cosine_similarity matrix
+    # (ref src/analyze.c:127-143; f32 dot and norms, double sqrt, product and divide)
+    for _ in range(2):
+        lib.bl_amd_cosine_matrix_device(C.c_void_p(v10.data_ptr()), 10000, 0, 10000,
+                                        C.c_void_p(m10.data_ptr()), stream)
+    torch.cuda.synchronize(dev)
+    t1 = time.perf_counter()
+    for _ in range(reps):
+        lib.bl_amd_cosine_matrix_device(C.c_void_p(v10.data_ptr()), 10000, 0, 10000,
+                                        C.c_void_p(m10.data_ptr()), stream)
+    torch.cuda.synchronize(dev)
+    cm_s = (time.perf_counter() - t1) / reps
+    return dm_s, cm_s
 
 
 def run_rank(args, under_launcher, out):
@@ -824,13 +917,15 @@ def run_rank(args, under_launcher, out):
     per_rank = per_rank.cpu().numpy()
 
     res = corpus.fetch()
-    # Outside the timed region: the same steps in FIR mode 0 (the reference's operation order, window energies
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res, my_first, all_vecs, rows)
+    # --full, outside the timed region: the same steps in FIR mode 0 (the reference's operation order, window energies
     # bit-identical to the CPU oracle) — what the timed default (mode 2: fused taps, normalisation folded in; DESIGN.md
     # section 4.1) buys, measured on real steps (one warm-up, then min(K, 3) steps between fences, max over ranks), and
     # whether any integer or feature of this batch depends on the mode.
     fir_active = int(lib.bl_amd_fir_mode())
     fir_report = {"timed_mode": fir_active}
-    if fir_active != 0 and not args.no_mode0_pass:
+    if args.full and fir_active != 0 and not args.no_mode0_pass:
         lib.bl_amd_set_fir_mode(0)
         n0 = max(1, min(args.steps, 3))
         step()
@@ -876,15 +971,16 @@ def run_rank(args, under_launcher, out):
         a, b = all_vecs[my_first + i].cpu().numpy(), all_vecs[j].cpu().numpy()
         want_d = lib.bl_distance(_lib.ForceVector(*[float(x) for x in a]), _lib.ForceVector(*[float(x) for x in b]))
         ok = ok and float(rows[i, j].item()) == want_d
-    # the oracle check is shared out: every rank re-analyses its part of the --verify songs on the host
+    # --full: the oracle check is shared out, every rank re-analyses its part of the --verify songs on the host
     verified, verify_details = 0, []
-    if args.verify > 0 and dist.is_initialized():   # one rank (re)builds the oracle, the others wait for it
+    n_verify = args.verify if args.full else 0
+    if n_verify > 0 and dist.is_initialized():   # one rank (re)builds the oracle, the others wait for it
         if rank == 0:
             from tests.oracle_py import build_oracle
             build_oracle()
         dist.barrier()
-    if args.verify > 0:
-        k = min(max(1, args.verify // world), songs)
+    if n_verify > 0:
+        k = min(max(1, n_verify // world), songs)
         picks = sorted(set(int(round(j * (songs - 1) / max(k - 1, 1))) for j in range(k)))
         v_ok, verify_details = verify_songs(res, picks, my_first, args.seconds)
         ok = ok and v_ok
@@ -975,7 +1071,7 @@ def run_rank(args, under_launcher, out):
 
         # the driver's clock on the other two batch shapes of BASELINE.json (the resident batch is freed first)
         others = None
-        if not args.no_other_configs:
+        if args.full and not args.no_other_configs:
             try:
                 del corpus
                 del rows, all_vecs
@@ -985,7 +1081,7 @@ def run_rank(args, under_launcher, out):
                 others = {"error": f"{type(e).__name__}: {e}"}
 
         # roofline.traffic collected in this run (N = 1; the resident batch is gone by now, the children fit)
-        if roof is not None and world == 1 and not args.no_live_traffic and not args.share_device:
+        if args.full and roof is not None and world == 1 and not args.no_live_traffic and not args.share_device:
             try:
                 del corpus
             except NameError:
@@ -1009,34 +1105,10 @@ def run_rank(args, under_launcher, out):
             else:
                 roof["traffic_source"]["live_collection_error"] = lt.get("error", "no k_env_windows3 row")
 
-        # BASELINE config 4: standalone 10 000 x 10 000 bl_distance matrix on one GPU
-        g = torch.Generator(device="cpu").manual_seed(4)
-        v10 = (torch.randn((10000, 4), generator=g) * 8).to(dev)
-        m10 = torch.empty((10000, 10000), dtype=torch.float32, device=dev)
-        for _ in range(2):
-            lib.bl_amd_distance_matrix_device(C.c_void_p(v10.data_ptr()), 10000, 0, 10000,
-                                              C.c_void_p(m10.data_ptr()), stream)
-        torch.cuda.synchronize(dev)
-        reps = 10
-        t1 = time.perf_counter()
-        for _ in range(reps):
-            lib.bl_amd_distance_matrix_device(C.c_void_p(v10.data_ptr()), 10000, 0, 10000,
-                                              C.c_void_p(m10.data_ptr()), stream)
-        torch.cuda.synchronize(dev)
-        dm_s = (time.perf_counter() - t1) / reps
+        dm_s = cm_s = None
+        if args.full:
+            dm_s, cm_s = matrices_10k(lib, dev, stream)
         dm_bytes = 4 * 10000 * 10000 + 16 * 10000
-        # its sibling on the same vectors: the 10 000 x 10 000 bl_cosine_similarity matrix
-        # (ref src/analyze.c:127-143; f32 dot and norms, double sqrt, product and divide)
-        for _ in range(2):
-            lib.bl_amd_cosine_matrix_device(C.c_void_p(v10.data_ptr()), 10000, 0, 10000,
-                                            C.c_void_p(m10.data_ptr()), stream)
-        torch.cuda.synchronize(dev)
-        t1 = time.perf_counter()
-        for _ in range(reps):
-            lib.bl_amd_cosine_matrix_device(C.c_void_p(v10.data_ptr()), 10000, 0, 10000,
-                                            C.c_void_p(m10.data_ptr()), stream)
-        torch.cuda.synchronize(dev)
-        cm_s = (time.perf_counter() - t1) / reps
 
         line = {
             "metric": "songs/sec bl_analyze (3-min 44.1kHz s16) + 10k x 10k distance-matrix sec",
@@ -1057,10 +1129,10 @@ def run_rank(args, under_launcher, out):
                        "songs_per_gpu": songs, "song_samples": song_samples, "parallelism": f"shard{world}",
                        "generator": "integer-only device synth, seeds = global song index"},
             "distance_matrix_10k_s": dm_s,
-            "distance_matrix_10k_gbs": dm_bytes / dm_s / 1e9,
-            "distance_matrix_10k_frac_hbm": dm_bytes / dm_s / 1e9 / HBM_PEAK_GBS,
+            "distance_matrix_10k_gbs": dm_bytes / dm_s / 1e9 if dm_s else None,
+            "distance_matrix_10k_frac_hbm": dm_bytes / dm_s / 1e9 / HBM_PEAK_GBS if dm_s else None,
             "cosine_matrix_10k_s": cm_s,
-            "cosine_matrix_10k_frac_hbm": dm_bytes / cm_s / 1e9 / HBM_PEAK_GBS,
+            "cosine_matrix_10k_frac_hbm": dm_bytes / cm_s / 1e9 / HBM_PEAK_GBS if cm_s else None,
             "whole_path_algorithmic_gbs_per_gpu": whole_path_gbs,
             "whole_path_frac_hbm": whole_path_gbs / HBM_PEAK_GBS,
             "kernels_ms": kern, "fir_modes": fir_report, "results_ok": ok, "verified_songs": verified,
@@ -1099,10 +1171,11 @@ def run_rank(args, under_launcher, out):
         }
         # the CPU baseline runs on rank 0 at every N (after the timed region and every reduction; the other
         # ranks wait in a gloo barrier, which blocks on a socket instead of spinning)
-        if args.no_cpu_baseline:
+        if not args.full or args.no_cpu_baseline:
+            why = "--no-cpu-baseline" if args.full else "no --full"
             line["cpu_baseline"] = {"value": None, "unit": "songs/s", "cores": None, "kind": "port",
-                                    "sample": "not measured in this run (--no-cpu-baseline): see the N = 1 line of the "
-                                              "same box, BENCH_r*.json", "sample_short": "not measured (--no-cpu-baseline)"}
+                                    "sample": f"not measured in this run ({why}): see the N = 1 line of the "
+                                              "same box, BENCH_r*.json", "sample_short": f"not measured ({why})"}
         else:
             try:
                 line["cpu_baseline"] = cpu_baseline(tuple(int(x) for x in args.cpu_ladder.split(",")))

@@ -144,3 +144,12 @@ def test_f64_floors():
     assert abs(bench.F64_ISSUE_NOMINAL_TWAVEINSTR_S - 0.6144) < 1e-9
     assert abs(bench.F64_ISSUE_NOMINAL_TWAVEINSTR_S * 64 * 2 - bench.FP64_VALU_PEAK_TFLOPS) < 0.1
     assert bench.F64_ISSUE_TWAVEINSTR_S < bench.F64_ISSUE_NOMINAL_TWAVEINSTR_S
+
+
+def test_steps_and_warmup_are_checked_before_anything_runs():
+    """`--steps` is the number of timed steps the line divides by: zero or a negative warm-up is refused at once."""
+    import subprocess
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *bad], stdout=subprocess.PIPE,
+                           stderr=subprocess.PIPE, text=True, timeout=120)
+        assert r.returncode == 2 and r.stdout == "" and "--steps must be at least 1" in r.stderr, r.stderr

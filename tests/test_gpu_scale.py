@@ -166,7 +166,7 @@ def test_bench_under_torchrun_runs_rccl_and_verifies(gpu_lib, tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", "29611", os.path.join(ROOT, "bench.py"),
            "--gpus", "1", "--steps", "1", "--warmup", "1", "--songs-per-gpu", "16", "--seconds", "20",
-           "--no-cpu-baseline", "--verify", "4"]
+           "--full", "--no-cpu-baseline", "--verify", "4"]
     line, det = _run_bench(cmd, tmp_path, env=env)
     assert line["n_gpus"] == 1 and line["results_ok"] is True and line["verified_songs"] == 4
     assert line["collective"] == "nccl" and det["collective"]["all_gather_calls"] >= 2
@@ -203,7 +203,7 @@ def test_bench_self_launch(gpu_lib, tmp_path):
     --launch takes the N = 1 case through the same self-launch path N > 1 uses (ranks started
     under torch.distributed.run on 127.0.0.1, RCCL process group, one JSON line on stdout)."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--launch", "--steps", "2", "--warmup", "1",
-           "--songs-per-gpu", "16", "--seconds", "20", "--no-cpu-baseline", "--verify", "4", "--no-live-traffic"]
+           "--songs-per-gpu", "16", "--seconds", "20", "--full", "--no-cpu-baseline", "--verify", "4", "--no-live-traffic"]
     line, det = _run_bench(cmd, tmp_path)
     assert line["n_gpus"] == 1 and line["steps"] == 2 and line["results_ok"] is True
     assert line["collective"] == "nccl" and det["collective"]["all_gather_calls"] >= 2
@@ -218,6 +218,36 @@ def test_bench_self_launch(gpu_lib, tmp_path):
         assert "1 HIP device(s)" in r2.stderr and "WORLD_SIZE" not in r2.stderr
 
 
+def test_bench_plain_run_dumps_what_the_timed_step_computed(gpu_lib, oracle, tmp_path):
+    """A plain run (no --full) times the steps and leaves every leg beside them out; --dump-outputs writes what the last
+    timed step computed: the song records (checked against the oracle on two songs), the gathered force vectors and the
+    row block of the distance matrix (the oracle's matrix of those vectors, bit for bit), all float32 / float64."""
+    dump = tmp_path / "out"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+           "--songs-per-gpu", "16", "--seconds", "20", "--dump-outputs", str(dump)]
+    line, det = _run_bench(cmd, tmp_path)
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["unit"] == "songs/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert line["results_ok"] is True and line["verified_songs"] == 0 and "value_fir_mode0" not in line
+    assert det["other_configs"] is None and det["distance_matrix_10k_s"] is None and det["cpu_baseline"]["value"] is None
+    assert "mode0_steps" not in det["fir_modes"] and det["kernels_ms"]["env_windows"]["launches"] == 2
+    files = {p.stem: np.load(p) for p in dump.glob("*.npy")}
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert sum(p.stat().st_size for p in dump.glob("*.npy")) < 64 << 20
+    assert set(bliss_amd.batch.RESULT_DTYPE.names) < set(files)
+    assert np.array_equal(files["song_index"], np.arange(16))
+    fv = np.stack([files[k] for k in ("tempo", "amplitude", "frequency", "attack")], axis=1)
+    assert np.array_equal(files["force_vectors"], fv) and np.array_equal(files["force_vectors_index"], np.arange(16))
+    assert np.array_equal(files["distance_rows_index"], np.arange(16)) and files["distance_rows"].shape == (16, 16)
+    assert np.array_equal(files["distance_rows"], oracle.distance_matrix(fv))
+    n = 44100 * 2 * 20
+    for i in (0, 15):
+        got = np.zeros(1, dtype=bliss_amd.batch.RESULT_DTYPE)
+        for k in got.dtype.names:
+            got[k] = files[k][i]
+        check_song(got[0], oracle.analyze(oracle.synth(i, 44100, 2, n), 2, 20), f"dump[{i}]")
+
+
 def test_bench_on_every_gpu_of_the_box(gpu_lib, tmp_path):
     """`python bench.py --gpus <all>` on a box with more than one HIP device: N ranks under torch.distributed.run, an
     RCCL group of N, the all-gather of the force vectors across xGMI, every rank's row block and its share of the
@@ -228,7 +258,7 @@ def test_bench_on_every_gpu_of_the_box(gpu_lib, tmp_path):
     if n < 2:
         pytest.skip("one HIP device on this box")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "1",
-           "--songs-per-gpu", "64", "--seconds", "30", "--cpu-ladder", "1,8", "--verify", str(4 * n), "--no-other-configs"]
+           "--songs-per-gpu", "64", "--seconds", "30", "--full", "--cpu-ladder", "1,8", "--verify", str(4 * n), "--no-other-configs"]
     line, det = _run_bench(cmd, tmp_path, timeout=1500)
     assert line["n_gpus"] == n and line["results_ok"] is True and line["verified_songs"] == 4 * n
     assert line["collective"] == "nccl" and det["collective"]["all_gather_calls"] >= 3
@@ -278,7 +308,7 @@ def test_bench_two_ranks_rehearsal_on_one_gpu(gpu_lib, tmp_path):
     the ranks' shards and seeds (rank 1 analyses songs 24..47), the gather order, row blocks that
     start at row 24, the oracle check shared out over the ranks, results_ok reduced over both."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-device", "--steps", "1", "--warmup", "1",
-           "--songs-per-gpu", "24", "--seconds", "20", "--cpu-ladder", "1,8", "--verify", "8", "--no-live-traffic"]
+           "--songs-per-gpu", "24", "--seconds", "20", "--full", "--cpu-ladder", "1,8", "--verify", "8", "--no-live-traffic"]
     line, det = _run_bench(cmd, tmp_path)
     assert line["n_gpus"] == 2 and line["results_ok"] is True and line["verified_songs"] == 8
     assert line["collective"] == "gloo" and det["collective"]["all_gather_calls"] >= 2

@@ -14,8 +14,8 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-BDEF="python bench.py --no-cpu-baseline --no-other-configs --no-live-traffic"
-BPMC="python bench.py --songs-per-gpu $PSONGS --steps 1 --warmup 0 --no-cpu-baseline --verify 0 --no-mode0-pass --no-other-configs --no-live-traffic"
+BDEF="python bench.py --full --no-cpu-baseline --no-other-configs --no-live-traffic"
+BPMC="python bench.py --full --songs-per-gpu $PSONGS --steps 1 --warmup 0 --no-cpu-baseline --verify 0 --no-mode0-pass --no-other-configs --no-live-traffic"
 (cd $ROOT && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- $BDEF \
    --details-out $OUT/bench_8192songs_under_rocprof_details.json > $OUT/bench_8192songs_under_rocprof.json 2> $OUT/trace.log)
 f=$(find $OUT/trace -name "*kernel_stats.csv" | head -1)
@@ -32,7 +32,7 @@ for C in "FETCH_SIZE" "WRITE_SIZE" \
 done
 python $ROOT/tools/pmc_to_json.py $OUT "$BPMC" $PSONGS > $OUT/hbm_traffic.json
 # the driver's own command: the compact line (what BENCH_r*.json parses) and the full record beside it
-(cd $ROOT && timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --details-out $OUT/bench_8192songs_details.json \
+(cd $ROOT && timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full --details-out $OUT/bench_8192songs_details.json \
    > $OUT/bench_8192songs.json 2> $OUT/bench_8192songs.log)
 rm -rf $OUT/trace $OUT/pmc[0-9]  # raw traces are large; the summaries above are what gets committed
 ls -la $OUT

@@ -9,7 +9,7 @@ i=0
 for C in "$@"; do
   i=$((i+1))
   (cd $GRAFT_REPO_ROOT && timeout 600 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/pass$i -- \
-     python bench.py --songs-per-gpu 256 --steps 1 --warmup 0 --no-cpu-baseline > $OUT/pass$i.log 2>&1)
+     python bench.py --full --songs-per-gpu 256 --steps 1 --warmup 0 --no-cpu-baseline > $OUT/pass$i.log 2>&1)
   f=$(find $OUT/pass$i -name "*counter_collection.csv" | head -1)
   python - "$f" <<'PY'
 import csv,sys,collections
