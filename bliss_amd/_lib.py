@@ -14,6 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BLISS_AMD_LIB") or os.path.join(_HERE, "libbliss_amd.so")
 
 BL_LOUD, BL_CALM, BL_UNKNOWN, BL_UNEXPECTED, BL_OK = 0, 1, 2, -2, 0
+BL_AMD_KNN_DISTANCE, BL_AMD_KNN_COSINE, BL_AMD_KNN_MAX_K = 0, 1, 128  # include/bliss_amd.h
 
 
 class ForceVector(C.Structure):  # ref include/bliss.h:26-31
@@ -119,6 +120,9 @@ SYMBOLS = {
     "bl_amd_selftest_cos": (C.c_int, [_P(C.c_uint64), C.c_uint64]),
     "bl_amd_playlist_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bl_amd_playlist_host": (C.c_int, [_P(ForceVector), C.c_int, C.c_int, _P(C.c_int32), _P(C.c_float)]),
+    "bl_amd_knn_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                    C.c_void_p]),
+    "bl_amd_knn_host": (C.c_int, [_P(ForceVector), C.c_int, C.c_int, C.c_int, _P(C.c_int32), _P(C.c_float)]),
     "bl_amd_synth_pcm_device": (C.c_int, [C.c_void_p, _P(SongDesc), C.c_int, C.c_uint32, C.c_uint32, C.c_void_p]),
     "bl_amd_set_fir_mode": (C.c_int, [C.c_int]),
     "bl_amd_fir_mode": (C.c_int, []),

@@ -344,3 +344,59 @@ def playlist(vecs, seed_index):
                                   dist.ctypes.data_as(C.POINTER(C.c_float)))
     _check(rc, "bl_amd_playlist_host")
     return order, dist
+
+
+_KNN_METRICS = {"distance": _lib.BL_AMD_KNN_DISTANCE, "cosine": _lib.BL_AMD_KNN_COSINE}
+
+
+def _knn_check(k, metric, shape):
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= _lib.BL_AMD_KNN_MAX_K:
+        raise ValueError(f"k must be an integer in [1, {_lib.BL_AMD_KNN_MAX_K}], got {k!r}")
+    if metric not in _KNN_METRICS:
+        raise ValueError(f"metric must be one of {sorted(_KNN_METRICS)}, got {metric!r}")
+    if len(shape) != 2 or shape[1] != 4 or shape[0] < 1:
+        raise ValueError(f"force vectors must have shape (n, 4) with n >= 1, got {tuple(shape)}")
+    return _KNN_METRICS[metric]
+
+
+def knn(vecs, k, metric="distance"):
+    """The k nearest songs of every song of (n, 4) force vectors: (index (n, k) int32, value (n, k) float32).
+    Values have the bits of bl_distance ("distance", nearest = smallest) or bl_cosine_similarity ("cosine",
+    nearest = largest); ties go to the smaller index and the song itself is never listed
+    (ref python/examples/make_m3u_playlist.py:62-72 for every seed).  Slots past n - 1 hold -1 and NaN."""
+    v = np.ascontiguousarray(vecs, dtype=np.float32)
+    m = _knn_check(k, metric, v.shape)
+    lib = _lib.load()
+    n = v.shape[0]
+    index = np.empty((n, k), dtype=np.int32)
+    value = np.empty((n, k), dtype=np.float32)
+    rc = lib.bl_amd_knn_host(v.ctypes.data_as(C.POINTER(_lib.ForceVector)), n, int(k), m,
+                             index.ctypes.data_as(C.POINTER(C.c_int32)), value.ctypes.data_as(C.POINTER(C.c_float)))
+    _check(rc, "bl_amd_knn_host")
+    return index, value
+
+
+def knn_device(d_vecs, k, metric="distance", row_begin=0, n_rows=None, stream=None):
+    """knn() for the queries d_vecs[row_begin:row_begin + n_rows] against all of d_vecs, a float32 (n, 4) CUDA
+    tensor; returns (index, value) CUDA tensors of shape (n_rows, k) on its device, asynchronously on `stream`
+    (default: the current stream of that device)."""
+    import torch
+    m = _knn_check(k, metric, tuple(d_vecs.shape))
+    if d_vecs.dtype != torch.float32 or not d_vecs.is_cuda or not d_vecs.is_contiguous():
+        raise ValueError("d_vecs must be a contiguous float32 CUDA tensor")
+    n = d_vecs.shape[0]
+    if n_rows is None:
+        n_rows = n - row_begin
+    if not (0 <= row_begin < n and 1 <= n_rows <= n - row_begin):
+        raise ValueError(f"rows [{row_begin}, {row_begin + n_rows}) are not inside [0, {n})")
+    lib = _lib.load()
+    v = d_vecs
+    index = torch.empty((n_rows, k), dtype=torch.int32, device=v.device)
+    value = torch.empty((n_rows, k), dtype=torch.float32, device=v.device)
+    s = stream.cuda_stream if stream is not None else torch.cuda.current_stream(v.device).cuda_stream
+    idx = v.device.index or 0
+    with torch.cuda.device(idx):
+        _check(lib.bl_amd_init(idx), "bl_amd_init")
+        _check(lib.bl_amd_knn_device(v.data_ptr(), n, int(row_begin), int(n_rows), int(k), m, index.data_ptr(),
+                                     value.data_ptr(), C.c_void_p(s)), "bl_amd_knn_device")
+    return index, value

@@ -24,6 +24,8 @@
  *   k_force        force, calm_or_loud          ref src/analyze.c:63-80
  *   k_pairwise     bl_distance / bl_cosine_similarity matrix
  *                                               ref src/analyze.c:96-100,135-140
+ *   k_knn, k_knn_merge  the k nearest songs of each query (bl_distance / bl_cosine_similarity
+ *                  values), never the matrix  ref python/examples/make_m3u_playlist.py:62-72
  *   k_synth        integer synthetic PCM (benchmark corpus)
  */
 #include <hip/hip_runtime.h>
@@ -1765,6 +1767,265 @@ __global__ __launch_bounds__(256) void k_rank_order(const float *__restrict__ di
 }
 
 /* ------------------------------------------------------------------------- */
+/* k_knn: the k nearest songs of each query without the N x N matrix            */
+/* Values: bl_distance / bl_cosine_similarity with k_pairwise's arithmetic (bl_dist_sq + a correctly rounded root,
+ * bl_cos.h's guarded quotient), so a listed value has the bits of the matrix entry.  Order: a 64-bit key per
+ * (value, song) — high word the order-preserving bits of the canonical value (-0 -> +0, every NaN -> 0xFFFFFFFF,
+ * cosine negated so that larger is nearer), low word the song index — so one unsigned compare is the contract's
+ * total order (value, then smaller index).  An empty slot is the all-ones key (index 0xFFFFFFFF is never a song).
+ *
+ * A wave owns KNN_QPW queries (wave-uniform vectors) and streams 64 candidate columns per step, one per lane.  Each
+ * query keeps its best 64 * KW keys sorted across the lanes (KW = 1 for k <= 64, 2 up to 128) and the k-th of them
+ * as a wave-uniform threshold: a candidate below it goes to the query's 64-key LDS queue, and a full queue is sorted
+ * (bitonic, 21 shuffle steps) and merged into the list (6 or 7 more).  For the distance the filter runs on the squared
+ * sum against a bound taken from the threshold (knn_bound) and only survivors take the root.  With few queries the
+ * columns are split over blockIdx.y; each split writes its sorted partial list and k_knn_merge streams those keys
+ * through the same filter and queue. */
+#define KNN_QPW 4       /* queries per wave */
+#define KNN_WAVES 4     /* waves per workgroup */
+#define KNN_EMPTY 0xFFFFFFFFFFFFFFFFull
+
+/* ascending total order on f32 as unsigned: -0 and +0 equal, every NaN after +inf */
+__device__ __forceinline__ unsigned knn_ord(float v) {
+  if (v != v) return 0xFFFFFFFFu;
+  const unsigned u = v == 0.f ? 0u : __float_as_uint(v);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+template <bool COSINE> __device__ __forceinline__ unsigned long long knn_key(float v, int j) {
+  return ((unsigned long long)knn_ord(COSINE ? -v : v) << 32) | (unsigned)j;
+}
+
+/* bl_distance from the sum: bl_sqrt.h's five-instruction root in its domain, the compiler's correctly rounded
+ * sqrtf elsewhere; the two agree on every f32 (bl_amd_selftest_sqrt) */
+__device__ __forceinline__ float knn_root(float s) {
+  return bl_sqrt_fast_ok(s) ? bl_sqrt_rn_fast<1>(s) : sqrtf(s);
+}
+
+/* bl_cosine_similarity from the prepared (root, reciprocal root) of both vectors: k_pairwise's expression */
+__device__ __forceinline__ float knn_cos(const float4 a, const double2 pa, const float4 b, const double2 pb) {
+  const float dot = bl_dot(a, b);
+  float c;
+  if (!bl_cos_fast(dot, pa.y * pb.y, c)) {
+    bl_cos_vec ca, cb;
+    ca.s = pa.x;
+    cb.s = pb.x;
+    c = bl_cos_plain(dot, ca, cb);
+  }
+  return c;
+}
+
+/* Largest squared sum worth a root: with t the threshold's distance, s > t^2 (1 + 2^-20) (as computed, > t^2 (1 + 2^-21))
+ * gives sqrt(s) > t (1 + 2^-22) >= t + 2 ulp(t), whose rounding exceeds t.  Below t = 2^-50 (t^2 near the subnormals),
+ * for a NaN or empty threshold and on overflow the bound is +inf: everything is keyed exactly. */
+__device__ __forceinline__ float knn_bound(unsigned long long thr) {
+  const unsigned hi = (unsigned)(thr >> 32);
+  const float t = __uint_as_float(hi & 0x7FFFFFFFu);
+  if (hi == 0xFFFFFFFFu || hi < 0x80000000u || t < 0x1p-50f) return __builtin_inff();
+  return t * t * (1.0f + 0x1p-20f);
+}
+
+/* ascending bitonic sort of one key per lane */
+__device__ __forceinline__ unsigned long long knn_sort64(unsigned long long x, int lane) {
+#pragma unroll
+  for (int size = 2; size <= 64; size <<= 1) {
+#pragma unroll
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      const unsigned long long y = __shfl_xor(x, stride);
+      const bool keep_min = ((lane & stride) == 0) == ((lane & size) == 0);
+      x = keep_min ? min(x, y) : max(x, y);
+    }
+  }
+  return x;
+}
+
+/* a bitonic sequence of 64 (one per lane) into ascending order */
+__device__ __forceinline__ unsigned long long knn_clean64(unsigned long long x, int lane) {
+#pragma unroll
+  for (int stride = 32; stride > 0; stride >>= 1) {
+    const unsigned long long y = __shfl_xor(x, stride);
+    x = (lane & stride) ? max(x, y) : min(x, y);
+  }
+  return x;
+}
+
+/* Per-query state: the sorted list (e0 = slots 0..63, e1 = 64..127 when KW = 2), its k-th key and the queue fill. */
+template <int KW> struct knn_top {
+  unsigned long long e0, e1, thr;
+  int qn;
+  __device__ __forceinline__ void init() {
+    e0 = e1 = thr = KNN_EMPTY;
+    qn = 0;
+  }
+  /* the 64 * KW smallest of the list and an ascending batch b: min against the reversed batch leaves them as one
+   * bitonic sequence (positions below 64 of a 128-list meet the batch's padding, so e0 is unchanged there) */
+  __device__ __forceinline__ void merge(unsigned long long b, int lane, int k) {
+    const unsigned long long br = __shfl(b, 63 - lane);
+    if (KW == 1) {
+      e0 = knn_clean64(min(e0, br), lane);
+    } else {
+      const unsigned long long t1 = min(e1, br);
+      const unsigned long long lo = min(e0, t1), hi = max(e0, t1);
+      e0 = knn_clean64(lo, lane);
+      e1 = knn_clean64(hi, lane);
+    }
+    thr = (KW == 1 || k <= 64) ? __shfl(e0, k - 1) : __shfl(e1, k - 65);
+  }
+  __device__ __forceinline__ void flush(unsigned long long *q, int lane, int k) {
+    bl_wave_sync();
+    unsigned long long x = lane < qn ? q[lane] : KNN_EMPTY;
+    bl_wave_sync();
+    merge(knn_sort64(x, lane), lane, k);
+    qn = 0;
+  }
+  /* p: this lane's key goes in (wave-uniform control flow around it) */
+  __device__ __forceinline__ void push(bool p, unsigned long long key, unsigned long long *q, int lane, int k) {
+    const unsigned long long m = __ballot(p);
+    if (m == 0) return;
+    const int cnt = __popcll(m);
+    if (qn + cnt > 64) flush(q, lane, k);
+    if (p) q[qn + __popcll(m & ((1ull << lane) - 1ull))] = key;
+    qn += cnt;
+  }
+  __device__ __forceinline__ void finish(unsigned long long *q, int lane, int k) {
+    if (qn > 0) flush(q, lane, k);
+  }
+};
+
+/* slots [0, k) of row r: index and recomputed value (same function as the key's, so the same bits) */
+template <int KW, bool COSINE>
+__device__ __forceinline__ void knn_emit(const knn_top<KW> &t, int lane, int k, size_t r, const float4 a,
+                                         const double2 pa, const float4 *__restrict__ vecs,
+                                         const double2 *__restrict__ prep, int32_t *__restrict__ out_index,
+                                         float *__restrict__ out_value) {
+#pragma unroll
+  for (int w = 0; w < KW; ++w) {
+    const int slot = w * 64 + lane;
+    if (slot >= k) continue;
+    const unsigned long long key = w == 0 ? t.e0 : t.e1;
+    int idx = -1;
+    float val = __builtin_nanf("");
+    if (key != KNN_EMPTY) {
+      idx = (int)(unsigned)key;
+      val = COSINE ? knn_cos(a, pa, vecs[idx], prep[idx]) : knn_root(bl_dist_sq(a, vecs[idx]));
+    }
+    out_index[r * k + slot] = idx;
+    out_value[r * k + slot] = val;
+  }
+}
+
+/* cosine: the per-vector part of bl_cos.h once per song: (sqrt((double)|v|^2), its reciprocal) */
+__global__ __launch_bounds__(256) void k_knn_prep(const float4 *__restrict__ vecs, int n, double2 *__restrict__ prep) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) {
+    const bl_cos_vec p = bl_cos_prep(vecs[i]);
+    prep[i] = make_double2(p.s, p.r);
+  }
+}
+
+/* blockIdx.x: KNN_WAVES * KNN_QPW query rows, blockIdx.y: column split [y * cols, (y + 1) * cols).  n_split == 1:
+ * the final lists go to out_index / out_value; otherwise the first k keys of each list go to
+ * part[(row * n_split + split) * k ...]. */
+template <int KW, bool COSINE>
+__global__ __launch_bounds__(256) void k_knn(const float4 *__restrict__ vecs, const double2 *__restrict__ prep, int n,
+                                             int row_begin, int n_rows, int k, int cols, int n_split,
+                                             unsigned long long *__restrict__ part, int32_t *__restrict__ out_index,
+                                             float *__restrict__ out_value) {
+  __shared__ unsigned long long queue[KNN_WAVES][KNN_QPW][64];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int r0 = (blockIdx.x * KNN_WAVES + wave) * KNN_QPW;
+  if (r0 >= n_rows) return;
+  const int nq = min(KNN_QPW, n_rows - r0);
+  const int c0 = blockIdx.y * cols, c1 = min(n, c0 + cols);
+  float4 a[KNN_QPW];
+  double2 pa[KNN_QPW];
+  float bnd[KNN_QPW];
+  knn_top<KW> top[KNN_QPW];
+#pragma unroll
+  for (int q = 0; q < KNN_QPW; ++q) {
+    const int row = row_begin + r0 + min(q, nq - 1);
+    a[q] = vecs[row];
+    pa[q] = COSINE ? prep[row] : make_double2(0.0, 0.0);
+    /* held in VGPRs: the same in every lane, but as scalars (16 + 16 SGPRs for the cosine) they overflowed the
+     * SGPR budget and spilled in the candidate loop; the empty asm only moves them to vector registers */
+    asm volatile("" : "+v"(a[q].x), "+v"(a[q].y), "+v"(a[q].z), "+v"(a[q].w));
+    if (COSINE) asm volatile("" : "+v"(pa[q].x), "+v"(pa[q].y));
+    bnd[q] = __builtin_inff();
+    top[q].init();
+  }
+  for (int j0 = c0; j0 < c1; j0 += 64) {
+    const int j = j0 + lane;
+    const bool valid = j < c1;
+    const int jj = valid ? j : c1 - 1;
+    const float4 b = vecs[jj];
+    const double2 pb = COSINE ? prep[jj] : make_double2(0.0, 0.0);
+#pragma unroll
+    for (int q = 0; q < KNN_QPW; ++q) {
+      if (q >= nq) break;
+      const bool cand = valid && j != row_begin + r0 + q;
+      if (COSINE) {
+        const unsigned long long key = knn_key<true>(knn_cos(a[q], pa[q], b, pb), j);
+        top[q].push(cand && key < top[q].thr, key, queue[wave][q], lane, k);
+      } else {
+        const float s = bl_dist_sq(a[q], b);
+        const bool p = cand && !(s > bnd[q]);
+        if (__ballot(p) == 0) continue;
+        const float d = __all(!p || bl_sqrt_fast_ok(s)) ? bl_sqrt_rn_fast<1>(s) : sqrtf(s);
+        const unsigned long long key = knn_key<false>(d, j);
+        top[q].push(p && key < top[q].thr, key, queue[wave][q], lane, k);
+        bnd[q] = knn_bound(top[q].thr);
+      }
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < KNN_QPW; ++q) {
+    if (q >= nq) break;
+    top[q].finish(queue[wave][q], lane, k);
+    const size_t r = (size_t)(r0 + q);
+    if (n_split == 1) {
+      knn_emit<KW, COSINE>(top[q], lane, k, r, a[q], pa[q], vecs, prep, out_index, out_value);
+    } else {
+      unsigned long long *dst = part + (r * n_split + blockIdx.y) * k;
+#pragma unroll
+      for (int w = 0; w < KW; ++w)
+        if (w * 64 + lane < k) dst[w * 64 + lane] = w == 0 ? top[q].e0 : top[q].e1;
+    }
+  }
+}
+
+/* one wave per query row: the n_split partial lists of the row, read as one stream of keys, through the filter */
+template <int KW, bool COSINE>
+__global__ __launch_bounds__(256) void k_knn_merge(const float4 *__restrict__ vecs, const double2 *__restrict__ prep,
+                                                   int row_begin, int n_rows, int k, int n_split,
+                                                   const unsigned long long *__restrict__ part,
+                                                   int32_t *__restrict__ out_index, float *__restrict__ out_value) {
+  __shared__ unsigned long long queue[KNN_WAVES][64];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int r = blockIdx.x * KNN_WAVES + wave;
+  if (r >= n_rows) return;
+  const unsigned long long *src = part + (size_t)r * n_split * k;
+  const int total = n_split * k;
+  knn_top<KW> top;
+  top.init();
+  for (int o = 0; o < total; o += 4 * 64) {
+    unsigned long long key[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int i = o + u * 64 + lane;
+      key[u] = i < total ? src[i] : KNN_EMPTY;
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) top.push(key[u] < top.thr, key[u], queue[wave], lane, k);
+  }
+  top.finish(queue[wave], lane, k);
+  const int row = row_begin + r;
+  knn_emit<KW, COSINE>(top, lane, k, (size_t)r, vecs[row], COSINE ? prep[row] : make_double2(0.0, 0.0), vecs, prep,
+                       out_index, out_value);
+}
+
+/* ------------------------------------------------------------------------- */
 /* k_synth: integer-only synthetic PCM, same bytes as oracle/orc_synth.c       */
 
 __device__ __forceinline__ unsigned syn_mix32(unsigned x) {
@@ -2256,6 +2517,57 @@ int blk_playlist(hipStream_t s, const struct force_vector_s *d_vecs, int n, int 
   hipLaunchKernelGGL(k_seed_dist, dim3(gx), dim3(256), 0, s, reinterpret_cast<const float4 *>(d_vecs),
                      n, seed_index, d_dist);
   hipLaunchKernelGGL(k_rank_order, dim3(gx), dim3(256), 0, s, d_dist, n, d_order);
+  BL_HIP_CHECK(hipGetLastError());
+  return BL_OK;
+}
+
+/* Column split of a kNN call: one split while the query waves alone fill the chip (16 per CU), else enough splits
+ * to reach that many waves, each of at least 4 096 columns (a split's list fills with its first k candidates, so
+ * short splits would spend their time filling).  cols is a multiple of 64. */
+static void knn_plan(int n, int n_rows, int n_cu, int &n_split, int &cols) {
+  const long long waves = ((long long)n_rows + KNN_QPW - 1) / KNN_QPW;
+  const long long target = (long long)n_cu * 16;
+  long long split = 1;
+  if (waves < target) split = std::min(std::min((target + waves - 1) / waves, std::max(1LL, (long long)n / 4096)), 1024LL);
+  cols = (int)((((long long)n + split - 1) / split + 63) / 64 * 64);
+  n_split = (int)(((long long)n + cols - 1) / cols);
+}
+
+size_t blk_knn_scratch_bytes(int n, int n_rows, int k, bool cosine, int n_cu) {
+  int n_split, cols;
+  knn_plan(n, n_rows, n_cu, n_split, cols);
+  const size_t prep = cosine ? sizeof(double2) * (size_t)n : 0;
+  const size_t part = n_split > 1 ? sizeof(unsigned long long) * (size_t)n_rows * n_split * k : 0;
+  return (prep + 255) / 256 * 256 + part;
+}
+
+template <int KW, bool COSINE>
+static void knn_launch(hipStream_t s, const float4 *v, const double2 *prep, int n, int row_begin, int n_rows, int k,
+                       int n_split, int cols, unsigned long long *part, int32_t *d_index, float *d_value) {
+  const int per_block = KNN_WAVES * KNN_QPW;
+  hipLaunchKernelGGL((k_knn<KW, COSINE>), dim3((n_rows + per_block - 1) / per_block, n_split), dim3(64 * KNN_WAVES),
+                     0, s, v, prep, n, row_begin, n_rows, k, cols, n_split, part, d_index, d_value);
+  if (n_split > 1)
+    hipLaunchKernelGGL((k_knn_merge<KW, COSINE>), dim3((n_rows + KNN_WAVES - 1) / KNN_WAVES), dim3(64 * KNN_WAVES),
+                       0, s, v, prep, row_begin, n_rows, k, n_split, part, d_index, d_value);
+}
+
+int blk_knn(hipStream_t s, const struct force_vector_s *d_vecs, int n, int row_begin, int n_rows, int k,
+            bool cosine, int n_cu, void *d_scratch, int32_t *d_index, float *d_value) {
+  const float4 *v = reinterpret_cast<const float4 *>(d_vecs);
+  int n_split, cols;
+  knn_plan(n, n_rows, n_cu, n_split, cols);
+  double2 *prep = cosine ? static_cast<double2 *>(d_scratch) : nullptr;
+  unsigned long long *part = n_split > 1 ? reinterpret_cast<unsigned long long *>(
+      static_cast<char *>(d_scratch) + (cosine ? (sizeof(double2) * (size_t)n + 255) / 256 * 256 : 0)) : nullptr;
+  if (cosine) hipLaunchKernelGGL(k_knn_prep, dim3((n + 255) / 256), dim3(256), 0, s, v, n, prep);
+  if (k > 64) {
+    if (cosine) knn_launch<2, true>(s, v, prep, n, row_begin, n_rows, k, n_split, cols, part, d_index, d_value);
+    else knn_launch<2, false>(s, v, prep, n, row_begin, n_rows, k, n_split, cols, part, d_index, d_value);
+  } else {
+    if (cosine) knn_launch<1, true>(s, v, prep, n, row_begin, n_rows, k, n_split, cols, part, d_index, d_value);
+    else knn_launch<1, false>(s, v, prep, n, row_begin, n_rows, k, n_split, cols, part, d_index, d_value);
+  }
   BL_HIP_CHECK(hipGetLastError());
   return BL_OK;
 }

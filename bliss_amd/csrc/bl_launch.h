@@ -103,6 +103,11 @@ int blk_sqrt_sweep(hipStream_t s, unsigned long long first, unsigned long long c
 int blk_cos_sweep(hipStream_t s, unsigned long long seed, int per_thread, unsigned long long *d_counts, int n_cu);
 int blk_playlist(hipStream_t s, const struct force_vector_s *d_vecs, int n, int seed_index,
                  int32_t *d_order, float *d_dist);
+/* the k nearest songs of rows [row_begin, row_begin + n_rows) (bl_amd_knn_device); d_scratch: at least
+ * blk_knn_scratch_bytes(n, n_rows, k, cosine, n_cu) bytes, 256-byte aligned */
+size_t blk_knn_scratch_bytes(int n, int n_rows, int k, bool cosine, int n_cu);
+int blk_knn(hipStream_t s, const struct force_vector_s *d_vecs, int n, int row_begin, int n_rows, int k,
+            bool cosine, int n_cu, void *d_scratch, int32_t *d_index, float *d_value);
 /* out[i] = (int16)(in[i] >> 16): the same-rate S32 -> S16 narrowing */
 int blk_narrow_s32(hipStream_t s, const int32_t *d_in, int16_t *d_out, size_t n, int n_cu);
 /* out[order[i]] = in[i] for 16-byte force vectors (shard-major -> caller order) */

@@ -82,6 +82,8 @@ struct bl_amd_ctx {
   bl_rs_geom rs_geom{};
   size_t rs_lds = 0;
   int rs_taps = 0, rs_phases = 0, rs_src_incr = 0, rs_dst_incr = 0;
+  /* bl_amd_knn_device: the cosine prep of the vectors and the column splits' partial lists */
+  bl_buf knn;
 };
 
 /* bl_runtime.hip */

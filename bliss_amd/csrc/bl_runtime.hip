@@ -129,7 +129,7 @@ void ctx_release(bl_amd_ctx *c) {
   prof_collect(c);
   bl_buf *bufs[] = {&c->songs,   &c->stats,   &c->hist, &c->spectrum, &c->energies, &c->lc,
                     &c->results, &c->misc,    &c->arena[0], &c->arena[1], &c->arena22[0], &c->arena22[1],
-                    &c->rs_songs, &c->rs_bank, &c->mx_my, &c->mx_gath, &c->mx_all, &c->mx_order, &c->mx_rows};
+                    &c->rs_songs, &c->rs_bank, &c->mx_my, &c->mx_gath, &c->mx_all, &c->mx_order, &c->mx_rows, &c->knn};
   for (bl_buf *b : bufs) release_buf(*b);
   for (int k = 0; k < 2; ++k) {
     unregister_wave(c, k);
@@ -856,6 +856,59 @@ int bl_amd_playlist_host(const struct force_vector_s *h_vecs, int n, int seed_in
     rc = BL_OK;
   if (dv) (void)hipFree(dv);
   if (dord) (void)hipFree(dord);
+  if (dd) (void)hipFree(dd);
+  return rc;
+}
+
+/* k nearest songs (bl_kernels.hip k_knn): every argument is checked before any device work, so a rejected call
+ * leaves the output untouched.  The scratch (cosine prep, partial lists of a column split) is the context's workspace,
+ * handed from call to call by ev_ws like the analysis workspace: nothing here waits for the device. */
+static bool knn_args_ok(const void *vecs, int n, int row_begin, int n_rows, int k, int metric, const void *index,
+                        const void *value) {
+  return vecs && index && value && n > 0 && k >= 1 && k <= BL_AMD_KNN_MAX_K &&
+         (metric == BL_AMD_KNN_DISTANCE || metric == BL_AMD_KNN_COSINE) && row_begin >= 0 && n_rows > 0 &&
+         row_begin < n && n_rows <= n - row_begin;
+}
+
+int bl_amd_knn_device(const struct force_vector_s *d_vecs, int n, int row_begin, int n_rows, int k, int metric,
+                      int32_t *d_index, float *d_value, void *stream) {
+  if (!knn_args_ok(d_vecs, n, row_begin, n_rows, k, metric, d_index, d_value)) return BL_UNEXPECTED;
+  bl_amd_ctx *c = blr_default_ctx();
+  if (!c) return BL_UNEXPECTED;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DevGuard dg(c->device);
+  if (!dg.ok) return BL_UNEXPECTED;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const bool cosine = metric == BL_AMD_KNN_COSINE;
+  if (c->ws_used) BL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_ws, 0));
+  if (blr_ensure(c->knn, blk_knn_scratch_bytes(n, n_rows, k, cosine, c->n_cu)) != BL_OK) return BL_UNEXPECTED;
+  if (blk_knn(s, d_vecs, n, row_begin, n_rows, k, cosine, c->n_cu, c->knn.p, d_index, d_value) != BL_OK)
+    return BL_UNEXPECTED;
+  BL_HIP_CHECK(hipEventRecord(c->ev_ws, s));
+  c->ws_used = true;
+  return BL_OK;
+}
+
+int bl_amd_knn_host(const struct force_vector_s *h_vecs, int n, int k, int metric, int32_t *h_index,
+                    float *h_value) {
+  if (!knn_args_ok(h_vecs, n, 0, n, k, metric, h_index, h_index /* h_value may be NULL */)) return BL_UNEXPECTED;
+  bl_amd_ctx *c = blr_default_ctx();
+  if (!c) return BL_UNEXPECTED;
+  DevGuard dg(c->device);
+  if (!dg.ok) return BL_UNEXPECTED;
+  const size_t out = (size_t)n * k;
+  void *dv = nullptr, *di = nullptr, *dd = nullptr;
+  int rc = BL_UNEXPECTED;
+  if (hipMalloc(&dv, sizeof(struct force_vector_s) * (size_t)n) == hipSuccess &&
+      hipMalloc(&di, sizeof(int32_t) * out) == hipSuccess && hipMalloc(&dd, sizeof(float) * out) == hipSuccess &&
+      hipMemcpy(dv, h_vecs, sizeof(struct force_vector_s) * (size_t)n, hipMemcpyHostToDevice) == hipSuccess &&
+      bl_amd_knn_device(static_cast<struct force_vector_s *>(dv), n, 0, n, k, metric, static_cast<int32_t *>(di),
+                        static_cast<float *>(dd), nullptr) == BL_OK &&
+      hipMemcpy(h_index, di, sizeof(int32_t) * out, hipMemcpyDeviceToHost) == hipSuccess &&
+      (!h_value || hipMemcpy(h_value, dd, sizeof(float) * out, hipMemcpyDeviceToHost) == hipSuccess))
+    rc = BL_OK;
+  if (dv) (void)hipFree(dv);
+  if (di) (void)hipFree(di);
   if (dd) (void)hipFree(dd);
   return rc;
 }

@@ -260,6 +260,24 @@ int bl_amd_playlist_device(const struct force_vector_s *d_vecs, int n, int seed_
 int bl_amd_playlist_host(const struct force_vector_s *h_vecs, int n, int seed_index,
                          int32_t *h_order, float *h_dist /* may be NULL */);
 
+/* k nearest songs of each query, without the N x N matrix.  Rows [row_begin, row_begin + n_rows) of d_vecs
+ * are the queries; the candidates are all n songs minus the query itself (its exact duplicates are ordinary
+ * candidates).  d_index / d_value: n_rows * k, row-major; slot j of row r = the (j+1)-th nearest song to song
+ * row_begin + r and its value, with the bits of bl_distance (BL_AMD_KNN_DISTANCE, nearest = smallest;
+ * ref src/analyze.c:96-100) or bl_cosine_similarity (BL_AMD_KNN_COSINE, nearest = largest;
+ * ref src/analyze.c:135-140).  Order: the returned f32 value (+0 and -0 equal, NaN after every number), ties by
+ * the smaller song index — the stable argsort of the matrix row.  If k > n - 1 the trailing slots hold index -1
+ * and a NaN.  1 <= k <= BL_AMD_KNN_MAX_K.  Asynchronous on `stream`; the result does not depend on the row
+ * range asked for. */
+#define BL_AMD_KNN_DISTANCE 0
+#define BL_AMD_KNN_COSINE 1
+#define BL_AMD_KNN_MAX_K 128
+int bl_amd_knn_device(const struct force_vector_s *d_vecs, int n, int row_begin, int n_rows, int k, int metric,
+                      int32_t *d_index, float *d_value, void *stream);
+/* All n songs as queries, host pointers, blocking.  h_value may be NULL. */
+int bl_amd_knn_host(const struct force_vector_s *h_vecs, int n, int k, int metric, int32_t *h_index,
+                    float *h_value);
+
 /* Integer-only synthetic PCM (the benchmark corpus of BASELINE.json),
  * generated in place on the device: song i = seed_base + i, written at
  * h_desc[i].pcm_offset.  Byte-identical to oracle/orc_synth.c. */
