@@ -38,6 +38,7 @@
 
 #include "bl_launch.h"
 #include "bl_fft_lavc.h"
+#include "bl_fft_tan.h"
 #include "bl_cos.h"
 #include "bl_sqrt.h"
 #include "bl_tail.h"
@@ -1056,10 +1057,13 @@ __global__ __launch_bounds__(64 * (EV_CWAVES + 1)) void k_env_windows3(
   const bl_dsong sg = songs[blockIdx.y];
   const bl_dstats st = stats[blockIdx.y];
   const int16_t *p = pcm + sg.pcm_off;
-  if (tid < 256) {
+  /* FIR modes 1 / 2 run bl_fft_tan.h's transform: tw512[0..127] holds (t, c) of W512^k and tw256 is not read (the
+   * lanes keep their constants in registers); mode 0 keeps bl_fft.h's (see the registers below) */
+  if (FIR_MODE == 0 && tid < 256) {
     tw256[tid] = tb.tw256_d[((tid & 15) * (tid >> 4)) & 255];
     tw512[tid] = tb.tw512_d[tid];
   }
+  if (FIR_MODE != 0 && tid < 128) tw512[tid] = tb.tw512t[tid];
   if (tid < 36) flags[tid] = 0; /* the sequence words and the zero pair behind them */
   if (tid < EV_TILE) terms[tid * EV_TROW + 257] = 0.0; /* the pad behind term 256 is read as a term */
   __syncthreads();
@@ -1168,17 +1172,36 @@ __global__ __launch_bounds__(64 * (EV_CWAVES + 1)) void k_env_windows3(
   /* mode 2 filters the integers k = s - mean themselves (the taps carry the division) */
   auto nrm = [&](int k) -> double { return FIR_MODE == 2 ? (double)k : bl_norm(k, rcp, rcp_lo); };
   const int r0 = run_begin(u0 + wave), r1 = run_begin(u0 + wave + 1);
-  /* all 15 pass-1 twiddles of the lane live in registers for the whole run: 194 / 192 / 213 VGPRs in FIR modes
-   * 0 / 1 / 2, no spill.  (Until round 6 modes 0 / 1 kept 12 and read three per round from LDS — a relic of a 220-VGPR
-   * build; the 185-VGPR one had the room: 44.15 -> 41.99 ms per 1 024 S180 songs in mode 0, identical records.  The
-   * eight split twiddles W512^(l + 16 k0) as well — 218 VGPRs — made mode 0 10 % SLOWER and mode 2 no faster:
-   * profiles/EXPERIMENTS.md.) */
-  constexpr int EV3_W1_REGS = 16;
-  c2d w1r[EV3_W1_REGS];
+  /* FIR modes 1 / 2: the DFT is bl_fft_tan.h's; the lane's 15 pass-1 tangents t(l, k1) and the 21 pass-2 folding factors
+   * of lane k1 = l live in registers for the whole run, 72 VGPRs where the 15 complex pass-1 twiddles took 60 (213 -> 212
+   * VGPRs in mode 2).  Mode 0 keeps bl_fft.h's transform and its 15 complex twiddles: with the tan form its FIR's
+   * schedule lost more than the DFT gained (212 instead of 194 VGPRs, 41.48 vs 40.96 ms per 1 024 S180 songs), and its
+   * energies stay those of the reference arithmetic's previous builds bit for bit.  (Until round 6 modes 0 / 1 kept 12
+   * twiddles and read three per round from LDS — a relic of a 220-VGPR build; the 185-VGPR one had the room: 44.15 ->
+   * 41.99 ms per 1 024 S180 songs in mode 0, identical records.  The eight split twiddles W512^(l + 16 k0) as well —
+   * 218 VGPRs — made mode 0 10 % SLOWER and mode 2 no faster: profiles/EXPERIMENTS.md.) */
+  constexpr bool EV3_TAN = FIR_MODE != 0;
+  double t1[16];
+  bl_fft16_fold<double> fold;
+  c2d w1r[16];
+  if (EV3_TAN) {
+    const bl_fft_tan_lane<double> *tl = reinterpret_cast<const bl_fft_tan_lane<double> *>(tb.tan_lane) + l;
+    t1[0] = 0.0;
 #pragma unroll
-  for (int k1 = 1; k1 < EV3_W1_REGS; ++k1) {
-    w1r[k1] = tw256[k1 * 16 + l];
-    asm volatile("" : "+v"(w1r[k1].re), "+v"(w1r[k1].im));
+    for (int k1 = 1; k1 < 16; ++k1) {
+      t1[k1] = tl->t1[k1];
+      asm volatile("" : "+v"(t1[k1]));
+    }
+    fold = tl->fold;
+#define EV3_PIN(A, N) _Pragma("unroll") for (int i = 0; i < N; ++i) asm volatile("" : "+v"(A[i]));
+    EV3_PIN(fold.rb, 4) EV3_PIN(fold.rc, 4) EV3_PIN(fold.rd, 4) EV3_PIN(fold.fb, 4) EV3_PIN(fold.fc, 2) EV3_PIN(fold.g, 3)
+#undef EV3_PIN
+  } else {
+#pragma unroll
+    for (int k1 = 1; k1 < 16; ++k1) {
+      w1r[k1] = tw256[k1 * 16 + l];
+      asm volatile("" : "+v"(w1r[k1].re), "+v"(w1r[k1].im));
+    }
   }
   int base5 = (4 * r0) % 5; /* ring position of block 4 rho, the block shared with the previous round */
 
@@ -1348,11 +1371,13 @@ __global__ __launch_bounds__(64 * (EV_CWAVES + 1)) void k_env_windows3(
     ev_wave_sync(); /* window data is in registers; block g's place becomes exchange space */
     stamp(s, 2);
     phase(2);
-    bl_fft16(re, im);
+    if (EV3_TAN) {
+      /* pass 1: register bl_pos16(k1) leaves holding its value divided by c(l, k1); pass 2 folds the factors back */
+      bl_fft512_pass1_tan(re, im, t1);
+    } else {
+      bl_fft16(re, im);
 #pragma unroll
-    for (int k1 = 1; k1 < 16; ++k1) {
-      const c2d w = k1 < EV3_W1_REGS ? w1r[k1] : tw256[k1 * 16 + l];
-      bl_cmul(re[bl_pos16(k1)], im[bl_pos16(k1)], w.re, w.im);
+      for (int k1 = 1; k1 < 16; ++k1) bl_cmul(re[bl_pos16(k1)], im[bl_pos16(k1)], w1r[k1].re, w1r[k1].im);
     }
     stamp(s, 3);
     phase(3);
@@ -1389,7 +1414,8 @@ __global__ __launch_bounds__(64 * (EV_CWAVES + 1)) void k_env_windows3(
 #pragma unroll
     for (int k0 = 0; k0 < 8; ++k0)
       if (k0 < 7 || l != 15) tg[256 - l - 16 * k0] = held[k0]; /* terms 130..256 of the round before */
-    bl_fft16(re, im);
+    if (EV3_TAN) bl_fft16_folded(re, im, fold);
+    else bl_fft16(re, im);
     /* the partner of pair k = k1 + 16 k0 is Z[256 - k]: register 15 - k0 of lane (16 - k1) mod 16 —
      * a mirror of the 16-lane row followed by a shift by one, two DPP moves per dword and no LDS
      * round trip; lane 0 is its own partner and takes its register 16 - k0 (k0 = 0: Z[0] itself) */
@@ -1404,7 +1430,10 @@ __global__ __launch_bounds__(64 * (EV_CWAVES + 1)) void k_env_windows3(
       const double pr = bl_dpp_f64_old<0x111>(zr, bl_dpp_f64<0x140>(sr));
       const double pi = bl_dpp_f64_old<0x111>(zi, bl_dpp_f64<0x140>(si));
       double own;
-      bl_fft512_power1<double, false>(re[bl_pos16(k0)], im[bl_pos16(k0)], pr, pi, tw512[l + 16 * k0], own, held[k0]);
+      if (EV3_TAN)
+        bl_fft512_power1_tan<double, false>(re[bl_pos16(k0)], im[bl_pos16(k0)], pr, pi, tw512[l + 16 * k0], own, held[k0]);
+      else
+        bl_fft512_power1<double, false>(re[bl_pos16(k0)], im[bl_pos16(k0)], pr, pi, tw512[l + 16 * k0], own, held[k0]);
       tg[l + 16 * k0] = own; /* terms 0..127 of this round */
       if (k0 == 7) mir7 = held[7];
     }
@@ -2108,7 +2137,9 @@ __global__ __launch_bounds__(256) void k_extract_vecs(const bl_amd_song_result *
 /* ========================================================================= */
 /* launchers (declared in bl_launch.h)                                        */
 
-size_t blk_tables_bytes(void) { return 256 * 16 * 2 + 512 * 4 + LV_TW_SLOTS * 16 * 8; }
+size_t blk_tables_bytes(void) {
+  return 256 * 16 * 2 + 512 * 4 + LV_TW_SLOTS * 16 * 8 + sizeof(bl_fft_tan_lane<double>) * 16 + 128 * 16;
+}
 
 void blk_tables_fill_host(unsigned char *h) {
   /* twiddle / window tables, computed in double on the host */
@@ -2125,6 +2156,10 @@ void blk_tables_fill_host(unsigned char *h) {
   /* libavcodec's cosine tables, per lane and pass (bl_fft_lavc.h) */
   float leafc[4];
   lv_fill_tables(reinterpret_cast<float(*)[2]>(hann + 512), leafc);
+  /* the tan-form constants of k_env_windows3's DFT (bl_fft_tan.h), long double on the host */
+  unsigned char *tan_at = reinterpret_cast<unsigned char *>(hann + 512) + LV_TW_SLOTS * 16 * 8;
+  bl_fft_tan_fill(reinterpret_cast<bl_fft_tan_lane<double> *>(tan_at),
+                  reinterpret_cast<c2d *>(tan_at + sizeof(bl_fft_tan_lane<double>) * 16));
 }
 
 bl_tables blk_tables_bind(const void *d_mem) {
@@ -2134,6 +2169,8 @@ bl_tables blk_tables_bind(const void *d_mem) {
   tb.tw512_d = tb.tw256_d + 256;
   tb.hann = reinterpret_cast<const float *>(tb.tw512_d + 256);
   tb.lv_tw = reinterpret_cast<const c2f *>(tb.hann + 512);
+  tb.tan_lane = reinterpret_cast<const double *>(tb.lv_tw + LV_TW_SLOTS * 16);
+  tb.tw512t = reinterpret_cast<const c2d *>(tb.tan_lane + 16 * BL_FFT_TAN_LANE_DOUBLES);
   {
     float tw[LV_TW_SLOTS * 16][2];
     lv_fill_tables(tw, tb.lv_leafc);

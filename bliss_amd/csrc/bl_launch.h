@@ -53,6 +53,8 @@ struct bl_tables {
   const float *hann;
   const c2f *lv_tw;   /* bl_fft_lavc.h: [LV_TW_SLOTS][16 lanes] (cos, "sin") pairs of libavcodec's tables */
   float lv_leafc[4];  /* sqrthalf, cos_16[1], cos_16[3] */
+  const double *tan_lane; /* bl_fft_tan.h: [16][BL_FFT_TAN_LANE_DOUBLES] per-lane constants of k_env_windows3's DFT */
+  const c2d *tw512t;      /* bl_fft_tan.h: (t, c) of W512^k, k = 0..127 */
   double log101;
 };
 
