@@ -400,3 +400,77 @@ def knn_device(d_vecs, k, metric="distance", row_begin=0, n_rows=None, stream=No
         _check(lib.bl_amd_knn_device(v.data_ptr(), n, int(row_begin), int(n_rows), int(k), m, index.data_ptr(),
                                      value.data_ptr(), C.c_void_p(s)), "bl_amd_knn_device")
     return index, value
+
+
+def _chain_check(seeds, length, metric, shape, n_limit):
+    """(metric code, seeds as a contiguous 1-D int32 numpy array or None for a tensor); n_limit: reject seeds outside
+    [0, n_limit) (None: leave them to the device, which answers with a -1 / NaN row)"""
+    if isinstance(length, bool) or not isinstance(length, (int, np.integer)) or length < 1:
+        raise ValueError(f"length must be an integer >= 1, got {length!r}")
+    if metric not in _KNN_METRICS:
+        raise ValueError(f"metric must be one of {sorted(_KNN_METRICS)}, got {metric!r}")
+    if len(shape) != 2 or shape[1] != 4 or shape[0] < 1:
+        raise ValueError(f"force vectors must have shape (n, 4) with n >= 1, got {tuple(shape)}")
+    if hasattr(seeds, "is_cuda"):   # a torch tensor: chain_device checks it
+        return _KNN_METRICS[metric], None
+    s = np.asarray(seeds)
+    if s.dtype == np.bool_ or not np.issubdtype(s.dtype, np.integer):
+        raise ValueError(f"seeds must be integers, got dtype {s.dtype}")
+    if s.ndim > 1 or s.size < 1:
+        raise ValueError(f"seeds must be a scalar or a non-empty 1-D sequence, got shape {s.shape}")
+    s = s.reshape(-1)
+    if n_limit is not None and (s.min() < 0 or s.max() >= n_limit):
+        raise ValueError(f"seeds must lie in [0, {n_limit})")
+    if s.min() < -2 ** 31 or s.max() >= 2 ** 31:
+        raise ValueError("seeds do not fit 32 bits")
+    return _KNN_METRICS[metric], np.ascontiguousarray(s, dtype=np.int32)
+
+
+def chain(vecs, seeds, length, metric="distance"):
+    """Song-to-song chains over (n, 4) force vectors, one per seed (a scalar seed gives one chain): slot 0 is the
+    seed and every next slot the song nearest to the previous one that the chain has not played yet, nearest as in
+    knn().  Returns (order (n_chains, length) int32, value (n_chains, length) float32); value[c, t] has the bits of
+    bl_distance / bl_cosine_similarity between the songs of slots t - 1 and t (slot 0: the seed with itself).
+    Slots past n hold -1 and NaN."""
+    v = np.ascontiguousarray(vecs, dtype=np.float32)
+    m, s = _chain_check(seeds, length, metric, v.shape, v.shape[0] if v.ndim == 2 else 0)
+    lib = _lib.load()
+    order = np.empty((s.size, length), dtype=np.int32)
+    value = np.empty((s.size, length), dtype=np.float32)
+    rc = lib.bl_amd_chain_host(v.ctypes.data_as(C.POINTER(_lib.ForceVector)), v.shape[0],
+                               s.ctypes.data_as(C.POINTER(C.c_int32)), s.size, int(length), m,
+                               order.ctypes.data_as(C.POINTER(C.c_int32)), value.ctypes.data_as(C.POINTER(C.c_float)))
+    _check(rc, "bl_amd_chain_host")
+    return order, value
+
+
+def chain_device(d_vecs, d_seeds, length, metric="distance", stream=None):
+    """chain() on the device: d_vecs a contiguous float32 (n, 4) CUDA tensor, d_seeds an int32 CUDA tensor on the same
+    device (0-D or 1-D) or host integers, which are uploaded.  Returns (order, value) CUDA tensors of shape
+    (n_chains, length), asynchronously on `stream` (default: the current stream of that device).  A seed outside
+    [0, n) gives a row of -1 / NaN."""
+    import torch
+    m, s = _chain_check(d_seeds, length, metric, tuple(d_vecs.shape), None)
+    if d_vecs.dtype != torch.float32 or not d_vecs.is_cuda or not d_vecs.is_contiguous():
+        raise ValueError("d_vecs must be a contiguous float32 CUDA tensor")
+    if s is None:
+        if d_seeds.dtype != torch.int32 or d_seeds.dim() > 1 or d_seeds.numel() < 1:
+            raise ValueError("d_seeds must be an int32 tensor with 0 or 1 dimensions and at least one element")
+        if not d_seeds.is_cuda or d_seeds.device != d_vecs.device:
+            raise ValueError("d_seeds must be on the device of d_vecs")
+    lib = _lib.load()
+    v = d_vecs
+    n = v.shape[0]
+    cur = stream if stream is not None else torch.cuda.current_stream(v.device)
+    idx = v.device.index or 0
+    with torch.cuda.device(idx), torch.cuda.stream(cur):
+        sd = torch.from_numpy(s).to(v.device) if s is not None else d_seeds.reshape(-1).contiguous()
+        n_chains = sd.numel()
+        order = torch.empty((n_chains, length), dtype=torch.int32, device=v.device)
+        value = torch.empty((n_chains, length), dtype=torch.float32, device=v.device)
+        _check(lib.bl_amd_init(idx), "bl_amd_init")
+        _check(lib.bl_amd_chain_device(v.data_ptr(), n, sd.data_ptr(), n_chains, int(length), m, order.data_ptr(),
+                                       value.data_ptr(), C.c_void_p(cur.cuda_stream)), "bl_amd_chain_device")
+        if s is not None:
+            sd.record_stream(cur)   # the uploaded seeds are freed when this returns
+    return order, value

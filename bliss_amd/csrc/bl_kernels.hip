@@ -26,6 +26,7 @@
  *                                               ref src/analyze.c:96-100,135-140
  *   k_knn, k_knn_merge  the k nearest songs of each query (bl_distance / bl_cosine_similarity
  *                  values), never the matrix  ref python/examples/make_m3u_playlist.py:62-72
+ *   k_chain, k_chain_step  song-to-song chains: every next song the nearest unplayed one (k_knn's values and order)
  *   k_synth        integer synthetic PCM (benchmark corpus)
  */
 #include <hip/hip_runtime.h>
@@ -2055,6 +2056,238 @@ __global__ __launch_bounds__(256) void k_knn_merge(const float4 *__restrict__ ve
 }
 
 /* ------------------------------------------------------------------------- */
+/* k_chain: song-to-song chains (bl_amd_chain_device)                           */
+/* Slot t + 1 of a chain is the unplayed song nearest to the song of slot t: `length` dependent steps of an argmin
+ * over n candidates.  Values and order are k_knn's (bl_dist_sq + knn_root or knn_cos, knn_key), the pick is the
+ * minimum key and the stored value is computed again at the store by the function its key came from.  Two shapes,
+ * same bytes:
+ *   k_chain       one workgroup per chain.  Lane `tid` owns the columns j = tid (mod blockDim.x) for the whole chain,
+ *                 so their played bits are the lane's own words (LDS, or the workspace when n bits do not fit) and need
+ *                 no atomics.  A step: every lane's minimum key over its unplayed columns, a wave min by shuffles,
+ *                 one LDS word per wave, one barrier (the words are double-buffered by the step's parity).
+ *   k_chain_step  few chains over many songs: one launch per step, blockIdx.x a column slice, blockIdx.y the chain.
+ *                 A slice's minimum key goes into the chain's `best` by an agent-scope atomic min; once that has
+ *                 returned the workgroup adds to the chain's arrival counter, and the workgroup whose add came last
+ *                 takes `best` (an atomic exchange that also re-arms it), writes the slot, sets the played bit and
+ *                 publishes the current song for the next launch.  Nobody waits for anybody: no polling.  Only
+ *                 8-byte and 4-byte agent-scope atomics carry data between workgroups of one launch; everything
+ *                 else (current song, played bits) crosses a kernel boundary. */
+#define CHAIN_MAX_WAVES 16
+#define CHAIN_BATCH 8 /* candidate loads a lane keeps in flight */
+#define CHAIN_LDS_HEAD (2 * CHAIN_MAX_WAVES * 8) /* bytes of wave minima in front of the LDS bitmap */
+#define CHAIN_LDS_MAX (160 * 1024)
+
+struct chain_state { /* one per chain of the column-split shape; `best` and `count` on different 128-byte lines */
+  unsigned long long best;
+  unsigned pad0[30];
+  unsigned count;
+  int cur;
+  unsigned pad1[30];
+};
+
+template <bool COSINE>
+__device__ __forceinline__ float chain_value(const float4 a, const double2 pa, const float4 b, const double2 pb) {
+  return COSINE ? knn_cos(a, pa, b, pb) : knn_root(bl_dist_sq(a, b));
+}
+
+/* candidate j into a lane's running minimum.  Distance: a sum above knn_bound(best) has a root above best's, so
+ * only sums at or below it (and NaN) take the root. */
+template <bool COSINE>
+__device__ __forceinline__ void chain_visit(const float4 a, const double2 pa, const float4 b, const double2 pb, int j,
+                                            unsigned long long &best, float &bnd) {
+  if (COSINE) {
+    best = min(best, knn_key<true>(knn_cos(a, pa, b, pb), j));
+  } else {
+    const float s = bl_dist_sq(a, b);
+    if (!(s > bnd)) {
+      const unsigned long long key = knn_key<false>(knn_root(s), j);
+      if (key < best) {
+        best = key;
+        bnd = knn_bound(best);
+      }
+    }
+  }
+}
+
+__device__ __forceinline__ unsigned long long chain_wave_min(unsigned long long x) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) x = min(x, (unsigned long long)__shfl_xor(x, off));
+  return x;
+}
+
+/* blockDim.x = 1 << lb threads (a multiple of 64, at most 1024).  `words` 32-column words of played bits per lane:
+ * word w of lane tid at bits[w * blockDim.x + tid] covers the columns tid + (32 w + i) * blockDim.x. */
+template <bool COSINE, bool LDS_BITS>
+__global__ __launch_bounds__(1024) void k_chain(const float4 *__restrict__ vecs, const double2 *__restrict__ prep, int n,
+                                                const int32_t *__restrict__ seeds, int length, int lb, int words,
+                                                unsigned *__restrict__ g_bits, int32_t *__restrict__ out_order,
+                                                float *__restrict__ out_value) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char chain_smem[];
+  unsigned long long *wmin = reinterpret_cast<unsigned long long *>(chain_smem);
+  const int B = 1 << lb, tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wave_mask = (B >> 6) - 1;
+  unsigned *bits = LDS_BITS ? reinterpret_cast<unsigned *>(chain_smem + CHAIN_LDS_HEAD)
+                            : g_bits + (size_t)blockIdx.x * words * B;
+  int32_t *order = out_order + (size_t)blockIdx.x * length;
+  float *value = out_value + (size_t)blockIdx.x * length;
+  const int steps = min(length, n);
+  int cur = seeds[blockIdx.x];
+  const bool ok = cur >= 0 && cur < n;
+  for (int t = (ok ? steps : 0) + tid; t < length; t += B) {
+    order[t] = -1;
+    value[t] = __builtin_nanf("");
+  }
+  if (!ok) return;
+  const int cols = tid < n ? ((n - 1 - tid) >> lb) + 1 : 0; /* columns of this lane */
+  for (int w = 0; w < words; ++w) bits[w * B + tid] = 0u;
+  if ((cur & (B - 1)) == tid) bits[((cur >> lb) >> 5) * B + tid] = 1u << ((cur >> lb) & 31);
+  for (int t = 0; t < steps; ++t) {
+    float4 a = vecs[cur];
+    double2 pa = COSINE ? prep[cur] : make_double2(0.0, 0.0);
+    /* wave-uniform, but held in VGPRs like k_knn's queries: as scalars they crowd the SGPR file in the loop */
+    asm volatile("" : "+v"(a.x), "+v"(a.y), "+v"(a.z), "+v"(a.w));
+    if (COSINE) asm volatile("" : "+v"(pa.x), "+v"(pa.y));
+    if (t == 0) {
+      if (tid == 0) {
+        order[0] = cur;
+        value[0] = chain_value<COSINE>(a, pa, a, pa);
+      }
+      continue;
+    }
+    unsigned long long best = KNN_EMPTY;
+    float bnd = __builtin_inff();
+    for (int i0 = 0; i0 < cols; i0 += 32) {
+      const unsigned played = bits[(i0 >> 5) * B + tid];
+      for (int u0 = 0; u0 < 32 && i0 + u0 < cols; u0 += CHAIN_BATCH) {
+        /* CHAIN_BATCH loads in flight, then the arithmetic: one load per visit leaves the step latency-bound */
+        float4 b[CHAIN_BATCH];
+        double2 pb[CHAIN_BATCH];
+#pragma unroll
+        for (int u = 0; u < CHAIN_BATCH; ++u) {
+          const int j = tid + (min(i0 + u0 + u, cols - 1) << lb);
+          b[u] = vecs[j];
+          pb[u] = COSINE ? prep[j] : make_double2(0.0, 0.0);
+        }
+#pragma unroll
+        for (int u = 0; u < CHAIN_BATCH; ++u)
+          if (i0 + u0 + u < cols && !((played >> (u0 + u)) & 1u))
+            chain_visit<COSINE>(a, pa, b[u], pb[u], tid + ((i0 + u0 + u) << lb), best, bnd);
+      }
+    }
+    best = chain_wave_min(best);
+    unsigned long long *slot = wmin + (t & 1) * CHAIN_MAX_WAVES;
+    if (lane == 0) slot[wave] = best;
+    __syncthreads();
+    unsigned long long m = slot[lane & wave_mask];
+#pragma unroll
+    for (int off = CHAIN_MAX_WAVES / 2; off > 0; off >>= 1) m = min(m, (unsigned long long)__shfl_xor(m, off));
+    if (m == KNN_EMPTY) break; /* cannot happen while t < n: a song is left */
+    const int pick = __builtin_amdgcn_readfirstlane((int)(unsigned)m);
+    if ((pick & (B - 1)) == tid) bits[((pick >> lb) >> 5) * B + tid] |= 1u << ((pick >> lb) & 31);
+    if (tid == 0) {
+      order[t] = pick;
+      value[t] = chain_value<COSINE>(a, pa, vecs[pick], COSINE ? prep[pick] : make_double2(0.0, 0.0));
+    }
+    cur = pick;
+  }
+}
+
+/* column-split shape, start of a call: played bits (word w of chain c at bits[c * words + w], bit j & 31 of word
+ * j >> 5 = song j), the chain's state, slot 0 and the padding.  grid (any, n_chains). */
+template <bool COSINE>
+__global__ __launch_bounds__(256) void k_chain_init(const float4 *__restrict__ vecs, const double2 *__restrict__ prep,
+                                                    int n, const int32_t *__restrict__ seeds, int length, int words,
+                                                    chain_state *__restrict__ state, unsigned *__restrict__ bits,
+                                                    int32_t *__restrict__ out_order, float *__restrict__ out_value) {
+  const int c = blockIdx.y;
+  const int seed = seeds[c];
+  const bool ok = seed >= 0 && seed < n;
+  const int steps = min(length, n);
+  const unsigned g = blockIdx.x * 256u + threadIdx.x, stride = gridDim.x * 256u;
+  for (unsigned w = g; w < (unsigned)words; w += stride)
+    bits[(size_t)c * words + w] = (ok && w == (unsigned)seed >> 5) ? 1u << (seed & 31) : 0u;
+  for (unsigned t = (ok ? steps : 0) + g; t < (unsigned)length; t += stride) {
+    out_order[(size_t)c * length + t] = -1;
+    out_value[(size_t)c * length + t] = __builtin_nanf("");
+  }
+  if (g == 0) {
+    state[c].best = KNN_EMPTY;
+    state[c].count = 0u;
+    state[c].cur = ok ? seed : -1;
+    if (ok) {
+      const float4 a = vecs[seed];
+      const double2 pa = COSINE ? prep[seed] : make_double2(0.0, 0.0);
+      out_order[(size_t)c * length] = seed;
+      out_value[(size_t)c * length] = chain_value<COSINE>(a, pa, a, pa);
+    }
+  }
+}
+
+/* slot t of every chain.  grid (n_groups, n_chains); workgroup x scans the columns [x * cols, (x + 1) * cols). */
+template <bool COSINE>
+__global__ __launch_bounds__(256) void k_chain_step(const float4 *__restrict__ vecs, const double2 *__restrict__ prep,
+                                                    int n, int cols, int t, int length, int words,
+                                                    chain_state *__restrict__ state, unsigned *__restrict__ bits_all,
+                                                    int32_t *__restrict__ out_order, float *__restrict__ out_value) {
+  __shared__ unsigned long long wmin[4];
+  const int c = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  chain_state *st = state + c;
+  const int cur = st->cur; /* published by the previous launch */
+  if (cur < 0) return;     /* a seed outside [0, n): the whole grid row leaves, nobody arrives */
+  const unsigned *bits = bits_all + (size_t)c * words;
+  float4 a = vecs[cur];
+  double2 pa = COSINE ? prep[cur] : make_double2(0.0, 0.0);
+  asm volatile("" : "+v"(a.x), "+v"(a.y), "+v"(a.z), "+v"(a.w));
+  if (COSINE) asm volatile("" : "+v"(pa.x), "+v"(pa.y));
+  const unsigned c0 = (unsigned)blockIdx.x * (unsigned)cols; /* n_groups * cols < n + cols <= 2^31 + 2^23 */
+  const unsigned c1 = min((unsigned)n, c0 + (unsigned)cols);
+  unsigned long long best = KNN_EMPTY;
+  float bnd = __builtin_inff();
+  for (unsigned j0 = c0 + tid; j0 < c1; j0 += 256u * CHAIN_BATCH) {
+    unsigned played[CHAIN_BATCH];
+    float4 b[CHAIN_BATCH];
+    double2 pb[CHAIN_BATCH];
+#pragma unroll
+    for (int u = 0; u < CHAIN_BATCH; ++u) {
+      const unsigned j = j0 + 256u * u < c1 ? j0 + 256u * u : j0;
+      played[u] = bits[j >> 5];
+      b[u] = vecs[j];
+      pb[u] = COSINE ? prep[j] : make_double2(0.0, 0.0);
+    }
+#pragma unroll
+    for (int u = 0; u < CHAIN_BATCH; ++u) {
+      const unsigned j = j0 + 256u * u;
+      if (j < c1 && !((played[u] >> (j & 31u)) & 1u)) chain_visit<COSINE>(a, pa, b[u], pb[u], (int)j, best, bnd);
+    }
+  }
+  best = chain_wave_min(best);
+  if (lane == 0) wmin[wave] = best;
+  __syncthreads();
+  if (tid != 0) return;
+  const unsigned long long m = min(min(wmin[0], wmin[1]), min(wmin[2], wmin[3]));
+  if (m != KNN_EMPTY) (void)__hip_atomic_fetch_min(&st->best, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  /* the min has been performed before the arrival is counted */
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  const unsigned ticket = __hip_atomic_fetch_add(&st->count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (ticket != gridDim.x - 1u) return;
+  /* every slice's min was performed before its add, and every add before this one returned */
+  const unsigned long long key = __hip_atomic_exchange(&st->best, KNN_EMPTY, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_store(&st->count, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (key == KNN_EMPTY) { /* cannot happen while t < n */
+    __hip_atomic_store(&st->cur, -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return;
+  }
+  const int pick = (int)(unsigned)key;
+  atomicOr(bits_all + (size_t)c * words + (pick >> 5), 1u << (pick & 31));
+  out_order[(size_t)c * length + t] = pick;
+  out_value[(size_t)c * length + t] =
+      chain_value<COSINE>(a, pa, vecs[pick], COSINE ? prep[pick] : make_double2(0.0, 0.0));
+  __hip_atomic_store(&st->cur, pick, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+/* ------------------------------------------------------------------------- */
 /* k_synth: integer-only synthetic PCM, same bytes as oracle/orc_synth.c       */
 
 __device__ __forceinline__ unsigned syn_mix32(unsigned x) {
@@ -2199,6 +2432,9 @@ int blk_configure_device(void) {
                                    hipFuncAttributeMaxDynamicSharedMemorySize, BL_FREQ_LDS_BYTES));
   BL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_freq_scan),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, BL_FREQ_SCAN_LDS_BYTES));
+  for (const void *fn : {reinterpret_cast<const void *>(k_chain<false, true>),
+                         reinterpret_cast<const void *>(k_chain<true, true>)})
+    BL_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, CHAIN_LDS_MAX));
   return BL_OK;
 }
 
@@ -2604,6 +2840,106 @@ int blk_knn(hipStream_t s, const struct force_vector_s *d_vecs, int n, int row_b
   } else {
     if (cosine) knn_launch<1, true>(s, v, prep, n, row_begin, n_rows, k, n_split, cols, part, d_index, d_value);
     else knn_launch<1, false>(s, v, prep, n, row_begin, n_rows, k, n_split, cols, part, d_index, d_value);
+  }
+  BL_HIP_CHECK(hipGetLastError());
+  return BL_OK;
+}
+
+/* Shape of a chain call (see k_chain).  Column split (2) when the corpus is large enough for a step's scan by one
+ * workgroup to cost more than a launch boundary with its two atomics, and the chains are few enough that their
+ * launches do not: the constants are the measured crossovers of DESIGN §4.7 (tools/chain_bench.py).  `force`: 0 = this
+ * rule, 1 / 2 = that shape (tools and tests). */
+#define CHAIN_SPLIT_MIN_N 8192      /* fewer songs: one workgroup per chain */
+#define CHAIN_SPLIT_FILL 2          /* split while n_chains * this <= CUs */
+#define CHAIN_SPLIT_COLS 2048       /* columns of a slice, at least */
+#define CHAIN_SPLIT_MAX_GROUPS 128  /* slices of a chain, at most: every slice costs two atomics on the chain's state */
+#define CHAIN_SPLIT_MAX_CHAINS 65535 /* gridDim.y */
+
+struct chain_plan {
+  int shape;
+  /* 1 */
+  int lb, words;
+  bool lds_bits;
+  size_t lds_bytes;
+  /* 2 */
+  int groups, cols, bit_words;
+};
+
+static chain_plan chain_make_plan(int n, int n_chains, int n_cu, int force) {
+  chain_plan p{};
+  p.shape = (n >= CHAIN_SPLIT_MIN_N && (long long)n_chains * CHAIN_SPLIT_FILL <= n_cu) ? 2 : 1;
+  if (force == 1 || force == 2) p.shape = force;
+  if (n_chains > CHAIN_SPLIT_MAX_CHAINS) p.shape = 1;
+  if (p.shape == 1) {
+    p.lb = n <= 16384 ? 8 : 10;
+    const long long per_lane = ((long long)n + (1 << p.lb) - 1) >> p.lb;
+    p.words = (int)((per_lane + 31) / 32);
+    p.lds_bytes = CHAIN_LDS_HEAD + sizeof(unsigned) * ((size_t)p.words << p.lb);
+    p.lds_bits = p.lds_bytes <= CHAIN_LDS_MAX;
+    if (!p.lds_bits) p.lds_bytes = CHAIN_LDS_HEAD;
+  } else {
+    const long long want = ((long long)n + CHAIN_SPLIT_COLS - 1) / CHAIN_SPLIT_COLS;
+    const long long cap = std::min((long long)CHAIN_SPLIT_MAX_GROUPS, std::max(1LL, 4LL * n_cu / n_chains));
+    const long long groups = std::max(1LL, std::min(want, cap));
+    p.cols = (int)((((long long)n + groups - 1) / groups + 255) / 256 * 256);
+    p.groups = (int)(((long long)n + p.cols - 1) / p.cols);
+    p.bit_words = (int)(((long long)n + 31) / 32);
+  }
+  return p;
+}
+
+int blk_chain_shape(int n, int n_chains, int n_cu, int force) { return chain_make_plan(n, n_chains, n_cu, force).shape; }
+
+static size_t chain_prep_bytes(int n, bool cosine) {
+  return cosine ? (sizeof(double2) * (size_t)n + 255) / 256 * 256 : 0;
+}
+
+size_t blk_chain_scratch_bytes(int n, int n_chains, bool cosine, int n_cu, int force) {
+  const chain_plan p = chain_make_plan(n, n_chains, n_cu, force);
+  size_t bytes = chain_prep_bytes(n, cosine);
+  if (p.shape == 1) {
+    if (!p.lds_bits) bytes += sizeof(unsigned) * ((size_t)p.words << p.lb) * n_chains;
+  } else {
+    bytes += sizeof(chain_state) * (size_t)n_chains + sizeof(unsigned) * (size_t)p.bit_words * n_chains;
+  }
+  return bytes;
+}
+
+template <bool COSINE>
+static void chain_launch(hipStream_t s, const chain_plan &p, const float4 *v, const double2 *prep, void *rest, int n,
+                         const int32_t *d_seeds, int n_chains, int length, int32_t *d_order, float *d_value) {
+  if (p.shape == 1) {
+    unsigned *g_bits = static_cast<unsigned *>(rest);
+    if (p.lds_bits)
+      hipLaunchKernelGGL((k_chain<COSINE, true>), dim3(n_chains), dim3(1 << p.lb), p.lds_bytes, s, v, prep, n, d_seeds,
+                         length, p.lb, p.words, g_bits, d_order, d_value);
+    else
+      hipLaunchKernelGGL((k_chain<COSINE, false>), dim3(n_chains), dim3(1 << p.lb), p.lds_bytes, s, v, prep, n,
+                         d_seeds, length, p.lb, p.words, g_bits, d_order, d_value);
+    return;
+  }
+  chain_state *state = static_cast<chain_state *>(rest);
+  unsigned *bits = reinterpret_cast<unsigned *>(state + n_chains);
+  const int fill = std::max(p.bit_words, length);
+  hipLaunchKernelGGL((k_chain_init<COSINE>), dim3(std::min(256, (fill + 255) / 256), n_chains), dim3(256), 0, s, v,
+                     prep, n, d_seeds, length, p.bit_words, state, bits, d_order, d_value);
+  const int steps = std::min(length, n);
+  for (int t = 1; t < steps; ++t)
+    hipLaunchKernelGGL((k_chain_step<COSINE>), dim3(p.groups, n_chains), dim3(256), 0, s, v, prep, n, p.cols, t,
+                       length, p.bit_words, state, bits, d_order, d_value);
+}
+
+int blk_chain(hipStream_t s, const struct force_vector_s *d_vecs, int n, const int32_t *d_seeds, int n_chains,
+              int length, bool cosine, int n_cu, int force, void *d_scratch, int32_t *d_order, float *d_value) {
+  const float4 *v = reinterpret_cast<const float4 *>(d_vecs);
+  const chain_plan p = chain_make_plan(n, n_chains, n_cu, force);
+  double2 *prep = cosine ? static_cast<double2 *>(d_scratch) : nullptr;
+  void *rest = static_cast<char *>(d_scratch) + chain_prep_bytes(n, cosine);
+  if (cosine) {
+    hipLaunchKernelGGL(k_knn_prep, dim3((n + 255) / 256), dim3(256), 0, s, v, n, prep);
+    chain_launch<true>(s, p, v, prep, rest, n, d_seeds, n_chains, length, d_order, d_value);
+  } else {
+    chain_launch<false>(s, p, v, prep, rest, n, d_seeds, n_chains, length, d_order, d_value);
   }
   BL_HIP_CHECK(hipGetLastError());
   return BL_OK;

@@ -110,6 +110,14 @@ int blk_playlist(hipStream_t s, const struct force_vector_s *d_vecs, int n, int 
 size_t blk_knn_scratch_bytes(int n, int n_rows, int k, bool cosine, int n_cu);
 int blk_knn(hipStream_t s, const struct force_vector_s *d_vecs, int n, int row_begin, int n_rows, int k,
             bool cosine, int n_cu, void *d_scratch, int32_t *d_index, float *d_value);
+/* song-to-song chains (bl_amd_chain_device).  blk_chain_shape: 1 = one workgroup per chain, 2 = column split with one
+ * launch per step; force: 0 = the launch layer's rule, 1 / 2 = that shape.  d_scratch: at least
+ * blk_chain_scratch_bytes(...) bytes for the same (n, n_chains, cosine, n_cu, force), 256-byte aligned; it is
+ * re-initialised by every call. */
+int blk_chain_shape(int n, int n_chains, int n_cu, int force);
+size_t blk_chain_scratch_bytes(int n, int n_chains, bool cosine, int n_cu, int force);
+int blk_chain(hipStream_t s, const struct force_vector_s *d_vecs, int n, const int32_t *d_seeds, int n_chains,
+              int length, bool cosine, int n_cu, int force, void *d_scratch, int32_t *d_order, float *d_value);
 /* out[i] = (int16)(in[i] >> 16): the same-rate S32 -> S16 narrowing */
 int blk_narrow_s32(hipStream_t s, const int32_t *d_in, int16_t *d_out, size_t n, int n_cu);
 /* out[order[i]] = in[i] for 16-byte force vectors (shard-major -> caller order) */

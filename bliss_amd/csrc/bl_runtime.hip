@@ -129,7 +129,7 @@ void ctx_release(bl_amd_ctx *c) {
   prof_collect(c);
   bl_buf *bufs[] = {&c->songs,   &c->stats,   &c->hist, &c->spectrum, &c->energies, &c->lc,
                     &c->results, &c->misc,    &c->arena[0], &c->arena[1], &c->arena22[0], &c->arena22[1],
-                    &c->rs_songs, &c->rs_bank, &c->mx_my, &c->mx_gath, &c->mx_all, &c->mx_order, &c->mx_rows, &c->knn};
+                    &c->rs_songs, &c->rs_bank, &c->mx_my, &c->mx_gath, &c->mx_all, &c->mx_order, &c->mx_rows, &c->knn, &c->chain};
   for (bl_buf *b : bufs) release_buf(*b);
   for (int k = 0; k < 2; ++k) {
     unregister_wave(c, k);
@@ -911,6 +911,83 @@ int bl_amd_knn_host(const struct force_vector_s *h_vecs, int n, int k, int metri
   if (di) (void)hipFree(di);
   if (dd) (void)hipFree(dd);
   return rc;
+}
+
+/* song-to-song chains (bl_kernels.hip k_chain, k_chain_step): arguments first, then the workspace like the kNN call */
+static std::atomic<int> g_chain_force{BL_AMD_CHAIN_AUTO};
+
+static bool chain_args_ok(const void *vecs, int n, const void *seeds, int n_chains, int length, int metric,
+                          const void *order, const void *value) {
+  return vecs && seeds && order && value && n > 0 && n_chains > 0 && length > 0 &&
+         (metric == BL_AMD_KNN_DISTANCE || metric == BL_AMD_KNN_COSINE);
+}
+
+int bl_amd_ctx_chain_device(bl_amd_ctx *c, const struct force_vector_s *d_vecs, int n, const int32_t *d_seeds,
+                            int n_chains, int length, int metric, int32_t *d_order, float *d_value, void *stream) {
+  if (!chain_args_ok(d_vecs, n, d_seeds, n_chains, length, metric, d_order, d_value) || !c) return BL_UNEXPECTED;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DevGuard dg(c->device);
+  if (!dg.ok) return BL_UNEXPECTED;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const bool cosine = metric == BL_AMD_KNN_COSINE;
+  const int force = g_chain_force.load();
+  if (c->ws_used) BL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_ws, 0));
+  if (blr_ensure(c->chain, blk_chain_scratch_bytes(n, n_chains, cosine, c->n_cu, force)) != BL_OK) return BL_UNEXPECTED;
+  if (blk_chain(s, d_vecs, n, d_seeds, n_chains, length, cosine, c->n_cu, force, c->chain.p, d_order, d_value) != BL_OK)
+    return BL_UNEXPECTED;
+  BL_HIP_CHECK(hipEventRecord(c->ev_ws, s));
+  c->ws_used = true;
+  return BL_OK;
+}
+
+int bl_amd_chain_device(const struct force_vector_s *d_vecs, int n, const int32_t *d_seeds, int n_chains, int length,
+                        int metric, int32_t *d_order, float *d_value, void *stream) {
+  if (!chain_args_ok(d_vecs, n, d_seeds, n_chains, length, metric, d_order, d_value)) return BL_UNEXPECTED;
+  return bl_amd_ctx_chain_device(blr_default_ctx(), d_vecs, n, d_seeds, n_chains, length, metric, d_order, d_value,
+                                 stream);
+}
+
+int bl_amd_chain_host(const struct force_vector_s *h_vecs, int n, const int32_t *h_seeds, int n_chains, int length,
+                      int metric, int32_t *h_order, float *h_value) {
+  if (!chain_args_ok(h_vecs, n, h_seeds, n_chains, length, metric, h_order, h_order /* h_value may be NULL */))
+    return BL_UNEXPECTED;
+  for (int c = 0; c < n_chains; ++c)
+    if (h_seeds[c] < 0 || h_seeds[c] >= n) return BL_UNEXPECTED;
+  bl_amd_ctx *c = blr_default_ctx();
+  if (!c) return BL_UNEXPECTED;
+  DevGuard dg(c->device);
+  if (!dg.ok) return BL_UNEXPECTED;
+  const size_t out = (size_t)n_chains * length;
+  void *dv = nullptr, *ds = nullptr, *di = nullptr, *dd = nullptr;
+  int rc = BL_UNEXPECTED;
+  if (hipMalloc(&dv, sizeof(struct force_vector_s) * (size_t)n) == hipSuccess &&
+      hipMalloc(&ds, sizeof(int32_t) * (size_t)n_chains) == hipSuccess &&
+      hipMalloc(&di, sizeof(int32_t) * out) == hipSuccess && hipMalloc(&dd, sizeof(float) * out) == hipSuccess &&
+      hipMemcpy(dv, h_vecs, sizeof(struct force_vector_s) * (size_t)n, hipMemcpyHostToDevice) == hipSuccess &&
+      hipMemcpy(ds, h_seeds, sizeof(int32_t) * (size_t)n_chains, hipMemcpyHostToDevice) == hipSuccess &&
+      bl_amd_chain_device(static_cast<struct force_vector_s *>(dv), n, static_cast<int32_t *>(ds), n_chains, length,
+                          metric, static_cast<int32_t *>(di), static_cast<float *>(dd), nullptr) == BL_OK &&
+      hipMemcpy(h_order, di, sizeof(int32_t) * out, hipMemcpyDeviceToHost) == hipSuccess &&
+      (!h_value || hipMemcpy(h_value, dd, sizeof(float) * out, hipMemcpyDeviceToHost) == hipSuccess))
+    rc = BL_OK;
+  if (dv) (void)hipFree(dv);
+  if (ds) (void)hipFree(ds);
+  if (di) (void)hipFree(di);
+  if (dd) (void)hipFree(dd);
+  return rc;
+}
+
+int bl_amd_chain_shape(int n, int n_chains) {
+  if (n < 1 || n_chains < 1) return BL_UNEXPECTED;
+  bl_amd_ctx *c = blr_default_ctx();
+  if (!c) return BL_UNEXPECTED;
+  return blk_chain_shape(n, n_chains, c->n_cu, g_chain_force.load());
+}
+
+int bl_amd_chain_force_shape(int shape) {
+  if (shape != BL_AMD_CHAIN_AUTO && shape != BL_AMD_CHAIN_PER_CHAIN && shape != BL_AMD_CHAIN_SPLIT)
+    return BL_UNEXPECTED;
+  return g_chain_force.exchange(shape);
 }
 
 int bl_amd_selftest_sqrt(uint64_t counts[3]) {

@@ -278,6 +278,34 @@ int bl_amd_knn_device(const struct force_vector_s *d_vecs, int n, int row_begin,
 int bl_amd_knn_host(const struct force_vector_s *h_vecs, int n, int k, int metric, int32_t *h_index,
                     float *h_value);
 
+/* Song-to-song chains (continuous play): chain c starts at song d_seeds[c]; slot t + 1 holds the song nearest to the
+ * song of slot t among the songs not yet in chain c.  d_order / d_value: n_chains * length, row-major.
+ * d_order[c][0] = d_seeds[c].  d_value[c][t] = the matrix entry M[d_order[c][t-1]][d_order[c][t]] by its bits
+ * (t = 0: M[seed][seed]), M = bl_distance (BL_AMD_KNN_DISTANCE, nearest = smallest) or bl_cosine_similarity
+ * (BL_AMD_KNN_COSINE, nearest = largest).  "Nearest" is bl_amd_knn's order: the f32 value, +0 = -0, NaN after
+ * every number, ties by the smaller song index.  Exact duplicates of the current song are ordinary candidates.
+ * If length > n the trailing slots hold -1 and a NaN.  A seed outside [0, n) gives a row of -1 / NaN.
+ * Chains are independent of each other: the result of a chain does not depend on n_chains or on the other seeds.
+ * n, n_chains, length >= 1.  Asynchronous on `stream`; no allocation, copy or synchronisation inside once the
+ * context's workspace is large enough.  Calls of one context are ordered on the device like its batches. */
+int bl_amd_chain_device(const struct force_vector_s *d_vecs, int n, const int32_t *d_seeds, int n_chains,
+                        int length, int metric, int32_t *d_order, float *d_value, void *stream);
+int bl_amd_ctx_chain_device(bl_amd_ctx *ctx, const struct force_vector_s *d_vecs, int n, const int32_t *d_seeds,
+                            int n_chains, int length, int metric, int32_t *d_order, float *d_value, void *stream);
+/* Host pointers, blocking.  Seeds are checked first: one outside [0, n) returns BL_UNEXPECTED and writes nothing.
+ * h_value may be NULL. */
+int bl_amd_chain_host(const struct force_vector_s *h_vecs, int n, const int32_t *h_seeds, int n_chains,
+                      int length, int metric, int32_t *h_order, float *h_value);
+/* The launch shape a chain call of (n, n_chains) takes on the calling thread's device: BL_AMD_CHAIN_PER_CHAIN (one
+ * workgroup per chain) or BL_AMD_CHAIN_SPLIT (columns split over workgroups, one launch per step); BL_UNEXPECTED
+ * without a device.  The result of a call never depends on it.  bl_amd_chain_force_shape pins the shape for the
+ * whole process (BL_AMD_CHAIN_AUTO undoes that) and returns the previous setting: for measurements and tests. */
+#define BL_AMD_CHAIN_AUTO 0
+#define BL_AMD_CHAIN_PER_CHAIN 1
+#define BL_AMD_CHAIN_SPLIT 2
+int bl_amd_chain_shape(int n, int n_chains);
+int bl_amd_chain_force_shape(int shape);
+
 /* Integer-only synthetic PCM (the benchmark corpus of BASELINE.json),
  * generated in place on the device: song i = seed_base + i, written at
  * h_desc[i].pcm_offset.  Byte-identical to oracle/orc_synth.c. */
