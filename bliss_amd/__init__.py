@@ -11,6 +11,7 @@ from . import distance, version
 from .batch import (Context, DeviceCorpus, analyze_batch_host, analyze_files, analyze_batch_host_rate, analyze_batch_host_s32,
                     analyze_corpus_multi, analyze_corpus_multi_device, chain, chain_device, cosine_matrix, distance_matrix, knn, knn_device,
                     playlist,
+                    duplicate_groups, duplicate_groups_device, radius, radius_device,
                     resample_batch_device,
                     resample_host, results_to_numpy)
 from .bl_song import bl_song
@@ -19,6 +20,7 @@ __all__ = ["_lib", "load", "BlSong", "ForceVector", "EnvelopeResult", "SongDesc"
            "BL_LOUD", "BL_CALM", "BL_UNKNOWN", "BL_UNEXPECTED", "BL_OK", "DeviceCorpus",
            "analyze_batch_host", "analyze_files", "analyze_batch_host_rate", "analyze_batch_host_s32", "analyze_corpus_multi", "analyze_corpus_multi_device", "Context",
            "distance_matrix", "cosine_matrix", "results_to_numpy", "playlist", "knn", "knn_device", "chain", "chain_device",
+           "radius", "radius_device", "duplicate_groups", "duplicate_groups_device",
            "resample_host", "resample_batch_device", "bl_song", "distance", "version"]
 
 

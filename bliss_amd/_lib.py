@@ -132,6 +132,21 @@ SYMBOLS = {
                                     _P(C.c_float)]),
     "bl_amd_chain_shape": (C.c_int, [C.c_int, C.c_int]),
     "bl_amd_chain_force_shape": (C.c_int, [C.c_int]),
+    "bl_amd_radius_bound": (C.c_float, [C.c_float]),
+    "bl_amd_radius_count_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p,
+                                             C.c_void_p]),
+    "bl_amd_ctx_radius_count_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                                 C.c_void_p, C.c_void_p]),
+    "bl_amd_radius_fill_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bl_amd_ctx_radius_fill_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bl_amd_radius_host": (C.c_int, [_P(ForceVector), C.c_int, C.c_int, C.c_float, _P(C.c_int64), _P(_P(C.c_int32)),
+                                     _P(_P(C.c_float))]),
+    "bl_amd_groups_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
+    "bl_amd_ctx_groups_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p,
+                                           C.c_void_p]),
+    "bl_amd_groups_host": (C.c_int, [_P(ForceVector), C.c_int, C.c_int, C.c_float, _P(C.c_int32)]),
     "bl_amd_synth_pcm_device": (C.c_int, [C.c_void_p, _P(SongDesc), C.c_int, C.c_uint32, C.c_uint32, C.c_void_p]),
     "bl_amd_set_fir_mode": (C.c_int, [C.c_int]),
     "bl_amd_fir_mode": (C.c_int, []),

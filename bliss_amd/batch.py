@@ -474,3 +474,118 @@ def chain_device(d_vecs, d_seeds, length, metric="distance", stream=None):
         if s is not None:
             sd.record_stream(cur)   # the uploaded seeds are freed when this returns
     return order, value
+
+
+def _radius_check(r, metric, shape):
+    """(metric code, the radius as a Python float that is an exact f32)"""
+    if isinstance(r, bool) or not isinstance(r, (int, float, np.integer, np.floating)):
+        raise ValueError(f"the radius must be a real number, got {r!r}")
+    if metric not in _KNN_METRICS:
+        raise ValueError(f"metric must be one of {sorted(_KNN_METRICS)}, got {metric!r}")
+    if len(shape) != 2 or shape[1] != 4 or shape[0] < 1:
+        raise ValueError(f"force vectors must have shape (n, 4) with n >= 1, got {tuple(shape)}")
+    with np.errstate(over="ignore"):
+        r32 = np.float32(r)
+    if np.isnan(r32):
+        raise ValueError("the radius must not be NaN")
+    return _KNN_METRICS[metric], float(r32)
+
+
+def _device_vecs_check(d_vecs):
+    import torch
+    if d_vecs.dtype != torch.float32 or not d_vecs.is_cuda or not d_vecs.is_contiguous():
+        raise ValueError("d_vecs must be a contiguous float32 CUDA tensor")
+
+
+def radius(vecs, r, metric="distance"):
+    """The songs within radius r of every song of (n, 4) force vectors, as compressed sparse row lists:
+    (offsets int64 (n + 1,), index int32 (total,), value float32 (total,)); row i is index[offsets[i]:offsets[i + 1]],
+    in ascending song index, and never lists i.  Within means bl_distance <= r ("distance") or bl_cosine_similarity
+    >= r ("cosine") on the f32 matrix entry, whose bits `value` holds; a NaN entry is never within."""
+    v = np.ascontiguousarray(vecs, dtype=np.float32)
+    m, r = _radius_check(r, metric, v.shape)
+    lib = _lib.load()
+    n = v.shape[0]
+    offsets = np.empty(n + 1, dtype=np.int64)
+    p_index, p_value = C.POINTER(C.c_int32)(), C.POINTER(C.c_float)()
+    rc = lib.bl_amd_radius_host(v.ctypes.data_as(C.POINTER(_lib.ForceVector)), n, m, r,
+                                offsets.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(p_index), C.byref(p_value))
+    _check(rc, "bl_amd_radius_host")
+    libc = C.CDLL(None)
+    libc.free.argtypes = [C.c_void_p]
+    libc.free.restype = None
+    try:
+        total = int(offsets[n])
+        index = np.ctypeslib.as_array(p_index, shape=(total,)).copy() if total else np.empty(0, dtype=np.int32)
+        value = np.ctypeslib.as_array(p_value, shape=(total,)).copy() if total else np.empty(0, dtype=np.float32)
+    finally:
+        libc.free(p_index)
+        libc.free(p_value)
+    return offsets, index, value
+
+
+def radius_device(d_vecs, r, metric="distance", row_begin=0, n_rows=None, values=True, stream=None):
+    """radius() for the queries d_vecs[row_begin:row_begin + n_rows] against all of d_vecs, a contiguous float32
+    (n, 4) CUDA tensor.  Returns (offsets int64 (n_rows + 1,), index int32 (total,), value float32 (total,) or None
+    without `values`) as CUDA tensors on its device.  Count and fill run on `stream` (default: the current stream of
+    that device); between them the total is read back, which is the one synchronisation."""
+    import torch
+    m, r = _radius_check(r, metric, tuple(d_vecs.shape))
+    _device_vecs_check(d_vecs)
+    n = d_vecs.shape[0]
+    if n_rows is None:
+        n_rows = n - row_begin
+    if not (0 <= row_begin < n and 1 <= n_rows <= n - row_begin):
+        raise ValueError(f"rows [{row_begin}, {row_begin + n_rows}) are not inside [0, {n})")
+    lib = _lib.load()
+    v = d_vecs
+    cur = stream if stream is not None else torch.cuda.current_stream(v.device)
+    idx = v.device.index or 0
+    with torch.cuda.device(idx), torch.cuda.stream(cur):
+        s = C.c_void_p(cur.cuda_stream)
+        offsets = torch.empty(n_rows + 1, dtype=torch.int64, device=v.device)
+        _check(lib.bl_amd_init(idx), "bl_amd_init")
+        _check(lib.bl_amd_radius_count_device(v.data_ptr(), n, int(row_begin), int(n_rows), m, r, offsets.data_ptr(), s),
+               "bl_amd_radius_count_device")
+        total = int(offsets[-1].item())
+        # one slot at least: an empty result still goes through the fill call, which then writes nothing
+        index = torch.empty(max(total, 1), dtype=torch.int32, device=v.device)
+        value = torch.empty(max(total, 1), dtype=torch.float32, device=v.device) if values else None
+        _check(lib.bl_amd_radius_fill_device(v.data_ptr(), n, int(row_begin), int(n_rows), m, r, offsets.data_ptr(),
+                                             index.data_ptr(), value.data_ptr() if values else None, s),
+               "bl_amd_radius_fill_device")
+    return offsets, index[:total], value[:total] if values else None
+
+
+def duplicate_groups(vecs, r, metric="distance"):
+    """A group label per song of (n, 4) force vectors, int32 (n,): the smallest song index among the songs connected
+    to it by steps of at most radius r (bl_distance <= r, or bl_cosine_similarity >= r), as radius() defines "within".
+    The same recording under two names gets one label; a song with no neighbour is its own group."""
+    v = np.ascontiguousarray(vecs, dtype=np.float32)
+    m, r = _radius_check(r, metric, v.shape)
+    lib = _lib.load()
+    n = v.shape[0]
+    group = np.empty(n, dtype=np.int32)
+    rc = lib.bl_amd_groups_host(v.ctypes.data_as(C.POINTER(_lib.ForceVector)), n, m, r,
+                                group.ctypes.data_as(C.POINTER(C.c_int32)))
+    _check(rc, "bl_amd_groups_host")
+    return group
+
+
+def duplicate_groups_device(d_vecs, r, metric="distance", stream=None):
+    """duplicate_groups() on the device: d_vecs a contiguous float32 (n, 4) CUDA tensor; returns an int32 (n,) CUDA
+    tensor on its device, asynchronously on `stream` (default: the current stream of that device)."""
+    import torch
+    m, r = _radius_check(r, metric, tuple(d_vecs.shape))
+    _device_vecs_check(d_vecs)
+    lib = _lib.load()
+    v = d_vecs
+    n = v.shape[0]
+    cur = stream if stream is not None else torch.cuda.current_stream(v.device)
+    idx = v.device.index or 0
+    with torch.cuda.device(idx), torch.cuda.stream(cur):
+        group = torch.empty(n, dtype=torch.int32, device=v.device)
+        _check(lib.bl_amd_init(idx), "bl_amd_init")
+        _check(lib.bl_amd_groups_device(v.data_ptr(), n, m, r, group.data_ptr(), C.c_void_p(cur.cuda_stream)),
+               "bl_amd_groups_device")
+    return group

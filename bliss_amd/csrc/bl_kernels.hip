@@ -27,6 +27,8 @@
  *   k_knn, k_knn_merge  the k nearest songs of each query (bl_distance / bl_cosine_similarity
  *                  values), never the matrix  ref python/examples/make_m3u_playlist.py:62-72
  *   k_chain, k_chain_step  song-to-song chains: every next song the nearest unplayed one (k_knn's values and order)
+ *   k_radius_count, k_radius_fill  the songs within a radius of each query as CSR lists (same values), never the matrix
+ *   k_groups_union  duplicate groups: connected components of the within-radius graph, union-find on the output
  *   k_synth        integer synthetic PCM (benchmark corpus)
  */
 #include <hip/hip_runtime.h>
@@ -2288,6 +2290,282 @@ __global__ __launch_bounds__(256) void k_chain_step(const float4 *__restrict__ v
 }
 
 /* ------------------------------------------------------------------------- */
+/* k_radius_*, k_groups_*: fixed-radius neighbourhoods (bl_amd_radius_*, bl_amd_groups_*) */
+/* Song j is within the radius of query i when the matrix entry passes a plain f32 compare: bl_distance <= radius or
+ * bl_cosine_similarity >= radius.  The distance is decided on the squared sum: the correctly rounded root is monotone,
+ * so rn(sqrt(s)) <= radius exactly when s <= s_max, the largest f32 whose rounded root is <= radius, which the host
+ * computes once per call (bl_amd_radius_bound) — no root in the count pass, and a NaN sum fails the compare as the NaN
+ * entry would.  The cosine compares knn_cos's f32.  `bound` is s_max or the cosine radius.
+ *
+ * Layout: k_knn's.  A wave owns RAD_QPW queries (wave-uniform vectors in VGPRs) and walks 64 candidate columns per
+ * step in ascending order; a query's hits of a step are one ballot, from which the tail lanes of the last step and
+ * the query's own column are masked off as scalars.  Count adds the popcount; fill writes the hit lanes at the row's
+ * running base plus their rank among the hits, which is ascending song order.  With few query rows the columns are
+ * split over blockIdx.y: a split's count goes to part[row * n_split + split], and fill starts a split at the row's
+ * offset plus the counts of the splits before it.  Every count is an integer function of the predicate alone, so the
+ * result depends neither on the row range nor on the split. */
+#define RAD_QPW 8   /* queries per wave */
+#define RAD_WAVES 4 /* waves per workgroup */
+
+template <bool COSINE>
+__device__ __forceinline__ void radius_load_queries(const float4 *__restrict__ vecs, const double2 *__restrict__ prep,
+                                                    int row0, int nq, float4 (&a)[RAD_QPW], double2 (&pa)[RAD_QPW]) {
+#pragma unroll
+  for (int q = 0; q < RAD_QPW; ++q) {
+    const int row = row0 + min(q, nq - 1);
+    a[q] = vecs[row];
+    pa[q] = COSINE ? prep[row] : make_double2(0.0, 0.0);
+    /* in VGPRs, as in k_knn: as scalars they crowd the SGPR file in the candidate loop */
+    asm volatile("" : "+v"(a[q].x), "+v"(a[q].y), "+v"(a[q].z), "+v"(a[q].w));
+    if (COSINE) asm volatile("" : "+v"(pa[q].x), "+v"(pa[q].y));
+  }
+}
+
+/* the compared quantity of the pair: the squared sum (distance) or the cosine itself */
+template <bool COSINE>
+__device__ __forceinline__ float radius_measure(const float4 a, const double2 pa, const float4 b, const double2 pb) {
+  return COSINE ? knn_cos(a, pa, b, pb) : bl_dist_sq(a, b);
+}
+template <bool COSINE> __device__ __forceinline__ bool radius_within(float m, float bound) {
+  return COSINE ? m >= bound : m <= bound;
+}
+
+/* the hit lanes of query `row` among the columns j0 .. j0 + 63; vmask: the lanes whose column exists */
+template <bool COSINE>
+__device__ __forceinline__ unsigned long long radius_hits(float m, float bound, unsigned long long vmask, int row, int j0) {
+  unsigned long long hits = __ballot(radius_within<COSINE>(m, bound)) & vmask;
+  const unsigned self = (unsigned)(row - j0);
+  if (self < 64u) hits &= ~(1ull << self);
+  return hits;
+}
+
+/* grid (query tiles of RAD_WAVES * RAD_QPW rows, n_split); part[row * n_split + split] = hits of the split */
+template <bool COSINE>
+__global__ __launch_bounds__(256) void k_radius_count(const float4 *__restrict__ vecs, const double2 *__restrict__ prep,
+                                                      int n, int row_begin, int n_rows, int cols, int n_split,
+                                                      float bound, unsigned *__restrict__ part) {
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int r0 = (blockIdx.x * RAD_WAVES + wave) * RAD_QPW;
+  if (r0 >= n_rows) return;
+  const int nq = min(RAD_QPW, n_rows - r0);
+  const int c0 = blockIdx.y * cols, c1 = min(n, c0 + cols);
+  float4 a[RAD_QPW];
+  double2 pa[RAD_QPW];
+  radius_load_queries<COSINE>(vecs, prep, row_begin + r0, nq, a, pa);
+  unsigned cnt[RAD_QPW];
+#pragma unroll
+  for (int q = 0; q < RAD_QPW; ++q) cnt[q] = 0;
+  int jn = min(c0 + lane, c1 - 1);
+  float4 b = vecs[jn];
+  double2 pb = COSINE ? prep[jn] : make_double2(0.0, 0.0);
+  for (int j0 = c0; j0 < c1; j0 += 64) {
+    const float4 bc = b;
+    const double2 pbc = pb;
+    jn = min(j0 + 64 + lane, c1 - 1); /* the next step's column, fetched under this step's arithmetic */
+    b = vecs[jn];
+    if (COSINE) pb = prep[jn];
+    const unsigned long long vmask = __ballot(j0 + lane < c1);
+#pragma unroll
+    for (int q = 0; q < RAD_QPW; ++q) /* rows past nq repeat the last query; their counts are not stored */
+      cnt[q] += __popcll(radius_hits<COSINE>(radius_measure<COSINE>(a[q], pa[q], bc, pbc), bound, vmask,
+                                             row_begin + r0 + q, j0));
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int q = 0; q < RAD_QPW; ++q)
+      if (q < nq) part[(size_t)(r0 + q) * n_split + blockIdx.y] = cnt[q];
+  }
+}
+
+/* offset[r] = hits of the rows before r, offset[n_rows] = the total, from the rows' counts: one workgroup, thread t
+ * owns a contiguous run of rows, the runs' sums are scanned through LDS, int64 throughout */
+__global__ __launch_bounds__(1024) void k_radius_offsets(const unsigned *__restrict__ counts, int n_rows,
+                                                         long long *__restrict__ offset) {
+  __shared__ long long run_sum[1024];
+  const int t = threadIdx.x;
+  const long long per = ((long long)n_rows + 1023) / 1024;
+  const long long r_lo = min((long long)t * per, (long long)n_rows), r_hi = min(r_lo + per, (long long)n_rows);
+  long long sum = 0;
+  for (long long r = r_lo; r < r_hi; ++r) sum += counts[r];
+  run_sum[t] = sum;
+  __syncthreads();
+  for (int d = 1; d < 1024; d <<= 1) { /* inclusive scan */
+    const long long add = t >= d ? run_sum[t - d] : 0;
+    __syncthreads();
+    run_sum[t] += add;
+    __syncthreads();
+  }
+  long long run = run_sum[t] - sum;
+  for (long long r = r_lo; r < r_hi; ++r) {
+    offset[r] = run;
+    run += counts[r];
+  }
+  if (t == 1023) offset[n_rows] = run_sum[1023];
+}
+
+/* column split, one wave per row: the row's per-split counts into the exclusive prefix fill starts each split at,
+ * and their sum into rowsum[r] */
+__global__ __launch_bounds__(256) void k_radius_split_scan(unsigned *__restrict__ part, int n_rows, int n_split,
+                                                           unsigned *__restrict__ rowsum) {
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= n_rows) return;
+  unsigned *p = part + (size_t)r * n_split;
+  unsigned run = 0;
+  for (int s0 = 0; s0 < n_split; s0 += 64) {
+    const int s = s0 + lane;
+    const unsigned c = s < n_split ? p[s] : 0u;
+    unsigned x = c;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const unsigned y = __shfl_up(x, d);
+      if (lane >= d) x += y;
+    }
+    if (s < n_split) p[s] = run + x - c;
+    run += __shfl(x, 63);
+  }
+  if (lane == 0) rowsum[r] = run;
+}
+
+/* grid as k_radius_count; row r's hits of split y go to out_*[offset[r] + before[r * n_split + y] ...] in ascending
+ * song order (before == nullptr: one split).  The stored value is computed from the measure that decided the hit. */
+template <bool COSINE, bool VALUES>
+__global__ __launch_bounds__(256) void k_radius_fill(const float4 *__restrict__ vecs, const double2 *__restrict__ prep,
+                                                     int n, int row_begin, int n_rows, int cols, int n_split, float bound,
+                                                     const unsigned *__restrict__ before,
+                                                     const long long *__restrict__ offset, int32_t *__restrict__ out_index,
+                                                     float *__restrict__ out_value) {
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int r0 = (blockIdx.x * RAD_WAVES + wave) * RAD_QPW;
+  if (r0 >= n_rows) return;
+  const int nq = min(RAD_QPW, n_rows - r0);
+  const int c0 = blockIdx.y * cols, c1 = min(n, c0 + cols);
+  float4 a[RAD_QPW];
+  double2 pa[RAD_QPW];
+  radius_load_queries<COSINE>(vecs, prep, row_begin + r0, nq, a, pa);
+  long long base[RAD_QPW];
+#pragma unroll
+  for (int q = 0; q < RAD_QPW; ++q) {
+    const size_t r = (size_t)(r0 + min(q, nq - 1));
+    base[q] = offset[r] + (before ? (long long)before[r * n_split + blockIdx.y] : 0);
+  }
+  const unsigned long long below = (1ull << lane) - 1ull;
+  int jn = min(c0 + lane, c1 - 1);
+  float4 b = vecs[jn];
+  double2 pb = COSINE ? prep[jn] : make_double2(0.0, 0.0);
+  for (int j0 = c0; j0 < c1; j0 += 64) {
+    const float4 bc = b;
+    const double2 pbc = pb;
+    jn = min(j0 + 64 + lane, c1 - 1);
+    b = vecs[jn];
+    if (COSINE) pb = prep[jn];
+    const unsigned long long vmask = __ballot(j0 + lane < c1);
+#pragma unroll
+    for (int q = 0; q < RAD_QPW; ++q) {
+      if (q >= nq) break;
+      const float m = radius_measure<COSINE>(a[q], pa[q], bc, pbc);
+      const unsigned long long hits = radius_hits<COSINE>(m, bound, vmask, row_begin + r0 + q, j0);
+      if (hits == 0) continue;
+      if ((hits >> lane) & 1ull) {
+        const long long pos = base[q] + __popcll(hits & below);
+        out_index[pos] = j0 + lane;
+        if (VALUES) out_value[pos] = COSINE ? m : knn_root(m);
+      }
+      base[q] += __popcll(hits);
+    }
+  }
+}
+
+/* Duplicate groups: the weakly connected components of the "within the radius" graph, by a lock-free union-find on
+ * the output itself.  parent[x] <= x always; only roots (parent[r] == r) are hooked, the larger root under the
+ * smaller by a compare-and-swap that is retried with the value found when it loses, so the root of a tree is the
+ * smallest index of its component.  Reads are agent-scope atomic loads: a value read was the entry's at some time,
+ * and an entry that has stopped being a root never becomes one again, so an out-of-date read costs a retry, never
+ * a wrong hook.  Path halving stores an ancestor over an ancestor, which keeps both properties. */
+__device__ __forceinline__ int groups_load(const int *p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__device__ __forceinline__ int groups_find(int *parent, int x) {
+  for (;;) {
+    const int p = groups_load(parent + x);
+    if (p == x) return x;
+    const int g = groups_load(parent + p);
+    if (g == p) return p;
+    __hip_atomic_store(parent + x, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    x = g;
+  }
+}
+
+__device__ __forceinline__ void groups_union(int *parent, int x, int y) {
+  /* two entries that hold the same value are in that song's tree: nothing to do (the dense case ends here) */
+  if (groups_load(parent + x) == groups_load(parent + y)) return;
+  for (;;) {
+    x = groups_find(parent, x);
+    y = groups_find(parent, y);
+    if (x == y) return;
+    const int hi = max(x, y), lo = min(x, y);
+    int seen = hi;
+    if (__hip_atomic_compare_exchange_strong(parent + hi, &seen, lo, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                             __HIP_MEMORY_SCOPE_AGENT))
+      return;
+    x = seen; /* hi was hooked under `seen` in between: join that tree with lo's */
+    y = lo;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_groups_init(int *__restrict__ parent, int n) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) parent[i] = i;
+}
+
+/* grid as k_radius_count over all n rows.  Both matrices are bitwise symmetric (bl_dist_sq squares differences;
+ * knn_cos multiplies commutatively and adds in component order), so a wave visits the columns above its rows only. */
+template <bool COSINE>
+__global__ __launch_bounds__(256) void k_groups_union(const float4 *__restrict__ vecs, const double2 *__restrict__ prep,
+                                                      int n, int cols, float bound, int *parent) {
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int r0 = (blockIdx.x * RAD_WAVES + wave) * RAD_QPW;
+  if (r0 >= n) return;
+  const int nq = min(RAD_QPW, n - r0);
+  const int c1 = min(n, (int)blockIdx.y * cols + cols);
+  const int c0 = max((int)blockIdx.y * cols, (r0 + 1) & ~63); /* cols is a multiple of 64 */
+  if (c0 >= c1) return;
+  float4 a[RAD_QPW];
+  double2 pa[RAD_QPW];
+  radius_load_queries<COSINE>(vecs, prep, r0, nq, a, pa);
+  for (int j0 = c0; j0 < c1; j0 += 64) {
+    const int j = j0 + lane;
+    const int jj = min(j, c1 - 1);
+    const float4 b = vecs[jj];
+    const double2 pb = COSINE ? prep[jj] : make_double2(0.0, 0.0);
+#pragma unroll
+    for (int q = 0; q < RAD_QPW; ++q) {
+      if (q >= nq) break;
+      const int row = r0 + q;
+      if (j < c1 && j > row && radius_within<COSINE>(radius_measure<COSINE>(a[q], pa[q], b, pb), bound))
+        groups_union(parent, row, j);
+    }
+  }
+}
+
+/* after the union launch: every entry to its root */
+__global__ __launch_bounds__(256) void k_groups_compress(int *parent, int n) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  int x = i;
+  for (;;) {
+    const int p = groups_load(parent + x);
+    if (p == x) break;
+    x = p;
+  }
+  __hip_atomic_store(parent + i, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+/* ------------------------------------------------------------------------- */
 /* k_synth: integer-only synthetic PCM, same bytes as oracle/orc_synth.c       */
 
 __device__ __forceinline__ unsigned syn_mix32(unsigned x) {
@@ -2941,6 +3219,124 @@ int blk_chain(hipStream_t s, const struct force_vector_s *d_vecs, int n, const i
   } else {
     chain_launch<false>(s, p, v, prep, rest, n, d_seeds, n_chains, length, d_order, d_value);
   }
+  BL_HIP_CHECK(hipGetLastError());
+  return BL_OK;
+}
+
+/* Column split of a radius call: one split while the query waves alone fill the chip (16 per CU), else enough splits
+ * to reach that many waves, each of at least 1 024 columns.  cols is a multiple of 64. */
+static void radius_plan(int n, int n_rows, int n_cu, int &n_split, int &cols) {
+  const long long waves = ((long long)n_rows + RAD_QPW - 1) / RAD_QPW;
+  const long long target = (long long)n_cu * 16;
+  long long split = 1;
+  if (waves < target) split = std::min(std::min((target + waves - 1) / waves, std::max(1LL, (long long)n / 1024)), 1024LL);
+  cols = (int)((((long long)n + split - 1) / split + 63) / 64 * 64);
+  n_split = (int)(((long long)n + cols - 1) / cols);
+}
+
+static size_t radius_prep_bytes(int n, bool cosine) {
+  return cosine ? (sizeof(double2) * (size_t)n + 255) / 256 * 256 : 0;
+}
+
+size_t blk_radius_scratch_bytes(int n, int n_rows, bool cosine, int n_cu) {
+  int n_split, cols;
+  radius_plan(n, n_rows, n_cu, n_split, cols);
+  /* counts per (row, split), and with a column split the rows' sums behind them */
+  return radius_prep_bytes(n, cosine) + sizeof(unsigned) * (size_t)n_rows * (n_split + (n_split > 1 ? 1 : 0));
+}
+
+static dim3 radius_grid(int n_rows, int n_split) {
+  const int per_block = RAD_WAVES * RAD_QPW;
+  return dim3((n_rows + per_block - 1) / per_block, n_split);
+}
+
+/* prep (cosine) and the per-(row, split) counts into the scratch */
+static unsigned *radius_count_launch(hipStream_t s, const float4 *v, int n, int row_begin, int n_rows, bool cosine,
+                                     float bound, int n_split, int cols, void *d_scratch) {
+  double2 *prep = cosine ? static_cast<double2 *>(d_scratch) : nullptr;
+  unsigned *part = reinterpret_cast<unsigned *>(static_cast<char *>(d_scratch) + radius_prep_bytes(n, cosine));
+  if (cosine) {
+    hipLaunchKernelGGL(k_knn_prep, dim3((n + 255) / 256), dim3(256), 0, s, v, n, prep);
+    hipLaunchKernelGGL((k_radius_count<true>), radius_grid(n_rows, n_split), dim3(64 * RAD_WAVES), 0, s, v, prep, n,
+                       row_begin, n_rows, cols, n_split, bound, part);
+  } else {
+    hipLaunchKernelGGL((k_radius_count<false>), radius_grid(n_rows, n_split), dim3(64 * RAD_WAVES), 0, s, v, prep, n,
+                       row_begin, n_rows, cols, n_split, bound, part);
+  }
+  return part;
+}
+
+int blk_radius_count(hipStream_t s, const struct force_vector_s *d_vecs, int n, int row_begin, int n_rows, bool cosine,
+                     float bound, int n_cu, void *d_scratch, long long *d_offset) {
+  int n_split, cols;
+  radius_plan(n, n_rows, n_cu, n_split, cols);
+  unsigned *part = radius_count_launch(s, reinterpret_cast<const float4 *>(d_vecs), n, row_begin, n_rows, cosine, bound,
+                                       n_split, cols, d_scratch);
+  const unsigned *counts = part;
+  if (n_split > 1) {
+    unsigned *rowsum = part + (size_t)n_rows * n_split;
+    hipLaunchKernelGGL(k_radius_split_scan, dim3((n_rows + 3) / 4), dim3(256), 0, s, part, n_rows, n_split, rowsum);
+    counts = rowsum;
+  }
+  hipLaunchKernelGGL(k_radius_offsets, dim3(1), dim3(1024), 0, s, counts, n_rows, d_offset);
+  BL_HIP_CHECK(hipGetLastError());
+  return BL_OK;
+}
+
+template <bool COSINE>
+static void radius_fill_launch(hipStream_t s, const float4 *v, const double2 *prep, int n, int row_begin, int n_rows,
+                               int n_split, int cols, float bound, const unsigned *before, const long long *d_offset,
+                               int32_t *d_index, float *d_value) {
+  if (d_value)
+    hipLaunchKernelGGL((k_radius_fill<COSINE, true>), radius_grid(n_rows, n_split), dim3(64 * RAD_WAVES), 0, s, v, prep,
+                       n, row_begin, n_rows, cols, n_split, bound, before, d_offset, d_index, d_value);
+  else
+    hipLaunchKernelGGL((k_radius_fill<COSINE, false>), radius_grid(n_rows, n_split), dim3(64 * RAD_WAVES), 0, s, v, prep,
+                       n, row_begin, n_rows, cols, n_split, bound, before, d_offset, d_index, d_value);
+}
+
+/* One split: a row's list starts at its offset, nothing else is needed.  Column split: the per-split counts are
+ * computed again here (the scratch may have served another call since the count), so fill depends on nothing but
+ * its arguments. */
+int blk_radius_fill(hipStream_t s, const struct force_vector_s *d_vecs, int n, int row_begin, int n_rows, bool cosine,
+                    float bound, int n_cu, void *d_scratch, const long long *d_offset, int32_t *d_index, float *d_value) {
+  const float4 *v = reinterpret_cast<const float4 *>(d_vecs);
+  int n_split, cols;
+  radius_plan(n, n_rows, n_cu, n_split, cols);
+  double2 *prep = cosine ? static_cast<double2 *>(d_scratch) : nullptr;
+  unsigned *before = nullptr;
+  if (n_split > 1) {
+    before = radius_count_launch(s, v, n, row_begin, n_rows, cosine, bound, n_split, cols, d_scratch);
+    hipLaunchKernelGGL(k_radius_split_scan, dim3((n_rows + 3) / 4), dim3(256), 0, s, before, n_rows, n_split,
+                       before + (size_t)n_rows * n_split);
+  } else if (cosine) {
+    hipLaunchKernelGGL(k_knn_prep, dim3((n + 255) / 256), dim3(256), 0, s, v, n, prep);
+  }
+  if (cosine) radius_fill_launch<true>(s, v, prep, n, row_begin, n_rows, n_split, cols, bound, before, d_offset, d_index, d_value);
+  else radius_fill_launch<false>(s, v, prep, n, row_begin, n_rows, n_split, cols, bound, before, d_offset, d_index, d_value);
+  BL_HIP_CHECK(hipGetLastError());
+  return BL_OK;
+}
+
+size_t blk_groups_scratch_bytes(int n, bool cosine) { return radius_prep_bytes(n, cosine); }
+
+int blk_groups(hipStream_t s, const struct force_vector_s *d_vecs, int n, bool cosine, float bound, int n_cu,
+               void *d_scratch, int32_t *d_group) {
+  const float4 *v = reinterpret_cast<const float4 *>(d_vecs);
+  int n_split, cols;
+  radius_plan(n, n, n_cu, n_split, cols);
+  double2 *prep = cosine ? static_cast<double2 *>(d_scratch) : nullptr;
+  const dim3 flat((n + 255) / 256);
+  hipLaunchKernelGGL(k_groups_init, flat, dim3(256), 0, s, d_group, n);
+  if (cosine) {
+    hipLaunchKernelGGL(k_knn_prep, flat, dim3(256), 0, s, v, n, prep);
+    hipLaunchKernelGGL((k_groups_union<true>), radius_grid(n, n_split), dim3(64 * RAD_WAVES), 0, s, v, prep, n, cols,
+                       bound, d_group);
+  } else {
+    hipLaunchKernelGGL((k_groups_union<false>), radius_grid(n, n_split), dim3(64 * RAD_WAVES), 0, s, v, prep, n, cols,
+                       bound, d_group);
+  }
+  hipLaunchKernelGGL(k_groups_compress, flat, dim3(256), 0, s, d_group, n);
   BL_HIP_CHECK(hipGetLastError());
   return BL_OK;
 }

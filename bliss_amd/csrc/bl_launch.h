@@ -118,6 +118,19 @@ int blk_chain_shape(int n, int n_chains, int n_cu, int force);
 size_t blk_chain_scratch_bytes(int n, int n_chains, bool cosine, int n_cu, int force);
 int blk_chain(hipStream_t s, const struct force_vector_s *d_vecs, int n, const int32_t *d_seeds, int n_chains,
               int length, bool cosine, int n_cu, int force, void *d_scratch, int32_t *d_order, float *d_value);
+/* the songs within a radius of rows [row_begin, row_begin + n_rows) (bl_amd_radius_*_device).  bound: the largest
+ * squared sum whose correctly rounded root is <= the radius (distance) or the radius itself (cosine).  d_scratch: at
+ * least blk_radius_scratch_bytes(n, n_rows, cosine, n_cu) bytes, 256-byte aligned; count and fill both rewrite it, and
+ * fill needs nothing of what count left there.  d_offset: n_rows + 1 entries. */
+size_t blk_radius_scratch_bytes(int n, int n_rows, bool cosine, int n_cu);
+int blk_radius_count(hipStream_t s, const struct force_vector_s *d_vecs, int n, int row_begin, int n_rows, bool cosine,
+                     float bound, int n_cu, void *d_scratch, long long *d_offset);
+int blk_radius_fill(hipStream_t s, const struct force_vector_s *d_vecs, int n, int row_begin, int n_rows, bool cosine,
+                    float bound, int n_cu, void *d_scratch, const long long *d_offset, int32_t *d_index, float *d_value);
+/* duplicate groups (bl_amd_groups_device): d_group[i] = the smallest index of i's component; d_scratch: the cosine prep */
+size_t blk_groups_scratch_bytes(int n, bool cosine);
+int blk_groups(hipStream_t s, const struct force_vector_s *d_vecs, int n, bool cosine, float bound, int n_cu,
+               void *d_scratch, int32_t *d_group);
 /* out[i] = (int16)(in[i] >> 16): the same-rate S32 -> S16 narrowing */
 int blk_narrow_s32(hipStream_t s, const int32_t *d_in, int16_t *d_out, size_t n, int n_cu);
 /* out[order[i]] = in[i] for 16-byte force vectors (shard-major -> caller order) */

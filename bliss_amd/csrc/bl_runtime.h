@@ -87,6 +87,8 @@ struct bl_amd_ctx {
   /* bl_amd_chain_device: cosine prep, the column split's per-chain state and played bits (or the per-chain
    * shape's played bits beyond what LDS holds) */
   bl_buf chain;
+  /* bl_amd_radius_*_device, bl_amd_groups_device: cosine prep and the per-(row, column split) counts */
+  bl_buf radius;
 };
 
 /* bl_runtime.hip */

@@ -15,6 +15,7 @@
  * 32 768 songs follow each other on the stream, and the shared workspace is handed from one
  * batch to the next by an event, not by a host synchronisation.
  */
+#include <float.h>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -129,7 +130,7 @@ void ctx_release(bl_amd_ctx *c) {
   prof_collect(c);
   bl_buf *bufs[] = {&c->songs,   &c->stats,   &c->hist, &c->spectrum, &c->energies, &c->lc,
                     &c->results, &c->misc,    &c->arena[0], &c->arena[1], &c->arena22[0], &c->arena22[1],
-                    &c->rs_songs, &c->rs_bank, &c->mx_my, &c->mx_gath, &c->mx_all, &c->mx_order, &c->mx_rows, &c->knn, &c->chain};
+                    &c->rs_songs, &c->rs_bank, &c->mx_my, &c->mx_gath, &c->mx_all, &c->mx_order, &c->mx_rows, &c->knn, &c->chain, &c->radius};
   for (bl_buf *b : bufs) release_buf(*b);
   for (int k = 0; k < 2; ++k) {
     unregister_wave(c, k);
@@ -974,6 +975,177 @@ int bl_amd_chain_host(const struct force_vector_s *h_vecs, int n, const int32_t 
   if (ds) (void)hipFree(ds);
   if (di) (void)hipFree(di);
   if (dd) (void)hipFree(dd);
+  return rc;
+}
+
+/* Radius queries and duplicate groups (bl_kernels.hip k_radius_*, k_groups_*): arguments first, then the workspace
+ * like the kNN call.  The distance is compared on the squared sum against bl_amd_radius_bound(radius), computed here
+ * once per call. */
+float bl_amd_radius_bound(float radius) {
+  if (radius != radius) return radius;
+  if (radius < 0.f) return -INFINITY;       /* no root is negative; -0 is not below 0 */
+  if (radius == INFINITY) return INFINITY;  /* an overflowed sum has the root +inf */
+  float s = radius * radius;
+  if (!(s <= FLT_MAX)) s = FLT_MAX;
+  while (s > 0.f && (float)sqrt((double)s) > radius) s = nextafterf(s, 0.f);
+  while (s < FLT_MAX) {
+    const float up = nextafterf(s, INFINITY);
+    if ((float)sqrt((double)up) > radius) break;
+    s = up;
+  }
+  return s;
+}
+
+static bool radius_args_ok(const void *vecs, int n, int row_begin, int n_rows, int metric, float radius,
+                           const void *out) {
+  return vecs && out && n > 0 && (metric == BL_AMD_KNN_DISTANCE || metric == BL_AMD_KNN_COSINE) && radius == radius &&
+         row_begin >= 0 && n_rows > 0 && row_begin < n && n_rows <= n - row_begin;
+}
+
+static float radius_kernel_bound(int metric, float radius) {
+  return metric == BL_AMD_KNN_COSINE ? radius : bl_amd_radius_bound(radius);
+}
+
+int bl_amd_ctx_radius_count_device(bl_amd_ctx *c, const struct force_vector_s *d_vecs, int n, int row_begin, int n_rows,
+                                   int metric, float radius, int64_t *d_offset, void *stream) {
+  if (!radius_args_ok(d_vecs, n, row_begin, n_rows, metric, radius, d_offset) || !c) return BL_UNEXPECTED;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DevGuard dg(c->device);
+  if (!dg.ok) return BL_UNEXPECTED;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const bool cosine = metric == BL_AMD_KNN_COSINE;
+  if (c->ws_used) BL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_ws, 0));
+  if (blr_ensure(c->radius, blk_radius_scratch_bytes(n, n_rows, cosine, c->n_cu)) != BL_OK) return BL_UNEXPECTED;
+  if (blk_radius_count(s, d_vecs, n, row_begin, n_rows, cosine, radius_kernel_bound(metric, radius), c->n_cu,
+                       c->radius.p, reinterpret_cast<long long *>(d_offset)) != BL_OK)
+    return BL_UNEXPECTED;
+  BL_HIP_CHECK(hipEventRecord(c->ev_ws, s));
+  c->ws_used = true;
+  return BL_OK;
+}
+
+int bl_amd_radius_count_device(const struct force_vector_s *d_vecs, int n, int row_begin, int n_rows, int metric,
+                               float radius, int64_t *d_offset, void *stream) {
+  if (!radius_args_ok(d_vecs, n, row_begin, n_rows, metric, radius, d_offset)) return BL_UNEXPECTED;
+  return bl_amd_ctx_radius_count_device(blr_default_ctx(), d_vecs, n, row_begin, n_rows, metric, radius, d_offset,
+                                        stream);
+}
+
+int bl_amd_ctx_radius_fill_device(bl_amd_ctx *c, const struct force_vector_s *d_vecs, int n, int row_begin, int n_rows,
+                                  int metric, float radius, const int64_t *d_offset, int32_t *d_index, float *d_value,
+                                  void *stream) {
+  if (!radius_args_ok(d_vecs, n, row_begin, n_rows, metric, radius, d_offset) || !d_index || !c) return BL_UNEXPECTED;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DevGuard dg(c->device);
+  if (!dg.ok) return BL_UNEXPECTED;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const bool cosine = metric == BL_AMD_KNN_COSINE;
+  if (c->ws_used) BL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_ws, 0));
+  if (blr_ensure(c->radius, blk_radius_scratch_bytes(n, n_rows, cosine, c->n_cu)) != BL_OK) return BL_UNEXPECTED;
+  if (blk_radius_fill(s, d_vecs, n, row_begin, n_rows, cosine, radius_kernel_bound(metric, radius), c->n_cu,
+                      c->radius.p, reinterpret_cast<const long long *>(d_offset), d_index, d_value) != BL_OK)
+    return BL_UNEXPECTED;
+  BL_HIP_CHECK(hipEventRecord(c->ev_ws, s));
+  c->ws_used = true;
+  return BL_OK;
+}
+
+int bl_amd_radius_fill_device(const struct force_vector_s *d_vecs, int n, int row_begin, int n_rows, int metric,
+                              float radius, const int64_t *d_offset, int32_t *d_index, float *d_value, void *stream) {
+  if (!radius_args_ok(d_vecs, n, row_begin, n_rows, metric, radius, d_offset) || !d_index) return BL_UNEXPECTED;
+  return bl_amd_ctx_radius_fill_device(blr_default_ctx(), d_vecs, n, row_begin, n_rows, metric, radius, d_offset,
+                                       d_index, d_value, stream);
+}
+
+int bl_amd_radius_host(const struct force_vector_s *h_vecs, int n, int metric, float radius, int64_t *h_offset,
+                       int32_t **h_index, float **h_value) {
+  if (!radius_args_ok(h_vecs, n, 0, n, metric, radius, h_offset) || !h_index) return BL_UNEXPECTED;
+  bl_amd_ctx *c = blr_default_ctx();
+  if (!c) return BL_UNEXPECTED;
+  DevGuard dg(c->device);
+  if (!dg.ok) return BL_UNEXPECTED;
+  void *dv = nullptr, *doff = nullptr, *di = nullptr, *dd = nullptr;
+  int32_t *hi = nullptr;
+  float *hv = nullptr;
+  std::vector<int64_t> off((size_t)n + 1);
+  int rc = BL_UNEXPECTED;
+  if (hipMalloc(&dv, sizeof(struct force_vector_s) * (size_t)n) == hipSuccess &&
+      hipMalloc(&doff, sizeof(int64_t) * ((size_t)n + 1)) == hipSuccess &&
+      hipMemcpy(dv, h_vecs, sizeof(struct force_vector_s) * (size_t)n, hipMemcpyHostToDevice) == hipSuccess &&
+      bl_amd_radius_count_device(static_cast<struct force_vector_s *>(dv), n, 0, n, metric, radius,
+                                 static_cast<int64_t *>(doff), nullptr) == BL_OK &&
+      hipMemcpy(off.data(), doff, sizeof(int64_t) * ((size_t)n + 1), hipMemcpyDeviceToHost) == hipSuccess) {
+    const size_t total = (size_t)off[(size_t)n], slots = total ? total : 1; /* an empty result is still a free()-able block */
+    hi = static_cast<int32_t *>(malloc(sizeof(int32_t) * slots));
+    hv = h_value ? static_cast<float *>(malloc(sizeof(float) * slots)) : nullptr;
+    if (hi && (hv || !h_value) && hipMalloc(&di, sizeof(int32_t) * slots) == hipSuccess &&
+        (!h_value || hipMalloc(&dd, sizeof(float) * slots) == hipSuccess) &&
+        bl_amd_radius_fill_device(static_cast<struct force_vector_s *>(dv), n, 0, n, metric, radius,
+                                  static_cast<int64_t *>(doff), static_cast<int32_t *>(di), static_cast<float *>(dd),
+                                  nullptr) == BL_OK &&
+        hipMemcpy(hi, di, sizeof(int32_t) * total, hipMemcpyDeviceToHost) == hipSuccess &&
+        (!h_value || hipMemcpy(hv, dd, sizeof(float) * total, hipMemcpyDeviceToHost) == hipSuccess))
+      rc = BL_OK;
+  }
+  if (dv) (void)hipFree(dv);
+  if (doff) (void)hipFree(doff);
+  if (di) (void)hipFree(di);
+  if (dd) (void)hipFree(dd);
+  if (rc == BL_OK) {
+    memcpy(h_offset, off.data(), sizeof(int64_t) * ((size_t)n + 1));
+    *h_index = hi;
+    if (h_value) *h_value = hv;
+  } else {
+    free(hi);
+    free(hv);
+  }
+  return rc;
+}
+
+static bool groups_args_ok(const void *vecs, int n, int metric, float radius, const void *group) {
+  return vecs && group && n > 0 && (metric == BL_AMD_KNN_DISTANCE || metric == BL_AMD_KNN_COSINE) && radius == radius;
+}
+
+int bl_amd_ctx_groups_device(bl_amd_ctx *c, const struct force_vector_s *d_vecs, int n, int metric, float radius,
+                             int32_t *d_group, void *stream) {
+  if (!groups_args_ok(d_vecs, n, metric, radius, d_group) || !c) return BL_UNEXPECTED;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DevGuard dg(c->device);
+  if (!dg.ok) return BL_UNEXPECTED;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const bool cosine = metric == BL_AMD_KNN_COSINE;
+  if (c->ws_used) BL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_ws, 0));
+  if (blr_ensure(c->radius, blk_groups_scratch_bytes(n, cosine)) != BL_OK) return BL_UNEXPECTED;
+  if (blk_groups(s, d_vecs, n, cosine, radius_kernel_bound(metric, radius), c->n_cu, c->radius.p, d_group) != BL_OK)
+    return BL_UNEXPECTED;
+  BL_HIP_CHECK(hipEventRecord(c->ev_ws, s));
+  c->ws_used = true;
+  return BL_OK;
+}
+
+int bl_amd_groups_device(const struct force_vector_s *d_vecs, int n, int metric, float radius, int32_t *d_group,
+                         void *stream) {
+  if (!groups_args_ok(d_vecs, n, metric, radius, d_group)) return BL_UNEXPECTED;
+  return bl_amd_ctx_groups_device(blr_default_ctx(), d_vecs, n, metric, radius, d_group, stream);
+}
+
+int bl_amd_groups_host(const struct force_vector_s *h_vecs, int n, int metric, float radius, int32_t *h_group) {
+  if (!groups_args_ok(h_vecs, n, metric, radius, h_group)) return BL_UNEXPECTED;
+  bl_amd_ctx *c = blr_default_ctx();
+  if (!c) return BL_UNEXPECTED;
+  DevGuard dg(c->device);
+  if (!dg.ok) return BL_UNEXPECTED;
+  void *dv = nullptr, *dg_out = nullptr;
+  int rc = BL_UNEXPECTED;
+  if (hipMalloc(&dv, sizeof(struct force_vector_s) * (size_t)n) == hipSuccess &&
+      hipMalloc(&dg_out, sizeof(int32_t) * (size_t)n) == hipSuccess &&
+      hipMemcpy(dv, h_vecs, sizeof(struct force_vector_s) * (size_t)n, hipMemcpyHostToDevice) == hipSuccess &&
+      bl_amd_groups_device(static_cast<struct force_vector_s *>(dv), n, metric, radius, static_cast<int32_t *>(dg_out),
+                           nullptr) == BL_OK &&
+      hipMemcpy(h_group, dg_out, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost) == hipSuccess)
+    rc = BL_OK;
+  if (dv) (void)hipFree(dv);
+  if (dg_out) (void)hipFree(dg_out);
   return rc;
 }
 

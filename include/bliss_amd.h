@@ -306,6 +306,52 @@ int bl_amd_chain_host(const struct force_vector_s *h_vecs, int n, const int32_t 
 int bl_amd_chain_shape(int n, int n_chains);
 int bl_amd_chain_force_shape(int shape);
 
+/* Radius queries: the songs within a radius of each query, however many, as compressed sparse row (CSR) lists and
+ * without the N x N matrix.  M is the bl_distance matrix (BL_AMD_KNN_DISTANCE; ref src/analyze.c:96-100) or the
+ * bl_cosine_similarity matrix (BL_AMD_KNN_COSINE; ref src/analyze.c:135-140), entries by their bits as
+ * bl_amd_*_matrix_device writes them.  Song j is within the radius of query i iff j != i and M[i][j] <= radius
+ * (distance) or M[i][j] >= radius (cosine): plain f32 compares, so a NaN entry is never within, +0 and -0 are equal,
+ * and exact duplicates of the query at other indices are ordinary candidates.  +-inf and negative radii are legal and
+ * mean what the compare says; a NaN radius is an argument error.  Rows [row_begin, row_begin + n_rows) of d_vecs are
+ * the queries, n >= 1, 0 <= row_begin, n_rows >= 1, row_begin + n_rows <= n; a rejected call returns BL_UNEXPECTED
+ * and writes nothing.
+ *   bl_amd_radius_count_device: d_offset (n_rows + 1 entries) receives the exclusive prefix sums of the list lengths:
+ *     d_offset[0] = 0, d_offset[r + 1] - d_offset[r] = the number of songs within the radius of song row_begin + r,
+ *     the last entry the total.  The sums are taken on the device, exactly, in int64.
+ *   bl_amd_radius_fill_device: d_offset is what the count call wrote for the same arguments; the songs of row r go to
+ *     d_index[d_offset[r] .. d_offset[r + 1]) in ascending song index, and their matrix entries, by their bits, to
+ *     the same slots of d_value (may be NULL).  It reads nothing the count call left behind but d_offset.
+ * Both are asynchronous on `stream`; no allocation, copy or synchronisation inside once the context's workspace is
+ * large enough; calls of one context are ordered on the device like its batches.  The result depends neither on the
+ * row range asked for nor on the launch shape taken.
+ *   bl_amd_radius_host: all n songs as queries, host pointers, blocking.  h_offset: n + 1 entries; *h_index and
+ *     *h_value are malloc'd (free() them; an empty result is a valid block too).  h_value may be NULL.
+ *   bl_amd_radius_bound: the exact bound the distance filter runs on: the largest f32 s with
+ *     (float)sqrt((double)s) <= radius, so that "bl_distance <= radius" is "squared sum <= bound" (the rounded root
+ *     is monotone).  -inf for a negative radius (nothing is within), 0 for +-0, +inf for +inf, the radius for NaN. */
+float bl_amd_radius_bound(float radius);
+int bl_amd_radius_count_device(const struct force_vector_s *d_vecs, int n, int row_begin, int n_rows, int metric,
+                               float radius, int64_t *d_offset, void *stream);
+int bl_amd_ctx_radius_count_device(bl_amd_ctx *ctx, const struct force_vector_s *d_vecs, int n, int row_begin,
+                                   int n_rows, int metric, float radius, int64_t *d_offset, void *stream);
+int bl_amd_radius_fill_device(const struct force_vector_s *d_vecs, int n, int row_begin, int n_rows, int metric,
+                              float radius, const int64_t *d_offset, int32_t *d_index, float *d_value, void *stream);
+int bl_amd_ctx_radius_fill_device(bl_amd_ctx *ctx, const struct force_vector_s *d_vecs, int n, int row_begin,
+                                  int n_rows, int metric, float radius, const int64_t *d_offset, int32_t *d_index,
+                                  float *d_value, void *stream);
+int bl_amd_radius_host(const struct force_vector_s *h_vecs, int n, int metric, float radius, int64_t *h_offset,
+                       int32_t **h_index, float **h_value);
+
+/* Duplicate groups: d_group[i] (n int32) = the smallest song index in the weakly connected component of song i in the
+ * graph that has an edge i -> j iff j is within the radius of i (as defined above): a pure function of (vecs, metric,
+ * radius).  A song with no neighbour is its own group.  The edges are never stored.  Asynchronous on `stream`, no host
+ * round trips; a NaN radius is an argument error. */
+int bl_amd_groups_device(const struct force_vector_s *d_vecs, int n, int metric, float radius, int32_t *d_group,
+                         void *stream);
+int bl_amd_ctx_groups_device(bl_amd_ctx *ctx, const struct force_vector_s *d_vecs, int n, int metric, float radius,
+                             int32_t *d_group, void *stream);
+int bl_amd_groups_host(const struct force_vector_s *h_vecs, int n, int metric, float radius, int32_t *h_group);
+
 /* Integer-only synthetic PCM (the benchmark corpus of BASELINE.json),
  * generated in place on the device: song i = seed_base + i, written at
  * h_desc[i].pcm_offset.  Byte-identical to oracle/orc_synth.c. */
