@@ -1,5 +1,6 @@
 """Batch helpers over the C-ABI: device-resident corpora (torch owns the memory,
 the library owns the arithmetic) and host-pointer conveniences."""
+import contextlib
 import ctypes as C
 import os
 
@@ -300,12 +301,9 @@ def resample_batch_device(d_in, frames, channels, in_rate, stream=None):
         in_off += (int(fr) * int(ch) + 7) & ~7
         out_off += (2 * of + 7) & ~7
     out = torch.zeros(out_off + 64, dtype=torch.int16, device=d_in.device)
-    s = stream.cuda_stream if stream is not None else torch.cuda.current_stream(d_in.device).cuda_stream
-    idx = d_in.device.index or 0
-    with torch.cuda.device(idx):
-        _check(lib.bl_amd_init(idx), "bl_amd_init")
+    with _on_device_of(lib, d_in, stream) as cur:
         _check(lib.bl_amd_resample_batch_device(d_in.data_ptr(), int(d_in.dtype == torch.int32), desc, n,
-                                                in_rate, out.data_ptr(), C.c_void_p(s)),
+                                                in_rate, out.data_ptr(), C.c_void_p(cur.cuda_stream)),
                "bl_amd_resample_batch_device")
     return out, placed
 
@@ -349,14 +347,46 @@ def playlist(vecs, seed_index):
 _KNN_METRICS = {"distance": _lib.BL_AMD_KNN_DISTANCE, "cosine": _lib.BL_AMD_KNN_COSINE}
 
 
-def _knn_check(k, metric, shape):
-    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= _lib.BL_AMD_KNN_MAX_K:
-        raise ValueError(f"k must be an integer in [1, {_lib.BL_AMD_KNN_MAX_K}], got {k!r}")
+def _metric_check(metric, shape):
+    """the metric's code, for a known metric over (n, 4) force vectors"""
     if metric not in _KNN_METRICS:
         raise ValueError(f"metric must be one of {sorted(_KNN_METRICS)}, got {metric!r}")
     if len(shape) != 2 or shape[1] != 4 or shape[0] < 1:
         raise ValueError(f"force vectors must have shape (n, 4) with n >= 1, got {tuple(shape)}")
     return _KNN_METRICS[metric]
+
+
+def _device_vecs_check(d_vecs):
+    import torch
+    if d_vecs.dtype != torch.float32 or not d_vecs.is_cuda or not d_vecs.is_contiguous():
+        raise ValueError("d_vecs must be a contiguous float32 CUDA tensor")
+
+
+def _rows_check(n, row_begin, n_rows):
+    """n_rows (None: all rows from row_begin) once [row_begin, row_begin + n_rows) lies inside [0, n)"""
+    if n_rows is None:
+        n_rows = n - row_begin
+    if not (0 <= row_begin < n and 1 <= n_rows <= n - row_begin):
+        raise ValueError(f"rows [{row_begin}, {row_begin + n_rows}) are not inside [0, {n})")
+    return n_rows
+
+
+@contextlib.contextmanager
+def _on_device_of(lib, tensor, stream):
+    """The tensor's device current and the library initialised on it; yields the torch stream to launch on (`stream`,
+    else that device's current one) without entering it: the caller decides under which stream it allocates."""
+    import torch
+    cur = stream if stream is not None else torch.cuda.current_stream(tensor.device)
+    idx = tensor.device.index or 0
+    with torch.cuda.device(idx):
+        _check(lib.bl_amd_init(idx), "bl_amd_init")
+        yield cur
+
+
+def _knn_check(k, metric, shape):
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= _lib.BL_AMD_KNN_MAX_K:
+        raise ValueError(f"k must be an integer in [1, {_lib.BL_AMD_KNN_MAX_K}], got {k!r}")
+    return _metric_check(metric, shape)
 
 
 def knn(vecs, k, metric="distance"):
@@ -382,23 +412,16 @@ def knn_device(d_vecs, k, metric="distance", row_begin=0, n_rows=None, stream=No
     (default: the current stream of that device)."""
     import torch
     m = _knn_check(k, metric, tuple(d_vecs.shape))
-    if d_vecs.dtype != torch.float32 or not d_vecs.is_cuda or not d_vecs.is_contiguous():
-        raise ValueError("d_vecs must be a contiguous float32 CUDA tensor")
+    _device_vecs_check(d_vecs)
     n = d_vecs.shape[0]
-    if n_rows is None:
-        n_rows = n - row_begin
-    if not (0 <= row_begin < n and 1 <= n_rows <= n - row_begin):
-        raise ValueError(f"rows [{row_begin}, {row_begin + n_rows}) are not inside [0, {n})")
+    n_rows = _rows_check(n, row_begin, n_rows)
     lib = _lib.load()
     v = d_vecs
     index = torch.empty((n_rows, k), dtype=torch.int32, device=v.device)
     value = torch.empty((n_rows, k), dtype=torch.float32, device=v.device)
-    s = stream.cuda_stream if stream is not None else torch.cuda.current_stream(v.device).cuda_stream
-    idx = v.device.index or 0
-    with torch.cuda.device(idx):
-        _check(lib.bl_amd_init(idx), "bl_amd_init")
+    with _on_device_of(lib, v, stream) as cur:
         _check(lib.bl_amd_knn_device(v.data_ptr(), n, int(row_begin), int(n_rows), int(k), m, index.data_ptr(),
-                                     value.data_ptr(), C.c_void_p(s)), "bl_amd_knn_device")
+                                     value.data_ptr(), C.c_void_p(cur.cuda_stream)), "bl_amd_knn_device")
     return index, value
 
 
@@ -407,12 +430,9 @@ def _chain_check(seeds, length, metric, shape, n_limit):
     [0, n_limit) (None: leave them to the device, which answers with a -1 / NaN row)"""
     if isinstance(length, bool) or not isinstance(length, (int, np.integer)) or length < 1:
         raise ValueError(f"length must be an integer >= 1, got {length!r}")
-    if metric not in _KNN_METRICS:
-        raise ValueError(f"metric must be one of {sorted(_KNN_METRICS)}, got {metric!r}")
-    if len(shape) != 2 or shape[1] != 4 or shape[0] < 1:
-        raise ValueError(f"force vectors must have shape (n, 4) with n >= 1, got {tuple(shape)}")
+    m = _metric_check(metric, shape)
     if hasattr(seeds, "is_cuda"):   # a torch tensor: chain_device checks it
-        return _KNN_METRICS[metric], None
+        return m, None
     s = np.asarray(seeds)
     if s.dtype == np.bool_ or not np.issubdtype(s.dtype, np.integer):
         raise ValueError(f"seeds must be integers, got dtype {s.dtype}")
@@ -423,7 +443,7 @@ def _chain_check(seeds, length, metric, shape, n_limit):
         raise ValueError(f"seeds must lie in [0, {n_limit})")
     if s.min() < -2 ** 31 or s.max() >= 2 ** 31:
         raise ValueError("seeds do not fit 32 bits")
-    return _KNN_METRICS[metric], np.ascontiguousarray(s, dtype=np.int32)
+    return m, np.ascontiguousarray(s, dtype=np.int32)
 
 
 def chain(vecs, seeds, length, metric="distance"):
@@ -451,8 +471,7 @@ def chain_device(d_vecs, d_seeds, length, metric="distance", stream=None):
     [0, n) gives a row of -1 / NaN."""
     import torch
     m, s = _chain_check(d_seeds, length, metric, tuple(d_vecs.shape), None)
-    if d_vecs.dtype != torch.float32 or not d_vecs.is_cuda or not d_vecs.is_contiguous():
-        raise ValueError("d_vecs must be a contiguous float32 CUDA tensor")
+    _device_vecs_check(d_vecs)
     if s is None:
         if d_seeds.dtype != torch.int32 or d_seeds.dim() > 1 or d_seeds.numel() < 1:
             raise ValueError("d_seeds must be an int32 tensor with 0 or 1 dimensions and at least one element")
@@ -461,14 +480,11 @@ def chain_device(d_vecs, d_seeds, length, metric="distance", stream=None):
     lib = _lib.load()
     v = d_vecs
     n = v.shape[0]
-    cur = stream if stream is not None else torch.cuda.current_stream(v.device)
-    idx = v.device.index or 0
-    with torch.cuda.device(idx), torch.cuda.stream(cur):
+    with _on_device_of(lib, v, stream) as cur, torch.cuda.stream(cur):
         sd = torch.from_numpy(s).to(v.device) if s is not None else d_seeds.reshape(-1).contiguous()
         n_chains = sd.numel()
         order = torch.empty((n_chains, length), dtype=torch.int32, device=v.device)
         value = torch.empty((n_chains, length), dtype=torch.float32, device=v.device)
-        _check(lib.bl_amd_init(idx), "bl_amd_init")
         _check(lib.bl_amd_chain_device(v.data_ptr(), n, sd.data_ptr(), n_chains, int(length), m, order.data_ptr(),
                                        value.data_ptr(), C.c_void_p(cur.cuda_stream)), "bl_amd_chain_device")
         if s is not None:
@@ -480,21 +496,12 @@ def _radius_check(r, metric, shape):
     """(metric code, the radius as a Python float that is an exact f32)"""
     if isinstance(r, bool) or not isinstance(r, (int, float, np.integer, np.floating)):
         raise ValueError(f"the radius must be a real number, got {r!r}")
-    if metric not in _KNN_METRICS:
-        raise ValueError(f"metric must be one of {sorted(_KNN_METRICS)}, got {metric!r}")
-    if len(shape) != 2 or shape[1] != 4 or shape[0] < 1:
-        raise ValueError(f"force vectors must have shape (n, 4) with n >= 1, got {tuple(shape)}")
+    m = _metric_check(metric, shape)
     with np.errstate(over="ignore"):
         r32 = np.float32(r)
     if np.isnan(r32):
         raise ValueError("the radius must not be NaN")
-    return _KNN_METRICS[metric], float(r32)
-
-
-def _device_vecs_check(d_vecs):
-    import torch
-    if d_vecs.dtype != torch.float32 or not d_vecs.is_cuda or not d_vecs.is_contiguous():
-        raise ValueError("d_vecs must be a contiguous float32 CUDA tensor")
+    return m, float(r32)
 
 
 def radius(vecs, r, metric="distance"):
@@ -511,16 +518,13 @@ def radius(vecs, r, metric="distance"):
     rc = lib.bl_amd_radius_host(v.ctypes.data_as(C.POINTER(_lib.ForceVector)), n, m, r,
                                 offsets.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(p_index), C.byref(p_value))
     _check(rc, "bl_amd_radius_host")
-    libc = C.CDLL(None)
-    libc.free.argtypes = [C.c_void_p]
-    libc.free.restype = None
     try:
         total = int(offsets[n])
         index = np.ctypeslib.as_array(p_index, shape=(total,)).copy() if total else np.empty(0, dtype=np.int32)
         value = np.ctypeslib.as_array(p_value, shape=(total,)).copy() if total else np.empty(0, dtype=np.float32)
     finally:
-        libc.free(p_index)
-        libc.free(p_value)
+        _libc_free(p_index)
+        _libc_free(p_value)
     return offsets, index, value
 
 
@@ -533,18 +537,12 @@ def radius_device(d_vecs, r, metric="distance", row_begin=0, n_rows=None, values
     m, r = _radius_check(r, metric, tuple(d_vecs.shape))
     _device_vecs_check(d_vecs)
     n = d_vecs.shape[0]
-    if n_rows is None:
-        n_rows = n - row_begin
-    if not (0 <= row_begin < n and 1 <= n_rows <= n - row_begin):
-        raise ValueError(f"rows [{row_begin}, {row_begin + n_rows}) are not inside [0, {n})")
+    n_rows = _rows_check(n, row_begin, n_rows)
     lib = _lib.load()
     v = d_vecs
-    cur = stream if stream is not None else torch.cuda.current_stream(v.device)
-    idx = v.device.index or 0
-    with torch.cuda.device(idx), torch.cuda.stream(cur):
+    with _on_device_of(lib, v, stream) as cur, torch.cuda.stream(cur):
         s = C.c_void_p(cur.cuda_stream)
         offsets = torch.empty(n_rows + 1, dtype=torch.int64, device=v.device)
-        _check(lib.bl_amd_init(idx), "bl_amd_init")
         _check(lib.bl_amd_radius_count_device(v.data_ptr(), n, int(row_begin), int(n_rows), m, r, offsets.data_ptr(), s),
                "bl_amd_radius_count_device")
         total = int(offsets[-1].item())
@@ -581,11 +579,8 @@ def duplicate_groups_device(d_vecs, r, metric="distance", stream=None):
     lib = _lib.load()
     v = d_vecs
     n = v.shape[0]
-    cur = stream if stream is not None else torch.cuda.current_stream(v.device)
-    idx = v.device.index or 0
-    with torch.cuda.device(idx), torch.cuda.stream(cur):
+    with _on_device_of(lib, v, stream) as cur, torch.cuda.stream(cur):
         group = torch.empty(n, dtype=torch.int32, device=v.device)
-        _check(lib.bl_amd_init(idx), "bl_amd_init")
         _check(lib.bl_amd_groups_device(v.data_ptr(), n, m, r, group.data_ptr(), C.c_void_p(cur.cuda_stream)),
                "bl_amd_groups_device")
     return group

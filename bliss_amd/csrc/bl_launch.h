@@ -1,7 +1,9 @@
 /*
- * bl_launch.h — internal seam between the kernel translation unit (bl_kernels.hip: device
- * code + launch geometry) and the runtime (bl_runtime.hip: contexts, workspaces, streams,
- * the C-ABI of include/bliss_amd.h; bl_multi.hip: the multi-device corpus path).
+ * bl_launch.h — internal seam between the kernel translation units (device code + launch
+ * geometry: bl_kernels.hip the per-song analysis and the pairwise matrix, bl_query_kernels.hip
+ * the vector queries, bl_rs_kernels.hip the rate converter) and the runtime (bl_runtime.hip:
+ * contexts, workspaces, streams, the C-ABI of include/bliss_amd.h; bl_multi.hip: the
+ * multi-device corpus path).  Also BL_HIP_CHECK, which every .hip file uses.
  * C++ only, not installed.
  */
 #ifndef BL_LAUNCH_H_
@@ -10,9 +12,21 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <stdio.h>
 
 #include "bl_device.h"
 #include "bl_fft.h"
+
+/* a failed HIP call: one line on stderr, the enclosing function returns BL_UNEXPECTED */
+#define BL_HIP_CHECK(expr)                                                              \
+  do {                                                                                  \
+    hipError_t e_ = (expr);                                                             \
+    if (e_ != hipSuccess) {                                                             \
+      fprintf(stderr, "bliss_amd: %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e_), \
+              __FILE__, __LINE__);                                                      \
+      return BL_UNEXPECTED;                                                             \
+    }                                                                                   \
+  } while (0)
 
 /* ---- device-side records ------------------------------------------------- */
 
@@ -105,6 +119,26 @@ int blk_sqrt_sweep(hipStream_t s, unsigned long long first, unsigned long long c
 int blk_cos_sweep(hipStream_t s, unsigned long long seed, int per_thread, unsigned long long *d_counts, int n_cu);
 int blk_playlist(hipStream_t s, const struct force_vector_s *d_vecs, int n, int seed_index,
                  int32_t *d_order, float *d_dist);
+/* out[i] = (int16)(in[i] >> 16): the same-rate S32 -> S16 narrowing (SURVEY.md §8d config 5) */
+int blk_narrow_s32(hipStream_t s, const int32_t *d_in, int16_t *d_out, size_t n, int n_cu);
+/* out[order[i]] = in[i] for 16-byte force vectors (shard-major -> caller order) */
+int blk_scatter_vecs(hipStream_t s, const struct force_vector_s *d_in, const int32_t *d_order,
+                     struct force_vector_s *d_out, int n);
+/* force vectors of a result array, in result order */
+int blk_extract_vecs(hipStream_t s, const bl_amd_song_result *d_res, struct force_vector_s *d_out,
+                     int n);
+/* bl_mean / bl_variance helpers: one song described by d_songs[0] */
+int blk_scan_one(hipStream_t s, const int16_t *pcm, const bl_dsong *d_songs, bl_dstats *d_stats,
+                 unsigned *d_hist, int n, int n_cu);
+int blk_variance_wrap_one(hipStream_t s, const int16_t *pcm, const bl_dsong *d_songs,
+                          bl_dstats *d_stats, int n, int n_cu);
+
+/* ---- vector queries over force vectors (bl_query_kernels.hip) ------------------ */
+
+int blk_query_configure_device(void);                  /* dynamic-LDS attributes, once per device */
+/* Column split shared by the queries: waves of `qpw` query rows, splits of at least `min_cols` columns; *cols is a
+ * multiple of 64 and *n_split the number of blockIdx.y slices.  Not static so that it can be checked on the host. */
+void blk_split_plan(int n, int n_rows, int n_cu, int qpw, int min_cols, int *n_split, int *cols);
 /* the k nearest songs of rows [row_begin, row_begin + n_rows) (bl_amd_knn_device); d_scratch: at least
  * blk_knn_scratch_bytes(n, n_rows, k, cosine, n_cu) bytes, 256-byte aligned */
 size_t blk_knn_scratch_bytes(int n, int n_rows, int k, bool cosine, int n_cu);
@@ -131,19 +165,6 @@ int blk_radius_fill(hipStream_t s, const struct force_vector_s *d_vecs, int n, i
 size_t blk_groups_scratch_bytes(int n, bool cosine);
 int blk_groups(hipStream_t s, const struct force_vector_s *d_vecs, int n, bool cosine, float bound, int n_cu,
                void *d_scratch, int32_t *d_group);
-/* out[i] = (int16)(in[i] >> 16): the same-rate S32 -> S16 narrowing (SURVEY.md §8d config 5) */
-int blk_narrow_s32(hipStream_t s, const int32_t *d_in, int16_t *d_out, size_t n, int n_cu);
-/* out[order[i]] = in[i] for 16-byte force vectors (shard-major -> caller order) */
-int blk_scatter_vecs(hipStream_t s, const struct force_vector_s *d_in, const int32_t *d_order,
-                     struct force_vector_s *d_out, int n);
-/* force vectors of a result array, in result order */
-int blk_extract_vecs(hipStream_t s, const bl_amd_song_result *d_res, struct force_vector_s *d_out,
-                     int n);
-/* bl_mean / bl_variance helpers: one song described by d_songs[0] */
-int blk_scan_one(hipStream_t s, const int16_t *pcm, const bl_dsong *d_songs, bl_dstats *d_stats,
-                 unsigned *d_hist, int n, int n_cu);
-int blk_variance_wrap_one(hipStream_t s, const int16_t *pcm, const bl_dsong *d_songs,
-                          bl_dstats *d_stats, int n, int n_cu);
 
 /* ---- device rate converter (bl_rs_kernels.hip) ------------------------------ */
 

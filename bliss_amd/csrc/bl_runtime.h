@@ -13,16 +13,6 @@
 
 #include "bl_launch.h"
 
-#define BL_HIP_CHECK(expr)                                                              \
-  do {                                                                                  \
-    hipError_t e_ = (expr);                                                             \
-    if (e_ != hipSuccess) {                                                             \
-      fprintf(stderr, "bliss_amd: %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e_), \
-              __FILE__, __LINE__);                                                      \
-      return BL_UNEXPECTED;                                                             \
-    }                                                                                   \
-  } while (0)
-
 #define BL_MAX_DEVICES 16
 #define BL_GROUP_SONGS_MAX 32768 /* gridDim.y of the (blocks, songs) launch grids */
 #define BL_PIN_SLOTS 4

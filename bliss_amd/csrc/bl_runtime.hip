@@ -1,7 +1,7 @@
 /*
  * bl_runtime.hip — contexts, workspaces, streams and the single-device C-ABI of
  * include/bliss_amd.h.  Host code only (compiled by hipcc for the HIP runtime API); every
- * kernel lives in bl_kernels.hip and is reached through the launchers of bl_launch.h.
+ * kernel lives in a bl_*kernels.hip file and is reached through the launchers of bl_launch.h.
  *
  * Contexts.  A bl_amd_ctx owns one device's scratch workspace, internal streams and pinned
  * staging.  The plain entry points (bl_amd_analyze_batch_device, ...) use the calling
@@ -63,6 +63,47 @@ void release_buf(bl_buf &b) {
   b.cap = 0;
 }
 
+/* a device block of the *_host entry points, freed when the call returns; zero bytes: no block, p stays nullptr.
+ * Every step answers "did it work", so a call is one && chain and any failure is BL_UNEXPECTED. */
+struct DevMem {
+  void *p = nullptr;
+  size_t bytes;
+  explicit DevMem(size_t n) : bytes(n) {
+    if (n && hipMalloc(&p, n) != hipSuccess) p = nullptr;
+  }
+  ~DevMem() {
+    if (p) (void)hipFree(p);
+  }
+  DevMem(const DevMem &) = delete;
+  DevMem &operator=(const DevMem &) = delete;
+  bool ok() const { return p || !bytes; }
+  bool up(const void *h) const { return p && hipMemcpy(p, h, bytes, hipMemcpyHostToDevice) == hipSuccess; }
+  bool down(void *h, size_t n) const { return ok() && hipMemcpy(h, p, n, hipMemcpyDeviceToHost) == hipSuccess; }
+  bool down(void *h) const { return down(h, bytes); }
+  template <class T> T *as() const { return static_cast<T *>(p); }
+};
+
+/* the metric and the row range of a vector query (bl_amd_knn_*, bl_amd_chain_*, bl_amd_radius_*, bl_amd_groups_*) */
+bool metric_ok(int metric) { return metric == BL_AMD_KNN_DISTANCE || metric == BL_AMD_KNN_COSINE; }
+bool rows_ok(int n, int row_begin, int n_rows) {
+  return row_begin >= 0 && n_rows > 0 && row_begin < n && n_rows <= n - row_begin;
+}
+
+/* one query on context c: `launch(stream, scratch)` runs with the context locked, its device current, the workspace's
+ * last user waited for on `stream` and `buf` grown to `bytes`; then the stream's position becomes the hand-over point */
+template <class Launch>
+int query_call(bl_amd_ctx *c, void *stream, bl_buf &buf, size_t bytes, Launch launch) {
+  std::lock_guard<std::mutex> lk(c->mu);
+  DevGuard dg(c->device);
+  if (!dg.ok) return BL_UNEXPECTED;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (c->ws_used) BL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_ws, 0));
+  if (blr_ensure(buf, bytes) != BL_OK || launch(s, buf.p) != BL_OK) return BL_UNEXPECTED;
+  BL_HIP_CHECK(hipEventRecord(c->ev_ws, s));
+  c->ws_used = true;
+  return BL_OK;
+}
+
 int ctx_init(bl_amd_ctx *c, int device) {
   int count = 0;
   hipError_t e = hipGetDeviceCount(&count);
@@ -86,7 +127,7 @@ int ctx_init(bl_amd_ctx *c, int device) {
   BL_HIP_CHECK(hipMalloc(&c->tables_mem, h.size()));
   BL_HIP_CHECK(hipMemcpy(c->tables_mem, h.data(), h.size(), hipMemcpyHostToDevice));
   c->tb = blk_tables_bind(c->tables_mem);
-  if (blk_configure_device() != BL_OK) return BL_UNEXPECTED;
+  if (blk_configure_device() != BL_OK || blk_query_configure_device() != BL_OK) return BL_UNEXPECTED;
   {
     /* songs per launch group; lowered by the tests to exercise the multi-group path */
     const char *gs = getenv("BL_AMD_GROUP_SONGS");
@@ -844,31 +885,24 @@ int bl_amd_playlist_host(const struct force_vector_s *h_vecs, int n, int seed_in
   bl_amd_ctx *c = blr_default_ctx();
   if (!c) return BL_UNEXPECTED;
   DevGuard dg(c->device);
-  void *dv = nullptr, *dord = nullptr, *dd = nullptr;
-  int rc = BL_UNEXPECTED;
-  if (hipMalloc(&dv, sizeof(struct force_vector_s) * (size_t)n) == hipSuccess &&
-      hipMalloc(&dord, sizeof(int32_t) * (size_t)n) == hipSuccess &&
-      hipMalloc(&dd, sizeof(float) * (size_t)n) == hipSuccess &&
-      hipMemcpy(dv, h_vecs, sizeof(struct force_vector_s) * (size_t)n, hipMemcpyHostToDevice) == hipSuccess &&
-      bl_amd_playlist_device(static_cast<struct force_vector_s *>(dv), n, seed_index,
-                             static_cast<int32_t *>(dord), static_cast<float *>(dd), nullptr) == BL_OK &&
-      hipMemcpy(h_order, dord, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost) == hipSuccess &&
-      (!h_dist || hipMemcpy(h_dist, dd, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost) == hipSuccess))
-    rc = BL_OK;
-  if (dv) (void)hipFree(dv);
-  if (dord) (void)hipFree(dord);
-  if (dd) (void)hipFree(dd);
-  return rc;
+  DevMem dv(sizeof(struct force_vector_s) * (size_t)n), dord(sizeof(int32_t) * (size_t)n), dd(sizeof(float) * (size_t)n);
+  return dv.up(h_vecs) && dord.ok() && dd.ok() &&
+                 bl_amd_playlist_device(dv.as<struct force_vector_s>(), n, seed_index, dord.as<int32_t>(), dd.as<float>(),
+                                        nullptr) == BL_OK &&
+                 dord.down(h_order) && (!h_dist || dd.down(h_dist))
+             ? BL_OK
+             : BL_UNEXPECTED;
 }
 
-/* k nearest songs (bl_kernels.hip k_knn): every argument is checked before any device work, so a rejected call
- * leaves the output untouched.  The scratch (cosine prep, partial lists of a column split) is the context's workspace,
- * handed from call to call by ev_ws like the analysis workspace: nothing here waits for the device. */
+/* Vector queries (bl_query_kernels.hip): k nearest songs, song-to-song chains, radius lists, duplicate groups.  Every
+ * argument is checked before any device work, so a rejected call leaves the outputs untouched, and the default-context
+ * wrappers check before they fetch the context.  The scratch (cosine prep, a column split's partial results) is the
+ * context's workspace, handed from call to call by ev_ws like the analysis workspace: nothing here waits for the
+ * device. */
 static bool knn_args_ok(const void *vecs, int n, int row_begin, int n_rows, int k, int metric, const void *index,
                         const void *value) {
-  return vecs && index && value && n > 0 && k >= 1 && k <= BL_AMD_KNN_MAX_K &&
-         (metric == BL_AMD_KNN_DISTANCE || metric == BL_AMD_KNN_COSINE) && row_begin >= 0 && n_rows > 0 &&
-         row_begin < n && n_rows <= n - row_begin;
+  return vecs && index && value && n > 0 && k >= 1 && k <= BL_AMD_KNN_MAX_K && metric_ok(metric) &&
+         rows_ok(n, row_begin, n_rows);
 }
 
 int bl_amd_knn_device(const struct force_vector_s *d_vecs, int n, int row_begin, int n_rows, int k, int metric,
@@ -876,18 +910,11 @@ int bl_amd_knn_device(const struct force_vector_s *d_vecs, int n, int row_begin,
   if (!knn_args_ok(d_vecs, n, row_begin, n_rows, k, metric, d_index, d_value)) return BL_UNEXPECTED;
   bl_amd_ctx *c = blr_default_ctx();
   if (!c) return BL_UNEXPECTED;
-  std::lock_guard<std::mutex> lk(c->mu);
-  DevGuard dg(c->device);
-  if (!dg.ok) return BL_UNEXPECTED;
-  hipStream_t s = static_cast<hipStream_t>(stream);
   const bool cosine = metric == BL_AMD_KNN_COSINE;
-  if (c->ws_used) BL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_ws, 0));
-  if (blr_ensure(c->knn, blk_knn_scratch_bytes(n, n_rows, k, cosine, c->n_cu)) != BL_OK) return BL_UNEXPECTED;
-  if (blk_knn(s, d_vecs, n, row_begin, n_rows, k, cosine, c->n_cu, c->knn.p, d_index, d_value) != BL_OK)
-    return BL_UNEXPECTED;
-  BL_HIP_CHECK(hipEventRecord(c->ev_ws, s));
-  c->ws_used = true;
-  return BL_OK;
+  return query_call(c, stream, c->knn, blk_knn_scratch_bytes(n, n_rows, k, cosine, c->n_cu),
+                    [&](hipStream_t s, void *scratch) {
+                      return blk_knn(s, d_vecs, n, row_begin, n_rows, k, cosine, c->n_cu, scratch, d_index, d_value);
+                    });
 }
 
 int bl_amd_knn_host(const struct force_vector_s *h_vecs, int n, int k, int metric, int32_t *h_index,
@@ -898,47 +925,32 @@ int bl_amd_knn_host(const struct force_vector_s *h_vecs, int n, int k, int metri
   DevGuard dg(c->device);
   if (!dg.ok) return BL_UNEXPECTED;
   const size_t out = (size_t)n * k;
-  void *dv = nullptr, *di = nullptr, *dd = nullptr;
-  int rc = BL_UNEXPECTED;
-  if (hipMalloc(&dv, sizeof(struct force_vector_s) * (size_t)n) == hipSuccess &&
-      hipMalloc(&di, sizeof(int32_t) * out) == hipSuccess && hipMalloc(&dd, sizeof(float) * out) == hipSuccess &&
-      hipMemcpy(dv, h_vecs, sizeof(struct force_vector_s) * (size_t)n, hipMemcpyHostToDevice) == hipSuccess &&
-      bl_amd_knn_device(static_cast<struct force_vector_s *>(dv), n, 0, n, k, metric, static_cast<int32_t *>(di),
-                        static_cast<float *>(dd), nullptr) == BL_OK &&
-      hipMemcpy(h_index, di, sizeof(int32_t) * out, hipMemcpyDeviceToHost) == hipSuccess &&
-      (!h_value || hipMemcpy(h_value, dd, sizeof(float) * out, hipMemcpyDeviceToHost) == hipSuccess))
-    rc = BL_OK;
-  if (dv) (void)hipFree(dv);
-  if (di) (void)hipFree(di);
-  if (dd) (void)hipFree(dd);
-  return rc;
+  DevMem dv(sizeof(struct force_vector_s) * (size_t)n), di(sizeof(int32_t) * out), dd(sizeof(float) * out);
+  return dv.up(h_vecs) && di.ok() && dd.ok() &&
+                 bl_amd_knn_device(dv.as<struct force_vector_s>(), n, 0, n, k, metric, di.as<int32_t>(), dd.as<float>(),
+                                   nullptr) == BL_OK &&
+                 di.down(h_index) && (!h_value || dd.down(h_value))
+             ? BL_OK
+             : BL_UNEXPECTED;
 }
 
-/* song-to-song chains (bl_kernels.hip k_chain, k_chain_step): arguments first, then the workspace like the kNN call */
 static std::atomic<int> g_chain_force{BL_AMD_CHAIN_AUTO};
 
 static bool chain_args_ok(const void *vecs, int n, const void *seeds, int n_chains, int length, int metric,
                           const void *order, const void *value) {
-  return vecs && seeds && order && value && n > 0 && n_chains > 0 && length > 0 &&
-         (metric == BL_AMD_KNN_DISTANCE || metric == BL_AMD_KNN_COSINE);
+  return vecs && seeds && order && value && n > 0 && n_chains > 0 && length > 0 && metric_ok(metric);
 }
 
 int bl_amd_ctx_chain_device(bl_amd_ctx *c, const struct force_vector_s *d_vecs, int n, const int32_t *d_seeds,
                             int n_chains, int length, int metric, int32_t *d_order, float *d_value, void *stream) {
   if (!chain_args_ok(d_vecs, n, d_seeds, n_chains, length, metric, d_order, d_value) || !c) return BL_UNEXPECTED;
-  std::lock_guard<std::mutex> lk(c->mu);
-  DevGuard dg(c->device);
-  if (!dg.ok) return BL_UNEXPECTED;
-  hipStream_t s = static_cast<hipStream_t>(stream);
   const bool cosine = metric == BL_AMD_KNN_COSINE;
   const int force = g_chain_force.load();
-  if (c->ws_used) BL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_ws, 0));
-  if (blr_ensure(c->chain, blk_chain_scratch_bytes(n, n_chains, cosine, c->n_cu, force)) != BL_OK) return BL_UNEXPECTED;
-  if (blk_chain(s, d_vecs, n, d_seeds, n_chains, length, cosine, c->n_cu, force, c->chain.p, d_order, d_value) != BL_OK)
-    return BL_UNEXPECTED;
-  BL_HIP_CHECK(hipEventRecord(c->ev_ws, s));
-  c->ws_used = true;
-  return BL_OK;
+  return query_call(c, stream, c->chain, blk_chain_scratch_bytes(n, n_chains, cosine, c->n_cu, force),
+                    [&](hipStream_t s, void *scratch) {
+                      return blk_chain(s, d_vecs, n, d_seeds, n_chains, length, cosine, c->n_cu, force, scratch, d_order,
+                                       d_value);
+                    });
 }
 
 int bl_amd_chain_device(const struct force_vector_s *d_vecs, int n, const int32_t *d_seeds, int n_chains, int length,
@@ -959,28 +971,17 @@ int bl_amd_chain_host(const struct force_vector_s *h_vecs, int n, const int32_t 
   DevGuard dg(c->device);
   if (!dg.ok) return BL_UNEXPECTED;
   const size_t out = (size_t)n_chains * length;
-  void *dv = nullptr, *ds = nullptr, *di = nullptr, *dd = nullptr;
-  int rc = BL_UNEXPECTED;
-  if (hipMalloc(&dv, sizeof(struct force_vector_s) * (size_t)n) == hipSuccess &&
-      hipMalloc(&ds, sizeof(int32_t) * (size_t)n_chains) == hipSuccess &&
-      hipMalloc(&di, sizeof(int32_t) * out) == hipSuccess && hipMalloc(&dd, sizeof(float) * out) == hipSuccess &&
-      hipMemcpy(dv, h_vecs, sizeof(struct force_vector_s) * (size_t)n, hipMemcpyHostToDevice) == hipSuccess &&
-      hipMemcpy(ds, h_seeds, sizeof(int32_t) * (size_t)n_chains, hipMemcpyHostToDevice) == hipSuccess &&
-      bl_amd_chain_device(static_cast<struct force_vector_s *>(dv), n, static_cast<int32_t *>(ds), n_chains, length,
-                          metric, static_cast<int32_t *>(di), static_cast<float *>(dd), nullptr) == BL_OK &&
-      hipMemcpy(h_order, di, sizeof(int32_t) * out, hipMemcpyDeviceToHost) == hipSuccess &&
-      (!h_value || hipMemcpy(h_value, dd, sizeof(float) * out, hipMemcpyDeviceToHost) == hipSuccess))
-    rc = BL_OK;
-  if (dv) (void)hipFree(dv);
-  if (ds) (void)hipFree(ds);
-  if (di) (void)hipFree(di);
-  if (dd) (void)hipFree(dd);
-  return rc;
+  DevMem dv(sizeof(struct force_vector_s) * (size_t)n), ds(sizeof(int32_t) * (size_t)n_chains), di(sizeof(int32_t) * out), dd(sizeof(float) * out);
+  return dv.up(h_vecs) && ds.up(h_seeds) && di.ok() && dd.ok() &&
+                 bl_amd_chain_device(dv.as<struct force_vector_s>(), n, ds.as<int32_t>(), n_chains, length, metric,
+                                     di.as<int32_t>(), dd.as<float>(), nullptr) == BL_OK &&
+                 di.down(h_order) && (!h_value || dd.down(h_value))
+             ? BL_OK
+             : BL_UNEXPECTED;
 }
 
-/* Radius queries and duplicate groups (bl_kernels.hip k_radius_*, k_groups_*): arguments first, then the workspace
- * like the kNN call.  The distance is compared on the squared sum against bl_amd_radius_bound(radius), computed here
- * once per call. */
+/* Radius queries and duplicate groups: the distance is compared on the squared sum against
+ * bl_amd_radius_bound(radius), computed here once per call. */
 float bl_amd_radius_bound(float radius) {
   if (radius != radius) return radius;
   if (radius < 0.f) return -INFINITY;       /* no root is negative; -0 is not below 0 */
@@ -998,8 +999,7 @@ float bl_amd_radius_bound(float radius) {
 
 static bool radius_args_ok(const void *vecs, int n, int row_begin, int n_rows, int metric, float radius,
                            const void *out) {
-  return vecs && out && n > 0 && (metric == BL_AMD_KNN_DISTANCE || metric == BL_AMD_KNN_COSINE) && radius == radius &&
-         row_begin >= 0 && n_rows > 0 && row_begin < n && n_rows <= n - row_begin;
+  return vecs && out && n > 0 && metric_ok(metric) && radius == radius && rows_ok(n, row_begin, n_rows);
 }
 
 static float radius_kernel_bound(int metric, float radius) {
@@ -1009,19 +1009,12 @@ static float radius_kernel_bound(int metric, float radius) {
 int bl_amd_ctx_radius_count_device(bl_amd_ctx *c, const struct force_vector_s *d_vecs, int n, int row_begin, int n_rows,
                                    int metric, float radius, int64_t *d_offset, void *stream) {
   if (!radius_args_ok(d_vecs, n, row_begin, n_rows, metric, radius, d_offset) || !c) return BL_UNEXPECTED;
-  std::lock_guard<std::mutex> lk(c->mu);
-  DevGuard dg(c->device);
-  if (!dg.ok) return BL_UNEXPECTED;
-  hipStream_t s = static_cast<hipStream_t>(stream);
   const bool cosine = metric == BL_AMD_KNN_COSINE;
-  if (c->ws_used) BL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_ws, 0));
-  if (blr_ensure(c->radius, blk_radius_scratch_bytes(n, n_rows, cosine, c->n_cu)) != BL_OK) return BL_UNEXPECTED;
-  if (blk_radius_count(s, d_vecs, n, row_begin, n_rows, cosine, radius_kernel_bound(metric, radius), c->n_cu,
-                       c->radius.p, reinterpret_cast<long long *>(d_offset)) != BL_OK)
-    return BL_UNEXPECTED;
-  BL_HIP_CHECK(hipEventRecord(c->ev_ws, s));
-  c->ws_used = true;
-  return BL_OK;
+  return query_call(c, stream, c->radius, blk_radius_scratch_bytes(n, n_rows, cosine, c->n_cu),
+                    [&](hipStream_t s, void *scratch) {
+                      return blk_radius_count(s, d_vecs, n, row_begin, n_rows, cosine, radius_kernel_bound(metric, radius),
+                                              c->n_cu, scratch, reinterpret_cast<long long *>(d_offset));
+                    });
 }
 
 int bl_amd_radius_count_device(const struct force_vector_s *d_vecs, int n, int row_begin, int n_rows, int metric,
@@ -1035,19 +1028,13 @@ int bl_amd_ctx_radius_fill_device(bl_amd_ctx *c, const struct force_vector_s *d_
                                   int metric, float radius, const int64_t *d_offset, int32_t *d_index, float *d_value,
                                   void *stream) {
   if (!radius_args_ok(d_vecs, n, row_begin, n_rows, metric, radius, d_offset) || !d_index || !c) return BL_UNEXPECTED;
-  std::lock_guard<std::mutex> lk(c->mu);
-  DevGuard dg(c->device);
-  if (!dg.ok) return BL_UNEXPECTED;
-  hipStream_t s = static_cast<hipStream_t>(stream);
   const bool cosine = metric == BL_AMD_KNN_COSINE;
-  if (c->ws_used) BL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_ws, 0));
-  if (blr_ensure(c->radius, blk_radius_scratch_bytes(n, n_rows, cosine, c->n_cu)) != BL_OK) return BL_UNEXPECTED;
-  if (blk_radius_fill(s, d_vecs, n, row_begin, n_rows, cosine, radius_kernel_bound(metric, radius), c->n_cu,
-                      c->radius.p, reinterpret_cast<const long long *>(d_offset), d_index, d_value) != BL_OK)
-    return BL_UNEXPECTED;
-  BL_HIP_CHECK(hipEventRecord(c->ev_ws, s));
-  c->ws_used = true;
-  return BL_OK;
+  return query_call(c, stream, c->radius, blk_radius_scratch_bytes(n, n_rows, cosine, c->n_cu),
+                    [&](hipStream_t s, void *scratch) {
+                      return blk_radius_fill(s, d_vecs, n, row_begin, n_rows, cosine, radius_kernel_bound(metric, radius),
+                                             c->n_cu, scratch, reinterpret_cast<const long long *>(d_offset), d_index,
+                                             d_value);
+                    });
 }
 
 int bl_amd_radius_fill_device(const struct force_vector_s *d_vecs, int n, int row_begin, int n_rows, int metric,
@@ -1064,63 +1051,42 @@ int bl_amd_radius_host(const struct force_vector_s *h_vecs, int n, int metric, f
   if (!c) return BL_UNEXPECTED;
   DevGuard dg(c->device);
   if (!dg.ok) return BL_UNEXPECTED;
-  void *dv = nullptr, *doff = nullptr, *di = nullptr, *dd = nullptr;
-  int32_t *hi = nullptr;
-  float *hv = nullptr;
   std::vector<int64_t> off((size_t)n + 1);
-  int rc = BL_UNEXPECTED;
-  if (hipMalloc(&dv, sizeof(struct force_vector_s) * (size_t)n) == hipSuccess &&
-      hipMalloc(&doff, sizeof(int64_t) * ((size_t)n + 1)) == hipSuccess &&
-      hipMemcpy(dv, h_vecs, sizeof(struct force_vector_s) * (size_t)n, hipMemcpyHostToDevice) == hipSuccess &&
-      bl_amd_radius_count_device(static_cast<struct force_vector_s *>(dv), n, 0, n, metric, radius,
-                                 static_cast<int64_t *>(doff), nullptr) == BL_OK &&
-      hipMemcpy(off.data(), doff, sizeof(int64_t) * ((size_t)n + 1), hipMemcpyDeviceToHost) == hipSuccess) {
-    const size_t total = (size_t)off[(size_t)n], slots = total ? total : 1; /* an empty result is still a free()-able block */
-    hi = static_cast<int32_t *>(malloc(sizeof(int32_t) * slots));
-    hv = h_value ? static_cast<float *>(malloc(sizeof(float) * slots)) : nullptr;
-    if (hi && (hv || !h_value) && hipMalloc(&di, sizeof(int32_t) * slots) == hipSuccess &&
-        (!h_value || hipMalloc(&dd, sizeof(float) * slots) == hipSuccess) &&
-        bl_amd_radius_fill_device(static_cast<struct force_vector_s *>(dv), n, 0, n, metric, radius,
-                                  static_cast<int64_t *>(doff), static_cast<int32_t *>(di), static_cast<float *>(dd),
-                                  nullptr) == BL_OK &&
-        hipMemcpy(hi, di, sizeof(int32_t) * total, hipMemcpyDeviceToHost) == hipSuccess &&
-        (!h_value || hipMemcpy(hv, dd, sizeof(float) * total, hipMemcpyDeviceToHost) == hipSuccess))
-      rc = BL_OK;
-  }
-  if (dv) (void)hipFree(dv);
-  if (doff) (void)hipFree(doff);
-  if (di) (void)hipFree(di);
-  if (dd) (void)hipFree(dd);
-  if (rc == BL_OK) {
-    memcpy(h_offset, off.data(), sizeof(int64_t) * ((size_t)n + 1));
-    *h_index = hi;
-    if (h_value) *h_value = hv;
-  } else {
+  DevMem dv(sizeof(struct force_vector_s) * (size_t)n), doff(sizeof(int64_t) * off.size());
+  if (!(dv.up(h_vecs) && doff.ok() &&
+        bl_amd_radius_count_device(dv.as<struct force_vector_s>(), n, 0, n, metric, radius, doff.as<int64_t>(),
+                                   nullptr) == BL_OK &&
+        doff.down(off.data())))
+    return BL_UNEXPECTED;
+  const size_t total = (size_t)off[(size_t)n], slots = total ? total : 1; /* an empty result is still a free()-able block */
+  int32_t *hi = static_cast<int32_t *>(malloc(sizeof(int32_t) * slots));
+  float *hv = h_value ? static_cast<float *>(malloc(sizeof(float) * slots)) : nullptr;
+  DevMem di(sizeof(int32_t) * slots), dd(h_value ? sizeof(float) * slots : 0);
+  if (!(hi && (hv || !h_value) && di.ok() && dd.ok() &&
+        bl_amd_radius_fill_device(dv.as<struct force_vector_s>(), n, 0, n, metric, radius, doff.as<int64_t>(),
+                                  di.as<int32_t>(), dd.as<float>(), nullptr) == BL_OK &&
+        di.down(hi, sizeof(int32_t) * total) && (!h_value || dd.down(hv, sizeof(float) * total)))) {
     free(hi);
     free(hv);
+    return BL_UNEXPECTED;
   }
-  return rc;
+  memcpy(h_offset, off.data(), sizeof(int64_t) * off.size());
+  *h_index = hi;
+  if (h_value) *h_value = hv;
+  return BL_OK;
 }
 
 static bool groups_args_ok(const void *vecs, int n, int metric, float radius, const void *group) {
-  return vecs && group && n > 0 && (metric == BL_AMD_KNN_DISTANCE || metric == BL_AMD_KNN_COSINE) && radius == radius;
+  return vecs && group && n > 0 && metric_ok(metric) && radius == radius;
 }
 
 int bl_amd_ctx_groups_device(bl_amd_ctx *c, const struct force_vector_s *d_vecs, int n, int metric, float radius,
                              int32_t *d_group, void *stream) {
   if (!groups_args_ok(d_vecs, n, metric, radius, d_group) || !c) return BL_UNEXPECTED;
-  std::lock_guard<std::mutex> lk(c->mu);
-  DevGuard dg(c->device);
-  if (!dg.ok) return BL_UNEXPECTED;
-  hipStream_t s = static_cast<hipStream_t>(stream);
   const bool cosine = metric == BL_AMD_KNN_COSINE;
-  if (c->ws_used) BL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_ws, 0));
-  if (blr_ensure(c->radius, blk_groups_scratch_bytes(n, cosine)) != BL_OK) return BL_UNEXPECTED;
-  if (blk_groups(s, d_vecs, n, cosine, radius_kernel_bound(metric, radius), c->n_cu, c->radius.p, d_group) != BL_OK)
-    return BL_UNEXPECTED;
-  BL_HIP_CHECK(hipEventRecord(c->ev_ws, s));
-  c->ws_used = true;
-  return BL_OK;
+  return query_call(c, stream, c->radius, blk_groups_scratch_bytes(n, cosine), [&](hipStream_t s, void *scratch) {
+    return blk_groups(s, d_vecs, n, cosine, radius_kernel_bound(metric, radius), c->n_cu, scratch, d_group);
+  });
 }
 
 int bl_amd_groups_device(const struct force_vector_s *d_vecs, int n, int metric, float radius, int32_t *d_group,
@@ -1135,18 +1101,13 @@ int bl_amd_groups_host(const struct force_vector_s *h_vecs, int n, int metric, f
   if (!c) return BL_UNEXPECTED;
   DevGuard dg(c->device);
   if (!dg.ok) return BL_UNEXPECTED;
-  void *dv = nullptr, *dg_out = nullptr;
-  int rc = BL_UNEXPECTED;
-  if (hipMalloc(&dv, sizeof(struct force_vector_s) * (size_t)n) == hipSuccess &&
-      hipMalloc(&dg_out, sizeof(int32_t) * (size_t)n) == hipSuccess &&
-      hipMemcpy(dv, h_vecs, sizeof(struct force_vector_s) * (size_t)n, hipMemcpyHostToDevice) == hipSuccess &&
-      bl_amd_groups_device(static_cast<struct force_vector_s *>(dv), n, metric, radius, static_cast<int32_t *>(dg_out),
-                           nullptr) == BL_OK &&
-      hipMemcpy(h_group, dg_out, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost) == hipSuccess)
-    rc = BL_OK;
-  if (dv) (void)hipFree(dv);
-  if (dg_out) (void)hipFree(dg_out);
-  return rc;
+  DevMem dv(sizeof(struct force_vector_s) * (size_t)n), dgrp(sizeof(int32_t) * (size_t)n);
+  return dv.up(h_vecs) && dgrp.ok() &&
+                 bl_amd_groups_device(dv.as<struct force_vector_s>(), n, metric, radius, dgrp.as<int32_t>(), nullptr) ==
+                     BL_OK &&
+                 dgrp.down(h_group)
+             ? BL_OK
+             : BL_UNEXPECTED;
 }
 
 int bl_amd_chain_shape(int n, int n_chains) {
@@ -1207,18 +1168,12 @@ static int matrix_host(const struct force_vector_s *h_vecs, int n, float *h_out,
   bl_amd_ctx *c = blr_default_ctx();
   if (!c) return BL_UNEXPECTED;
   DevGuard dg(c->device);
-  void *dv = nullptr, *dout = nullptr;
-  BL_HIP_CHECK(hipMalloc(&dv, sizeof(struct force_vector_s) * (size_t)n));
-  if (hipMalloc(&dout, sizeof(float) * (size_t)n * n) != hipSuccess) { (void)hipFree(dv); return BL_UNEXPECTED; }
-  int rc = BL_UNEXPECTED;
-  if (hipMemcpy(dv, h_vecs, sizeof(struct force_vector_s) * (size_t)n, hipMemcpyHostToDevice) == hipSuccess &&
-      matrix_device(static_cast<struct force_vector_s *>(dv), n, 0, n, static_cast<float *>(dout),
-                    nullptr, cosine) == BL_OK &&
-      hipMemcpy(h_out, dout, sizeof(float) * (size_t)n * n, hipMemcpyDeviceToHost) == hipSuccess)
-    rc = BL_OK;
-  (void)hipFree(dv);
-  (void)hipFree(dout);
-  return rc;
+  DevMem dv(sizeof(struct force_vector_s) * (size_t)n), dout(sizeof(float) * (size_t)n * n);
+  return dv.up(h_vecs) && dout.ok() &&
+                 matrix_device(dv.as<struct force_vector_s>(), n, 0, n, dout.as<float>(), nullptr, cosine) == BL_OK &&
+                 dout.down(h_out)
+             ? BL_OK
+             : BL_UNEXPECTED;
 }
 
 int bl_amd_distance_matrix_host(const struct force_vector_s *h_vecs, int n, float *h_out) {

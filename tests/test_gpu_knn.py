@@ -52,7 +52,7 @@ def assert_same(idx, val, want_idx, want_val, nan_bits=True):
 
 
 def ord_key(val, idx):
-    """the contract's ascending order as one unsigned 64-bit key (see bl_kernels.hip knn_ord); pass -value for the
+    """the contract's ascending order as one unsigned 64-bit key (see bl_metric.h bl_ord); pass -value for the
     cosine"""
     u = val.view(np.uint32).copy()
     u[val == 0] = 0

@@ -1,0 +1,249 @@
+#!/usr/bin/env python3
+"""Do two source trees compile to the same gfx950 kernels?
+
+    tools/kernel_asm_diff.py OLD NEW [--plans] [--keep DIR]
+
+OLD and NEW are each a checkout (a directory with bliss_amd/csrc/Makefile) or anything `git archive` accepts
+(a commit, a tag, HEAD).  Every bliss_amd/csrc/*.hip file with a __global__ in it is compiled device-only to
+assembly with the command line its own Makefile uses for the object (so -ffp-contract=off and the rest are the
+tree's, not this script's), and every function of the two sides is compared by name, wherever in the tree it was
+defined:
+
+  * the instruction text, with comments, directives and debug/section noise dropped and the local labels renumbered
+    in order of appearance (their numbers depend on the position of the function in its file);
+  * every .amdhsa_* field of the kernel descriptor (VGPR / AGPR / SGPR granules, LDS, scratch, ...) and the
+    compiler's own report behind the kernel: TotalNumSgprs, NumVgprs, NumAgprs, ScratchSize, LDSByteSize, Occupancy.
+
+Prints the kernels that differ or exist on one side only and exits 1 if there are any.  Needs hipcc, no GPU.
+
+--plans also checks, on the NEW tree, that the launch layer's blk_split_plan returns what the two plan functions it
+replaced returned (knn_plan: 4 queries per wave, splits of at least 4 096 columns; radius_plan: 8 and 1 024), over a
+grid of (n, n_rows, n_cu).  The reference is the old formulas transcribed below, with C's integer semantics.
+"""
+import argparse
+import os
+import re
+import shlex
+import subprocess
+import sys
+import tempfile
+
+CSRC = os.path.join("bliss_amd", "csrc")
+REPORT = ("TotalNumSgprs", "NumVgprs", "NumAgprs", "ScratchSize", "LDSByteSize", "Occupancy")
+
+
+def materialise(spec, tmp, name):
+    if os.path.isfile(os.path.join(spec, CSRC, "Makefile")):
+        return os.path.abspath(spec)
+    out = os.path.join(tmp, name)
+    os.makedirs(out)
+    top = subprocess.check_output(["git", "rev-parse", "--show-toplevel"], text=True).strip()
+    ar = subprocess.Popen(["git", "-C", top, "archive", spec, "bliss_amd", "include"], stdout=subprocess.PIPE)
+    subprocess.check_call(["tar", "-x", "-C", out], stdin=ar.stdout)
+    if ar.wait() != 0:
+        sys.exit(f"git archive {spec} failed")
+    return out
+
+
+def object_command(csrc, stem):
+    """the hipcc command line of the Makefile for <stem>.o, as a list"""
+    out = subprocess.check_output(["make", "-C", csrc, "--no-print-directory", "-n", "-B", stem + ".o"], text=True)
+    for line in out.splitlines():
+        words = shlex.split(line)
+        if words and stem + ".hip" in words and "-c" in words:
+            return words
+    sys.exit(f"{csrc}/Makefile has no rule that compiles {stem}.hip")
+
+
+def device_asm(tree, workdir):
+    """{file stem: assembly text} of the tree's kernel translation units"""
+    csrc = os.path.join(tree, CSRC)
+    res = {}
+    for fn in sorted(os.listdir(csrc)):
+        if not fn.endswith(".hip") or "__global__" not in open(os.path.join(csrc, fn)).read():
+            continue
+        stem = fn[:-4]
+        cmd = object_command(csrc, stem)
+        o = cmd.index("-o")
+        dst = os.path.join(workdir, stem + ".s")
+        cmd = cmd[:o] + cmd[o + 2:]
+        cmd[cmd.index("-c")] = "-S"
+        subprocess.check_call(cmd + ["--cuda-device-only", "-Wno-unused-command-line-argument", "-o", dst], cwd=csrc)
+        res[stem] = open(dst).read()
+    return res
+
+
+LABEL = re.compile(r"\.L[A-Za-z_]*\d+(?:_\d+)?")
+
+
+def functions(asm):
+    """{symbol: {"text": [instructions], "desc": {field: value}, "report": {name: value}}}"""
+    fns, cur, last, in_desc = {}, None, None, False
+    for raw in asm.splitlines():
+        if raw.lstrip().startswith(";"):
+            m = re.match(r"\s*;\s*(\w+):\s*(\S+)", raw)
+            if m and cur is None and last and m.group(1) in REPORT:
+                fns[last]["report"].setdefault(m.group(1), m.group(2))
+            continue
+        line = re.sub(r"\s+", " ", raw.split(";", 1)[0].strip())
+        m = re.match(r"\.type ([\w$.]+),@function", line)
+        if m:
+            cur = m.group(1)
+            fns[cur] = {"text": [], "desc": {}, "report": {}}
+        elif cur is None or not line or line == cur + ":":
+            pass
+        elif line.startswith(".amdhsa_kernel ") or line == ".end_amdhsa_kernel":
+            in_desc = line != ".end_amdhsa_kernel"
+        elif in_desc:
+            field, _, value = line.partition(" ")
+            fns[cur]["desc"][field] = value
+        elif re.match(r"\.Lfunc_end\d+:", line):
+            fns[cur]["text"] = renumber(fns[cur]["text"])
+            last, cur = cur, None
+        elif not line.startswith(".") or (line.startswith(".L") and line.endswith(":")):
+            fns[cur]["text"].append(line)
+    return fns
+
+
+def renumber(body):
+    names = {}
+    for line in body:
+        for lab in LABEL.findall(line):
+            names.setdefault(lab, f".L{len(names)}")
+    return [LABEL.sub(lambda m: names[m.group(0)], line) for line in body]
+
+
+def demangle(syms):
+    try:
+        out = subprocess.run(["c++filt"], input="\n".join(syms), text=True, capture_output=True, check=True).stdout
+        return dict(zip(syms, out.splitlines()))
+    except (OSError, subprocess.CalledProcessError):
+        return {s: s for s in syms}
+
+
+def compare(old, new):
+    fo, fn = {}, {}
+    for side, dst in ((old, fo), (new, fn)):
+        for stem, asm in side.items():
+            for sym, f in functions(asm).items():
+                f["file"] = stem + ".hip"
+                dst[sym] = f
+    nice = demangle(sorted(set(fo) | set(fn)))
+    bad = 0
+    for sym in sorted(set(fo) | set(fn)):
+        a, b = fo.get(sym), fn.get(sym)
+        why = []
+        if a is None or b is None:
+            why.append("only in " + ("NEW" if a is None else "OLD"))
+        else:
+            if a["text"] != b["text"]:
+                first = next((i for i, (x, y) in enumerate(zip(a["text"], b["text"])) if x != y),
+                             min(len(a["text"]), len(b["text"])))
+                why.append(f"instructions differ ({len(a['text'])} vs {len(b['text'])} lines, first at {first}: "
+                           f"{a['text'][first:first + 1]} vs {b['text'][first:first + 1]})")
+            for part in ("desc", "report"):
+                for k in sorted(set(a[part]) | set(b[part])):
+                    if a[part].get(k) != b[part].get(k):
+                        why.append(f"{k}: {a[part].get(k)} vs {b[part].get(k)}")
+        if why:
+            bad += 1
+            print(f"DIFF {nice[sym]}\n     " + "\n     ".join(why))
+    kernels = [s for s in fn if fn[s]["desc"]]
+    moved = sum(1 for s in kernels if s in fo and fo[s]["file"] != fn[s]["file"])
+    print(f"{len(set(fo) | set(fn))} functions compared ({len(kernels)} kernels in NEW, {moved} of them in another "
+          f"file than in OLD): {bad} differ")
+    return bad
+
+
+# ---- --plans ---------------------------------------------------------------------------------------------------
+
+PLAN_N = (1, 63, 64, 65, 1023, 1024, 4095, 4096, 10000, 65536, 1000000, 2**31 - 1)
+PLAN_CU = (1, 64, 256, 304)
+PLAN_KINDS = (("knn_plan", 4, 4096), ("radius_plan", 8, 1024))
+
+HARNESS = r"""
+#include <stdio.h>
+void blk_split_plan(int n, int n_rows, int n_cu, int qpw, int min_cols, int *n_split, int *cols);
+int main() {
+  int n, n_rows, n_cu, qpw, min_cols;
+  while (scanf("%d %d %d %d %d", &n, &n_rows, &n_cu, &qpw, &min_cols) == 5) {
+    int n_split = 0, cols = 0;
+    blk_split_plan(n, n_rows, n_cu, qpw, min_cols, &n_split, &cols);
+    printf("%d %d\n", n_split, cols);
+  }
+  return 0;
+}
+"""
+
+
+def c_int(x):
+    return (x + 2**31) % 2**32 - 2**31
+
+
+def c_div(a, b):
+    q = abs(a) // abs(b)
+    return q if (a < 0) == (b < 0) else -q
+
+
+def old_plan(n, n_rows, n_cu, qpw, min_cols):
+    """knn_plan / radius_plan of the commit before the query kernels got their own file (long long arithmetic, the
+    two results narrowed to int)"""
+    waves = (n_rows + qpw - 1) // qpw
+    target = n_cu * 16
+    split = 1
+    if waves < target:
+        split = min(min((target + waves - 1) // waves, max(1, n // min_cols)), 1024)
+    cols = c_int(((n + split - 1) // split + 63) // 64 * 64)
+    n_split = c_int(c_div(n + cols - 1, cols))
+    return n_split, cols
+
+
+def check_plans(tree, workdir):
+    csrc = os.path.join(tree, CSRC)
+    subprocess.check_call(["make", "-C", csrc, "--no-print-directory", "bl_query_kernels.o"], stdout=subprocess.DEVNULL)
+    src = os.path.join(workdir, "plan_harness.cpp")
+    exe = os.path.join(workdir, "plan_harness")
+    open(src, "w").write(HARNESS)
+    hipcc = object_command(csrc, "bl_query_kernels")[0]
+    subprocess.check_call([hipcc, "-O1", "-c", src, "-o", exe + ".o"])
+    subprocess.check_call([hipcc, exe + ".o", os.path.join(csrc, "bl_query_kernels.o"), "-o", exe])
+    cases = [(n, r, cu, q, mc) for _, q, mc in PLAN_KINDS for n in PLAN_N
+             for r in sorted({1, 4, 8, 33, 1000, n}) for cu in PLAN_CU]
+    out = subprocess.run([exe], input="".join("%d %d %d %d %d\n" % c for c in cases), text=True, capture_output=True,
+                         check=True).stdout.split()
+    got = list(zip(map(int, out[0::2]), map(int, out[1::2])))
+    if len(got) != len(cases):
+        sys.exit("plan harness answered %d of %d cases" % (len(got), len(cases)))
+    bad = 0
+    for c, g in zip(cases, got):
+        want = old_plan(*c)
+        if g != want:
+            bad += 1
+            print("PLAN n=%d n_rows=%d n_cu=%d qpw=%d min_cols=%d:" % c, "(n_split, cols) =", g, "want", want)
+    print(f"{len(cases)} split plans compared with the old knn_plan / radius_plan formulas: {bad} differ")
+    return bad
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("old")
+    ap.add_argument("new")
+    ap.add_argument("--plans", action="store_true", help="also check blk_split_plan of NEW against the old formulas")
+    ap.add_argument("--keep", metavar="DIR", help="leave the assembly files here")
+    a = ap.parse_args()
+    with tempfile.TemporaryDirectory() as tmp:
+        work = a.keep or tmp
+        sides = []
+        for name, spec in (("old", a.old), ("new", a.new)):
+            tree = materialise(spec, tmp, name + "_tree")
+            wd = os.path.join(work, name)
+            os.makedirs(wd, exist_ok=True)
+            sides.append((tree, wd))
+        bad = compare(device_asm(*sides[0]), device_asm(*sides[1]))
+        if a.plans:
+            bad += check_plans(*sides[1])
+    sys.exit(1 if bad else 0)
+
+
+if __name__ == "__main__":
+    main()
