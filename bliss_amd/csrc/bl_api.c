@@ -2,7 +2,7 @@
  * bl_api.c — the reference's C API (include/bliss.h) on top of the HIP path.
  *
  * Host code stays in C, as in the reference; every analysis result comes from
- * the kernels in bl_kernels.hip through the thin launch layer declared in
+ * the kernels in the bl_*_kernels.hip files through the thin launch layer declared in
  * bl_device.h.  There is no CPU implementation of the analysis in this
  * library: without a usable HIP device the analysis entry points print a
  * message and return BL_UNEXPECTED (or the float conversion of it, as the

@@ -1,6 +1,6 @@
 /*
  * bl_device.h — internal interface between the C host layer (bl_api.c) and the
- * HIP translation unit (bl_kernels.hip).  Not installed; the public C-ABI is
+ * HIP translation units (bl_launch.h names them).  Not installed; the public C-ABI is
  * include/bliss.h + include/bliss_amd.h.
  */
 #ifndef BL_DEVICE_H_

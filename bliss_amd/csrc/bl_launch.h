@@ -1,10 +1,11 @@
 /*
  * bl_launch.h — internal seam between the kernel translation units (device code + launch
- * geometry: bl_kernels.hip the per-song analysis and the pairwise matrix, bl_query_kernels.hip
- * the vector queries, bl_rs_kernels.hip the rate converter) and the runtime (bl_runtime.hip:
- * contexts, workspaces, streams, the C-ABI of include/bliss_amd.h; bl_multi.hip: the
- * multi-device corpus path).  Also BL_HIP_CHECK, which every .hip file uses.
- * C++ only, not installed.
+ * geometry: bl_kernels.hip the launch order of the per-song analysis, whose stages are
+ * bl_stats_kernels.hip, bl_freq_kernels.hip and bl_env_kernels.hip; bl_matrix_kernels.hip the
+ * pairwise matrix, bl_query_kernels.hip the vector queries, bl_rs_kernels.hip the rate converter)
+ * and the runtime (bl_runtime.hip: contexts, workspaces, streams, the C-ABI of
+ * include/bliss_amd.h; bl_multi.hip: the multi-device corpus path).  Also BL_HIP_CHECK, which
+ * every .hip file uses.  C++ only, not installed.
  */
 #ifndef BL_LAUNCH_H_
 #define BL_LAUNCH_H_
@@ -80,12 +81,38 @@ enum { PK_SCAN, PK_AMP, PK_FREQ, PK_FREQ_FIN, PK_ENV, PK_TAIL, PK_DIST, PK_FREQ_
  * launch, 0 after it, on the stream the kernel is launched on */
 typedef void (*blk_mark_fn)(void *user, int kernel_id, hipStream_t stream, int begin);
 
+/* what a launcher puts around a launch: begin at construction, end when the scope closes */
+struct Mark {
+  blk_mark_fn fn;
+  void *user;
+  int k;
+  hipStream_t s;
+  Mark(blk_mark_fn f, void *u, int kk, hipStream_t ss) : fn(f), user(u), k(kk), s(ss) {
+    if (fn) fn(user, k, s, 1);
+  }
+  ~Mark() {
+    if (fn) fn(user, k, s, 0);
+  }
+};
+
+/* grid.x of a (grid.x, songs) launch */
+inline int grid_x_for(long long units_max, int n_songs, int blocks_per_cu, int n_cu) {
+  /* enough blocks to fill the chip several times over, never more than the
+   * longest song has work for */
+  long long want = ((long long)n_cu * blocks_per_cu + n_songs - 1) / n_songs;
+  if (want < 1) want = 1;
+  if (want > units_max) want = units_max;
+  if (want < 1) want = 1;
+  if (want > 65535) want = 65535;
+  return (int)want;
+}
+
 /* ---- launchers (all asynchronous on the given stream, current device) ------ */
 
 size_t blk_tables_bytes(void);
 void blk_tables_fill_host(unsigned char *h);           /* twiddles + Hann, double math on the host */
 bl_tables blk_tables_bind(const void *d_mem);          /* pointers into the device copy */
-int blk_configure_device(void);                        /* dynamic-LDS attributes, once per device */
+int blk_configure_device(void);                        /* dynamic-LDS attributes of the analysis stages, once per device */
 
 struct blk_analyze_args {
   const int16_t *pcm;        /* arena base */
@@ -106,10 +133,44 @@ struct blk_analyze_args {
   blk_mark_fn mark;          /* may be nullptr */
   void *mark_user;
 };
-int blk_analyze(const blk_analyze_args &a);
+int blk_analyze(const blk_analyze_args &a);             /* bl_kernels.hip: the launch order of the stages below */
+
+/* ---- the stages of blk_analyze, one translation unit each --------------------- */
+/* Each launches on a.stream unless it takes a stream, for all a.n_songs songs unless it takes a range. */
+
+/* statistics, amplitude, force (bl_stats_kernels.hip) */
+void blk_stats_init(const blk_analyze_args &a);
+int blk_pcm_scan(const blk_analyze_args &a);            /* zeroes a.hist first; k_freq_scan stands in for it when fused */
+void blk_song_prep(const blk_analyze_args &a);          /* k_trim, k_song_prep, k_variance_wrap(_finish) */
+void blk_amp_finish(const blk_analyze_args &a, hipStream_t s);
+void blk_force(const blk_analyze_args &a);
+/* frequency (bl_freq_kernels.hip) */
+int blk_freq_configure_device(void);
+bool blk_freq_scan_fused(int what);                     /* do the statistics ride along with the frequency pass? */
+void blk_freq_scan(const blk_analyze_args &a);          /* k_freq_scan: frequency pass + statistics */
+void blk_freq_frames(const blk_analyze_args &a, hipStream_t s);
+void blk_freq_finish(const blk_analyze_args &a, hipStream_t s);
+/* envelope (bl_env_kernels.hip) */
+int blk_env_configure_device(void);
+int blk_fir_mode();                                     /* 0 | 1 | 2: bl_amd_set_fir_mode, BL_AMD_FIR_FUSED, the compiled default */
+/* window energies of the songs [first, first + count), the longest of them maxn samples */
+int blk_env_windows(const blk_analyze_args &a, int fir_mode, int first, int count, int maxn);
+void blk_env_tail(const blk_analyze_args &a, hipStream_t s, int first, int count);
+/* bl_mean / bl_variance helpers (bl_stats_kernels.hip): one song described by d_songs[0] */
+int blk_scan_one(hipStream_t s, const int16_t *pcm, const bl_dsong *d_songs, bl_dstats *d_stats,
+                 unsigned *d_hist, int n, int n_cu);
+int blk_variance_wrap_one(hipStream_t s, const int16_t *pcm, const bl_dsong *d_songs,
+                          bl_dstats *d_stats, int n, int n_cu);
+
+/* ---- benchmark corpus and sample narrowing (bl_kernels.hip) -------------------- */
 
 int blk_synth(hipStream_t s, int16_t *pcm, const bl_dsong *d_songs, int n_songs, int max_n,
               int n_cu, unsigned seed_base, unsigned rate);
+/* out[i] = (int16)(in[i] >> 16): the same-rate S32 -> S16 narrowing (SURVEY.md §8d config 5) */
+int blk_narrow_s32(hipStream_t s, const int32_t *d_in, int16_t *d_out, size_t n, int n_cu);
+
+/* ---- matrix, playlist and self-tests over force vectors (bl_matrix_kernels.hip) -- */
+
 int blk_pairwise(hipStream_t s, const struct force_vector_s *d_vecs, int n, int row_begin,
                  int n_rows, float *d_out, bool cosine, blk_mark_fn mark, void *mark_user);
 /* exhaustive self-test of bl_sqrt.h over f32 bit patterns [first, first + count): d_counts[0..2] +=
@@ -119,19 +180,12 @@ int blk_sqrt_sweep(hipStream_t s, unsigned long long first, unsigned long long c
 int blk_cos_sweep(hipStream_t s, unsigned long long seed, int per_thread, unsigned long long *d_counts, int n_cu);
 int blk_playlist(hipStream_t s, const struct force_vector_s *d_vecs, int n, int seed_index,
                  int32_t *d_order, float *d_dist);
-/* out[i] = (int16)(in[i] >> 16): the same-rate S32 -> S16 narrowing (SURVEY.md §8d config 5) */
-int blk_narrow_s32(hipStream_t s, const int32_t *d_in, int16_t *d_out, size_t n, int n_cu);
 /* out[order[i]] = in[i] for 16-byte force vectors (shard-major -> caller order) */
 int blk_scatter_vecs(hipStream_t s, const struct force_vector_s *d_in, const int32_t *d_order,
                      struct force_vector_s *d_out, int n);
 /* force vectors of a result array, in result order */
 int blk_extract_vecs(hipStream_t s, const bl_amd_song_result *d_res, struct force_vector_s *d_out,
                      int n);
-/* bl_mean / bl_variance helpers: one song described by d_songs[0] */
-int blk_scan_one(hipStream_t s, const int16_t *pcm, const bl_dsong *d_songs, bl_dstats *d_stats,
-                 unsigned *d_hist, int n, int n_cu);
-int blk_variance_wrap_one(hipStream_t s, const int16_t *pcm, const bl_dsong *d_songs,
-                          bl_dstats *d_stats, int n, int n_cu);
 
 /* ---- vector queries over force vectors (bl_query_kernels.hip) ------------------ */
 

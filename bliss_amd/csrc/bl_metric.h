@@ -1,7 +1,8 @@
 /*
  * bl_metric.h — the per-pair arithmetic of bl_distance / bl_cosine_similarity on the device, shared by k_pairwise
- * (bl_kernels.hip) and the vector queries (bl_query_kernels.hip), so that a value a query lists has the bits of the
- * matrix entry.  Also the 64-bit (value, song) key that gives the queries their total order, and bl_wave_sync.
+ * (bl_matrix_kernels.hip) and the vector queries (bl_query_kernels.hip), so that a value a query lists has the bits of the
+ * matrix entry.  Also the 64-bit (value, song) key that gives the queries their total order, and bl_wave_sync,
+ * which the frequency and envelope kernels use as well.
  * Everything is __device__ __forceinline__ and follows the reference's unfused f32 arithmetic operation by operation
  * (-ffp-contract=off): the operand order of every expression here is part of the contract.
  */

@@ -1,9 +1,9 @@
 /*
  * bl_query_kernels.hip — gfx950 kernels and launch layer of the vector queries over force vectors: answers that
- * would otherwise be read off the N x N matrix of k_pairwise (bl_kernels.hip), without building it.  The queries
+ * would otherwise be read off the N x N matrix of k_pairwise (bl_matrix_kernels.hip), without building it.  The queries
  * share one design: a listed value has the bits of the matrix entry (bl_metric.h), a 64-bit (value, song) key gives
  * the order, the cosine takes a per-song "prep" array computed once per call, and with few query rows the columns are
- * split over blockIdx.y.  Must be compiled with -ffp-contract=off, like bl_kernels.hip.
+ * split over blockIdx.y.  Must be compiled with -ffp-contract=off, like every kernel file.
  *
  * Kernels:
  *   k_knn_prep     cosine: (root, reciprocal root) of |v|^2 per song

@@ -1,6 +1,6 @@
 /*
  * bl_resample.h — internal: the rate converter behind bl_audio_decode() (bl_resample.c) and the
- * plan (filter bank + stepping) that the device form (k_resample, bl_kernels.hip) shares with it.
+ * plan (filter bank + stepping) that the device form (k_resample_*, bl_rs_kernels.hip) shares with it.
  */
 #ifndef BL_RESAMPLE_H_
 #define BL_RESAMPLE_H_

@@ -25,6 +25,12 @@ def test_committed_profile_is_read_and_scaled():
     assert 1.9 < p["whole_step_traffic_ratio"] < 2.3  # two passes over the PCM (k_freq_scan, k_env_windows3)
 
 
+# the files that hold the analysis kernels the profile describes, their launch order and their arithmetic headers
+KERNEL_SOURCES = ["bliss_amd/csrc/" + f for f in (
+    "bl_kernels.hip", "bl_stats_kernels.hip", "bl_freq_kernels.hip", "bl_env_kernels.hip", "bl_scan.h", "bl_fir.h",
+    "bl_fft.h", "bl_fft_lavc.h", "bl_fft_tan.h", "bl_tail.h")]
+
+
 def test_committed_profile_belongs_to_the_committed_kernels():
     """The bench line scales the counters of the newest profiles/*_hbm_traffic.json to its launch: that profile must
     have been taken at (or after) the last commit that touched the kernels, or its numbers describe other code."""
@@ -34,7 +40,7 @@ def test_committed_profile_belongs_to_the_committed_kernels():
     head = (p.get("git_head") or "").split("+")[0]
     git = ["git", "-C", ROOT]
     try:
-        last = subprocess.run(git + ["log", "-1", "--format=%H", "--", "bliss_amd/csrc/bl_kernels.hip", "bliss_amd/csrc/bl_fft.h"],
+        last = subprocess.run(git + ["log", "-1", "--format=%H", "--"] + KERNEL_SOURCES,
                               stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True, check=True).stdout.strip()
     except (OSError, subprocess.CalledProcessError):
         pytest.skip("not a git checkout")

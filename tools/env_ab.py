@@ -4,7 +4,7 @@ corpus analysed with every table, results compared field by field with the shipp
 HIP events, and — for --probe tables — the s_memtime stamps of workgroup (0, 0) summarised per wave: where a
 compute wave's round goes (arithmetic phases, exchange phases, the wait in front of the hand-over).
 A table is six hex digits, one priority (0..3) per phase, phase 0 in the lowest digit; the measurement build
-instantiates the ones of EV_PRIO_TABS (bl_kernels.hip) beside the shipped 222011.  Prints one JSON object.
+instantiates the ones of EV_PRIO_TABS (bl_env_kernels.hip) beside the shipped 222011.  Prints one JSON object.
 usage: python tools/env_ab.py [--songs 1024] [--seconds 180] [--tabs 000000,111111,322110] [--probe 222011] [--reps 3]"""
 import argparse
 import ctypes as C

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Do two source trees compile to the same gfx950 kernels?
 
-    tools/kernel_asm_diff.py OLD NEW [--plans] [--keep DIR]
+    tools/kernel_asm_diff.py OLD NEW [--make VAR=VALUE ...] [--keep DIR]
 
 OLD and NEW are each a checkout (a directory with bliss_amd/csrc/Makefile) or anything `git archive` accepts
 (a commit, a tag, HEAD).  Every bliss_amd/csrc/*.hip file with a __global__ in it is compiled device-only to
@@ -16,9 +16,9 @@ defined:
 
 Prints the kernels that differ or exist on one side only and exits 1 if there are any.  Needs hipcc, no GPU.
 
---plans also checks, on the NEW tree, that the launch layer's blk_split_plan returns what the two plan functions it
-replaced returned (knn_plan: 4 queries per wave, splits of at least 4 096 columns; radius_plan: 8 and 1 024), over a
-grid of (n, n_rows, n_cu).  The reference is the old formulas transcribed below, with C's integer semantics.
+--make VAR=VALUE (repeatable) is handed to both Makefiles, so the other builds can be compared too: --make MEASURE=1
+is the measurement build (every k_env_windows3 priority table, every k_pairwise root), --make XDEFS=-DBL_AMD_CHECKED_HIST
+the one with the range-tested histogram adds.
 """
 import argparse
 import os
@@ -45,9 +45,10 @@ def materialise(spec, tmp, name):
     return out
 
 
-def object_command(csrc, stem):
-    """the hipcc command line of the Makefile for <stem>.o, as a list"""
-    out = subprocess.check_output(["make", "-C", csrc, "--no-print-directory", "-n", "-B", stem + ".o"], text=True)
+def object_command(csrc, stem, make_vars):
+    """the hipcc command line of the Makefile for <stem>.o, as a list (O=o: MEASURE=1 would rename the objects)"""
+    out = subprocess.check_output(["make", "-C", csrc, "--no-print-directory", "-n", "-B", "O=o", *make_vars, stem + ".o"],
+                                  text=True)
     for line in out.splitlines():
         words = shlex.split(line)
         if words and stem + ".hip" in words and "-c" in words:
@@ -55,7 +56,7 @@ def object_command(csrc, stem):
     sys.exit(f"{csrc}/Makefile has no rule that compiles {stem}.hip")
 
 
-def device_asm(tree, workdir):
+def device_asm(tree, workdir, make_vars):
     """{file stem: assembly text} of the tree's kernel translation units"""
     csrc = os.path.join(tree, CSRC)
     res = {}
@@ -63,7 +64,7 @@ def device_asm(tree, workdir):
         if not fn.endswith(".hip") or "__global__" not in open(os.path.join(csrc, fn)).read():
             continue
         stem = fn[:-4]
-        cmd = object_command(csrc, stem)
+        cmd = object_command(csrc, stem, make_vars)
         o = cmd.index("-o")
         dst = os.path.join(workdir, stem + ".s")
         cmd = cmd[:o] + cmd[o + 2:]
@@ -155,80 +156,12 @@ def compare(old, new):
     return bad
 
 
-# ---- --plans ---------------------------------------------------------------------------------------------------
-
-PLAN_N = (1, 63, 64, 65, 1023, 1024, 4095, 4096, 10000, 65536, 1000000, 2**31 - 1)
-PLAN_CU = (1, 64, 256, 304)
-PLAN_KINDS = (("knn_plan", 4, 4096), ("radius_plan", 8, 1024))
-
-HARNESS = r"""
-#include <stdio.h>
-void blk_split_plan(int n, int n_rows, int n_cu, int qpw, int min_cols, int *n_split, int *cols);
-int main() {
-  int n, n_rows, n_cu, qpw, min_cols;
-  while (scanf("%d %d %d %d %d", &n, &n_rows, &n_cu, &qpw, &min_cols) == 5) {
-    int n_split = 0, cols = 0;
-    blk_split_plan(n, n_rows, n_cu, qpw, min_cols, &n_split, &cols);
-    printf("%d %d\n", n_split, cols);
-  }
-  return 0;
-}
-"""
-
-
-def c_int(x):
-    return (x + 2**31) % 2**32 - 2**31
-
-
-def c_div(a, b):
-    q = abs(a) // abs(b)
-    return q if (a < 0) == (b < 0) else -q
-
-
-def old_plan(n, n_rows, n_cu, qpw, min_cols):
-    """knn_plan / radius_plan of the commit before the query kernels got their own file (long long arithmetic, the
-    two results narrowed to int)"""
-    waves = (n_rows + qpw - 1) // qpw
-    target = n_cu * 16
-    split = 1
-    if waves < target:
-        split = min(min((target + waves - 1) // waves, max(1, n // min_cols)), 1024)
-    cols = c_int(((n + split - 1) // split + 63) // 64 * 64)
-    n_split = c_int(c_div(n + cols - 1, cols))
-    return n_split, cols
-
-
-def check_plans(tree, workdir):
-    csrc = os.path.join(tree, CSRC)
-    subprocess.check_call(["make", "-C", csrc, "--no-print-directory", "bl_query_kernels.o"], stdout=subprocess.DEVNULL)
-    src = os.path.join(workdir, "plan_harness.cpp")
-    exe = os.path.join(workdir, "plan_harness")
-    open(src, "w").write(HARNESS)
-    hipcc = object_command(csrc, "bl_query_kernels")[0]
-    subprocess.check_call([hipcc, "-O1", "-c", src, "-o", exe + ".o"])
-    subprocess.check_call([hipcc, exe + ".o", os.path.join(csrc, "bl_query_kernels.o"), "-o", exe])
-    cases = [(n, r, cu, q, mc) for _, q, mc in PLAN_KINDS for n in PLAN_N
-             for r in sorted({1, 4, 8, 33, 1000, n}) for cu in PLAN_CU]
-    out = subprocess.run([exe], input="".join("%d %d %d %d %d\n" % c for c in cases), text=True, capture_output=True,
-                         check=True).stdout.split()
-    got = list(zip(map(int, out[0::2]), map(int, out[1::2])))
-    if len(got) != len(cases):
-        sys.exit("plan harness answered %d of %d cases" % (len(got), len(cases)))
-    bad = 0
-    for c, g in zip(cases, got):
-        want = old_plan(*c)
-        if g != want:
-            bad += 1
-            print("PLAN n=%d n_rows=%d n_cu=%d qpw=%d min_cols=%d:" % c, "(n_split, cols) =", g, "want", want)
-    print(f"{len(cases)} split plans compared with the old knn_plan / radius_plan formulas: {bad} differ")
-    return bad
-
-
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("old")
     ap.add_argument("new")
-    ap.add_argument("--plans", action="store_true", help="also check blk_split_plan of NEW against the old formulas")
+    ap.add_argument("--make", action="append", default=[], metavar="VAR=VALUE", dest="make_vars",
+                    help="a make variable for both trees' Makefiles (repeatable), e.g. MEASURE=1")
     ap.add_argument("--keep", metavar="DIR", help="leave the assembly files here")
     a = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmp:
@@ -239,9 +172,7 @@ def main():
             wd = os.path.join(work, name)
             os.makedirs(wd, exist_ok=True)
             sides.append((tree, wd))
-        bad = compare(device_asm(*sides[0]), device_asm(*sides[1]))
-        if a.plans:
-            bad += check_plans(*sides[1])
+        bad = compare(device_asm(*sides[0], a.make_vars), device_asm(*sides[1], a.make_vars))
     sys.exit(1 if bad else 0)
 
 

@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
-"""Static instruction budget of k_env_windows3 per phase: cross-compiles bl_kernels.hip for
+"""Static instruction budget of k_env_windows3 per phase: cross-compiles bl_env_kernels.hip for
 gfx950 to assembly (no GPU needed) and, for the FIR mode 0 / 1 / 2 instantiations of the product priority table
 (BL_ENV_PRIO as the source defines it; --all-tables: every table a measurement build instantiates), counts the VALU, f64, DPP and LDS instructions between consecutive s_setprio markers, plus the kernel's VGPR count and
 spills.  The compute waves' round is the stretch of segments that starts with phase 0; the setprio value of each
 segment is printed beside it so that the phases can be told apart whatever the table.
-usage: python tools/valu_budget.py [--src bliss_amd/csrc/bl_kernels.hip] [--json] [--all-tables]"""
+usage: python tools/valu_budget.py [--src bliss_amd/csrc/bl_env_kernels.hip] [--json] [--all-tables]"""
 import argparse
 import json
 import os
@@ -95,7 +95,7 @@ def segments(body):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--src", default=os.path.join(ROOT, "bliss_amd", "csrc", "bl_kernels.hip"))
+    ap.add_argument("--src", default=os.path.join(ROOT, "bliss_amd", "csrc", "bl_env_kernels.hip"))
     ap.add_argument("--json", action="store_true")
     ap.add_argument("--all-tables", action="store_true")
     a = ap.parse_args()
