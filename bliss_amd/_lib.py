@@ -121,9 +121,15 @@ SYMBOLS = {
     "bl_amd_selftest_cos": (C.c_int, [_P(C.c_uint64), C.c_uint64]),
     "bl_amd_playlist_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bl_amd_playlist_host": (C.c_int, [_P(ForceVector), C.c_int, C.c_int, _P(C.c_int32), _P(C.c_float)]),
+    "bl_amd_playlist_vec_device": (C.c_int, [C.c_void_p, C.c_int, ForceVector, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bl_amd_playlist_vec_host": (C.c_int, [_P(ForceVector), C.c_int, ForceVector, _P(C.c_int32), _P(C.c_float)]),
     "bl_amd_knn_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                     C.c_void_p]),
     "bl_amd_knn_host": (C.c_int, [_P(ForceVector), C.c_int, C.c_int, C.c_int, _P(C.c_int32), _P(C.c_float)]),
+    "bl_amd_cross_knn_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]),
+    "bl_amd_cross_knn_host": (C.c_int, [_P(ForceVector), C.c_int, _P(ForceVector), C.c_int, C.c_int, C.c_int,
+                                        _P(C.c_int32), _P(C.c_float)]),
     "bl_amd_chain_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                       C.c_void_p, C.c_void_p]),
     "bl_amd_ctx_chain_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
@@ -143,6 +149,16 @@ SYMBOLS = {
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bl_amd_radius_host": (C.c_int, [_P(ForceVector), C.c_int, C.c_int, C.c_float, _P(C.c_int64), _P(_P(C.c_int32)),
                                      _P(_P(C.c_float))]),
+    "bl_amd_cross_radius_count_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float,
+                                                   C.c_void_p, C.c_void_p]),
+    "bl_amd_ctx_cross_radius_count_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                                       C.c_float, C.c_void_p, C.c_void_p]),
+    "bl_amd_cross_radius_fill_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bl_amd_ctx_cross_radius_fill_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                                      C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bl_amd_cross_radius_host": (C.c_int, [_P(ForceVector), C.c_int, _P(ForceVector), C.c_int, C.c_int, C.c_float,
+                                           _P(C.c_int64), _P(_P(C.c_int32)), _P(_P(C.c_float))]),
     "bl_amd_groups_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
     "bl_amd_ctx_groups_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p,
                                            C.c_void_p]),

@@ -584,3 +584,147 @@ def duplicate_groups_device(d_vecs, r, metric="distance", stream=None):
         _check(lib.bl_amd_groups_device(v.data_ptr(), n, m, r, group.data_ptr(), C.c_void_p(cur.cuda_stream)),
                "bl_amd_groups_device")
     return group
+
+
+def _cross_shapes_check(q_shape, v_shape):
+    for name, shape in (("queries", q_shape), ("vecs", v_shape)):
+        if len(shape) != 2 or shape[1] != 4 or shape[0] < 1:
+            raise ValueError(f"{name} must have shape (m, 4) with m >= 1, got {tuple(shape)}")
+
+
+def _cross_host_vecs(queries, vecs):
+    """(queries, vecs) as contiguous float32 numpy arrays.  Plain sequences are converted; an array that says what it
+    holds must hold float32, so that the two sides cannot silently differ in precision."""
+    for name, x in (("queries", queries), ("vecs", vecs)):
+        if hasattr(x, "dtype") and x.dtype != np.float32:
+            raise ValueError(f"{name} must be float32, got {x.dtype}")
+    q, v = np.ascontiguousarray(queries, dtype=np.float32), np.ascontiguousarray(vecs, dtype=np.float32)
+    _cross_shapes_check(q.shape, v.shape)
+    return q, v
+
+
+def _cross_device_check(d_queries, d_vecs):
+    import torch
+    for name, t in (("d_queries", d_queries), ("d_vecs", d_vecs)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a torch tensor")
+    _cross_shapes_check(tuple(d_queries.shape), tuple(d_vecs.shape))
+    if d_queries.dtype != torch.float32 or d_vecs.dtype != torch.float32:
+        raise ValueError(f"d_queries and d_vecs must both be float32, got {d_queries.dtype} and {d_vecs.dtype}")
+    if d_queries.device != d_vecs.device:
+        raise ValueError(f"d_queries ({d_queries.device}) and d_vecs ({d_vecs.device}) must be on the same device")
+    if not d_vecs.is_cuda:
+        raise ValueError("d_queries and d_vecs must be CUDA tensors")
+    if not d_queries.is_contiguous() or not d_vecs.is_contiguous():
+        raise ValueError("d_queries and d_vecs must be contiguous")
+
+
+def knn_cross(queries, vecs, k, metric="distance"):
+    """The k nearest songs of the library `vecs` (n, 4) to each of `queries` (m, 4), vectors that need not be songs of
+    it: (index (m, k) int32, value (m, k) float32), ordered and valued as knn() does.  Unlike knn() nothing is left
+    out: a query equal to library song 7 lists song 7 first, at distance 0.  Slots past n hold -1 and NaN."""
+    m_code = _knn_check(k, metric, (1, 4))   # the shapes are checked per side below
+    q, v = _cross_host_vecs(queries, vecs)
+    lib = _lib.load()
+    m = q.shape[0]
+    index = np.empty((m, k), dtype=np.int32)
+    value = np.empty((m, k), dtype=np.float32)
+    fv = C.POINTER(_lib.ForceVector)
+    rc = lib.bl_amd_cross_knn_host(q.ctypes.data_as(fv), m, v.ctypes.data_as(fv), v.shape[0], int(k), m_code,
+                                   index.ctypes.data_as(C.POINTER(C.c_int32)),
+                                   value.ctypes.data_as(C.POINTER(C.c_float)))
+    _check(rc, "bl_amd_cross_knn_host")
+    return index, value
+
+
+def knn_cross_device(d_queries, d_vecs, k, metric="distance", stream=None):
+    """knn_cross() on the device: d_queries (m, 4) and d_vecs (n, 4) contiguous float32 CUDA tensors on one device;
+    d_queries may be a view into d_vecs and needs 16-byte alignment only.  Returns (index, value) CUDA tensors of
+    shape (m, k), asynchronously on `stream` (default: the current stream of that device).  Queries are independent:
+    shard by slicing d_queries."""
+    import torch
+    m_code = _knn_check(k, metric, (1, 4))
+    _cross_device_check(d_queries, d_vecs)
+    lib = _lib.load()
+    q, v = d_queries, d_vecs
+    m = q.shape[0]
+    index = torch.empty((m, k), dtype=torch.int32, device=v.device)
+    value = torch.empty((m, k), dtype=torch.float32, device=v.device)
+    with _on_device_of(lib, v, stream) as cur:
+        _check(lib.bl_amd_cross_knn_device(q.data_ptr(), m, v.data_ptr(), v.shape[0], int(k), m_code,
+                                           index.data_ptr(), value.data_ptr(), C.c_void_p(cur.cuda_stream)),
+               "bl_amd_cross_knn_device")
+    return index, value
+
+
+def _radius_cross_check(r, metric):
+    return _radius_check(r, metric, (1, 4))   # the shapes are checked per side
+
+
+def radius_cross(queries, vecs, r, metric="distance"):
+    """The songs of the library `vecs` (n, 4) within radius r of each of `queries` (m, 4), as compressed sparse row
+    lists: (offset int64 (m + 1,), index int32 (total,), value float32 (total,)), as radius() defines "within" and
+    orders a row.  Unlike radius() nothing is left out: with r = 0 a query that is in the library finds its copy."""
+    m_code, r = _radius_cross_check(r, metric)
+    q, v = _cross_host_vecs(queries, vecs)
+    lib = _lib.load()
+    m = q.shape[0]
+    offsets = np.empty(m + 1, dtype=np.int64)
+    p_index, p_value = C.POINTER(C.c_int32)(), C.POINTER(C.c_float)()
+    fv = C.POINTER(_lib.ForceVector)
+    rc = lib.bl_amd_cross_radius_host(q.ctypes.data_as(fv), m, v.ctypes.data_as(fv), v.shape[0], m_code, r,
+                                      offsets.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(p_index), C.byref(p_value))
+    _check(rc, "bl_amd_cross_radius_host")
+    try:
+        total = int(offsets[m])
+        index = np.ctypeslib.as_array(p_index, shape=(total,)).copy() if total else np.empty(0, dtype=np.int32)
+        value = np.ctypeslib.as_array(p_value, shape=(total,)).copy() if total else np.empty(0, dtype=np.float32)
+    finally:
+        _libc_free(p_index)
+        _libc_free(p_value)
+    return offsets, index, value
+
+
+def radius_cross_device(d_queries, d_vecs, r, metric="distance", values=True, stream=None):
+    """radius_cross() on the device, tensors as for knn_cross_device().  Returns (offset int64 (m + 1,), index int32
+    (total,), value float32 (total,) or None without `values`) as CUDA tensors.  Count and fill run on `stream`;
+    between them the total is read back, which is the one synchronisation."""
+    import torch
+    m_code, r = _radius_cross_check(r, metric)
+    _cross_device_check(d_queries, d_vecs)
+    lib = _lib.load()
+    q, v = d_queries, d_vecs
+    m, n = q.shape[0], v.shape[0]
+    with _on_device_of(lib, v, stream) as cur, torch.cuda.stream(cur):
+        s = C.c_void_p(cur.cuda_stream)
+        offsets = torch.empty(m + 1, dtype=torch.int64, device=v.device)
+        _check(lib.bl_amd_cross_radius_count_device(q.data_ptr(), m, v.data_ptr(), n, m_code, r, offsets.data_ptr(), s),
+               "bl_amd_cross_radius_count_device")
+        total = int(offsets[-1].item())
+        index = torch.empty(max(total, 1), dtype=torch.int32, device=v.device)   # as in radius_device
+        value = torch.empty(max(total, 1), dtype=torch.float32, device=v.device) if values else None
+        _check(lib.bl_amd_cross_radius_fill_device(q.data_ptr(), m, v.data_ptr(), n, m_code, r, offsets.data_ptr(),
+                                                   index.data_ptr(), value.data_ptr() if values else None, s),
+               "bl_amd_cross_radius_fill_device")
+    return offsets, index[:total], value[:total] if values else None
+
+
+def playlist_vec(vecs, seed_vec):
+    """playlist() from a seed that need not be a song of `vecs`: the song indices by increasing bl_distance from the
+    4-component `seed_vec`, and the distances.  Stable for ties; a seed equal to a song lists it at distance 0."""
+    v = np.ascontiguousarray(vecs, dtype=np.float32)
+    if v.ndim != 2 or v.shape[1] != 4 or v.shape[0] < 1:
+        raise ValueError(f"force vectors must have shape (n, 4) with n >= 1, got {v.shape}")
+    sv = np.asarray(seed_vec, dtype=np.float32)
+    if sv.shape != (4,):
+        raise ValueError(f"the seed must be one force vector of 4 components, got shape {sv.shape}")
+    lib = _lib.load()
+    n = v.shape[0]
+    order = np.empty(n, dtype=np.int32)
+    dist = np.empty(n, dtype=np.float32)
+    seed = _lib.ForceVector(*(float(x) for x in sv))
+    rc = lib.bl_amd_playlist_vec_host(v.ctypes.data_as(C.POINTER(_lib.ForceVector)), n, seed,
+                                      order.ctypes.data_as(C.POINTER(C.c_int32)),
+                                      dist.ctypes.data_as(C.POINTER(C.c_float)))
+    _check(rc, "bl_amd_playlist_vec_host")
+    return order, dist

@@ -180,6 +180,9 @@ int blk_sqrt_sweep(hipStream_t s, unsigned long long first, unsigned long long c
 int blk_cos_sweep(hipStream_t s, unsigned long long seed, int per_thread, unsigned long long *d_counts, int n_cu);
 int blk_playlist(hipStream_t s, const struct force_vector_s *d_vecs, int n, int seed_index,
                  int32_t *d_order, float *d_dist);
+/* the same from a seed vector that is no row of d_vecs (bl_amd_playlist_vec_device) */
+int blk_playlist_vec(hipStream_t s, const struct force_vector_s *d_vecs, int n, struct force_vector_s seed,
+                     int32_t *d_order, float *d_dist);
 /* out[order[i]] = in[i] for 16-byte force vectors (shard-major -> caller order) */
 int blk_scatter_vecs(hipStream_t s, const struct force_vector_s *d_in, const int32_t *d_order,
                      struct force_vector_s *d_out, int n);
@@ -198,6 +201,12 @@ void blk_split_plan(int n, int n_rows, int n_cu, int qpw, int min_cols, int *n_s
 size_t blk_knn_scratch_bytes(int n, int n_rows, int k, bool cosine, int n_cu);
 int blk_knn(hipStream_t s, const struct force_vector_s *d_vecs, int n, int row_begin, int n_rows, int k,
             bool cosine, int n_cu, void *d_scratch, int32_t *d_index, float *d_value);
+/* the k nearest of all n songs to each of d_queries[0 .. n_queries), vectors outside the library that may alias it
+ * (bl_amd_cross_knn_device): no candidate is excluded.  The split plan is blk_split_plan(n, n_queries, ...). */
+size_t blk_knn_cross_scratch_bytes(int n, int n_queries, int k, bool cosine, int n_cu);
+int blk_knn_cross(hipStream_t s, const struct force_vector_s *d_queries, int n_queries,
+                  const struct force_vector_s *d_vecs, int n, int k, bool cosine, int n_cu, void *d_scratch,
+                  int32_t *d_index, float *d_value);
 /* song-to-song chains (bl_amd_chain_device).  blk_chain_shape: 1 = one workgroup per chain, 2 = column split with one
  * launch per step; force: 0 = the launch layer's rule, 1 / 2 = that shape.  d_scratch: at least
  * blk_chain_scratch_bytes(...) bytes for the same (n, n_chains, cosine, n_cu, force), 256-byte aligned; it is
@@ -215,6 +224,14 @@ int blk_radius_count(hipStream_t s, const struct force_vector_s *d_vecs, int n, 
                      float bound, int n_cu, void *d_scratch, long long *d_offset);
 int blk_radius_fill(hipStream_t s, const struct force_vector_s *d_vecs, int n, int row_begin, int n_rows, bool cosine,
                     float bound, int n_cu, void *d_scratch, const long long *d_offset, int32_t *d_index, float *d_value);
+/* the same for d_queries[0 .. n_queries) outside the library (bl_amd_cross_radius_*_device); d_offset: n_queries + 1 */
+size_t blk_radius_cross_scratch_bytes(int n, int n_queries, bool cosine, int n_cu);
+int blk_radius_cross_count(hipStream_t s, const struct force_vector_s *d_queries, int n_queries,
+                           const struct force_vector_s *d_vecs, int n, bool cosine, float bound, int n_cu,
+                           void *d_scratch, long long *d_offset);
+int blk_radius_cross_fill(hipStream_t s, const struct force_vector_s *d_queries, int n_queries,
+                          const struct force_vector_s *d_vecs, int n, bool cosine, float bound, int n_cu, void *d_scratch,
+                          const long long *d_offset, int32_t *d_index, float *d_value);
 /* duplicate groups (bl_amd_groups_device): d_group[i] = the smallest index of i's component; d_scratch: the cosine prep */
 size_t blk_groups_scratch_bytes(int n, bool cosine);
 int blk_groups(hipStream_t s, const struct force_vector_s *d_vecs, int n, bool cosine, float bound, int n_cu,

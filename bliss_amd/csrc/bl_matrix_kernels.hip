@@ -7,7 +7,7 @@
  * Kernels (reference code each one replaces):
  *   k_pairwise     bl_distance / bl_cosine_similarity matrix
  *                                               ref src/analyze.c:96-100,135-140
- *   k_seed_dist, k_rank_order  seeded playlist  ref python/examples/make_m3u_playlist.py:62-72
+ *   k_seed_dist, k_seed_dist_vec, k_rank_order  seeded playlist  ref python/examples/make_m3u_playlist.py:62-72
  *   k_scatter_vecs, k_extract_vecs  force vectors between result records, shard order and caller order
  *   k_sqrt_sweep, k_cos_sweep  self-tests of bl_sqrt.h and bl_cos.h on the device
  */
@@ -148,6 +148,13 @@ __global__ __launch_bounds__(256) void k_seed_dist(const float4 *__restrict__ ve
                                                    float *__restrict__ dist) {
   const int j = blockIdx.x * 256 + threadIdx.x;
   if (j < n) dist[j] = bl_dist(vecs[seed], vecs[j]);
+}
+
+/* the same from a seed that is no song of the library: the vector itself is the kernel's argument */
+__global__ __launch_bounds__(256) void k_seed_dist_vec(const float4 *__restrict__ vecs, int n, float4 seed,
+                                                       float *__restrict__ dist) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j < n) dist[j] = bl_dist(seed, vecs[j]);
 }
 
 __global__ __launch_bounds__(256) void k_rank_order(const float *__restrict__ dist, int n,
@@ -317,6 +324,16 @@ int blk_playlist(hipStream_t s, const struct force_vector_s *d_vecs, int n, int 
   const int gx = (n + 255) / 256;
   hipLaunchKernelGGL(k_seed_dist, dim3(gx), dim3(256), 0, s, reinterpret_cast<const float4 *>(d_vecs),
                      n, seed_index, d_dist);
+  hipLaunchKernelGGL(k_rank_order, dim3(gx), dim3(256), 0, s, d_dist, n, d_order);
+  BL_HIP_CHECK(hipGetLastError());
+  return BL_OK;
+}
+
+int blk_playlist_vec(hipStream_t s, const struct force_vector_s *d_vecs, int n, struct force_vector_s seed,
+                     int32_t *d_order, float *d_dist) {
+  const int gx = (n + 255) / 256;
+  hipLaunchKernelGGL(k_seed_dist_vec, dim3(gx), dim3(256), 0, s, reinterpret_cast<const float4 *>(d_vecs), n,
+                     make_float4(seed.tempo, seed.amplitude, seed.frequency, seed.attack), d_dist);
   hipLaunchKernelGGL(k_rank_order, dim3(gx), dim3(256), 0, s, d_dist, n, d_order);
   BL_HIP_CHECK(hipGetLastError());
   return BL_OK;

@@ -894,6 +894,30 @@ int bl_amd_playlist_host(const struct force_vector_s *h_vecs, int n, int seed_in
              : BL_UNEXPECTED;
 }
 
+int bl_amd_playlist_vec_device(const struct force_vector_s *d_vecs, int n, struct force_vector_s seed,
+                               int32_t *d_order, float *d_dist, void *stream) {
+  if (n <= 0 || !d_vecs || !d_order || !d_dist) return BL_UNEXPECTED;
+  bl_amd_ctx *c = blr_default_ctx();
+  if (!c) return BL_UNEXPECTED;
+  DevGuard dg(c->device);
+  return blk_playlist_vec(static_cast<hipStream_t>(stream), d_vecs, n, seed, d_order, d_dist);
+}
+
+int bl_amd_playlist_vec_host(const struct force_vector_s *h_vecs, int n, struct force_vector_s seed,
+                             int32_t *h_order, float *h_dist) {
+  if (n <= 0 || !h_vecs || !h_order) return BL_UNEXPECTED;
+  bl_amd_ctx *c = blr_default_ctx();
+  if (!c) return BL_UNEXPECTED;
+  DevGuard dg(c->device);
+  DevMem dv(sizeof(struct force_vector_s) * (size_t)n), dord(sizeof(int32_t) * (size_t)n), dd(sizeof(float) * (size_t)n);
+  return dv.up(h_vecs) && dord.ok() && dd.ok() &&
+                 bl_amd_playlist_vec_device(dv.as<struct force_vector_s>(), n, seed, dord.as<int32_t>(), dd.as<float>(),
+                                            nullptr) == BL_OK &&
+                 dord.down(h_order) && (!h_dist || dd.down(h_dist))
+             ? BL_OK
+             : BL_UNEXPECTED;
+}
+
 /* Vector queries (bl_query_kernels.hip): k nearest songs, song-to-song chains, radius lists, duplicate groups.  Every
  * argument is checked before any device work, so a rejected call leaves the outputs untouched, and the default-context
  * wrappers check before they fetch the context.  The scratch (cosine prep, a column split's partial results) is the
@@ -929,6 +953,44 @@ int bl_amd_knn_host(const struct force_vector_s *h_vecs, int n, int k, int metri
   return dv.up(h_vecs) && di.ok() && dd.ok() &&
                  bl_amd_knn_device(dv.as<struct force_vector_s>(), n, 0, n, k, metric, di.as<int32_t>(), dd.as<float>(),
                                    nullptr) == BL_OK &&
+                 di.down(h_index) && (!h_value || dd.down(h_value))
+             ? BL_OK
+             : BL_UNEXPECTED;
+}
+
+/* Cross forms: the queries are n_queries vectors of their own, and no candidate is excluded */
+static bool knn_cross_args_ok(const void *queries, int n_queries, const void *vecs, int n, int k, int metric,
+                              const void *index, const void *value) {
+  return queries && n_queries > 0 && knn_args_ok(vecs, n, 0, n, k, metric, index, value);
+}
+
+int bl_amd_cross_knn_device(const struct force_vector_s *d_queries, int n_queries, const struct force_vector_s *d_vecs,
+                            int n, int k, int metric, int32_t *d_index, float *d_value, void *stream) {
+  if (!knn_cross_args_ok(d_queries, n_queries, d_vecs, n, k, metric, d_index, d_value)) return BL_UNEXPECTED;
+  bl_amd_ctx *c = blr_default_ctx();
+  if (!c) return BL_UNEXPECTED;
+  const bool cosine = metric == BL_AMD_KNN_COSINE;
+  return query_call(c, stream, c->knn, blk_knn_cross_scratch_bytes(n, n_queries, k, cosine, c->n_cu),
+                    [&](hipStream_t s, void *scratch) {
+                      return blk_knn_cross(s, d_queries, n_queries, d_vecs, n, k, cosine, c->n_cu, scratch, d_index,
+                                           d_value);
+                    });
+}
+
+int bl_amd_cross_knn_host(const struct force_vector_s *h_queries, int n_queries, const struct force_vector_s *h_vecs,
+                          int n, int k, int metric, int32_t *h_index, float *h_value) {
+  if (!knn_cross_args_ok(h_queries, n_queries, h_vecs, n, k, metric, h_index, h_index /* h_value may be NULL */))
+    return BL_UNEXPECTED;
+  bl_amd_ctx *c = blr_default_ctx();
+  if (!c) return BL_UNEXPECTED;
+  DevGuard dg(c->device);
+  if (!dg.ok) return BL_UNEXPECTED;
+  const size_t out = (size_t)n_queries * k;
+  DevMem dq(sizeof(struct force_vector_s) * (size_t)n_queries), dv(sizeof(struct force_vector_s) * (size_t)n);
+  DevMem di(sizeof(int32_t) * out), dd(sizeof(float) * out);
+  return dq.up(h_queries) && dv.up(h_vecs) && di.ok() && dd.ok() &&
+                 bl_amd_cross_knn_device(dq.as<struct force_vector_s>(), n_queries, dv.as<struct force_vector_s>(), n, k,
+                                         metric, di.as<int32_t>(), dd.as<float>(), nullptr) == BL_OK &&
                  di.down(h_index) && (!h_value || dd.down(h_value))
              ? BL_OK
              : BL_UNEXPECTED;
@@ -1065,6 +1127,88 @@ int bl_amd_radius_host(const struct force_vector_s *h_vecs, int n, int metric, f
   if (!(hi && (hv || !h_value) && di.ok() && dd.ok() &&
         bl_amd_radius_fill_device(dv.as<struct force_vector_s>(), n, 0, n, metric, radius, doff.as<int64_t>(),
                                   di.as<int32_t>(), dd.as<float>(), nullptr) == BL_OK &&
+        di.down(hi, sizeof(int32_t) * total) && (!h_value || dd.down(hv, sizeof(float) * total)))) {
+    free(hi);
+    free(hv);
+    return BL_UNEXPECTED;
+  }
+  memcpy(h_offset, off.data(), sizeof(int64_t) * off.size());
+  *h_index = hi;
+  if (h_value) *h_value = hv;
+  return BL_OK;
+}
+
+static bool radius_cross_args_ok(const void *queries, int n_queries, const void *vecs, int n, int metric, float radius,
+                                 const void *out) {
+  return queries && n_queries > 0 && radius_args_ok(vecs, n, 0, n, metric, radius, out);
+}
+
+int bl_amd_ctx_cross_radius_count_device(bl_amd_ctx *c, const struct force_vector_s *d_queries, int n_queries,
+                                         const struct force_vector_s *d_vecs, int n, int metric, float radius,
+                                         int64_t *d_offset, void *stream) {
+  if (!radius_cross_args_ok(d_queries, n_queries, d_vecs, n, metric, radius, d_offset) || !c) return BL_UNEXPECTED;
+  const bool cosine = metric == BL_AMD_KNN_COSINE;
+  return query_call(c, stream, c->radius, blk_radius_cross_scratch_bytes(n, n_queries, cosine, c->n_cu),
+                    [&](hipStream_t s, void *scratch) {
+                      return blk_radius_cross_count(s, d_queries, n_queries, d_vecs, n, cosine,
+                                                    radius_kernel_bound(metric, radius), c->n_cu, scratch,
+                                                    reinterpret_cast<long long *>(d_offset));
+                    });
+}
+
+int bl_amd_cross_radius_count_device(const struct force_vector_s *d_queries, int n_queries,
+                                     const struct force_vector_s *d_vecs, int n, int metric, float radius,
+                                     int64_t *d_offset, void *stream) {
+  if (!radius_cross_args_ok(d_queries, n_queries, d_vecs, n, metric, radius, d_offset)) return BL_UNEXPECTED;
+  return bl_amd_ctx_cross_radius_count_device(blr_default_ctx(), d_queries, n_queries, d_vecs, n, metric, radius,
+                                              d_offset, stream);
+}
+
+int bl_amd_ctx_cross_radius_fill_device(bl_amd_ctx *c, const struct force_vector_s *d_queries, int n_queries,
+                                        const struct force_vector_s *d_vecs, int n, int metric, float radius,
+                                        const int64_t *d_offset, int32_t *d_index, float *d_value, void *stream) {
+  if (!radius_cross_args_ok(d_queries, n_queries, d_vecs, n, metric, radius, d_offset) || !d_index || !c)
+    return BL_UNEXPECTED;
+  const bool cosine = metric == BL_AMD_KNN_COSINE;
+  return query_call(c, stream, c->radius, blk_radius_cross_scratch_bytes(n, n_queries, cosine, c->n_cu),
+                    [&](hipStream_t s, void *scratch) {
+                      return blk_radius_cross_fill(s, d_queries, n_queries, d_vecs, n, cosine,
+                                                   radius_kernel_bound(metric, radius), c->n_cu, scratch,
+                                                   reinterpret_cast<const long long *>(d_offset), d_index, d_value);
+                    });
+}
+
+int bl_amd_cross_radius_fill_device(const struct force_vector_s *d_queries, int n_queries,
+                                    const struct force_vector_s *d_vecs, int n, int metric, float radius,
+                                    const int64_t *d_offset, int32_t *d_index, float *d_value, void *stream) {
+  if (!radius_cross_args_ok(d_queries, n_queries, d_vecs, n, metric, radius, d_offset) || !d_index) return BL_UNEXPECTED;
+  return bl_amd_ctx_cross_radius_fill_device(blr_default_ctx(), d_queries, n_queries, d_vecs, n, metric, radius,
+                                             d_offset, d_index, d_value, stream);
+}
+
+int bl_amd_cross_radius_host(const struct force_vector_s *h_queries, int n_queries, const struct force_vector_s *h_vecs,
+                             int n, int metric, float radius, int64_t *h_offset, int32_t **h_index, float **h_value) {
+  if (!radius_cross_args_ok(h_queries, n_queries, h_vecs, n, metric, radius, h_offset) || !h_index) return BL_UNEXPECTED;
+  bl_amd_ctx *c = blr_default_ctx();
+  if (!c) return BL_UNEXPECTED;
+  DevGuard dg(c->device);
+  if (!dg.ok) return BL_UNEXPECTED;
+  std::vector<int64_t> off((size_t)n_queries + 1);
+  DevMem dq(sizeof(struct force_vector_s) * (size_t)n_queries), dv(sizeof(struct force_vector_s) * (size_t)n);
+  DevMem doff(sizeof(int64_t) * off.size());
+  if (!(dq.up(h_queries) && dv.up(h_vecs) && doff.ok() &&
+        bl_amd_cross_radius_count_device(dq.as<struct force_vector_s>(), n_queries, dv.as<struct force_vector_s>(), n,
+                                         metric, radius, doff.as<int64_t>(), nullptr) == BL_OK &&
+        doff.down(off.data())))
+    return BL_UNEXPECTED;
+  const size_t total = (size_t)off[(size_t)n_queries], slots = total ? total : 1; /* as in bl_amd_radius_host */
+  int32_t *hi = static_cast<int32_t *>(malloc(sizeof(int32_t) * slots));
+  float *hv = h_value ? static_cast<float *>(malloc(sizeof(float) * slots)) : nullptr;
+  DevMem di(sizeof(int32_t) * slots), dd(h_value ? sizeof(float) * slots : 0);
+  if (!(hi && (hv || !h_value) && di.ok() && dd.ok() &&
+        bl_amd_cross_radius_fill_device(dq.as<struct force_vector_s>(), n_queries, dv.as<struct force_vector_s>(), n,
+                                        metric, radius, doff.as<int64_t>(), di.as<int32_t>(), dd.as<float>(),
+                                        nullptr) == BL_OK &&
         di.down(hi, sizeof(int32_t) * total) && (!h_value || dd.down(hv, sizeof(float) * total)))) {
     free(hi);
     free(hv);

@@ -260,6 +260,14 @@ int bl_amd_playlist_device(const struct force_vector_s *d_vecs, int n, int seed_
 int bl_amd_playlist_host(const struct force_vector_s *h_vecs, int n, int seed_index,
                          int32_t *h_order, float *h_dist /* may be NULL */);
 
+/* The same from a seed that is no song of the library (a track analysed but not added, a mean of songs): the vector
+ * is passed by value, as bl_distance takes its vectors.  d_dist[j] = bl_distance(seed, vecs[j]), d_order the stable
+ * argsort; a seed equal to a song lists that song like any other, at distance 0. */
+int bl_amd_playlist_vec_device(const struct force_vector_s *d_vecs, int n, struct force_vector_s seed,
+                               int32_t *d_order, float *d_dist, void *stream);
+int bl_amd_playlist_vec_host(const struct force_vector_s *h_vecs, int n, struct force_vector_s seed,
+                             int32_t *h_order, float *h_dist /* may be NULL */);
+
 /* k nearest songs of each query, without the N x N matrix.  Rows [row_begin, row_begin + n_rows) of d_vecs
  * are the queries; the candidates are all n songs minus the query itself (its exact duplicates are ordinary
  * candidates).  d_index / d_value: n_rows * k, row-major; slot j of row r = the (j+1)-th nearest song to song
@@ -277,6 +285,30 @@ int bl_amd_knn_device(const struct force_vector_s *d_vecs, int n, int row_begin,
 /* All n songs as queries, host pointers, blocking.  h_value may be NULL. */
 int bl_amd_knn_host(const struct force_vector_s *h_vecs, int n, int k, int metric, int32_t *h_index,
                     float *h_value);
+
+/* Cross queries: the queries are n_queries >= 1 vectors of their own (freshly analysed tracks, a mean of songs)
+ * against the library of n >= 1 songs.  X[q][j] = bl_distance(queries[q], vecs[j]) or
+ * bl_cosine_similarity(queries[q], vecs[j]) with the query as the first operand; its bits are what
+ * bl_amd_*_matrix_device writes at [n + q][j] for the concatenation vecs || queries.  Three rules hold for every cross
+ * query (bl_amd_cross_knn_*, bl_amd_cross_radius_*; the names begin with "cross" so that bl_amd_knn_* and
+ * bl_amd_radius_* stay the self forms, all of them):
+ *   1. No candidate is ever excluded — the one semantic difference from the self forms above.  A query equal to
+ *      library song 7 lists song 7, at distance 0.
+ *   2. Queries are independent: the answer for query q depends neither on n_queries nor on the other queries.  Shard
+ *      by offsetting the query pointer; there is no row_begin.
+ *   3. d_queries needs 16-byte alignment only and may alias any part of d_vecs: both are only read.
+ * A rejected call returns BL_UNEXPECTED and writes nothing.  Asynchronous on `stream`; no allocation, copy or
+ * synchronisation inside once the context's workspace is large enough; calls of one context are ordered on the
+ * device like its batches.
+ *   bl_amd_cross_knn_device: d_index / d_value: n_queries * k, row-major; slot j of row q = the (j+1)-th nearest
+ *     library song to queries[q] under bl_amd_knn's order (the f32 value, +0 = -0, NaN after every number, ties by the
+ *     smaller index) and X[q][that song].  1 <= k <= BL_AMD_KNN_MAX_K.  If k > n the trailing k - n slots hold -1 and
+ *     a NaN (the self form pads from n - 1).
+ *   bl_amd_cross_knn_host: host pointers, blocking.  h_value may be NULL. */
+int bl_amd_cross_knn_device(const struct force_vector_s *d_queries, int n_queries, const struct force_vector_s *d_vecs,
+                            int n, int k, int metric, int32_t *d_index, float *d_value, void *stream);
+int bl_amd_cross_knn_host(const struct force_vector_s *h_queries, int n_queries, const struct force_vector_s *h_vecs,
+                          int n, int k, int metric, int32_t *h_index, float *h_value);
 
 /* Song-to-song chains (continuous play): chain c starts at song d_seeds[c]; slot t + 1 holds the song nearest to the
  * song of slot t among the songs not yet in chain c.  d_order / d_value: n_chains * length, row-major.
@@ -341,6 +373,28 @@ int bl_amd_ctx_radius_fill_device(bl_amd_ctx *ctx, const struct force_vector_s *
                                   float *d_value, void *stream);
 int bl_amd_radius_host(const struct force_vector_s *h_vecs, int n, int metric, float radius, int64_t *h_offset,
                        int32_t **h_index, float **h_value);
+
+/* Radius queries from vectors outside the library (the cross rules above bl_amd_cross_knn_device): the CSR contract
+ * of bl_amd_radius_* with n_queries + 1 offsets.  Song j is within the radius of query q iff X[q][j] <= radius
+ * (distance) or X[q][j] >= radius (cosine) — there is no j != i clause, so radius 0 finds the library's copy of a
+ * query.  The distance bound is bl_amd_radius_bound; a NaN radius is an argument error, +-inf and negative radii mean
+ * what the compare says.  Offsets are int64, summed on the device; indices ascend within a row; d_value may be NULL.
+ *   bl_amd_cross_radius_host: host pointers, blocking.  h_offset: n_queries + 1 entries; *h_index and *h_value are
+ *     malloc'd (free() them; an empty result is a valid block too).  h_value may be NULL. */
+int bl_amd_cross_radius_count_device(const struct force_vector_s *d_queries, int n_queries,
+                                     const struct force_vector_s *d_vecs, int n, int metric, float radius,
+                                     int64_t *d_offset, void *stream);
+int bl_amd_ctx_cross_radius_count_device(bl_amd_ctx *ctx, const struct force_vector_s *d_queries, int n_queries,
+                                         const struct force_vector_s *d_vecs, int n, int metric, float radius,
+                                         int64_t *d_offset, void *stream);
+int bl_amd_cross_radius_fill_device(const struct force_vector_s *d_queries, int n_queries,
+                                    const struct force_vector_s *d_vecs, int n, int metric, float radius,
+                                    const int64_t *d_offset, int32_t *d_index, float *d_value, void *stream);
+int bl_amd_ctx_cross_radius_fill_device(bl_amd_ctx *ctx, const struct force_vector_s *d_queries, int n_queries,
+                                        const struct force_vector_s *d_vecs, int n, int metric, float radius,
+                                        const int64_t *d_offset, int32_t *d_index, float *d_value, void *stream);
+int bl_amd_cross_radius_host(const struct force_vector_s *h_queries, int n_queries, const struct force_vector_s *h_vecs,
+                             int n, int metric, float radius, int64_t *h_offset, int32_t **h_index, float **h_value);
 
 /* Duplicate groups: d_group[i] (n int32) = the smallest song index in the weakly connected component of song i in the
  * graph that has an edge i -> j iff j is within the radius of i (as defined above): a pure function of (vecs, metric,
