@@ -9,7 +9,7 @@ from ._lib import (BL_CALM, BL_LOUD, BL_OK, BL_UNEXPECTED, BL_UNKNOWN, BlSong, E
                    ForceVector, SongDesc, SongResult, load)
 from . import distance, version
 from .batch import (Context, DeviceCorpus, analyze_batch_host, analyze_files, analyze_batch_host_rate, analyze_batch_host_s32,
-                    analyze_corpus_multi, analyze_corpus_multi_device, chain, chain_device, cosine_matrix, distance_matrix, knn, knn_device,
+                    analyze_corpus_multi, analyze_corpus_multi_device, chain, chain_device, mix, mix_device, cosine_matrix, distance_matrix, knn, knn_device,
                     playlist, knn_cross, knn_cross_device, playlist_vec, radius_cross, radius_cross_device,
                     duplicate_groups, duplicate_groups_device, radius, radius_device,
                     resample_batch_device,
@@ -19,7 +19,7 @@ from .bl_song import bl_song
 __all__ = ["_lib", "load", "BlSong", "ForceVector", "EnvelopeResult", "SongDesc", "SongResult",
            "BL_LOUD", "BL_CALM", "BL_UNKNOWN", "BL_UNEXPECTED", "BL_OK", "DeviceCorpus",
            "analyze_batch_host", "analyze_files", "analyze_batch_host_rate", "analyze_batch_host_s32", "analyze_corpus_multi", "analyze_corpus_multi_device", "Context",
-           "distance_matrix", "cosine_matrix", "results_to_numpy", "playlist", "knn", "knn_device", "chain", "chain_device",
+           "distance_matrix", "cosine_matrix", "results_to_numpy", "playlist", "knn", "knn_device", "chain", "chain_device", "mix", "mix_device",
            "radius", "radius_device", "knn_cross", "knn_cross_device", "radius_cross", "radius_cross_device", "playlist_vec",
            "duplicate_groups", "duplicate_groups_device",
            "resample_host", "resample_batch_device", "bl_song", "distance", "version"]

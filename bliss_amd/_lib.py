@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("BLISS_AMD_LIB") or os.path.join(_HERE, "libbliss_amd.
 BL_LOUD, BL_CALM, BL_UNKNOWN, BL_UNEXPECTED, BL_OK = 0, 1, 2, -2, 0
 BL_AMD_KNN_DISTANCE, BL_AMD_KNN_COSINE, BL_AMD_KNN_MAX_K = 0, 1, 128  # include/bliss_amd.h
 BL_AMD_CHAIN_AUTO, BL_AMD_CHAIN_PER_CHAIN, BL_AMD_CHAIN_SPLIT = 0, 1, 2  # include/bliss_amd.h
+BL_AMD_MIX_MAX_GAP = 16  # include/bliss_amd.h
 
 
 class ForceVector(C.Structure):  # ref include/bliss.h:26-31
@@ -138,6 +139,12 @@ SYMBOLS = {
                                     _P(C.c_float)]),
     "bl_amd_chain_shape": (C.c_int, [C.c_int, C.c_int]),
     "bl_amd_chain_force_shape": (C.c_int, [C.c_int]),
+    "bl_amd_mix_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                    C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bl_amd_ctx_mix_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                        C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bl_amd_mix_host": (C.c_int, [_P(ForceVector), C.c_int, _P(C.c_int32), _P(ForceVector), C.c_int, C.c_int, C.c_int,
+                                  _P(C.c_int32), C.c_int, _P(C.c_uint8), _P(C.c_int32), _P(C.c_float)]),
     "bl_amd_radius_bound": (C.c_float, [C.c_float]),
     "bl_amd_radius_count_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p,
                                              C.c_void_p]),

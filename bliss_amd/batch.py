@@ -492,6 +492,119 @@ def chain_device(d_vecs, d_seeds, length, metric="distance", stream=None):
     return order, value
 
 
+def _mix_gap_check(gap, tags):
+    if isinstance(gap, bool) or not isinstance(gap, (int, np.integer)) or not 0 <= gap <= _lib.BL_AMD_MIX_MAX_GAP:
+        raise ValueError(f"gap must be an integer in [0, {_lib.BL_AMD_MIX_MAX_GAP}], got {gap!r}")
+    if gap > 0 and tags is None:
+        raise ValueError("gap > 0 needs tags")
+    return int(gap)
+
+
+def _mix_seeds_check(seeds, seed_vecs):
+    if (seeds is None) == (seed_vecs is None):
+        raise ValueError("exactly one of seeds and seed_vecs must be given")
+
+
+def mix(vecs, seeds, length, metric="distance", tags=None, gap=0, exclude=None, seed_vecs=None):
+    """chain() under rules.  tags: n integers (artist, album ...; negative = untagged) of which no value may repeat
+    within `gap` slots (0 <= gap <= 16; 0 ignores the tags).  exclude: n bools or bytes, non-zero = never picked.
+    seed_vecs: (m, 4) float32 vectors instead of seeds (pass seeds=None): slot 0 is the song nearest to the vector
+    among the songs not excluded.  An index seed takes slot 0 even if it is excluded.  A chain with no allowed song
+    left ends: the rest of its row holds -1 and NaN.  To continue a chain, call again with seed = its last song and
+    exclude = everything played so far.  Returns (order, value) as chain() does."""
+    v = np.ascontiguousarray(vecs, dtype=np.float32)
+    _mix_seeds_check(seeds, seed_vecs)
+    gap = _mix_gap_check(gap, tags)
+    n = v.shape[0] if v.ndim == 2 else 0
+    q = None
+    if seed_vecs is not None:
+        if hasattr(seed_vecs, "dtype") and seed_vecs.dtype != np.float32:
+            raise ValueError(f"seed_vecs must be float32, got {seed_vecs.dtype}")
+        q = np.ascontiguousarray(seed_vecs, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != 4 or q.shape[0] < 1:
+            raise ValueError(f"seed_vecs must have shape (m, 4) with m >= 1, got {q.shape}")
+        m, s = _chain_check(0, length, metric, v.shape, None)[0], None
+    else:
+        m, s = _chain_check(seeds, length, metric, v.shape, n)
+    tg = None
+    if tags is not None:
+        tg = np.asarray(tags)
+        if tg.dtype == np.bool_ or not np.issubdtype(tg.dtype, np.integer) or tg.shape != (n,):
+            raise ValueError(f"tags must be {n} integers, got dtype {tg.dtype} and shape {tg.shape}")
+        if tg.size and (tg.min() < -2 ** 31 or tg.max() >= 2 ** 31):
+            raise ValueError("tags do not fit 32 bits")
+        tg = np.ascontiguousarray(tg, dtype=np.int32)
+    ex = None
+    if exclude is not None:
+        ex = np.asarray(exclude)
+        if ex.dtype not in (np.bool_, np.uint8) or ex.shape != (n,):
+            raise ValueError(f"exclude must be {n} bools or uint8, got dtype {ex.dtype} and shape {ex.shape}")
+        ex = np.ascontiguousarray(ex).view(np.uint8)
+    lib = _lib.load()
+    n_chains = q.shape[0] if q is not None else s.size
+    order = np.empty((n_chains, length), dtype=np.int32)
+    value = np.empty((n_chains, length), dtype=np.float32)
+    fv, i32 = C.POINTER(_lib.ForceVector), C.POINTER(C.c_int32)
+    rc = lib.bl_amd_mix_host(v.ctypes.data_as(fv), n, s.ctypes.data_as(i32) if s is not None else None,
+                             q.ctypes.data_as(fv) if q is not None else None, n_chains, int(length), m,
+                             tg.ctypes.data_as(i32) if tg is not None else None, gap,
+                             ex.ctypes.data_as(C.POINTER(C.c_uint8)) if ex is not None else None,
+                             order.ctypes.data_as(i32), value.ctypes.data_as(C.POINTER(C.c_float)))
+    _check(rc, "bl_amd_mix_host")
+    return order, value
+
+
+def mix_device(d_vecs, d_seeds, length, metric="distance", tags=None, gap=0, exclude=None, seed_vecs=None, stream=None):
+    """mix() on the device: d_vecs as chain_device() takes it, d_seeds as chain_device() takes them or None with
+    seed_vecs, a contiguous, 16-byte aligned float32 (m, 4) CUDA tensor that may be a view into d_vecs.  tags: an
+    int32 CUDA tensor of n entries; exclude: a bool or uint8 CUDA tensor of n entries; both contiguous and on the
+    device of d_vecs.
+    Returns (order, value) CUDA tensors of shape (n_chains, length), asynchronously on `stream`."""
+    import torch
+    _mix_seeds_check(d_seeds, seed_vecs)
+    gap = _mix_gap_check(gap, tags)
+    shape = tuple(d_vecs.shape)
+    if seed_vecs is not None:
+        m, s = _chain_check(0, length, metric, shape, None)[0], None
+        if not isinstance(seed_vecs, torch.Tensor) or seed_vecs.dtype != torch.float32 or seed_vecs.dim() != 2 or \
+                seed_vecs.shape[1] != 4 or seed_vecs.shape[0] < 1:
+            raise ValueError("seed_vecs must be a float32 tensor of shape (m, 4) with m >= 1")
+    else:
+        m, s = _chain_check(d_seeds, length, metric, shape, None)
+    n = shape[0]
+    for name, t, kinds in (("tags", tags, (torch.int32,)), ("exclude", exclude, (torch.bool, torch.uint8))):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype not in kinds or tuple(t.shape) != (n,)):
+            raise ValueError(f"{name} must be a tensor of {n} entries of {' or '.join(str(k) for k in kinds)}")
+    _device_vecs_check(d_vecs)
+    if seed_vecs is None and s is None:
+        if d_seeds.dtype != torch.int32 or d_seeds.dim() > 1 or d_seeds.numel() < 1:
+            raise ValueError("d_seeds must be an int32 tensor with 0 or 1 dimensions and at least one element")
+    for name, t in (("d_seeds", d_seeds if s is None else None), ("seed_vecs", seed_vecs), ("tags", tags),
+                    ("exclude", exclude)):
+        if t is not None and (not t.is_cuda or t.device != d_vecs.device or
+                              (name != "d_seeds" and not t.is_contiguous())):
+            raise ValueError(f"{name} must be a contiguous tensor on the device of d_vecs")
+    if seed_vecs is not None and seed_vecs.data_ptr() % 16:   # a view such as flat[1:9].view(2, 4) is contiguous
+        raise ValueError("seed_vecs must be 16-byte aligned")
+    lib = _lib.load()
+    v = d_vecs
+    with _on_device_of(lib, v, stream) as cur, torch.cuda.stream(cur):
+        sd = None
+        if seed_vecs is None:
+            sd = torch.from_numpy(s).to(v.device) if s is not None else d_seeds.reshape(-1).contiguous()
+        n_chains = seed_vecs.shape[0] if seed_vecs is not None else sd.numel()
+        order = torch.empty((n_chains, length), dtype=torch.int32, device=v.device)
+        value = torch.empty((n_chains, length), dtype=torch.float32, device=v.device)
+        _check(lib.bl_amd_mix_device(v.data_ptr(), n, sd.data_ptr() if sd is not None else None,
+                                     seed_vecs.data_ptr() if seed_vecs is not None else None, n_chains, int(length), m,
+                                     tags.data_ptr() if tags is not None else None, gap,
+                                     exclude.data_ptr() if exclude is not None else None, order.data_ptr(),
+                                     value.data_ptr(), C.c_void_p(cur.cuda_stream)), "bl_amd_mix_device")
+        if s is not None:
+            sd.record_stream(cur)   # the uploaded seeds are freed when this returns
+    return order, value
+
+
 def _radius_check(r, metric, shape):
     """(metric code, the radius as a Python float that is an exact f32)"""
     if isinstance(r, bool) or not isinstance(r, (int, float, np.integer, np.floating)):

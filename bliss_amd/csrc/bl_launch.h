@@ -215,6 +215,12 @@ int blk_chain_shape(int n, int n_chains, int n_cu, int force);
 size_t blk_chain_scratch_bytes(int n, int n_chains, bool cosine, int n_cu, int force);
 int blk_chain(hipStream_t s, const struct force_vector_s *d_vecs, int n, const int32_t *d_seeds, int n_chains,
               int length, bool cosine, int n_cu, int force, void *d_scratch, int32_t *d_order, float *d_value);
+/* chains under rules (bl_amd_mix_device): exactly one of d_seeds / d_seed_vecs, d_tags used when gap > 0, d_exclude
+ * nullptr or n bytes.  Shape, force and scratch as blk_chain's. */
+size_t blk_mix_scratch_bytes(int n, int n_chains, bool cosine, int n_cu, int force);
+int blk_mix(hipStream_t s, const struct force_vector_s *d_vecs, int n, const int32_t *d_seeds,
+            const struct force_vector_s *d_seed_vecs, int n_chains, int length, bool cosine, const int32_t *d_tags,
+            int gap, const uint8_t *d_exclude, int n_cu, int force, void *d_scratch, int32_t *d_order, float *d_value);
 /* the songs within a radius of rows [row_begin, row_begin + n_rows) (bl_amd_radius_*_device).  bound: the largest
  * squared sum whose correctly rounded root is <= the radius (distance) or the radius itself (cosine).  d_scratch: at
  * least blk_radius_scratch_bytes(n, n_rows, cosine, n_cu) bytes, 256-byte aligned; count and fill both rewrite it, and

@@ -11,6 +11,8 @@
  *   k_knn_cross, k_knn_cross_merge, k_radius_cross_count, k_radius_cross_fill  siblings of those for queries that
  *                  are vectors outside the library (bl_amd_cross_*): a second operand, and no candidate excluded
  *   k_chain, k_chain_init, k_chain_step  song-to-song chains: every next song the nearest unplayed one
+ *   k_mix, k_mix_init, k_mix_step  siblings of those under rules (bl_amd_mix_*): excluded songs, a gap between songs
+ *                  of one tag, seeds that are vectors
  *   k_radius_count, k_radius_offsets, k_radius_split_scan, k_radius_fill  the songs within a radius of each query
  *                  as CSR lists
  *   k_groups_init, k_groups_union, k_groups_compress  duplicate groups: connected components of the within-radius
@@ -571,6 +573,337 @@ __global__ __launch_bounds__(256) void k_chain_step(const float4 *__restrict__ v
 }
 
 /* ------------------------------------------------------------------------- */
+/* k_mix: chains under rules (bl_amd_mix_device)                                */
+/* A chain whose step takes the nearest *allowed* song: not played, not excluded, and (gap > 0) of a tag that none of
+ * the last `gap` slots carries.  Siblings of k_chain, k_chain_init and k_chain_step over the same pieces (bl_metric.h,
+ * chain_wave_min, the chain's bit layouts and its arrival protocol), not a flag on them: their registers stay theirs.
+ *   Exclusion   costs nothing per step: the played bits start from the mask instead of from zero.
+ *   Tags        the tags of the last `gap` slots are a wave-uniform history (mix_hist), newest first, -1 where there
+ *               is none.  k_mix keeps it in registers, every thread pushing the tag of the pick it has just read from
+ *               LDS; in the split shape it lives in the chain's state, written by the last-arriving workgroup and read
+ *               by the next launch, like `cur`.  A candidate's tag is fetched with its vector (TAGS) but tested only
+ *               once its key has passed the squared-sum bound and would become the lane's best: a blocked candidate
+ *               changes neither `best` nor `bnd`, so it cannot prune an allowed one behind it.
+ *   Vector seed slot 0 is the same scan with the seed vector as the query (its cosine prep by bl_cos_prep, as
+ *               k_knn_prep makes a song's) and an empty history, so no tag blocks; the value has the seed as first
+ *               operand.
+ *   The end     no allowed song: the minimum is the empty key, and the rest of the row is -1 / NaN.
+ * With TAGS = false, no mask and index seeds the arithmetic per candidate is k_chain's. */
+struct mix_state { /* chain_state with the tag history on the line of `count` and `cur` */
+  unsigned long long best;
+  unsigned pad0[30];
+  unsigned count;
+  int cur;
+  int hist[BL_AMD_MIX_MAX_GAP];
+  unsigned pad1[30 - BL_AMD_MIX_MAX_GAP];
+};
+static_assert(sizeof(mix_state) == sizeof(chain_state), "blk_mix_scratch_bytes is blk_chain_scratch_bytes");
+
+/* tags of the last `gap` slots, h[0] the newest; entries at and past `gap` stay -1, which no tag >= 0 equals */
+struct mix_hist {
+  int h[BL_AMD_MIX_MAX_GAP];
+  __device__ __forceinline__ void clear() {
+#pragma unroll
+    for (int k = 0; k < BL_AMD_MIX_MAX_GAP; ++k) h[k] = -1;
+  }
+  __device__ __forceinline__ void push(int tag, int gap) { /* gap >= 1 */
+#pragma unroll
+    for (int k = BL_AMD_MIX_MAX_GAP - 1; k > 0; --k)
+      if (k < gap) h[k] = h[k - 1];
+    h[0] = tag;
+  }
+  /* k_mix holds the history in VGPRs: sixteen more scalars in its candidate loop overflow the SGPR file, as the
+   * query vectors do in k_knn */
+  __device__ __forceinline__ void to_vgprs() {
+#pragma unroll
+    for (int k = 0; k < BL_AMD_MIX_MAX_GAP; ++k) asm volatile("" : "+v"(h[k]));
+  }
+  __device__ __forceinline__ bool blocks(int tag) const {
+    bool m = false;
+#pragma unroll
+    for (int k = 0; k < BL_AMD_MIX_MAX_GAP; ++k) m |= h[k] == tag;
+    return tag >= 0 && m;
+  }
+};
+
+/* chain_visit with the tag rule: candidate j of tag `tag` into the lane's minimum unless the history blocks it */
+template <bool COSINE, bool TAGS>
+__device__ __forceinline__ void mix_visit(const float4 a, const double2 pa, const float4 b, const double2 pb, int j,
+                                          int tag, const mix_hist &hist, unsigned long long &best, float &bnd) {
+  if (COSINE) {
+    const unsigned long long key = bl_key<true>(bl_cosine(a, pa, b, pb), j);
+    if (key < best && !(TAGS && hist.blocks(tag))) best = key;
+  } else {
+    const float s = bl_dist_sq(a, b);
+    if (!(s > bnd)) {
+      const unsigned long long key = bl_key<false>(bl_root(s), j);
+      if (key < best && !(TAGS && hist.blocks(tag))) {
+        best = key;
+        bnd = bl_sq_bound(best);
+      }
+    }
+  }
+}
+
+/* the query of a step: song `cur`, or (q != nullptr: slot 0 of a vector seed) the vector *q with its own prep */
+template <bool COSINE>
+__device__ __forceinline__ void mix_query(const float4 *__restrict__ vecs, const double2 *__restrict__ prep, int cur,
+                                          const float4 *__restrict__ q, float4 &a, double2 &pa) {
+  pa = make_double2(0.0, 0.0);
+  if (q) {
+    a = *q;
+    if (COSINE) {
+      const bl_cos_vec p = bl_cos_prep(a);
+      pa = make_double2(p.s, p.r);
+    }
+  } else {
+    a = vecs[cur];
+    if (COSINE) pa = prep[cur];
+  }
+  /* in VGPRs, as in k_chain */
+  asm volatile("" : "+v"(a.x), "+v"(a.y), "+v"(a.z), "+v"(a.w));
+  if (COSINE) asm volatile("" : "+v"(pa.x), "+v"(pa.y));
+}
+
+/* k_chain's launch and bit layout.  Exactly one of seeds / qvecs (n_chains seed vectors) is non-null; tags is
+ * non-null exactly when TAGS; exclude is null or n bytes, non-zero = never picked. */
+template <bool COSINE, bool LDS_BITS, bool TAGS>
+__global__ __launch_bounds__(1024) void k_mix(const float4 *__restrict__ vecs, const double2 *__restrict__ prep, int n,
+                                              const int32_t *__restrict__ seeds, const float4 *__restrict__ qvecs,
+                                              int length, int lb, int words, const int32_t *__restrict__ tags, int gap,
+                                              const unsigned char *__restrict__ exclude, unsigned *__restrict__ g_bits,
+                                              int32_t *__restrict__ out_order, float *__restrict__ out_value) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char chain_smem[];
+  unsigned long long *wmin = reinterpret_cast<unsigned long long *>(chain_smem);
+  const int B = 1 << lb, tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wave_mask = (B >> 6) - 1;
+  unsigned *bits = LDS_BITS ? reinterpret_cast<unsigned *>(chain_smem + CHAIN_LDS_HEAD)
+                            : g_bits + (size_t)blockIdx.x * words * B;
+  int32_t *order = out_order + (size_t)blockIdx.x * length;
+  float *value = out_value + (size_t)blockIdx.x * length;
+  const int steps = min(length, n);
+  int cur = qvecs ? 0 : seeds[blockIdx.x];
+  const bool ok = cur >= 0 && cur < n;
+  for (int t = (ok ? steps : 0) + tid; t < length; t += B) {
+    order[t] = -1;
+    value[t] = __builtin_nanf("");
+  }
+  if (!ok) return;
+  const int cols = tid < n ? ((n - 1 - tid) >> lb) + 1 : 0; /* columns of this lane */
+  for (int w = 0; w < words; ++w) {
+    unsigned x = 0u;
+    if (exclude && cols > 0) { /* bit i of word w: column tid + (32 w + i) * B; integer arithmetic only, eight
+                                * bytes in flight: as compares the 32 bits of a word took the SGPR file */
+#pragma unroll 1
+      for (int i0 = 0; i0 < 32; i0 += 8) {
+        unsigned e[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) e[u] = exclude[tid + (min(32 * w + i0 + u, cols - 1) << lb)];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) x |= ((e[u] + 255u) >> 8) << (i0 + u);
+      }
+      const int left = cols - 32 * w; /* columns this word has; the bits past them repeat the last column's */
+      if (left < 32) x &= left > 0 ? (1u << left) - 1u : 0u;
+    }
+    bits[w * B + tid] = x;
+  }
+  mix_hist hist;
+  hist.clear();
+  /* the query of the first scan: the seed vector, or the seed song, which also takes slot 0 whatever the mask says
+   * and is the first entry of the history */
+  float4 a;
+  double2 pa;
+  mix_query<COSINE>(vecs, prep, cur, qvecs ? qvecs + blockIdx.x : nullptr, a, pa);
+  int t = 0;
+  if (!qvecs) {
+    if ((cur & (B - 1)) == tid) bits[((cur >> lb) >> 5) * B + tid] |= 1u << ((cur >> lb) & 31);
+    if (TAGS) hist.push(tags[cur], gap);
+    if (tid == 0) {
+      order[0] = cur;
+      value[0] = bl_value<COSINE>(a, pa, a, pa);
+    }
+    t = 1;
+  }
+  if (TAGS) hist.to_vgprs();
+  for (; t < steps; ++t) {
+    unsigned long long best = BL_KEY_EMPTY;
+    float bnd = __builtin_inff();
+    for (int i0 = 0; i0 < cols; i0 += 32) {
+      const unsigned played = bits[(i0 >> 5) * B + tid];
+      for (int u0 = 0; u0 < 32 && i0 + u0 < cols; u0 += CHAIN_BATCH) {
+        float4 b[CHAIN_BATCH];
+        double2 pb[CHAIN_BATCH];
+        int tg[CHAIN_BATCH];
+#pragma unroll
+        for (int u = 0; u < CHAIN_BATCH; ++u) {
+          const int j = tid + (min(i0 + u0 + u, cols - 1) << lb);
+          b[u] = vecs[j];
+          pb[u] = COSINE ? prep[j] : make_double2(0.0, 0.0);
+          tg[u] = TAGS ? tags[j] : -1;
+        }
+#pragma unroll
+        for (int u = 0; u < CHAIN_BATCH; ++u)
+          if (i0 + u0 + u < cols && !((played >> (u0 + u)) & 1u))
+            mix_visit<COSINE, TAGS>(a, pa, b[u], pb[u], tid + ((i0 + u0 + u) << lb), tg[u], hist, best, bnd);
+      }
+    }
+    best = chain_wave_min(best);
+    unsigned long long *slot = wmin + (t & 1) * CHAIN_MAX_WAVES;
+    if (lane == 0) slot[wave] = best;
+    __syncthreads();
+    unsigned long long m = slot[lane & wave_mask];
+#pragma unroll
+    for (int off = CHAIN_MAX_WAVES / 2; off > 0; off >>= 1) m = min(m, (unsigned long long)__shfl_xor(m, off));
+    if (m == BL_KEY_EMPTY) break; /* no song is allowed: the chain ends here, for every thread alike */
+    const int pick = __builtin_amdgcn_readfirstlane((int)(unsigned)m);
+    if ((pick & (B - 1)) == tid) bits[((pick >> lb) >> 5) * B + tid] |= 1u << ((pick >> lb) & 31);
+    float4 an; /* the pick is the next query */
+    double2 pan;
+    mix_query<COSINE>(vecs, prep, pick, nullptr, an, pan);
+    if (tid == 0) {
+      order[t] = pick;
+      value[t] = bl_value<COSINE>(a, pa, an, pan);
+    }
+    if (TAGS) {
+      hist.push(tags[pick], gap);
+      hist.to_vgprs();
+    }
+    a = an;
+    pa = pan;
+  }
+  for (int u = t + tid; u < steps; u += B) { /* the slots of a chain that ended early; nobody else wrote them */
+    order[u] = -1;
+    value[u] = __builtin_nanf("");
+  }
+}
+
+/* column-split shape, start of a call: k_chain_init with the played bits taken from the mask (a wave's ballot over
+ * 64 songs is two words), the whole row padded (a chain may end at any slot), and the history.  An index seed takes
+ * slot 0 here; a vector seed (seeds == nullptr) leaves it to the step launched with t = 0.  grid (any, n_chains).
+ * Unlike k_chain_init, which clears all `words`, only the words that cover songs below n are written, on purpose:
+ * words == ceil(n / 32) today and no step reads a bit at or past n.  If `words` is ever padded beyond that, the words
+ * past the last song hold stale bits and must be cleared here before anything may read them. */
+template <bool COSINE>
+__global__ __launch_bounds__(256) void k_mix_init(const float4 *__restrict__ vecs, const double2 *__restrict__ prep,
+                                                  int n, const int32_t *__restrict__ seeds, int length, int words,
+                                                  const int32_t *__restrict__ tags,
+                                                  const unsigned char *__restrict__ exclude,
+                                                  mix_state *__restrict__ state, unsigned *__restrict__ bits,
+                                                  int32_t *__restrict__ out_order, float *__restrict__ out_value) {
+  const int c = blockIdx.y, lane = threadIdx.x & 63;
+  const int seed = seeds ? seeds[c] : 0;
+  const bool ok = seed >= 0 && seed < n;
+  const bool at_seed = seeds && ok; /* slot 0 is the seed song */
+  const unsigned g = blockIdx.x * 256u + threadIdx.x, stride = gridDim.x * 256u;
+  for (unsigned j0 = g - lane; j0 < (unsigned)n; j0 += stride) { /* j0: a multiple of 64, the same in the whole wave */
+    const unsigned j = j0 + lane;
+    unsigned long long m = __ballot(exclude && j < (unsigned)n && exclude[min(j, (unsigned)n - 1u)] != 0);
+    if (at_seed && (unsigned)seed - j0 < 64u) m |= 1ull << ((unsigned)seed - j0);
+    const unsigned w = (j0 >> 5) + lane;
+    if (lane < 2 && w < (unsigned)words) bits[(size_t)c * words + w] = (unsigned)(m >> (32 * lane));
+  }
+  for (unsigned t = (at_seed ? 1u : 0u) + g; t < (unsigned)length; t += stride) {
+    out_order[(size_t)c * length + t] = -1;
+    out_value[(size_t)c * length + t] = __builtin_nanf("");
+  }
+  if (g == 0) {
+    state[c].best = BL_KEY_EMPTY;
+    state[c].count = 0u;
+    state[c].cur = ok ? seed : -1;
+#pragma unroll
+    for (int k = 0; k < BL_AMD_MIX_MAX_GAP; ++k) state[c].hist[k] = -1;
+    if (at_seed) {
+      if (tags) state[c].hist[0] = tags[seed];
+      const float4 a = vecs[seed];
+      const double2 pa = COSINE ? prep[seed] : make_double2(0.0, 0.0);
+      out_order[(size_t)c * length] = seed;
+      out_value[(size_t)c * length] = bl_value<COSINE>(a, pa, a, pa);
+    }
+  }
+}
+
+/* slot t of every chain: k_chain_step with the tag rule.  qvecs != nullptr (t = 0 of a call with vector seeds): the
+ * query of chain c is qvecs[c].  grid (n_groups, n_chains). */
+template <bool COSINE, bool TAGS>
+__global__ __launch_bounds__(256) void k_mix_step(const float4 *__restrict__ vecs, const double2 *__restrict__ prep,
+                                                  int n, int cols, int t, int length, int words,
+                                                  const int32_t *__restrict__ tags, int gap,
+                                                  const float4 *__restrict__ qvecs, mix_state *__restrict__ state,
+                                                  unsigned *__restrict__ bits_all, int32_t *__restrict__ out_order,
+                                                  float *__restrict__ out_value) {
+  __shared__ unsigned long long wmin[4];
+  const int c = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  mix_state *st = state + c;
+  const int cur = st->cur; /* published by the previous launch */
+  if (cur < 0) return;     /* a seed outside [0, n), or a chain that has ended: nobody arrives */
+  mix_hist hist;
+  hist.clear();
+  if (TAGS) {
+#pragma unroll
+    for (int k = 0; k < BL_AMD_MIX_MAX_GAP; ++k) hist.h[k] = st->hist[k];
+  }
+  const unsigned *bits = bits_all + (size_t)c * words;
+  float4 a;
+  double2 pa;
+  mix_query<COSINE>(vecs, prep, cur, qvecs ? qvecs + c : nullptr, a, pa);
+  const unsigned c0 = (unsigned)blockIdx.x * (unsigned)cols;
+  const unsigned c1 = min((unsigned)n, c0 + (unsigned)cols);
+  unsigned long long best = BL_KEY_EMPTY;
+  float bnd = __builtin_inff();
+  for (unsigned j0 = c0 + tid; j0 < c1; j0 += 256u * CHAIN_BATCH) {
+    unsigned played[CHAIN_BATCH];
+    float4 b[CHAIN_BATCH];
+    double2 pb[CHAIN_BATCH];
+    int tg[CHAIN_BATCH];
+#pragma unroll
+    for (int u = 0; u < CHAIN_BATCH; ++u) {
+      const unsigned j = j0 + 256u * u < c1 ? j0 + 256u * u : j0;
+      played[u] = bits[j >> 5];
+      b[u] = vecs[j];
+      pb[u] = COSINE ? prep[j] : make_double2(0.0, 0.0);
+      tg[u] = TAGS ? tags[j] : -1;
+    }
+#pragma unroll
+    for (int u = 0; u < CHAIN_BATCH; ++u) {
+      const unsigned j = j0 + 256u * u;
+      if (j < c1 && !((played[u] >> (j & 31u)) & 1u))
+        mix_visit<COSINE, TAGS>(a, pa, b[u], pb[u], (int)j, tg[u], hist, best, bnd);
+    }
+  }
+  best = chain_wave_min(best);
+  if (lane == 0) wmin[wave] = best;
+  __syncthreads();
+  if (tid != 0) return;
+  const unsigned long long m = min(min(wmin[0], wmin[1]), min(wmin[2], wmin[3]));
+  if (m != BL_KEY_EMPTY) (void)__hip_atomic_fetch_min(&st->best, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  /* the min has been performed before the arrival is counted */
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  const unsigned ticket = __hip_atomic_fetch_add(&st->count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (ticket != gridDim.x - 1u) return;
+  /* every slice's min was performed before its add, and every add before this one returned */
+  const unsigned long long key = __hip_atomic_exchange(&st->best, BL_KEY_EMPTY, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_store(&st->count, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (key == BL_KEY_EMPTY) { /* no song is allowed: the chain has ended, the row keeps k_mix_init's padding */
+    __hip_atomic_store(&st->cur, -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return;
+  }
+  const int pick = (int)(unsigned)key;
+  atomicOr(bits_all + (size_t)c * words + (pick >> 5), 1u << (pick & 31));
+  out_order[(size_t)c * length + t] = pick;
+  out_value[(size_t)c * length + t] =
+      bl_value<COSINE>(a, pa, vecs[pick], COSINE ? prep[pick] : make_double2(0.0, 0.0));
+  if (TAGS) { /* every workgroup of this launch has read the history before it arrived */
+    hist.push(tags[pick], gap);
+#pragma unroll
+    for (int k = 0; k < BL_AMD_MIX_MAX_GAP; ++k)
+      __hip_atomic_store(&st->hist[k], hist.h[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __hip_atomic_store(&st->cur, pick, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+/* ------------------------------------------------------------------------- */
 /* k_radius_*, k_groups_*: fixed-radius neighbourhoods (bl_amd_radius_*, bl_amd_groups_*) */
 /* Song j is within the radius of query i when the matrix entry passes a plain f32 compare: bl_distance <= radius or
  * bl_cosine_similarity >= radius.  The distance is decided on the squared sum: the correctly rounded root is monotone,
@@ -945,7 +1278,11 @@ __global__ __launch_bounds__(256) void k_groups_compress(int *parent, int n) {
 
 int blk_query_configure_device(void) {
   for (const void *fn : {reinterpret_cast<const void *>(k_chain<false, true>),
-                         reinterpret_cast<const void *>(k_chain<true, true>)})
+                         reinterpret_cast<const void *>(k_chain<true, true>),
+                         reinterpret_cast<const void *>(k_mix<false, true, false>),
+                         reinterpret_cast<const void *>(k_mix<false, true, true>),
+                         reinterpret_cast<const void *>(k_mix<true, true, false>),
+                         reinterpret_cast<const void *>(k_mix<true, true, true>)})
     BL_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, CHAIN_LDS_MAX));
   return BL_OK;
 }
@@ -1151,6 +1488,56 @@ int blk_chain(hipStream_t s, const struct force_vector_s *d_vecs, int n, const i
   const double2 *prep = launch_prep(s, v, n, cosine, d_scratch);
   if (cosine) chain_launch<true>(s, p, v, prep, rest, n, d_seeds, n_chains, length, d_order, d_value);
   else chain_launch<false>(s, p, v, prep, rest, n, d_seeds, n_chains, length, d_order, d_value);
+  BL_HIP_CHECK(hipGetLastError());
+  return BL_OK;
+}
+
+/* Chains under rules (k_mix): the plan, the shapes and the scratch layout are the chain's (sizeof(mix_state) ==
+ * sizeof(chain_state)).  d_tags is nullptr when gap == 0, which picks the kernels without the tag rule. */
+size_t blk_mix_scratch_bytes(int n, int n_chains, bool cosine, int n_cu, int force) {
+  return blk_chain_scratch_bytes(n, n_chains, cosine, n_cu, force);
+}
+
+template <bool COSINE, bool TAGS>
+static void mix_launch(hipStream_t s, const chain_plan &p, const float4 *v, const double2 *prep, void *rest, int n,
+                       const int32_t *d_seeds, const float4 *q, int n_chains, int length, const int32_t *d_tags, int gap,
+                       const unsigned char *d_exclude, int32_t *d_order, float *d_value) {
+  if (p.shape == 1) {
+    unsigned *g_bits = static_cast<unsigned *>(rest);
+    if (p.lds_bits)
+      hipLaunchKernelGGL((k_mix<COSINE, true, TAGS>), dim3(n_chains), dim3(1 << p.lb), p.lds_bytes, s, v, prep, n,
+                         d_seeds, q, length, p.lb, p.words, d_tags, gap, d_exclude, g_bits, d_order, d_value);
+    else
+      hipLaunchKernelGGL((k_mix<COSINE, false, TAGS>), dim3(n_chains), dim3(1 << p.lb), p.lds_bytes, s, v, prep, n,
+                         d_seeds, q, length, p.lb, p.words, d_tags, gap, d_exclude, g_bits, d_order, d_value);
+    return;
+  }
+  mix_state *state = static_cast<mix_state *>(rest);
+  unsigned *bits = reinterpret_cast<unsigned *>(state + n_chains);
+  const int fill = std::max(n, length);
+  hipLaunchKernelGGL((k_mix_init<COSINE>), dim3(std::min(256, (fill + 255) / 256), n_chains), dim3(256), 0, s, v, prep,
+                     n, d_seeds, length, p.bit_words, d_tags, d_exclude, state, bits, d_order, d_value);
+  const int steps = std::min(length, n);
+  for (int t = q ? 0 : 1; t < steps; ++t) /* a vector seed's slot 0 is a step of its own, the query from q */
+    hipLaunchKernelGGL((k_mix_step<COSINE, TAGS>), dim3(p.groups, n_chains), dim3(256), 0, s, v, prep, n, p.cols, t,
+                       length, p.bit_words, d_tags, gap, t == 0 ? q : nullptr, state, bits, d_order, d_value);
+}
+
+int blk_mix(hipStream_t s, const struct force_vector_s *d_vecs, int n, const int32_t *d_seeds,
+            const struct force_vector_s *d_seed_vecs, int n_chains, int length, bool cosine, const int32_t *d_tags,
+            int gap, const uint8_t *d_exclude, int n_cu, int force, void *d_scratch, int32_t *d_order, float *d_value) {
+  const float4 *v = reinterpret_cast<const float4 *>(d_vecs), *q = reinterpret_cast<const float4 *>(d_seed_vecs);
+  const chain_plan p = chain_make_plan(n, n_chains, n_cu, force);
+  void *rest = static_cast<char *>(d_scratch) + prep_bytes(n, cosine);
+  const double2 *prep = launch_prep(s, v, n, cosine, d_scratch);
+  const int32_t *tags = gap > 0 ? d_tags : nullptr;
+  if (cosine) {
+    if (tags) mix_launch<true, true>(s, p, v, prep, rest, n, d_seeds, q, n_chains, length, tags, gap, d_exclude, d_order, d_value);
+    else mix_launch<true, false>(s, p, v, prep, rest, n, d_seeds, q, n_chains, length, tags, gap, d_exclude, d_order, d_value);
+  } else {
+    if (tags) mix_launch<false, true>(s, p, v, prep, rest, n, d_seeds, q, n_chains, length, tags, gap, d_exclude, d_order, d_value);
+    else mix_launch<false, false>(s, p, v, prep, rest, n, d_seeds, q, n_chains, length, tags, gap, d_exclude, d_order, d_value);
+  }
   BL_HIP_CHECK(hipGetLastError());
   return BL_OK;
 }

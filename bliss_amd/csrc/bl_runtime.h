@@ -74,8 +74,8 @@ struct bl_amd_ctx {
   int rs_taps = 0, rs_phases = 0, rs_src_incr = 0, rs_dst_incr = 0;
   /* bl_amd_knn_device: the cosine prep of the vectors and the column splits' partial lists */
   bl_buf knn;
-  /* bl_amd_chain_device: cosine prep, the column split's per-chain state and played bits (or the per-chain
-   * shape's played bits beyond what LDS holds) */
+  /* bl_amd_chain_device, bl_amd_mix_device: cosine prep, the column split's per-chain state and played bits (or the
+   * per-chain shape's played bits beyond what LDS holds) */
   bl_buf chain;
   /* bl_amd_radius_*_device, bl_amd_groups_device: cosine prep and the per-(row, column split) counts */
   bl_buf radius;

@@ -1042,6 +1042,66 @@ int bl_amd_chain_host(const struct force_vector_s *h_vecs, int n, const int32_t 
              : BL_UNEXPECTED;
 }
 
+/* Chains under rules: the chain's workspace, shape switch and call path */
+static bool mix_args_ok(const void *vecs, int n, const void *seeds, const void *seed_vecs, int n_chains, int length,
+                        int metric, const void *tags, int gap, const void *order, const void *value) {
+  return vecs && order && value && n > 0 && n_chains > 0 && length > 0 && metric_ok(metric) &&
+         (seeds != nullptr) != (seed_vecs != nullptr) && gap >= 0 && gap <= BL_AMD_MIX_MAX_GAP && (gap == 0 || tags);
+}
+
+int bl_amd_ctx_mix_device(bl_amd_ctx *c, const struct force_vector_s *d_vecs, int n, const int32_t *d_seeds,
+                          const struct force_vector_s *d_seed_vecs, int n_chains, int length, int metric,
+                          const int32_t *d_tags, int gap, const uint8_t *d_exclude, int32_t *d_order, float *d_value,
+                          void *stream) {
+  if (!mix_args_ok(d_vecs, n, d_seeds, d_seed_vecs, n_chains, length, metric, d_tags, gap, d_order, d_value) || !c)
+    return BL_UNEXPECTED;
+  const bool cosine = metric == BL_AMD_KNN_COSINE;
+  const int force = g_chain_force.load();
+  return query_call(c, stream, c->chain, blk_mix_scratch_bytes(n, n_chains, cosine, c->n_cu, force),
+                    [&](hipStream_t s, void *scratch) {
+                      return blk_mix(s, d_vecs, n, d_seeds, d_seed_vecs, n_chains, length, cosine, d_tags, gap, d_exclude,
+                                     c->n_cu, force, scratch, d_order, d_value);
+                    });
+}
+
+int bl_amd_mix_device(const struct force_vector_s *d_vecs, int n, const int32_t *d_seeds,
+                      const struct force_vector_s *d_seed_vecs, int n_chains, int length, int metric,
+                      const int32_t *d_tags, int gap, const uint8_t *d_exclude, int32_t *d_order, float *d_value,
+                      void *stream) {
+  if (!mix_args_ok(d_vecs, n, d_seeds, d_seed_vecs, n_chains, length, metric, d_tags, gap, d_order, d_value))
+    return BL_UNEXPECTED;
+  return bl_amd_ctx_mix_device(blr_default_ctx(), d_vecs, n, d_seeds, d_seed_vecs, n_chains, length, metric, d_tags, gap,
+                               d_exclude, d_order, d_value, stream);
+}
+
+int bl_amd_mix_host(const struct force_vector_s *h_vecs, int n, const int32_t *h_seeds,
+                    const struct force_vector_s *h_seed_vecs, int n_chains, int length, int metric,
+                    const int32_t *h_tags, int gap, const uint8_t *h_exclude, int32_t *h_order, float *h_value) {
+  if (!mix_args_ok(h_vecs, n, h_seeds, h_seed_vecs, n_chains, length, metric, h_tags, gap, h_order,
+                   h_order /* h_value may be NULL */))
+    return BL_UNEXPECTED;
+  for (int c = 0; h_seeds && c < n_chains; ++c)
+    if (h_seeds[c] < 0 || h_seeds[c] >= n) return BL_UNEXPECTED;
+  bl_amd_ctx *c = blr_default_ctx();
+  if (!c) return BL_UNEXPECTED;
+  DevGuard dg(c->device);
+  if (!dg.ok) return BL_UNEXPECTED;
+  const bool use_tags = gap > 0;
+  const size_t out = (size_t)n_chains * length;
+  DevMem dv(sizeof(struct force_vector_s) * (size_t)n), ds(h_seeds ? sizeof(int32_t) * (size_t)n_chains : 0);
+  DevMem dq(h_seed_vecs ? sizeof(struct force_vector_s) * (size_t)n_chains : 0);
+  DevMem dt(use_tags ? sizeof(int32_t) * (size_t)n : 0), dx(h_exclude ? (size_t)n : 0);
+  DevMem di(sizeof(int32_t) * out), dd(sizeof(float) * out);
+  return dv.up(h_vecs) && (!h_seeds || ds.up(h_seeds)) && (!h_seed_vecs || dq.up(h_seed_vecs)) &&
+                 (!use_tags || dt.up(h_tags)) && (!h_exclude || dx.up(h_exclude)) && di.ok() && dd.ok() &&
+                 bl_amd_mix_device(dv.as<struct force_vector_s>(), n, ds.as<int32_t>(), dq.as<struct force_vector_s>(),
+                                   n_chains, length, metric, dt.as<int32_t>(), gap, dx.as<uint8_t>(), di.as<int32_t>(),
+                                   dd.as<float>(), nullptr) == BL_OK &&
+                 di.down(h_order) && (!h_value || dd.down(h_value))
+             ? BL_OK
+             : BL_UNEXPECTED;
+}
+
 /* Radius queries and duplicate groups: the distance is compared on the squared sum against
  * bl_amd_radius_bound(radius), computed here once per call. */
 float bl_amd_radius_bound(float radius) {

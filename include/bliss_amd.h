@@ -338,6 +338,39 @@ int bl_amd_chain_host(const struct force_vector_s *h_vecs, int n, const int32_t 
 int bl_amd_chain_shape(int n, int n_chains);
 int bl_amd_chain_force_shape(int shape);
 
+/* Chains under rules (radio-style continuous play).  Everything not said here is bl_amd_chain_device's contract:
+ * d_order / d_value of n_chains * length, the metric constants, the order of "nearest", values by the bits of the
+ * matrix entry, independent chains, asynchronous on `stream`, nothing written by a rejected call.
+ *   Seeds    exactly one of d_seeds and d_seed_vecs is non-NULL.  d_seeds: slot 0 is the seed, value M[seed][seed], even
+ *            if the seed is excluded; a seed outside [0, n) gives a row of -1 / NaN.  d_seed_vecs: n_chains vectors,
+ *            16-byte aligned, may alias d_vecs; slot 0 is the song nearest to the vector among the songs not excluded
+ *            (tags play no part), its value bl_distance(seed, vecs[j]) / bl_cosine_similarity(seed, vecs[j]) by the
+ *            bits bl_amd_cross_knn_device lists; a row of -1 / NaN if every song is excluded.
+ *   Exclude  d_exclude is NULL or n bytes, one mask for all chains: a song with a non-zero byte is never picked.
+ *   Tags     d_tags is NULL or n int32 (artist, album ...); a negative tag means untagged: never blocked, blocks
+ *            nothing.  0 <= gap <= BL_AMD_MIX_MAX_GAP; gap == 0 ignores the tags, gap > 0 needs them.
+ *   A step   at slot t >= 1 song j is allowed iff it is in none of the slots 0 .. t-1, is not excluded, and tags[j] < 0
+ *            or tags[j] differs from the tag of every song in slots max(0, t-gap) .. t-1.  Slot t is the allowed song
+ *            nearest to the song of slot t-1, its value that matrix entry.  If no song is allowed the chain ends:
+ *            slots t .. length-1 hold -1 and a NaN.
+ * With d_seeds, d_exclude == NULL and gap == 0 the result is bl_amd_chain_device's, byte for byte.  The launch shape
+ * is bl_amd_chain_shape(n, n_chains), bl_amd_chain_force_shape pins it here too, and the result never depends on it.
+ * To continue a chain call again with seed = its last song and d_exclude = everything played so far. */
+#define BL_AMD_MIX_MAX_GAP 16
+int bl_amd_mix_device(const struct force_vector_s *d_vecs, int n, const int32_t *d_seeds,
+                      const struct force_vector_s *d_seed_vecs, int n_chains, int length, int metric,
+                      const int32_t *d_tags, int gap, const uint8_t *d_exclude, int32_t *d_order, float *d_value,
+                      void *stream);
+int bl_amd_ctx_mix_device(bl_amd_ctx *ctx, const struct force_vector_s *d_vecs, int n, const int32_t *d_seeds,
+                          const struct force_vector_s *d_seed_vecs, int n_chains, int length, int metric,
+                          const int32_t *d_tags, int gap, const uint8_t *d_exclude, int32_t *d_order, float *d_value,
+                          void *stream);
+/* Host pointers, blocking.  Index seeds are checked first: one outside [0, n) returns BL_UNEXPECTED and writes nothing.
+ * h_value may be NULL. */
+int bl_amd_mix_host(const struct force_vector_s *h_vecs, int n, const int32_t *h_seeds,
+                    const struct force_vector_s *h_seed_vecs, int n_chains, int length, int metric,
+                    const int32_t *h_tags, int gap, const uint8_t *h_exclude, int32_t *h_order, float *h_value);
+
 /* Radius queries: the songs within a radius of each query, however many, as compressed sparse row (CSR) lists and
  * without the N x N matrix.  M is the bl_distance matrix (BL_AMD_KNN_DISTANCE; ref src/analyze.c:96-100) or the
  * bl_cosine_similarity matrix (BL_AMD_KNN_COSINE; ref src/analyze.c:135-140), entries by their bits as
