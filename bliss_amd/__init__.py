@@ -6,14 +6,15 @@ All computation happens in libbliss_amd.so (hand-written HIP kernels for gfx950)
 """
 from . import _lib
 from ._lib import (BL_CALM, BL_LOUD, BL_OK, BL_UNEXPECTED, BL_UNKNOWN, BlSong, EnvelopeResult,
-                   ForceVector, SongDesc, SongResult, load)
+                   ForceVector, SongDesc, SongLevels, SongResult, load)
 from . import distance, version
 from .batch import (Context, DeviceCorpus, analyze_batch_host, analyze_files, analyze_batch_host_rate, analyze_batch_host_s32,
                     analyze_corpus_multi, analyze_corpus_multi_device, chain, chain_device, mix, mix_device, cosine_matrix, distance_matrix, knn, knn_device,
                     playlist, knn_cross, knn_cross_device, playlist_vec, radius_cross, radius_cross_device,
                     duplicate_groups, duplicate_groups_device, radius, radius_device,
                     resample_batch_device,
-                    resample_host, results_to_numpy)
+                    resample_host, results_to_numpy,
+                    gapless_links, levels_batch_host, levels_db, levels_to_numpy)
 from .bl_song import bl_song
 
 __all__ = ["_lib", "load", "BlSong", "ForceVector", "EnvelopeResult", "SongDesc", "SongResult",
@@ -22,6 +23,7 @@ __all__ = ["_lib", "load", "BlSong", "ForceVector", "EnvelopeResult", "SongDesc"
            "distance_matrix", "cosine_matrix", "results_to_numpy", "playlist", "knn", "knn_device", "chain", "chain_device", "mix", "mix_device",
            "radius", "radius_device", "knn_cross", "knn_cross_device", "radius_cross", "radius_cross_device", "playlist_vec",
            "duplicate_groups", "duplicate_groups_device",
+           "SongLevels", "levels_batch_host", "levels_to_numpy", "levels_db", "gapless_links",
            "resample_host", "resample_batch_device", "bl_song", "distance", "version"]
 
 

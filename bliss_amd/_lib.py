@@ -57,6 +57,12 @@ class SongResult(C.Structure):  # include/bliss_amd.h bl_amd_song_result
                 ("atk_sum", C.c_double)]
 
 
+class SongLevels(C.Structure):  # include/bliss_amd.h bl_amd_song_levels
+    _fields_ = [("sum", C.c_int64 * 2), ("sum_sq", C.c_uint64 * 2), ("peak", C.c_int32 * 2),
+                ("zero_cross", C.c_int32 * 2), ("clipped", C.c_int32 * 2), ("lead", C.c_int32), ("trail", C.c_int32),
+                ("frames", C.c_int32), ("status", C.c_int32), ("head", C.c_int16 * 2), ("tail", C.c_int16 * 2)]
+
+
 class Shard(C.Structure):  # include/bliss_amd.h bl_amd_shard
     _fields_ = [("device", C.c_int32), ("n_songs", C.c_int32), ("d_pcm", C.c_void_p),
                 ("h_desc", C.POINTER(SongDesc)), ("d_results", C.c_void_p), ("d_rows", C.c_void_p)]
@@ -170,6 +176,14 @@ SYMBOLS = {
     "bl_amd_ctx_groups_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p,
                                            C.c_void_p]),
     "bl_amd_groups_host": (C.c_int, [_P(ForceVector), C.c_int, C.c_int, C.c_float, _P(C.c_int32)]),
+    "bl_amd_levels_batch_device": (C.c_int, [C.c_void_p, _P(SongDesc), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "bl_amd_ctx_levels_batch_device": (C.c_int, [C.c_void_p, C.c_void_p, _P(SongDesc), C.c_int, C.c_int, C.c_void_p,
+                                                 C.c_void_p]),
+    "bl_amd_levels_batch_host": (C.c_int, [_P(C.c_void_p), _P(C.c_int32), _P(C.c_int32), C.c_int, C.c_int,
+                                           _P(SongLevels)]),
+    "bl_amd_gapless_host": (C.c_int, [_P(SongLevels), C.c_int, _P(C.c_uint8)]),
+    "bl_amd_levels_peak_db": (C.c_double, [_P(SongLevels), C.c_int]),
+    "bl_amd_levels_rms_db": (C.c_double, [_P(SongLevels), C.c_int]),
     "bl_amd_synth_pcm_device": (C.c_int, [C.c_void_p, _P(SongDesc), C.c_int, C.c_uint32, C.c_uint32, C.c_void_p]),
     "bl_amd_set_fir_mode": (C.c_int, [C.c_int]),
     "bl_amd_fir_mode": (C.c_int, []),

@@ -22,6 +22,43 @@ def results_to_numpy(raw_bytes):
     return np.frombuffer(bytes(raw_bytes), dtype=RESULT_DTYPE).copy()
 
 
+LEVELS_DTYPE = np.dtype([
+    ("sum", "<i8", (2,)), ("sum_sq", "<u8", (2,)), ("peak", "<i4", (2,)), ("zero_cross", "<i4", (2,)),
+    ("clipped", "<i4", (2,)), ("lead", "<i4"), ("trail", "<i4"), ("frames", "<i4"), ("status", "<i4"),
+    ("head", "<i2", (2,)), ("tail", "<i2", (2,))], align=True)
+assert LEVELS_DTYPE.itemsize == C.sizeof(_lib.SongLevels) == 80
+
+LEVELS_DB_DTYPE = np.dtype([("peak_db", "<f8", (2,)), ("rms_db", "<f8", (2,)), ("dc", "<f8", (2,)),
+                            ("zcr", "<f8", (2,))])
+
+
+def levels_to_numpy(raw):
+    """bytes / uint8 array of bl_amd_song_levels records -> structured numpy array with the header's field names."""
+    return np.frombuffer(bytes(raw), dtype=LEVELS_DTYPE).copy()
+
+
+def _silence_check(silence):
+    if isinstance(silence, bool) or not isinstance(silence, (int, np.integer)) or not 0 <= silence <= 32767:
+        raise ValueError(f"silence must be an integer in [0, 32767], got {silence!r}")
+    return int(silence)
+
+
+def _levels_songs_check(lengths, channels):
+    """per-song channel list, once there is a song and every song has 1 or 2 channels and at least 2 samples"""
+    n = len(lengths)
+    if n < 1:
+        raise ValueError("at least one song is needed")
+    channels = [channels] * n if np.isscalar(channels) else list(channels)
+    if len(channels) != n:
+        raise ValueError(f"{n} songs but {len(channels)} channel counts")
+    for ln, ch in zip(lengths, channels):
+        if isinstance(ch, bool) or not isinstance(ch, (int, np.integer)) or ch not in (1, 2):
+            raise ValueError(f"channels must be 1 or 2, got {ch!r}")
+        if int(ln) < 2:
+            raise ValueError(f"a song needs at least 2 samples, got {int(ln)}")
+    return [int(ch) for ch in channels]
+
+
 def _check(rc, what):
     if rc != _lib.BL_OK:
         raise RuntimeError(f"{what} failed with BL_UNEXPECTED ({rc}); see stderr")
@@ -106,6 +143,31 @@ class DeviceCorpus:
         self.torch.cuda.synchronize(self.device)
         return results_to_numpy(self.results.cpu().numpy().tobytes())
 
+    def levels(self, silence=0, ctx=None):
+        """Enqueue the signal levels of every song (bl_amd_levels_batch_device) on torch's current stream; returns the
+        uint8 CUDA tensor of bl_amd_song_levels records this corpus owns (fetch_levels() reads it).  silence: a frame
+        is silent while every channel has |s| <= silence (lead / trail).  ctx: an explicit Context."""
+        silence = _silence_check(silence)
+        _levels_songs_check([d.n_samples for d in self.desc], [d.channels for d in self.desc])
+        if getattr(self, "levels_raw", None) is None:
+            with self.torch.cuda.device(self.device):
+                self.levels_raw = self.torch.zeros(self.n_songs * C.sizeof(_lib.SongLevels), dtype=self.torch.uint8,
+                                                   device=self.device)
+        args = (C.c_void_p(self.pcm.data_ptr()), self.desc, self.n_songs, silence,
+                C.c_void_p(self.levels_raw.data_ptr()), self._stream())
+        if ctx is None:
+            _check(self.lib.bl_amd_levels_batch_device(*args), "bl_amd_levels_batch_device")
+        else:
+            _check(self.lib.bl_amd_ctx_levels_batch_device(ctx.handle, *args), "bl_amd_ctx_levels_batch_device")
+        return self.levels_raw
+
+    def fetch_levels(self):
+        """Wait for the device and return what the last levels() call computed, as a structured array."""
+        if getattr(self, "levels_raw", None) is None:
+            raise RuntimeError("levels() has not been called on this corpus")
+        self.torch.cuda.synchronize(self.device)
+        return levels_to_numpy(self.levels_raw.cpu().numpy().tobytes())
+
     def force_vectors(self):
         """(n_songs, 4) float32 CUDA tensor view-copy of the force vectors."""
         rec = self.results.view(self.n_songs, C.sizeof(_lib.SongResult))
@@ -158,6 +220,55 @@ def analyze_batch_host(pcm_list, channels, durations):
     args, out, _keep = _host_args(pcm_list, channels, durations, np.int16)
     _check(lib.bl_amd_analyze_batch_host(*args, out), "bl_amd_analyze_batch_host")
     return results_to_numpy(bytes(out))
+
+
+def levels_batch_host(pcm_list, channels, silence=0):
+    """Signal levels of songs in host memory (bl_amd_levels_batch_host): pcm_list a list of 1-D int16 arrays
+    (interleaved), channels per song or one for all.  Returns the structured array of levels_to_numpy()."""
+    silence = _silence_check(silence)
+    arrs = [np.ascontiguousarray(p, dtype=np.int16).reshape(-1) for p in pcm_list]
+    channels = _levels_songs_check([a.size for a in arrs], channels)
+    lib = _lib.load()
+    n = len(arrs)
+    ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in arrs])
+    ns = (C.c_int32 * n)(*[a.size for a in arrs])
+    chs = (C.c_int32 * n)(*channels)
+    out = (_lib.SongLevels * n)()
+    _check(lib.bl_amd_levels_batch_host(ptrs, ns, chs, n, silence, out), "bl_amd_levels_batch_host")
+    return levels_to_numpy(bytes(out))
+
+
+def _levels_array(levels):
+    lv = np.ascontiguousarray(levels)
+    if lv.dtype != LEVELS_DTYPE or lv.ndim != 1 or lv.size < 1:
+        raise ValueError("levels must be a non-empty 1-D array of bl_amd_song_levels records (levels_to_numpy)")
+    return lv
+
+
+def gapless_links(levels):
+    """bool array of n - 1 entries: song i runs into song i + 1 (bl_amd_gapless_host: the rule of the reference's
+    examples/detect-gapless.c on the last two samples of one song and the first two of the next)."""
+    lv = _levels_array(levels)
+    lib = _lib.load()
+    linked = np.zeros(max(lv.size - 1, 1), dtype=np.uint8)
+    _check(lib.bl_amd_gapless_host(lv.ctypes.data_as(C.POINTER(_lib.SongLevels)), lv.size,
+                                   linked.ctypes.data_as(C.POINTER(C.c_uint8))), "bl_amd_gapless_host")
+    return linked[:lv.size - 1].astype(bool)
+
+
+def levels_db(levels):
+    """What a player reads off the integers, per channel, as a structured array: peak_db = 20 log10(peak / 32768),
+    rms_db = 10 log10(sum_sq / (frames 2^30)) (-inf for silence and for channel 1 of a mono song), dc = sum / frames
+    and zcr = zero_cross / max(frames - 1, 1)."""
+    lv = _levels_array(levels)
+    out = np.empty(lv.size, dtype=LEVELS_DB_DTYPE)
+    frames = lv["frames"].astype(np.float64)[:, None]
+    with np.errstate(divide="ignore"):
+        out["peak_db"] = 20.0 * np.log10(lv["peak"].astype(np.float64) / 32768.0)
+        out["rms_db"] = 10.0 * np.log10(lv["sum_sq"].astype(np.float64) / (frames * 2.0 ** 30))
+    out["dc"] = lv["sum"].astype(np.float64) / frames
+    out["zcr"] = lv["zero_cross"].astype(np.float64) / np.maximum(frames - 1.0, 1.0)
+    return out
 
 
 def analyze_files(filenames, n_threads=0, keep_pcm=False):

@@ -206,3 +206,35 @@ void bl_rectangular_filter(double *sample_array_out, double *sample_array_in, in
   for (; lag < end; ++lag) *last += *lag;
   for (int k = 0; k < nSamples; ++k) sample_array_out[k] /= smooth_width;
 }
+
+/* ---- signal levels: the host arithmetic over bl_amd_song_levels (include/bliss_amd.h) ---- */
+
+/* One interleaved slot of ref examples/detect-gapless.c:35-54: both samples at least 5 away from zero, and their
+ * difference, as an f32 quotient by INT16_MAX whose magnitude is compared as a double, below 0.01.  In integers:
+ * |tail - head| <= 327 (327 / 32767 = 0.00998, 328 / 32767 = 0.01001). */
+static int gapless_slot(int16_t tail, int16_t head) {
+  if (abs((int)tail) < 5 || abs((int)head) < 5) return 0;
+  const float diff = fabsf(((float)tail - (float)head) / (float)INT16_MAX);
+  return (double)diff < 0.01;
+}
+
+/* ref examples/detect-gapless.c:49: gapless if either slot says so */
+int bl_amd_gapless_host(const bl_amd_song_levels *h_levels, int n_songs, uint8_t *h_linked) {
+  if (!h_levels || n_songs < 1 || (n_songs > 1 && !h_linked)) return BL_UNEXPECTED;
+  for (int i = 0; i + 1 < n_songs; ++i)
+    h_linked[i] = (uint8_t)(gapless_slot(h_levels[i].tail[0], h_levels[i + 1].head[0]) ||
+                            gapless_slot(h_levels[i].tail[1], h_levels[i + 1].head[1]));
+  return BL_OK;
+}
+
+/* 20 log10(peak / 32768): 0 dB is full scale, silence is -inf */
+double bl_amd_levels_peak_db(const bl_amd_song_levels *lv, int channel) {
+  if (!lv || channel < 0 || channel > 1) return NAN;
+  return 20.0 * log10((double)lv->peak[channel] / 32768.0);
+}
+
+/* 10 log10(mean square / 2^30): 0 dB is a song of nothing but -32768 */
+double bl_amd_levels_rms_db(const bl_amd_song_levels *lv, int channel) {
+  if (!lv || channel < 0 || channel > 1 || lv->frames < 1) return NAN;
+  return 10.0 * log10((double)lv->sum_sq[channel] / ((double)lv->frames * 1073741824.0));
+}

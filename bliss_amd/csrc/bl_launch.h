@@ -1,8 +1,9 @@
 /*
  * bl_launch.h — internal seam between the kernel translation units (device code + launch
  * geometry: bl_kernels.hip the launch order of the per-song analysis, whose stages are
- * bl_stats_kernels.hip, bl_freq_kernels.hip and bl_env_kernels.hip; bl_matrix_kernels.hip the
- * pairwise matrix, bl_query_kernels.hip the vector queries, bl_rs_kernels.hip the rate converter)
+ * bl_stats_kernels.hip, bl_freq_kernels.hip and bl_env_kernels.hip; bl_level_kernels.hip the signal
+ * levels, bl_matrix_kernels.hip the pairwise matrix, bl_query_kernels.hip the vector queries,
+ * bl_rs_kernels.hip the rate converter)
  * and the runtime (bl_runtime.hip: contexts, workspaces, streams, the C-ABI of
  * include/bliss_amd.h; bl_multi.hip: the multi-device corpus path).  Also BL_HIP_CHECK, which
  * every .hip file uses.  C++ only, not installed.
@@ -161,6 +162,17 @@ int blk_scan_one(hipStream_t s, const int16_t *pcm, const bl_dsong *d_songs, bl_
                  unsigned *d_hist, int n, int n_cu);
 int blk_variance_wrap_one(hipStream_t s, const int16_t *pcm, const bl_dsong *d_songs,
                           bl_dstats *d_stats, int n, int n_cu);
+
+/* ---- per-song signal levels (bl_level_kernels.hip) ----------------------------- */
+
+struct bl_level_song { /* what the level kernels read of a bl_amd_song_desc; record i belongs to d_levels[i] */
+  unsigned long long pcm_off; /* int16 elements from the arena base, a multiple of 8 */
+  int n, channels;            /* n >= 2 interleaved samples of 1 | 2 channels */
+};
+#define BL_LEVEL_GROUP_SONGS 32768 /* songs per launch: gridDim.y of the (blocks, songs) grid */
+/* bl_amd_levels_batch_device: zeroes d_levels, then fills every field of its n_songs records; max_n: the longest n */
+int blk_levels(hipStream_t s, const int16_t *d_pcm, const bl_level_song *d_songs, int n_songs, int max_n, int silence,
+               int n_cu, bl_amd_song_levels *d_levels);
 
 /* ---- benchmark corpus and sample narrowing (bl_kernels.hip) -------------------- */
 

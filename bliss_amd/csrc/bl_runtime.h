@@ -79,6 +79,8 @@ struct bl_amd_ctx {
   bl_buf chain;
   /* bl_amd_radius_*_device, bl_amd_groups_device: cosine prep and the per-(row, column split) counts */
   bl_buf radius;
+  /* bl_amd_levels_batch_device: the songs' records (bl_level_song) */
+  bl_buf level_songs;
 };
 
 /* bl_runtime.hip */

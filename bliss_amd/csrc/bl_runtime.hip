@@ -171,7 +171,7 @@ void ctx_release(bl_amd_ctx *c) {
   prof_collect(c);
   bl_buf *bufs[] = {&c->songs,   &c->stats,   &c->hist, &c->spectrum, &c->energies, &c->lc,
                     &c->results, &c->misc,    &c->arena[0], &c->arena[1], &c->arena22[0], &c->arena22[1],
-                    &c->rs_songs, &c->rs_bank, &c->mx_my, &c->mx_gath, &c->mx_all, &c->mx_order, &c->mx_rows, &c->knn, &c->chain, &c->radius};
+                    &c->rs_songs, &c->rs_bank, &c->mx_my, &c->mx_gath, &c->mx_all, &c->mx_order, &c->mx_rows, &c->knn, &c->chain, &c->radius, &c->level_songs};
   for (bl_buf *b : bufs) release_buf(*b);
   for (int k = 0; k < 2; ++k) {
     unregister_wave(c, k);
@@ -810,6 +810,102 @@ int bl_amd_ctx_analyze_batch_device(bl_amd_ctx *ctx, const int16_t *d_pcm, const
 int bl_amd_analyze_batch_device(const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs,
                                 bl_amd_song_result *d_results, void *stream) {
   return bl_amd_ctx_analyze_batch_device(blr_default_ctx(), d_pcm, h_desc, n_songs, d_results, stream);
+}
+
+/* ---- signal levels (bl_level_kernels.hip) ---------------------------------- */
+
+/* samples per wave of bl_amd_levels_batch_host: the songs are uploaded, analysed and fetched 256 MiB of PCM at a
+ * time (a song longer than that is a wave of its own) */
+#define BL_LEVELS_WAVE_SAMPLES ((size_t)128 << 20)
+
+static bool levels_song_ok(unsigned long long pcm_offset, int n_samples, int channels) {
+  return n_samples >= 2 && (channels == 1 || channels == 2) && !(pcm_offset & 7);
+}
+
+static bool levels_args_ok(const void *d_pcm, const bl_amd_song_desc *h_desc, int n_songs, int silence,
+                           const void *d_levels) {
+  if (!d_pcm || ((uintptr_t)d_pcm & 15) || !h_desc || !d_levels || n_songs < 1 || silence < 0 || silence > 32767)
+    return false;
+  for (int i = 0; i < n_songs; ++i)
+    if (!levels_song_ok(h_desc[i].pcm_offset, h_desc[i].n_samples, h_desc[i].channels)) return false;
+  return true;
+}
+
+int bl_amd_ctx_levels_batch_device(bl_amd_ctx *c, const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs,
+                                   int silence, bl_amd_song_levels *d_levels, void *stream) {
+  if (!levels_args_ok(d_pcm, h_desc, n_songs, silence, d_levels) || !c) return BL_UNEXPECTED;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DevGuard dg(c->device);
+  if (!dg.ok) return BL_UNEXPECTED;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  /* the records go through a pinned slot, as blr_analyze_device uploads its own: copied when this returns */
+  const size_t bytes = sizeof(bl_level_song) * (size_t)n_songs;
+  bl_pin_slot *slot = nullptr;
+  if (ring_get(c, bytes, &slot) != BL_OK) return BL_UNEXPECTED;
+  bl_level_song *hs = static_cast<bl_level_song *>(slot->p);
+  int max_n = 0;
+  for (int i = 0; i < n_songs; ++i) {
+    hs[i].pcm_off = h_desc[i].pcm_offset;
+    hs[i].n = h_desc[i].n_samples;
+    hs[i].channels = h_desc[i].channels;
+    max_n = std::max(max_n, h_desc[i].n_samples);
+  }
+  if (c->ws_used) BL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_ws, 0));
+  if (blr_ensure(c->level_songs, bytes) != BL_OK) return BL_UNEXPECTED;
+  bl_level_song *d_songs = static_cast<bl_level_song *>(c->level_songs.p);
+  BL_HIP_CHECK(hipMemcpyAsync(d_songs, hs, bytes, hipMemcpyHostToDevice, s));
+  BL_HIP_CHECK(hipEventRecord(slot->ev, s));
+  slot->busy = true;
+  if (blk_levels(s, d_pcm, d_songs, n_songs, max_n, silence, c->n_cu, d_levels) != BL_OK) return BL_UNEXPECTED;
+  BL_HIP_CHECK(hipEventRecord(c->ev_ws, s));
+  c->ws_used = true;
+  return BL_OK;
+}
+
+int bl_amd_levels_batch_device(const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs, int silence,
+                               bl_amd_song_levels *d_levels, void *stream) {
+  if (!levels_args_ok(d_pcm, h_desc, n_songs, silence, d_levels)) return BL_UNEXPECTED;
+  return bl_amd_ctx_levels_batch_device(blr_default_ctx(), d_pcm, h_desc, n_songs, silence, d_levels, stream);
+}
+
+int bl_amd_levels_batch_host(const int16_t *const *h_pcm, const int32_t *n_samples, const int32_t *channels,
+                             int n_songs, int silence, bl_amd_song_levels *h_levels) {
+  if (!h_pcm || !n_samples || !channels || !h_levels || n_songs < 1 || silence < 0 || silence > 32767)
+    return BL_UNEXPECTED;
+  for (int i = 0; i < n_songs; ++i)
+    if (!h_pcm[i] || !levels_song_ok(0, n_samples[i], channels[i])) return BL_UNEXPECTED;
+  bl_amd_ctx *c = blr_default_ctx();
+  if (!c) return BL_UNEXPECTED;
+  DevGuard dg(c->device);
+  if (!dg.ok) return BL_UNEXPECTED;
+  std::vector<bl_amd_song_desc> desc;
+  for (int b = 0; b < n_songs;) {
+    /* one wave: songs [b, e), every one at a multiple of 8 samples */
+    desc.clear();
+    size_t total = 0;
+    int e = b;
+    while (e < n_songs && (e == b || total + (size_t)n_samples[e] <= BL_LEVELS_WAVE_SAMPLES)) {
+      bl_amd_song_desc d;
+      d.pcm_offset = total;
+      d.n_samples = n_samples[e];
+      d.channels = channels[e];
+      d.duration = 0;
+      desc.push_back(d);
+      total += ((size_t)n_samples[e] + 7) & ~(size_t)7;
+      ++e;
+    }
+    DevMem arena(sizeof(int16_t) * total), out(sizeof(bl_amd_song_levels) * (size_t)(e - b));
+    if (!arena.ok() || !out.ok()) return BL_UNEXPECTED;
+    for (int i = b; i < e; ++i)
+      BL_HIP_CHECK(hipMemcpy(arena.as<int16_t>() + desc[i - b].pcm_offset, h_pcm[i],
+                             sizeof(int16_t) * (size_t)n_samples[i], hipMemcpyHostToDevice));
+    if (bl_amd_levels_batch_device(arena.as<int16_t>(), desc.data(), e - b, silence, out.as<bl_amd_song_levels>(),
+                                   nullptr) != BL_OK ||
+        !out.down(h_levels + b))
+      return BL_UNEXPECTED;
+    b = e;
+  }
+  return BL_OK;
 }
 
 int bl_amd_synth_pcm_device(int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs,

@@ -439,6 +439,54 @@ int bl_amd_ctx_groups_device(bl_amd_ctx *ctx, const struct force_vector_s *d_vec
                              int32_t *d_group, void *stream);
 int bl_amd_groups_host(const struct force_vector_s *h_vecs, int n, int metric, float radius, int32_t *h_group);
 
+/* Signal levels: what a player needs of a song's PCM beyond the four ratings — how loud it is (peak, RMS, DC), how
+ * often it crosses zero, how many samples sit at full scale, where the silence at either end stops, and the four
+ * samples that say whether it runs into the next track.  None of it is in the reference's API: its author's ROADMAP.md
+ * lists "zero-crossing rate" and "rough measure of the dB level of songs" as next, and head / tail are the samples
+ * ref examples/detect-gapless.c:28-33 reads.  Every field is an exact integer.
+ * F = n_samples / channels (integer division) is the number of frames; channel c of frame t is
+ * pcm[t * channels + c].  A sample behind frame F - 1 (the last one of a stereo song with an odd n_samples) only shows
+ * up in `tail`.  For a mono song every [1] entry of the per-channel fields is 0.
+ *   lead    the number of frames before the first frame in which some channel has |s| > silence
+ *   trail   the number of frames after the last such frame; a song with no such frame has lead = trail = F */
+typedef struct bl_amd_song_levels { /* 80 bytes */
+  int64_t sum[2];        /* sum of the samples of channel c (DC) */
+  uint64_t sum_sq[2];    /* sum of their squares; (-32768)^2 = 2^30 counts in full */
+  int32_t peak[2];       /* max |s|, 0 .. 32768 */
+  int32_t zero_cross[2]; /* frames t in [1, F) with (s[t] < 0) != (s[t-1] < 0); 0 counts as non-negative */
+  int32_t clipped[2];    /* samples equal to 32767 or -32768 */
+  int32_t lead, trail;   /* see above */
+  int32_t frames;        /* F */
+  int32_t status;        /* BL_OK */
+  int16_t head[2];       /* pcm[0], pcm[1]: interleaved, whatever `channels` is */
+  int16_t tail[2];       /* pcm[n_samples - 2], pcm[n_samples - 1] */
+} bl_amd_song_levels;
+/* bl_amd_levels_batch_device: the levels of n_songs songs whose PCM sits in device memory, one streaming pass.  The
+ * descriptors are those of bl_amd_analyze_batch_device with other limits: pcm_offset a multiple of 8, channels 1 or 2,
+ * n_samples >= 2 (not the analysers' 5120: levels make sense for any clip), duration ignored; d_pcm 16-byte aligned.
+ * 0 <= silence <= 32767, n_songs >= 1.  A rejected call returns BL_UNEXPECTED and writes nothing.  Asynchronous on
+ * `stream`; h_desc is copied before the call returns; d_levels (n_songs records) need not be zeroed by the caller.
+ * Calls of one context are ordered on the device like its batches.  The record of a song is a pure function of its
+ * samples, `channels` and `silence`: it depends neither on the other songs, nor on n_songs, nor on the launch grid,
+ * and no sample outside [pcm_offset, pcm_offset + n_samples) is read.
+ *   bl_amd_levels_batch_host: the same from host memory, blocking: the songs are uploaded and analysed in waves.
+ *   bl_amd_gapless_host: plain host arithmetic, no device.  h_linked[i], i < n_songs - 1, is 1 iff song i runs into
+ *     song i + 1 under the rule of ref examples/detect-gapless.c:35-54: for an interleaved slot k in {0, 1} with
+ *     |tail_i[k]| >= 5 and |head_{i+1}[k]| >= 5, fabs(((float)tail_i[k] - head_{i+1}[k]) / (float)INT16_MAX) < 0.01
+ *     (in integers: |tail - head| <= 327); slot 0 or slot 1 suffices.  n_songs == 1 writes nothing.
+ *   bl_amd_levels_peak_db = 20 log10(peak / 32768), bl_amd_levels_rms_db = 10 log10(sum_sq / (frames * 2^30)), in
+ *     double from the exact integers: -inf for a zero argument (also channel 1 of a mono song), NaN for a channel
+ *     outside [0, 1]. */
+int bl_amd_levels_batch_device(const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs, int silence,
+                               bl_amd_song_levels *d_levels, void *stream);
+int bl_amd_ctx_levels_batch_device(bl_amd_ctx *ctx, const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs,
+                                   int silence, bl_amd_song_levels *d_levels, void *stream);
+int bl_amd_levels_batch_host(const int16_t *const *h_pcm, const int32_t *n_samples, const int32_t *channels,
+                             int n_songs, int silence, bl_amd_song_levels *h_levels);
+int bl_amd_gapless_host(const bl_amd_song_levels *h_levels, int n_songs, uint8_t *h_linked);
+double bl_amd_levels_peak_db(const bl_amd_song_levels *lv, int channel);
+double bl_amd_levels_rms_db(const bl_amd_song_levels *lv, int channel);
+
 /* Integer-only synthetic PCM (the benchmark corpus of BASELINE.json),
  * generated in place on the device: song i = seed_base + i, written at
  * h_desc[i].pcm_offset.  Byte-identical to oracle/orc_synth.c. */
