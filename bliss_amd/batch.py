@@ -442,7 +442,8 @@ def cosine_matrix(vecs):
 
 def playlist(vecs, seed_index):
     """Song indices ordered by increasing bl_distance from song `seed_index`, and the
-    distances (ref python/examples/make_m3u_playlist.py:62-72).  Stable for ties."""
+    distances (ref python/examples/make_m3u_playlist.py:62-72).  Stable for ties.  NaN distances after every
+    number, in index order: numpy's stable argsort."""
     lib = _lib.load()
     v = np.ascontiguousarray(vecs, dtype=np.float32).reshape(-1, 4)
     n = v.shape[0]
@@ -935,7 +936,8 @@ def radius_cross_device(d_queries, d_vecs, r, metric="distance", values=True, st
 
 def playlist_vec(vecs, seed_vec):
     """playlist() from a seed that need not be a song of `vecs`: the song indices by increasing bl_distance from the
-    4-component `seed_vec`, and the distances.  Stable for ties; a seed equal to a song lists it at distance 0."""
+    4-component `seed_vec`, and the distances.  Stable for ties; a seed equal to a song lists it at distance 0.  NaN
+    distances after every number, in index order: numpy's stable argsort."""
     v = np.ascontiguousarray(vecs, dtype=np.float32)
     if v.ndim != 2 or v.shape[1] != 4 or v.shape[0] < 1:
         raise ValueError(f"force vectors must have shape (n, 4) with n >= 1, got {v.shape}")

@@ -142,7 +142,8 @@ __global__ __launch_bounds__(256) void k_sqrt_sweep(unsigned long long first, un
 /* seeded playlist: ref python/examples/make_m3u_playlist.py:62-72                */
 /* distances from one seed vector to every song (bl_distance arithmetic), then the songs
  * in order of increasing distance.  The order is the stable argsort: rank(i) = number of
- * songs that are closer, or equally close with a smaller index — an exact, deterministic
+ * songs that are closer, or equally close with a smaller index (a NaN distance: farther than
+ * every number, as close as another NaN) — an exact, deterministic
  * O(n^2) count (4.3e9 comparisons at n = 65 536, a few ms) instead of a comparison sort. */
 __global__ __launch_bounds__(256) void k_seed_dist(const float4 *__restrict__ vecs, int n, int seed,
                                                    float *__restrict__ dist) {
@@ -159,18 +160,21 @@ __global__ __launch_bounds__(256) void k_seed_dist_vec(const float4 *__restrict_
 
 __global__ __launch_bounds__(256) void k_rank_order(const float *__restrict__ dist, int n,
                                                     int *__restrict__ order) {
-  __shared__ float tile[256];
+  /* compared as bl_ord keys, the total order of the queries: every NaN distance after +inf and equal to every other
+   * NaN, so the NaN songs take the last ranks in index order (numpy's stable argsort) and every rank is taken once;
+   * a plain float compare is false both ways for a NaN and would rank all of them 0 */
+  __shared__ unsigned tile[256];
   const int i = blockIdx.x * 256 + threadIdx.x;
-  const float di = i < n ? dist[i] : 0.f;
+  const unsigned ki = i < n ? bl_ord(dist[i]) : 0u;
   int rank = 0;
   for (int j0 = 0; j0 < n; j0 += 256) {
     const int j = j0 + threadIdx.x;
-    tile[threadIdx.x] = j < n ? dist[j] : 0.f;
+    tile[threadIdx.x] = j < n ? bl_ord(dist[j]) : 0u;
     __syncthreads();
     const int lim = min(256, n - j0);
     for (int k = 0; k < lim; ++k) {
-      const float dj = tile[k];
-      rank += (dj < di || (dj == di && j0 + k < i)) ? 1 : 0;
+      const unsigned kj = tile[k];
+      rank += (kj < ki || (kj == ki && j0 + k < i)) ? 1 : 0;
     }
     __syncthreads();
   }

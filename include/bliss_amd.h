@@ -254,7 +254,8 @@ int bl_amd_selftest_cos(uint64_t counts[6], uint64_t triples);
 
 /* Seeded playlist (ref python/examples/make_m3u_playlist.py:62-72): d_dist[j] =
  * bl_distance(vecs[seed_index], vecs[j]) and d_order = the song indices by increasing
- * distance (stable: ties by index).  d_order: n int32, d_dist: n floats. */
+ * distance (stable: ties by index).  NaN distances after every number, in index order: numpy's
+ * stable argsort; d_dist keeps the NaN.  d_order: n int32, a permutation of 0..n-1; d_dist: n floats. */
 int bl_amd_playlist_device(const struct force_vector_s *d_vecs, int n, int seed_index,
                            int32_t *d_order, float *d_dist, void *stream);
 int bl_amd_playlist_host(const struct force_vector_s *h_vecs, int n, int seed_index,
@@ -262,7 +263,8 @@ int bl_amd_playlist_host(const struct force_vector_s *h_vecs, int n, int seed_in
 
 /* The same from a seed that is no song of the library (a track analysed but not added, a mean of songs): the vector
  * is passed by value, as bl_distance takes its vectors.  d_dist[j] = bl_distance(seed, vecs[j]), d_order the stable
- * argsort; a seed equal to a song lists that song like any other, at distance 0. */
+ * argsort; a seed equal to a song lists that song like any other, at distance 0.  NaN distances after every number,
+ * in index order: numpy's stable argsort (a seed with a NaN component lists the songs 0..n-1). */
 int bl_amd_playlist_vec_device(const struct force_vector_s *d_vecs, int n, struct force_vector_s seed,
                                int32_t *d_order, float *d_dist, void *stream);
 int bl_amd_playlist_vec_host(const struct force_vector_s *h_vecs, int n, struct force_vector_s seed,
