@@ -25,7 +25,7 @@
 /* ------------------------------------------------------------------------- */
 /* k_env_windows3: normalise + FIR + DFT + ordered sum, wave-autonomous        */
 /*
- * One workgroup per CU: 7 compute waves + 1 summing wave (2 waves per SIMD, 213-220 VGPRs), no workgroup
+ * One workgroup per CU: 7 compute waves + 1 summing wave (2 waves per SIMD, 194-234 VGPRs), no workgroup
  * barrier inside the loop.
  *
  * A compute wave walks a CONTIGUOUS run of rounds of four windows (one window per 16-lane group; the song's
@@ -37,6 +37,14 @@
  * the place of the window's own block, partner values of the real-input split through DPP (row mirror + shift),
  * and the 4 x 257 power terms.  The first round of a run is preceded by a short pass that filters the one block
  * it cannot inherit.
+ *
+ * FIR mode 2 (the default) forms the filter's sum exactly, on the integers (bl_fir_int.h): in the main loop a block
+ * of 256 samples is a 16 x 16 tile of outputs and five int8 matrix products (v_mfma_i32_16x16x64_i8 / x32_i8: the
+ * matrix pipe, beside the f64 VALU the rest of the round lives on) of the samples' byte planes with the digit planes
+ * of the Toeplitz tap matrix; a lane loads its 8 samples of each of the round's four tiles, ends up with four
+ * consecutive outputs per tile, converts (3 integer + 4 f64-rate instructions per output where the fma chain took
+ * 17 + a conversion per sample) and scales once.  The block in front of a run and the zero-state heads form the same
+ * exact sum in f64, so a sample's bits do not depend on where the launch geometry puts the run boundaries.
  *
  * The f32-rounded, strictly ordered sum of ref tempo_atk_sort.c:142-149 is a dependent chain of three
  * instructions per term.  It runs on the eighth wave, IN TWO HALVES ON TWICE THE LANES: a compute wave hands over
@@ -259,13 +267,13 @@ __global__ __launch_bounds__(64 * (EV_CWAVES + 1)) void k_env_windows3(
   double *buf = reinterpret_cast<double *>(smem) + wave * EV3_SLOTS;
   const int mean = st.mean;
   const double rcp = st.rcp, rcp_lo = st.rcp_lo;
-#define FC(m) st.firc[m]
-  /* mode 2 filters the integers k = s - mean themselves (the taps carry the division) */
+  const double fsc = st.fsc;
+  /* mode 2 filters the integers k = s - mean themselves, exactly, and scales the sum once (bl_fir_int.h) */
   auto nrm = [&](int k) -> double { return FIR_MODE == 2 ? (double)k : bl_norm(k, rcp, rcp_lo); };
   const int r0 = run_begin(u0 + wave), r1 = run_begin(u0 + wave + 1);
   /* FIR modes 1 / 2: the DFT is bl_fft_tan.h's; the lane's 15 pass-1 tangents t(l, k1) and the 21 pass-2 folding factors
    * of lane k1 = l live in registers for the whole run, 72 VGPRs where the 15 complex pass-1 twiddles took 60 (213 -> 212
-   * VGPRs in mode 2).  Mode 0 keeps bl_fft.h's transform and its 15 complex twiddles: with the tan form its FIR's
+   * VGPRs in mode 2 then; 234 with the matrix form of the FIR).  Mode 0 keeps bl_fft.h's transform and its 15 complex twiddles: with the tan form its FIR's
    * schedule lost more than the DFT gained (212 instead of 194 VGPRs, 41.48 vs 40.96 ms per 1 024 S180 songs), and its
    * energies stay those of the reference arithmetic's previous builds bit for bit.  (Until round 6 modes 0 / 1 kept 12
    * twiddles and read three per round from LDS — a relic of a 220-VGPR build; the 185-VGPR one had the room: 44.15 ->
@@ -294,6 +302,21 @@ __global__ __launch_bounds__(64 * (EV_CWAVES + 1)) void k_env_windows3(
       asm volatile("" : "+v"(w1r[k1].re), "+v"(w1r[k1].im));
     }
   }
+  /* FIR mode 2, main loop: the lane's rows of the four digit planes of the tap matrix (output row l, K-group g) and
+   * the constant part of every output, split over the initial values of the sums a0, a2, a4 (bl_fir_int.h) */
+  typedef int ev_v4i __attribute__((ext_vector_type(4)));
+  unsigned cp[4][2];
+  ev_v4i ini0, ini2, ini4;
+  if (FIR_MODE == 2) {
+    bl_firi_tap_planes(l, g, cp);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(cp[j][0]), "+v"(cp[j][1]));
+    int k0, k2, k4;
+    bl_firi_const(mean, &k0, &k2, &k4);
+    ini0 = ev_v4i{k0, k0, k0, k0};
+    ini2 = ev_v4i{k2, k2, k2, k2};
+    ini4 = ev_v4i{k4, k4, k4, k4};
+  }
   int base5 = (4 * r0) % 5; /* ring position of block 4 rho, the block shared with the previous round */
 
   if (r0 < r1) { /* the block the first round cannot inherit: samples [1024 r0, 1024 r0 + 256) */
@@ -316,14 +339,16 @@ __global__ __launch_bounds__(64 * (EV_CWAVES + 1)) void k_env_windows3(
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
 #define XW(m) r[i + 16 - (m)]
-      dst[EV3_UNIT(i >> 1) + (i & 1)] = BL_FIR_SEL(FIR_MODE, XW, FC);
+      dst[EV3_UNIT(i >> 1) + (i & 1)] = BL_FIR_SEL(FIR_MODE, XW, fsc);
 #undef XW
     }
   }
 
-  /* lane ln owns outputs 16 ln .. 16 ln + 15 of the round's 1 024 new samples and loads the 32
-   * samples they read (four 16-byte loads), plus the sample that starts its zero-state output;
-   * fetched one round ahead.  Buffer loads: the song is the buffer, the lane's byte offset one register
+  /* Modes 0 / 1: lane ln owns outputs 16 ln .. 16 ln + 15 of the round's 1 024 new samples and loads the 32
+   * samples they read (four 16-byte loads).  Mode 2: the round's four blocks are four 16 x 16 tiles (output 16 a + b
+   * of a block at row b, column a); load t is the lane's part of the sample matrix of tile t, the eight samples
+   * 16 (l - 1) + 8 g .. + 7 of the block (column l, K-group g), and the lane ends up with outputs 16 l + 4 g .. + 3
+   * of every block.  Both: plus the sample that starts its zero-state output; fetched one round ahead.  Buffer loads: the song is the buffer, the lane's byte offset one register
    * that moves on by 2 048 per round, and what lies beyond the song's last window reads as zero by the
    * hardware's range check — it only reaches windows that are never summed, so any sample will do there.
    * Two VALU instructions per round instead of the 21 that clamped 64-bit addresses took (round 5). */
@@ -337,13 +362,14 @@ __global__ __launch_bounds__(64 * (EV_CWAVES + 1)) void k_env_windows3(
 #endif
   const __amdgpu_buffer_rsrc_t prs =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<int16_t *>(p), 0, (int)(2u * (unsigned)n_used), 0x00020000);
-  unsigned voff = 2u * (unsigned)(1024 * r0 + 240 + 16 * ln);  /* first input = first output - 16 */
+  /* first input = first output - 16 */
+  unsigned voff = 2u * (unsigned)(1024 * r0 + 240 + (FIR_MODE == 2 ? 16 * l + 8 * g : 16 * ln));
   unsigned voffh = 2u * (unsigned)(1024 * r0 + 256 * g + l);
   typedef unsigned ev_v4u __attribute__((__vector_size__(16)));
   auto fetch = [&]() {
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-      const ev_v4u v = __builtin_amdgcn_raw_buffer_load_b128(prs, (int)(voff + 16u * u), 0, 0);
+      const ev_v4u v = __builtin_amdgcn_raw_buffer_load_b128(prs, (int)(voff + (FIR_MODE == 2 ? 512u : 16u) * u), 0, 0);
       pre[u] = make_uint4(v[0], v[1], v[2], v[3]);
     }
     preh = (short)__builtin_amdgcn_raw_buffer_load_b16(prs, (int)voffh, 0, 0);
@@ -374,9 +400,54 @@ __global__ __launch_bounds__(64 * (EV_CWAVES + 1)) void k_env_windows3(
     }
     stamp(s, 0);
     phase(0);
-    /* 1. normalise (ref :109-114) the 32 samples into registers */
     double yv[16], yh;
-    {
+    const int kh = (int)preh - mean;   /* this round's head sample: fetch() below overwrites preh */
+    if (FIR_MODE == 2) {
+      /* 1 + 2. the FIR as exact int8 matrix products (bl_fir_int.h): per tile the l' and h planes of the lane's eight
+       * samples (four byte permutes, two xor) and five products, one per weight 2^0 .. 2^32.  Taps are the A operand
+       * (rows = position b in a row of 16), samples the B operand (columns = row a of the block): result register r
+       * of the lane is output 16 l + 4 g + r, four consecutive samples.  K = 64 operands are [c_(j+1) | c_j] against
+       * [l' | h]; the two end weights have one plane each and use the K = 32 form. */
+      ev_v4i acc[4][5];
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const unsigned w[4] = {pre[t].x, pre[t].y, pre[t].z, pre[t].w};
+        unsigned lp[2], hp[2];
+        bl_firi_sample_planes(w, lp, hp);
+        const ev_v4i smp = {(int)lp[0], (int)lp[1], (int)hp[0], (int)hp[1]};
+        const ev_v4i zero = {0, 0, 0, 0};
+#define EV3_W64(A, B) (long)(((unsigned long long)(B) << 32) | (unsigned long long)(A))
+#define EV3_TAP2(J) ev_v4i{(int)cp[(J) + 1][0], (int)cp[(J) + 1][1], (int)cp[J][0], (int)cp[J][1]}
+        acc[t][0] = __builtin_amdgcn_mfma_i32_16x16x32_i8(EV3_W64(cp[0][0], cp[0][1]), EV3_W64(lp[0], lp[1]), ini0, 0, 0, 0);
+        acc[t][1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(EV3_TAP2(0), smp, zero, 0, 0, 0);
+        acc[t][2] = __builtin_amdgcn_mfma_i32_16x16x64_i8(EV3_TAP2(1), smp, ini2, 0, 0, 0);
+        acc[t][3] = __builtin_amdgcn_mfma_i32_16x16x64_i8(EV3_TAP2(2), smp, zero, 0, 0, 0);
+        acc[t][4] = __builtin_amdgcn_mfma_i32_16x16x32_i8(EV3_W64(cp[3][0], cp[3][1]), EV3_W64(hp[0], hp[1]), ini4, 0, 0, 0);
+#undef EV3_W64
+#undef EV3_TAP2
+      }
+      fetch(); /* next round's samples */
+#pragma unroll
+      for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          yv[4 * t + r] = bl_firi_combine(acc[t][0][r], acc[t][1][r], acc[t][2][r], acc[t][3][r], acc[t][4][r]) * fsc;
+      /* zero-state heads of the four windows: the first 16 outputs of a window start from a zeroed delay line
+       * (ref :121); lane (g, l) filters sample l of window g with the taps that exist, tap m being the sample of
+       * lane l - m of the same 16-lane row, zero when there is none (DPP row_shr:m).  The taps are gathered as
+       * integers (a 32-bit DPP move folds into the add), the nine pair sums converted, and the sum is the f64 form of
+       * the same exact Y: a head has the main loop's bits where both have all their samples */
+#define KH(m) __builtin_amdgcn_update_dpp(0, kh, 0x110 + (m), 0xF, 0xF, true) /* row_shr:m, 0 when there is no lane */
+      const double hp_[9] = {(double)kh /* tap 16 lies before the window: zero */,
+                             (double)(KH(1) + KH(15)), (double)(KH(2) + KH(14)), (double)(KH(3) + KH(13)),
+                             (double)(KH(4) + KH(12)), (double)(KH(5) + KH(11)), (double)(KH(6) + KH(10)),
+                             (double)(KH(7) + KH(9)), (double)KH(8)};
+#undef KH
+#define XP(m) hp_[m]
+      yh = BL_FIR_INT_P(XP) * fsc;
+#undef XP
+    } else {
+      /* 1. normalise (ref :109-114) the 32 samples into registers */
       double r[32];
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
@@ -388,39 +459,16 @@ __global__ __launch_bounds__(64 * (EV_CWAVES + 1)) void k_env_windows3(
           r[8 * u + 2 * k + 1] = nrm(hi - mean);
         }
       }
-      const int kh = (int)preh - mean;   /* this round's head sample: fetch() below overwrites preh */
       const double xh = nrm(kh);
       fetch(); /* next round's samples */
       /* 2. FIR (ref :123-138): outputs 16 ln .. 16 ln + 15 of the round's new samples */
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
 #define XR(m) r[i + 16 - (m)]
-        yv[i] = BL_FIR_SEL(FIR_MODE, XR, FC);
+        yv[i] = BL_FIR_SEL(FIR_MODE, XR, fsc);
 #undef XR
       }
-      /* zero-state heads of the four windows: the first 16 outputs of a window start from a zeroed delay line
-       * (ref :121); lane (g, l) filters sample l of window g with the taps that exist, tap m being the sample of
-       * lane l - m of the same 16-lane row, zero when there is none (DPP row_shr:m).  Mode 2 gathers the taps as
-       * integers: the pair sums k[l - m] + k[l - 16 + m] are exact either way, a 32-bit DPP move
-       * costs half of a 64-bit one and folds into the add, and only the nine sums are converted —
-       * 34 instead of 49 instructions, the same bits */
-      if (FIR_MODE == 2) {
-#define KH(m) __builtin_amdgcn_update_dpp(0, kh, 0x110 + (m), 0xF, 0xF, true) /* row_shr:m, 0 when there is no lane */
-        const double p0 = (double)kh; /* tap 16 lies before the window: zero */
-        const double p1 = (double)(KH(1) + KH(15)), p2 = (double)(KH(2) + KH(14)), p3 = (double)(KH(3) + KH(13));
-        const double p4 = (double)(KH(4) + KH(12)), p5 = (double)(KH(5) + KH(11)), p6 = (double)(KH(6) + KH(10));
-        const double p7 = (double)(KH(7) + KH(9)), p8 = (double)KH(8);
-#undef KH
-        double y_ = FC(7) * p7;
-        y_ = __builtin_fma(FC(6), p6, y_);
-        y_ = __builtin_fma(FC(5), p5, y_);
-        y_ = __builtin_fma(FC(4), p4, y_);
-        y_ = __builtin_fma(FC(3), p3, y_);
-        y_ = __builtin_fma(FC(2), p2, y_);
-        y_ = __builtin_fma(FC(1), p1, y_);
-        y_ = __builtin_fma(p8, FC(8), y_);
-        yh = __builtin_fma(FC(0), p0, y_);
-      } else {
+      /* zero-state heads of the four windows, as in mode 2 above but on the normalised doubles */
       double hx[17];
       hx[0] = xh;
       hx[1] = bl_dpp_f64<0x111>(xh);  hx[2] = bl_dpp_f64<0x112>(xh);  hx[3] = bl_dpp_f64<0x113>(xh);
@@ -430,9 +478,8 @@ __global__ __launch_bounds__(64 * (EV_CWAVES + 1)) void k_env_windows3(
       hx[13] = bl_dpp_f64<0x11D>(xh); hx[14] = bl_dpp_f64<0x11E>(xh); hx[15] = bl_dpp_f64<0x11F>(xh);
       hx[16] = 0.0;
 #define XH(m) hx[m]
-      yh = BL_FIR_SEL(FIR_MODE, XH, FC);
+      yh = BL_FIR_SEL(FIR_MODE, XH, fsc);
 #undef XH
-      }
     }
     /* ring positions: window g reads block g (first half) and block g + 1 (second half); the
      * lanes of group g have just filtered block g + 1 */
@@ -442,8 +489,20 @@ __global__ __launch_bounds__(64 * (EV_CWAVES + 1)) void k_env_windows3(
     stamp(s, 1);
     phase(1);
     ev_wave_sync(); /* previous round's LDS reads (DFT exchanges) are complete */
+    if (FIR_MODE == 2) {
+      /* tile t is block t + 1 of the round; the lane's four outputs are units 2 g and 2 g + 1 of row l.  Eight
+       * consecutive lanes write slots 9 l + 4 g + const: all different mod 8, as in the other modes */
 #pragma unroll
-    for (int i = 0; i < 16; ++i) blk_b[EV3_ROW(l) + EV3_UNIT(i >> 1) + (i & 1)] = yv[i];
+      for (int t = 0; t < 4; ++t) {
+        const int xt = base5 + t + 1, pt = xt >= 5 ? xt - 5 : xt;
+        double *d = buf + pt * EV3_BLK + EV3_ROW(l) + EV3_UNIT(2 * g);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) d[EV3_UNIT(r >> 1) + (r & 1)] = yv[4 * t + r];
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < 16; ++i) blk_b[EV3_ROW(l) + EV3_UNIT(i >> 1) + (i & 1)] = yv[i];
+    }
     buf[EV3_HEADS + ln] = yh;
     ev_wave_sync();
     /* 3. DFT input of window g: lane l holds y[32*m1 + 2*l], y[32*m1 + 2*l + 1] */
@@ -545,7 +604,6 @@ __global__ __launch_bounds__(64 * (EV_CWAVES + 1)) void k_env_windows3(
   publish_held_only();
   if (ln == 0) flags[wave] = seq;
 }
-#undef FC
 
 /* ------------------------------------------------------------------------- */
 /* k_env_tail: one lane per song, three waves per 64 songs                    */
@@ -725,7 +783,8 @@ extern "C" __attribute__((visibility("default"))) int bl_amd_measure_env(int var
 /* Which form of the 17-tap FIR k_env_windows3 runs:
  *   0  the reference's unfused order (BL_FIR) — bit-identical window energies;
  *   1  each product folded into the sum by an fma (BL_FIR_FUSED);
- *   2  as 1, with the normalisation folded into the taps (BL_FIR_FOLD) — the default.
+ *   2  the normalisation folded into the filter, on the integers: the exact sum of integer taps times integer
+ *      samples, scaled once (bl_fir_int.h) — the default.
  * bl_amd_set_fir_mode() wins over the environment variable BL_AMD_FIR_FUSED, which wins over the
  * compiled default.  Read on every launch, so one process can run all of them (the A/B tools do). */
 static std::atomic<int> g_fir_mode{-1};

@@ -2,12 +2,13 @@
  * bl_fir.h — the sample arithmetic in front of the envelope DFT: the 17-tap band-pass FIR of
  * ref src/tempo_atk_sort.c:109-138 in its three forms and the normalisation that feeds it.  k_env_windows3
  * (bl_env_kernels.hip) runs it; k_song_prep (bl_stats_kernels.hip) prepares its per-song constants from the same
- * taps (bl_dstats::rcp, rcp_lo, firc).  Must be compiled with -ffp-contract=off: the FMAs here are the explicit ones.
+ * taps (bl_dstats::rcp, rcp_lo, fsc).  Must be compiled with -ffp-contract=off: the FMAs here are the explicit ones.
  */
 #ifndef BL_FIR_H_
 #define BL_FIR_H_
 
 #include <hip/hip_runtime.h>
+#include "bl_fir_int.h"
 
 /* FIR taps: literal digits of ref include/bandpass_coeffs.h:1-7 (symmetric) */
 #define BL_C0 (-0.0023470)
@@ -70,27 +71,13 @@ __device__ __forceinline__ double bl_norm(int k, double rcp, double rcp_lo) {
     y_ = __builtin_fma(BL_C0, X(0) + X(16), y_);                    \
     y_;                                                             \
   })
-/* Mode 2: the normalisation folded into the taps.  k = s - mean is an exact integer and so is every
- * pair sum; c'_m = RN(c_m / (2 vprime)) (k_song_prep) carries the division.  One rounding per tap
- * (the product inside the fma) where the reference has three (quotient, pair sum, product): the
- * output differs from the reference's by a few 1e-16 of its largest partial sum, as in mode 1, and
- * the 66 f64 instructions per round that normalise the samples are gone.  FC(m) names tap m. */
-#define BL_FIR_FOLD(X, FC)                                          \
-  ({                                                                \
-    double y_ = FC(7) * (X(7) + X(9));                              \
-    y_ = __builtin_fma(FC(6), X(6) + X(10), y_);                    \
-    y_ = __builtin_fma(FC(5), X(5) + X(11), y_);                    \
-    y_ = __builtin_fma(FC(4), X(4) + X(12), y_);                    \
-    y_ = __builtin_fma(FC(3), X(3) + X(13), y_);                    \
-    y_ = __builtin_fma(FC(2), X(2) + X(14), y_);                    \
-    y_ = __builtin_fma(FC(1), X(1) + X(15), y_);                    \
-    y_ = __builtin_fma(X(8), FC(8), y_);                            \
-    y_ = __builtin_fma(FC(0), X(0) + X(16), y_);                    \
-    y_;                                                             \
-  })
+/* Mode 2: the normalisation folded into the filter, on the integers.  k = s - mean is an exact integer and the taps
+ * are integers times 1e-7, so the whole sum Y = sum C_m k[j - m] is formed exactly and scaled once by the per-song
+ * sc = 1e-7 / (2 vprime) (k_song_prep): one rounding per output.  bl_fir_int.h has the two forms that give that Y —
+ * BL_FIR_INT, in f64, and the int8 matrix products of the kernel's main loop — and the argument. */
 #ifndef BL_FIR_FUSED_DEFAULT
 #define BL_FIR_FUSED_DEFAULT 2
 #endif
-#define BL_FIR_SEL(MODE, X, FC) ((MODE) == 2 ? BL_FIR_FOLD(X, FC) : (MODE) == 1 ? BL_FIR_FUSED(X) : BL_FIR(X))
+#define BL_FIR_SEL(MODE, X, SC) ((MODE) == 2 ? BL_FIR_INT(X) * (SC) : (MODE) == 1 ? BL_FIR_FUSED(X) : BL_FIR(X))
 
 #endif /* BL_FIR_H_ */

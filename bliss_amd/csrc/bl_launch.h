@@ -57,8 +57,7 @@ struct bl_dstats {
   int wrap_pass; /* 1: variance must come from k_variance_wrap */
   int status;
   long long wrap_acc; /* accumulator of k_variance_wrap */
-  double firc[9];     /* RN(c_m / (2 vprime)), m = 0..8: the FIR taps with the normalisation folded in
-                       * (BL_AMD_FIR_FUSED=2 only) */
+  double fsc;         /* 1e-7 / (2 vprime): the one scaling of FIR mode 2's integer sums (bl_firi_scale) */
 };
 
 typedef bl_c2<double> c2d;

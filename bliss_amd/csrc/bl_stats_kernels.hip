@@ -166,7 +166,7 @@ __global__ void k_stats_init(bl_dstats *stats, int n_songs) {
   if (i >= n_songs) return;
   bl_dstats s;
   s.sum = 0; s.sumsq = 0; s.first = 0xFFFFFFFFu; s.last = -1;
-  s.mean = 0; s.variance = 0; s.vprime = 0; s.rcp = 0; s.rcp_lo = 0; s.wrap_pass = 0; s.status = BL_OK;
+  s.mean = 0; s.variance = 0; s.vprime = 0; s.rcp = 0; s.rcp_lo = 0; s.fsc = 0; s.wrap_pass = 0; s.status = BL_OK;
   s.wrap_acc = 0;
   stats[i] = s;
 }
@@ -185,9 +185,9 @@ __device__ __forceinline__ void prep_finish(bl_dstats &s, int n) {
   const double v2 = 2.0 * s.vprime;
   s.rcp = 1.0 / v2;
   s.rcp_lo = __builtin_fma(-s.rcp, v2, 1.0) / v2;
-  const double taps[9] = {BL_C0, BL_C1, BL_C2, BL_C3, BL_C4, BL_C5, BL_C6, BL_C7, BL_C8};
-#pragma unroll
-  for (int m = 0; m < 9; ++m) s.firc[m] = __builtin_fma(taps[m], s.rcp, taps[m] * s.rcp_lo);
+  /* FIR mode 2 filters the integers with the integer taps and scales once (bl_fir_int.h): within one ulp of
+   * 1e-7 / (2 vprime), correctly rounded but for near-ties */
+  s.fsc = bl_firi_scale(s.rcp, s.rcp_lo);
   (void)n;
 }
 
