@@ -1,9 +1,11 @@
 #!/usr/bin/env python
 """Randomised parity soak of the device rate converter against the host form (the one pinned on
 the reference's digests): random input rates (standard and odd), sample kinds, channel counts,
-lengths around filter / tile boundaries, random arena offsets, several songs per call.
+lengths around filter / tile boundaries, random arena offsets (input: any for mono, even for stereo; output: even —
+what the descriptor check admits; random gaps between the songs), several songs per call.
 Prints one JSON object; any mismatch is listed (and the exit code is 1)."""
 import argparse
+import ctypes as C
 import json
 import os
 import sys
@@ -23,6 +25,7 @@ def main():
     args = ap.parse_args()
     import torch
     import bliss_amd
+    from bliss_amd import _lib
     lib = bliss_amd.load()
     assert lib.bl_amd_init(0) == 0
     rng = np.random.default_rng(args.seed)
@@ -53,14 +56,27 @@ def main():
             else:
                 x = rng.integers(-(1 << 31), 1 << 31, fr * ch).astype(np.int32)
             lens.append(fr); chans.append(ch); pcms.append(x)
-        total = sum((p.size + 7) & ~7 for p in pcms)
-        arena = np.zeros(total, dtype=kind)
-        off = 0
-        for p in pcms:
-            arena[off:off + p.size] = p
-            off += (p.size + 7) & ~7
-        out, placed = bliss_amd.resample_batch_device(torch.from_numpy(arena).cuda(), lens, chans, rate)
+        desc = (_lib.ResampleDesc * n)()
+        placed = []
+        in_off = out_off = 0
+        for i, (p, ch) in enumerate(zip(pcms, chans)):
+            in_off += int(rng.integers(0, 24))
+            in_off += in_off & 1 if ch == 2 else 0
+            out_off += 2 * int(rng.integers(0, 12))
+            of = lib.bl_amd_resample_out_frames(lens[i], rate)
+            desc[i].in_offset, desc[i].out_offset, desc[i].frames, desc[i].channels = in_off, out_off, lens[i], ch
+            placed.append((out_off, 2 * of))
+            in_off += p.size
+            out_off += 2 * of
+        arena = np.zeros(in_off + 64, dtype=kind)
+        for d, p in zip(desc, pcms):
+            arena[d.in_offset:d.in_offset + p.size] = p
+        d_in = torch.from_numpy(arena).cuda()
+        out = torch.zeros(out_off + 64, dtype=torch.int16, device="cuda")
+        rc = lib.bl_amd_resample_batch_device(d_in.data_ptr(), int(kind == np.int32), desc, n, rate, out.data_ptr(),
+                                              C.c_void_p(torch.cuda.current_stream().cuda_stream))
         torch.cuda.synchronize()
+        assert rc == 0, rc
         host = out.cpu().numpy()
         for i, (p, ch) in enumerate(zip(pcms, chans)):
             want = bliss_amd.resample_host(p, ch, rate)
