@@ -42,8 +42,9 @@
  * of 256 samples is a 16 x 16 tile of outputs and five int8 matrix products (v_mfma_i32_16x16x64_i8 / x32_i8: the
  * matrix pipe, beside the f64 VALU the rest of the round lives on) of the samples' byte planes with the digit planes
  * of the Toeplitz tap matrix; a lane loads its 8 samples of each of the round's four tiles, ends up with four
- * consecutive outputs per tile, converts (3 integer + 4 f64-rate instructions per output where the fma chain took
- * 17 + a conversion per sample) and scales once.  The block in front of a run and the zero-state heads form the same
+ * consecutive outputs per tile and converts (3 integer + 3 f64-rate instructions per output where the fma chain took
+ * 17 + a conversion per sample).  The sums are never scaled: the transform is linear, so the song's factor enters
+ * squared in the split's constants (bl_fft512_power1_sq, bl_fft_tan.h).  The block in front of a run and the zero-state heads form the same
  * exact sum in f64, so a sample's bits do not depend on where the launch geometry puts the run boundaries.
  *
  * The f32-rounded, strictly ordered sum of ref tempo_atk_sort.c:142-149 is a dependent chain of three
@@ -156,13 +157,16 @@ __global__ __launch_bounds__(64 * (EV_CWAVES + 1)) void k_env_windows3(
   const bl_dsong sg = songs[blockIdx.y];
   const bl_dstats st = stats[blockIdx.y];
   const int16_t *p = pcm + sg.pcm_off;
-  /* FIR modes 1 / 2 run bl_fft_tan.h's transform: tw512[0..127] holds (t, c) of W512^k and tw256 is not read (the
-   * lanes keep their constants in registers); mode 0 keeps bl_fft.h's (see the registers below) */
+  /* FIR modes 1 / 2 run bl_fft_tan.h's transform: tw512[0..127] holds (t, c) of W512^k — in mode 2, whose transform
+   * runs on the unscaled integer sums, the song's (2 kappa cos, -kappa sin) in the same place (bl_fft512_power1_sq) —
+   * and tw256 is not read (the lanes keep their constants in registers); mode 0 keeps bl_fft.h's (see the registers
+   * below) */
   if (FIR_MODE == 0 && tid < 256) {
     tw256[tid] = tb.tw256_d[((tid & 15) * (tid >> 4)) & 255];
     tw512[tid] = tb.tw512_d[tid];
   }
-  if (FIR_MODE != 0 && tid < 128) tw512[tid] = tb.tw512t[tid];
+  if (FIR_MODE == 1 && tid < 128) tw512[tid] = tb.tw512t[tid];
+  if (FIR_MODE == 2 && tid < 128) tw512[tid] = bl_fft_sq_consts<double>(tb.cs512[tid], st.kappa);
   if (tid < 36) flags[tid] = 0; /* the sequence words and the zero pair behind them */
   if (tid < EV_TILE) terms[tid * EV_TROW + 257] = 0.0; /* the pad behind term 256 is read as a term */
   __syncthreads();
@@ -267,8 +271,9 @@ __global__ __launch_bounds__(64 * (EV_CWAVES + 1)) void k_env_windows3(
   double *buf = reinterpret_cast<double *>(smem) + wave * EV3_SLOTS;
   const int mean = st.mean;
   const double rcp = st.rcp, rcp_lo = st.rcp_lo;
-  const double fsc = st.fsc;
-  /* mode 2 filters the integers k = s - mean themselves, exactly, and scales the sum once (bl_fir_int.h) */
+  /* mode 2 filters the integers k = s - mean themselves, exactly (bl_fir_int.h), and transforms the sums as they are:
+   * the scale enters squared, through kappa and the pair constants of the split */
+  const double kappa = st.kappa;
   auto nrm = [&](int k) -> double { return FIR_MODE == 2 ? (double)k : bl_norm(k, rcp, rcp_lo); };
   const int r0 = run_begin(u0 + wave), r1 = run_begin(u0 + wave + 1);
   /* FIR modes 1 / 2: the DFT is bl_fft_tan.h's; the lane's 15 pass-1 tangents t(l, k1) and the 21 pass-2 folding factors
@@ -339,7 +344,7 @@ __global__ __launch_bounds__(64 * (EV_CWAVES + 1)) void k_env_windows3(
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
 #define XW(m) r[i + 16 - (m)]
-      dst[EV3_UNIT(i >> 1) + (i & 1)] = BL_FIR_SEL(FIR_MODE, XW, fsc);
+      dst[EV3_UNIT(i >> 1) + (i & 1)] = BL_FIR_SEL(FIR_MODE, XW);
 #undef XW
     }
   }
@@ -431,7 +436,7 @@ __global__ __launch_bounds__(64 * (EV_CWAVES + 1)) void k_env_windows3(
       for (int t = 0; t < 4; ++t)
 #pragma unroll
         for (int r = 0; r < 4; ++r)
-          yv[4 * t + r] = bl_firi_combine(acc[t][0][r], acc[t][1][r], acc[t][2][r], acc[t][3][r], acc[t][4][r]) * fsc;
+          yv[4 * t + r] = bl_firi_combine(acc[t][0][r], acc[t][1][r], acc[t][2][r], acc[t][3][r], acc[t][4][r]);
       /* zero-state heads of the four windows: the first 16 outputs of a window start from a zeroed delay line
        * (ref :121); lane (g, l) filters sample l of window g with the taps that exist, tap m being the sample of
        * lane l - m of the same 16-lane row, zero when there is none (DPP row_shr:m).  The taps are gathered as
@@ -444,7 +449,7 @@ __global__ __launch_bounds__(64 * (EV_CWAVES + 1)) void k_env_windows3(
                              (double)(KH(7) + KH(9)), (double)KH(8)};
 #undef KH
 #define XP(m) hp_[m]
-      yh = BL_FIR_INT_P(XP) * fsc;
+      yh = BL_FIR_INT_P(XP);
 #undef XP
     } else {
       /* 1. normalise (ref :109-114) the 32 samples into registers */
@@ -465,7 +470,7 @@ __global__ __launch_bounds__(64 * (EV_CWAVES + 1)) void k_env_windows3(
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
 #define XR(m) r[i + 16 - (m)]
-        yv[i] = BL_FIR_SEL(FIR_MODE, XR, fsc);
+        yv[i] = BL_FIR_SEL(FIR_MODE, XR);
 #undef XR
       }
       /* zero-state heads of the four windows, as in mode 2 above but on the normalised doubles */
@@ -478,7 +483,7 @@ __global__ __launch_bounds__(64 * (EV_CWAVES + 1)) void k_env_windows3(
       hx[13] = bl_dpp_f64<0x11D>(xh); hx[14] = bl_dpp_f64<0x11E>(xh); hx[15] = bl_dpp_f64<0x11F>(xh);
       hx[16] = 0.0;
 #define XH(m) hx[m]
-      yh = BL_FIR_SEL(FIR_MODE, XH, fsc);
+      yh = BL_FIR_SEL(FIR_MODE, XH);
 #undef XH
     }
     /* ring positions: window g reads block g (first half) and block g + 1 (second half); the
@@ -580,16 +585,19 @@ __global__ __launch_bounds__(64 * (EV_CWAVES + 1)) void k_env_windows3(
       const double pr = bl_dpp_f64_old<0x111>(zr, bl_dpp_f64<0x140>(sr));
       const double pi = bl_dpp_f64_old<0x111>(zi, bl_dpp_f64<0x140>(si));
       double own;
-      if (EV3_TAN)
+      if (FIR_MODE == 2)
+        bl_fft512_power1_sq<double>(re[bl_pos16(k0)], im[bl_pos16(k0)], pr, pi, tw512[l + 16 * k0], kappa, own, held[k0]);
+      else if (EV3_TAN)
         bl_fft512_power1_tan<double, false>(re[bl_pos16(k0)], im[bl_pos16(k0)], pr, pi, tw512[l + 16 * k0], own, held[k0]);
       else
         bl_fft512_power1<double, false>(re[bl_pos16(k0)], im[bl_pos16(k0)], pr, pi, tw512[l + 16 * k0], own, held[k0]);
       tg[l + 16 * k0] = own; /* terms 0..127 of this round */
       if (k0 == 7) mir7 = held[7];
     }
-    /* |X_128|^2 = |Z_128|^2 has no 1/4 of its own: give back the one the halved input took */
+    /* |X_128|^2 = |Z_128|^2 has no 1/4 of its own: give back the one the halved input took (mode 2: 4 f^2 = 2 kappa
+     * for the scale f its input never took) */
     const double mr = re[bl_pos16(8)], mi = im[bl_pos16(8)];
-    const double mid = 4.0 * __builtin_fma(mr, mr, mi * mi);
+    const double mid = (FIR_MODE == 2 ? 2.0 * kappa : 4.0) * __builtin_fma(mr, mr, mi * mi);
     if (l == 0) tg[128] = mid;
     if (l == 15) tg[129] = mir7; /* term 129 belongs to the first half */
     /* The LDS executes one wave's instructions in order: the sequence word below lands after the terms above

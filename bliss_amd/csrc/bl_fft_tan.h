@@ -23,7 +23,15 @@
  * The per-lane constants are loop-invariant: 15 t of pass 1 (which replace the 15 complex twiddles the lane kept
  * before) and the 21 folding factors of pass 2, 36 doubles per lane.
  *
- * Everything here is __host__ __device__ (tests/host/test_fft_tan_host.cpp runs the lane code on the CPU).
+ * FIR mode 2 hands the transform the exact integer filter sums Y (bl_fir_int.h) and never scales them: with f the
+ * per-song factor 1 / (1e7 * 2 V'), |DFT(f Y)|^2 = f^2 |DFT(Y)|^2, and f^2 rides in the constants of the split
+ * (bl_fft512_power1_sq: 12 instructions per pair, e and o never formed).  The transform starts from integers
+ * (|Y| < 2^45: pass-1 values below 2^54, far below the 2^423 of the 2^-600 trick; squares below 2^110) and
+ * kappa = 2 f^2 is a normal number for every admissible V' = variance / 2^15, |variance| from 1 to 2^31:
+ * 2 (2^15 / 2e7)^2 ~ 5.4e-6 at one end, 2 / (1e7 * 2^17)^2 ~ 1.2e-24 at the other.
+ *
+ * Everything here is __host__ __device__ (tests/host/test_fft_tan_host.cpp and test_fft_sq_host.cpp run the lane code
+ * on the CPU).
  */
 #ifndef BL_FFT_TAN_H_
 #define BL_FFT_TAN_H_
@@ -130,6 +138,27 @@ BL_HD void bl_fft512_power1_tan(T zr, T zi, T pr, T pi, bl_c2<T> tc, T &own, T &
   if (QUARTER) { own = (T)0.25 * own; mir = (T)0.25 * mir; }
 }
 
+/* The same pair from the squares, for an UNSCALED transform (FIR mode 2).  With z = Z_k, p = Z_(256-k), e = z + conj p,
+ * o = -i (z - conj p), w = W512^k = cos a - i sin a:
+ *     |e|^2 + |o|^2 = 2 (|z|^2 + |p|^2)        Re(e conj(w o)) = 2 cos a Im(z p) - sin a (|z|^2 - |p|^2)
+ * so |e +- w o|^2 = 2 S +- (4 cos a M - 2 sin a Dm) with A = |z|^2, B = |p|^2, M = zr pi + zi pr, S = A + B,
+ * Dm = A - B.  The caller's constants carry the square of the scale f the input was never multiplied by:
+ *     kappa = 2 f^2,  cs = (c', s') = (4 f^2 cos a, -2 f^2 sin a) = (2 kappa cos a, -kappa sin a)
+ * and own = f^2 |e + w o|^2, mir = f^2 |e - w o|^2: what bl_fft512_power1_tan<T, false> gives for the input f Y.
+ * 12 instructions where that one takes 14.  The pair k = 0 (z = p = Z_0) needs no special case: Dm = 0 and the two
+ * results are 4 f^2 (zr + zi)^2 and 4 f^2 (zr - zi)^2.  Both terms carry an absolute error of order eps times the
+ * pair's energy, as there. */
+template <typename T>
+BL_HD void bl_fft512_power1_sq(T zr, T zi, T pr, T pi, bl_c2<T> cs, T kappa, T &own, T &mir) {
+  const T A = bl_fma(zr, zr, zi * zi);
+  const T B = bl_fma(pr, pr, pi * pi);
+  const T M = bl_fma(zr, pi, zi * pr);
+  const T S = A + B, Dm = A - B;
+  const T D = bl_fma(cs.re, M, cs.im * Dm);
+  own = bl_fma(kappa, S, D);
+  mir = bl_fma(kappa, S, -D);
+}
+
 #if defined(__HIPCC__)
 #define BL_TAN_HOST __host__ static inline
 #else
@@ -173,6 +202,23 @@ BL_TAN_HOST void bl_fft_tan_fill(bl_fft_tan_lane<double> *lanes, bl_c2<double> *
     tw512t[k].re = (double)-tanl(a);
     tw512t[k].im = (double)cosl(a);
   }
+}
+/* cs512[128]: (cos a, sin a) of W512^k, k = 0..127, a = 2 pi k / 512: what k_env_windows3 scales by the song's kappa
+ * into the (c', s') of bl_fft512_power1_sq */
+BL_TAN_HOST void bl_fft_sq_fill(bl_c2<double> *cs512) {
+  const long double PI = 3.14159265358979323846264338327950288L;
+  for (int k = 0; k < 128; ++k) {
+    const long double a = 2.0L * PI * k / 512.0L;
+    cs512[k].re = (double)cosl(a);
+    cs512[k].im = (double)sinl(a);
+  }
+}
+/* the pair constants of one song from cs512: both products round once (2 kappa is exact) */
+template <typename T> BL_HD bl_c2<T> bl_fft_sq_consts(bl_c2<T> cs, T kappa) {
+  bl_c2<T> r;
+  r.re = ((T)2 * kappa) * cs.re;
+  r.im = -kappa * cs.im;
+  return r;
 }
 
 #endif /* BL_FFT_TAN_H_ */

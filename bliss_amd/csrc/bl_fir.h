@@ -72,12 +72,14 @@ __device__ __forceinline__ double bl_norm(int k, double rcp, double rcp_lo) {
     y_;                                                             \
   })
 /* Mode 2: the normalisation folded into the filter, on the integers.  k = s - mean is an exact integer and the taps
- * are integers times 1e-7, so the whole sum Y = sum C_m k[j - m] is formed exactly and scaled once by the per-song
- * sc = 1e-7 / (2 vprime) (k_song_prep): one rounding per output.  bl_fir_int.h has the two forms that give that Y —
+ * are integers times 1e-7, so the whole sum Y = sum C_m k[j - m] is formed exactly; the per-song scale
+ * sc = 1e-7 / (2 vprime) (k_song_prep) is applied, squared, to the power terms of the transform of Y: no rounding
+ * per output at all.  bl_fir_int.h has the two forms that give that Y —
  * BL_FIR_INT, in f64, and the int8 matrix products of the kernel's main loop — and the argument. */
 #ifndef BL_FIR_FUSED_DEFAULT
 #define BL_FIR_FUSED_DEFAULT 2
 #endif
-#define BL_FIR_SEL(MODE, X, SC) ((MODE) == 2 ? BL_FIR_INT(X) * (SC) : (MODE) == 1 ? BL_FIR_FUSED(X) : BL_FIR(X))
+/* mode 2 yields the unscaled Y: k_env_windows3 applies sc squared to the power terms (bl_fft512_power1_sq) */
+#define BL_FIR_SEL(MODE, X) ((MODE) == 2 ? BL_FIR_INT(X) : (MODE) == 1 ? BL_FIR_FUSED(X) : BL_FIR(X))
 
 #endif /* BL_FIR_H_ */

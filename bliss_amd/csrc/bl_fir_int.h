@@ -7,7 +7,8 @@
  *     Y_j = sum_m C_m k[j - m]       is an integer, |Y_j| < 2^45, formed without any rounding, and
  *     y_j = Y_j * sc,                sc = RN(1 / (1e7 * 2 vprime)) (bl_firi_scale), is the filter output (halved, as
  * everything in that kernel: see bl_norm in bl_fir.h) with ONE rounding where the fma form had nine and the
- * reference's about 25.  Two routes to the same Y, hence the same bits:
+ * reference's about 25.  The kernel does not even form y: its DFT is linear, so it transforms Y itself and multiplies
+ * the power terms by kappa = 2 sc^2 (bl_firi_power_scale; bl_fft512_power1_sq in bl_fft_tan.h).  Two routes to the same Y, hence the same bits:
  *
  *  - the f64 form (BL_FIR_INT): the nine products of the integer taps with the exact pair sums, as doubles.  Every
  *    partial sum is an integer below 2^53, so no operation rounds.  The block in front of a run and the zero-state
@@ -114,6 +115,18 @@ BL_FIRI_HD double bl_firi_scale(double rcp, double rcp_lo) {
   const double q = rcp / BL_FIRI_UNSCALE;
   const double r = __builtin_fma(-q, BL_FIRI_UNSCALE, rcp) + rcp_lo;
   return q + r / BL_FIRI_UNSCALE;
+}
+
+/* kappa = 2 sc^2 = 2 / (1e7 * 2 vprime)^2, the factor FIR mode 2 applies to the power terms of the UNSCALED sums
+ * (bl_fft512_power1_sq in bl_fft_tan.h) instead of sc to every sample.  From the same unevaluated rcp + rcp_lo: the
+ * square in double-double (p + pe to ~2^-104), then the division by 1e14 (exact in f64) the way bl_firi_scale divides,
+ * rounded once; the doubling is exact.  Not sc * sc, which would stack two roundings onto every term of a song. */
+BL_FIRI_HD double bl_firi_power_scale(double rcp, double rcp_lo) {
+  const double p = rcp * rcp;
+  const double pe = __builtin_fma(rcp, rcp, -p) + 2.0 * (rcp * rcp_lo);
+  const double q = p / 1e14;
+  const double r = __builtin_fma(-q, 1e14, p) + pe;
+  return 2.0 * (q + r / 1e14);
 }
 
 /* ---- the int8 matrix form ---- */

@@ -85,7 +85,7 @@ __global__ __launch_bounds__(256) void k_narrow_s32(const int4 *__restrict__ in,
 /* launchers (declared in bl_launch.h)                                        */
 
 size_t blk_tables_bytes(void) {
-  return 256 * 16 * 2 + 512 * 4 + LV_TW_SLOTS * 16 * 8 + sizeof(bl_fft_tan_lane<double>) * 16 + 128 * 16;
+  return 256 * 16 * 2 + 512 * 4 + LV_TW_SLOTS * 16 * 8 + sizeof(bl_fft_tan_lane<double>) * 16 + 128 * 16 + 128 * 16;
 }
 
 void blk_tables_fill_host(unsigned char *h) {
@@ -107,6 +107,7 @@ void blk_tables_fill_host(unsigned char *h) {
   unsigned char *tan_at = reinterpret_cast<unsigned char *>(hann + 512) + LV_TW_SLOTS * 16 * 8;
   bl_fft_tan_fill(reinterpret_cast<bl_fft_tan_lane<double> *>(tan_at),
                   reinterpret_cast<c2d *>(tan_at + sizeof(bl_fft_tan_lane<double>) * 16));
+  bl_fft_sq_fill(reinterpret_cast<c2d *>(tan_at + sizeof(bl_fft_tan_lane<double>) * 16) + 128);
 }
 
 bl_tables blk_tables_bind(const void *d_mem) {
@@ -118,6 +119,7 @@ bl_tables blk_tables_bind(const void *d_mem) {
   tb.lv_tw = reinterpret_cast<const c2f *>(tb.hann + 512);
   tb.tan_lane = reinterpret_cast<const double *>(tb.lv_tw + LV_TW_SLOTS * 16);
   tb.tw512t = reinterpret_cast<const c2d *>(tb.tan_lane + 16 * BL_FFT_TAN_LANE_DOUBLES);
+  tb.cs512 = tb.tw512t + 128;
   {
     float tw[LV_TW_SLOTS * 16][2];
     lv_fill_tables(tw, tb.lv_leafc);

@@ -57,7 +57,8 @@ struct bl_dstats {
   int wrap_pass; /* 1: variance must come from k_variance_wrap */
   int status;
   long long wrap_acc; /* accumulator of k_variance_wrap */
-  double fsc;         /* 1e-7 / (2 vprime): the one scaling of FIR mode 2's integer sums (bl_firi_scale) */
+  double fsc;         /* 1e-7 / (2 vprime): the scale of FIR mode 2's integer sums (bl_firi_scale) */
+  double kappa;       /* 2 (1e-7 / (2 vprime))^2: what FIR mode 2 multiplies the power terms by (bl_firi_power_scale) */
 };
 
 typedef bl_c2<double> c2d;
@@ -70,6 +71,7 @@ struct bl_tables {
   float lv_leafc[4];  /* sqrthalf, cos_16[1], cos_16[3] */
   const double *tan_lane; /* bl_fft_tan.h: [16][BL_FFT_TAN_LANE_DOUBLES] per-lane constants of k_env_windows3's DFT */
   const c2d *tw512t;      /* bl_fft_tan.h: (t, c) of W512^k, k = 0..127 */
+  const c2d *cs512;       /* bl_fft_tan.h: (cos, sin) of W512^k, k = 0..127 (FIR mode 2 scales them per song) */
   double log101;
 };
 

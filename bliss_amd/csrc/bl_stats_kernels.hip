@@ -166,7 +166,7 @@ __global__ void k_stats_init(bl_dstats *stats, int n_songs) {
   if (i >= n_songs) return;
   bl_dstats s;
   s.sum = 0; s.sumsq = 0; s.first = 0xFFFFFFFFu; s.last = -1;
-  s.mean = 0; s.variance = 0; s.vprime = 0; s.rcp = 0; s.rcp_lo = 0; s.fsc = 0; s.wrap_pass = 0; s.status = BL_OK;
+  s.mean = 0; s.variance = 0; s.vprime = 0; s.rcp = 0; s.rcp_lo = 0; s.fsc = 0; s.kappa = 0; s.wrap_pass = 0; s.status = BL_OK;
   s.wrap_acc = 0;
   stats[i] = s;
 }
@@ -188,6 +188,9 @@ __device__ __forceinline__ void prep_finish(bl_dstats &s, int n) {
   /* FIR mode 2 filters the integers with the integer taps and scales once (bl_fir_int.h): within one ulp of
    * 1e-7 / (2 vprime), correctly rounded but for near-ties */
   s.fsc = bl_firi_scale(s.rcp, s.rcp_lo);
+  /* the kernel leaves the sums unscaled and multiplies the power terms instead: 2 fsc^2 from the same rcp + rcp_lo,
+   * rounded once */
+  s.kappa = bl_firi_power_scale(s.rcp, s.rcp_lo);
   (void)n;
 }
 

@@ -5,7 +5,8 @@ HIP events, and — for --probe tables — the s_memtime stamps of workgroup (0,
 compute wave's round goes (arithmetic phases, exchange phases, the wait in front of the hand-over).
 A table is six hex digits, one priority (0..3) per phase, phase 0 in the lowest digit; the measurement build
 instantiates the ones of EV_PRIO_TABS (bl_env_kernels.hip) beside the shipped 222011.  Prints one JSON object.
-usage: python tools/env_ab.py [--songs 1024] [--seconds 180] [--tabs 000000,111111,322110] [--probe 222011] [--reps 3]"""
+usage: python tools/env_ab.py [--songs 1024] [--seconds 180] [--tabs 000000,111111,322110] [--probe 222011] [--reps 3]
+       [--no-build]"""
 import argparse
 import ctypes as C
 import json
@@ -30,8 +31,10 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--dump", default="", help="directory for the raw stamps (probe<v>.npy)")
+    ap.add_argument("--no-build", action="store_true", help="use bliss_amd/libbliss_amd_measure.so as it is")
     a = ap.parse_args()
-    subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "bliss_amd", "csrc"), "measure"], check=True)
+    if not a.no_build:
+        subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "bliss_amd", "csrc"), "measure"], check=True)
     os.environ["BLISS_AMD_LIB"] = os.path.join(ROOT, "bliss_amd", "libbliss_amd_measure.so")
     import torch
     import bliss_amd
