@@ -8,8 +8,9 @@
  * Kernels:
  *   k_knn_prep     cosine: (root, reciprocal root) of |v|^2 per song
  *   k_knn, k_knn_merge  the k nearest songs of each query   ref python/examples/make_m3u_playlist.py:62-72
- *   k_knn_cross, k_knn_cross_merge, k_radius_cross_count, k_radius_cross_fill  siblings of those for queries that
- *                  are vectors outside the library (bl_amd_cross_*): a second operand, and no candidate excluded
+ *                  k_knn, k_knn_merge, k_radius_count and k_radius_fill carry a flag CROSS: false for queries that
+ *                  are songs of the library, true for vectors outside it (bl_amd_cross_*), of which no candidate is
+ *                  excluded; the self form passes the library as its own query array
  *   k_chain, k_chain_init, k_chain_step  song-to-song chains: every next song the nearest unplayed one
  *   k_mix, k_mix_init, k_mix_step  siblings of those under rules (bl_amd_mix_*): excluded songs, a gap between songs
  *                  of one tag, seeds that are vectors
@@ -143,9 +144,16 @@ __global__ __launch_bounds__(256) void k_knn_prep(const float4 *__restrict__ vec
 
 /* blockIdx.x: KNN_WAVES * KNN_QPW query rows, blockIdx.y: column split [y * cols, (y + 1) * cols).  n_split == 1:
  * the final lists go to out_index / out_value; otherwise the first k keys of each list go to
- * part[(row * n_split + split) * k ...]. */
-template <int KW, bool COSINE>
-__global__ __launch_bounds__(256) void k_knn(const float4 *__restrict__ vecs, const double2 *__restrict__ prep, int n,
+ * part[(row * n_split + split) * k ...].  Query r is qvecs[row_begin + r] with its prep qprep[row_begin + r].
+ *   CROSS = false  the queries are songs of the library: the launch passes vecs / prep as qvecs / qprep, and a
+ *                  query's own column is no candidate.
+ *   CROSS = true   the queries are vectors outside the library (bl_amd_cross_knn_device): they start at row 0
+ *                  (row_begin is not read) and every column is a candidate.
+ * One kernel with a flag, not two: the flag on the kernel itself leaves both forms' registers and occupancy what
+ * the two copies had; a body inlined into two kernels did not. */
+template <int KW, bool COSINE, bool CROSS>
+__global__ __launch_bounds__(256) void k_knn(const float4 *__restrict__ qvecs, const double2 *__restrict__ qprep,
+                                             const float4 *__restrict__ vecs, const double2 *__restrict__ prep, int n,
                                              int row_begin, int n_rows, int k, int cols, int n_split,
                                              unsigned long long *__restrict__ part, int32_t *__restrict__ out_index,
                                              float *__restrict__ out_value) {
@@ -156,15 +164,16 @@ __global__ __launch_bounds__(256) void k_knn(const float4 *__restrict__ vecs, co
   if (r0 >= n_rows) return;
   const int nq = min(KNN_QPW, n_rows - r0);
   const int c0 = blockIdx.y * cols, c1 = min(n, c0 + cols);
+  const int q0 = (CROSS ? 0 : row_begin) + r0; /* the wave's first row in qvecs */
   float4 a[KNN_QPW];
   double2 pa[KNN_QPW];
   float bnd[KNN_QPW];
   knn_top<KW> top[KNN_QPW];
 #pragma unroll
   for (int q = 0; q < KNN_QPW; ++q) {
-    const int row = row_begin + r0 + min(q, nq - 1);
-    a[q] = vecs[row];
-    pa[q] = COSINE ? prep[row] : make_double2(0.0, 0.0);
+    const int row = q0 + min(q, nq - 1);
+    a[q] = qvecs[row];
+    pa[q] = COSINE ? qprep[row] : make_double2(0.0, 0.0);
     /* held in VGPRs: the same in every lane, but as scalars (16 + 16 SGPRs for the cosine) they overflowed the
      * SGPR budget and spilled in the candidate loop; the empty asm only moves them to vector registers */
     asm volatile("" : "+v"(a[q].x), "+v"(a[q].y), "+v"(a[q].z), "+v"(a[q].w));
@@ -181,7 +190,7 @@ __global__ __launch_bounds__(256) void k_knn(const float4 *__restrict__ vecs, co
 #pragma unroll
     for (int q = 0; q < KNN_QPW; ++q) {
       if (q >= nq) break;
-      const bool cand = valid && j != row_begin + r0 + q;
+      const bool cand = valid && (CROSS || j != q0 + q);
       if (COSINE) {
         const unsigned long long key = bl_key<true>(bl_cosine(a[q], pa[q], b, pb), j);
         top[q].push(cand && key < top[q].thr, key, queue[wave][q], lane, k);
@@ -212,9 +221,11 @@ __global__ __launch_bounds__(256) void k_knn(const float4 *__restrict__ vecs, co
   }
 }
 
-/* one wave per query row: the n_split partial lists of the row, read as one stream of keys, through the filter */
-template <int KW, bool COSINE>
-__global__ __launch_bounds__(256) void k_knn_merge(const float4 *__restrict__ vecs, const double2 *__restrict__ prep,
+/* one wave per query row: the n_split partial lists of the row, read as one stream of keys, through the filter; the
+ * emitted values are computed from the query array again, indexed as in k_knn */
+template <int KW, bool COSINE, bool CROSS>
+__global__ __launch_bounds__(256) void k_knn_merge(const float4 *__restrict__ qvecs, const double2 *__restrict__ qprep,
+                                                   const float4 *__restrict__ vecs, const double2 *__restrict__ prep,
                                                    int row_begin, int n_rows, int k, int n_split,
                                                    const unsigned long long *__restrict__ part,
                                                    int32_t *__restrict__ out_index, float *__restrict__ out_value) {
@@ -238,110 +249,8 @@ __global__ __launch_bounds__(256) void k_knn_merge(const float4 *__restrict__ ve
     for (int u = 0; u < 4; ++u) top.push(key[u] < top.thr, key[u], queue[wave], lane, k);
   }
   top.finish(queue[wave], lane, k);
-  const int row = row_begin + r;
-  knn_emit<KW, COSINE>(top, lane, k, (size_t)r, vecs[row], COSINE ? prep[row] : make_double2(0.0, 0.0), vecs, prep,
-                       out_index, out_value);
-}
-
-/* k_knn for queries that are no songs of the library (bl_amd_cross_knn_device): query r is qvecs[r] with its prep
- * qprep[r], and every column is a candidate, so there is no own column to leave out.  qvecs may alias vecs: nothing
- * here writes either.  A sibling of k_knn, not a template parameter on it: k_knn's registers stay what they were. */
-template <int KW, bool COSINE>
-__global__ __launch_bounds__(256) void k_knn_cross(const float4 *__restrict__ qvecs, const double2 *__restrict__ qprep,
-                                                   const float4 *__restrict__ vecs, const double2 *__restrict__ prep,
-                                                   int n, int n_rows, int k, int cols, int n_split,
-                                                   unsigned long long *__restrict__ part,
-                                                   int32_t *__restrict__ out_index, float *__restrict__ out_value) {
-  __shared__ unsigned long long queue[KNN_WAVES][KNN_QPW][64];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int r0 = (blockIdx.x * KNN_WAVES + wave) * KNN_QPW;
-  if (r0 >= n_rows) return;
-  const int nq = min(KNN_QPW, n_rows - r0);
-  const int c0 = blockIdx.y * cols, c1 = min(n, c0 + cols);
-  float4 a[KNN_QPW];
-  double2 pa[KNN_QPW];
-  float bnd[KNN_QPW];
-  knn_top<KW> top[KNN_QPW];
-#pragma unroll
-  for (int q = 0; q < KNN_QPW; ++q) {
-    const int row = r0 + min(q, nq - 1);
-    a[q] = qvecs[row];
-    pa[q] = COSINE ? qprep[row] : make_double2(0.0, 0.0);
-    /* in VGPRs, as in k_knn */
-    asm volatile("" : "+v"(a[q].x), "+v"(a[q].y), "+v"(a[q].z), "+v"(a[q].w));
-    if (COSINE) asm volatile("" : "+v"(pa[q].x), "+v"(pa[q].y));
-    bnd[q] = __builtin_inff();
-    top[q].init();
-  }
-  for (int j0 = c0; j0 < c1; j0 += 64) {
-    const int j = j0 + lane;
-    const bool valid = j < c1;
-    const int jj = valid ? j : c1 - 1;
-    const float4 b = vecs[jj];
-    const double2 pb = COSINE ? prep[jj] : make_double2(0.0, 0.0);
-#pragma unroll
-    for (int q = 0; q < KNN_QPW; ++q) {
-      if (q >= nq) break;
-      if (COSINE) {
-        const unsigned long long key = bl_key<true>(bl_cosine(a[q], pa[q], b, pb), j);
-        top[q].push(valid && key < top[q].thr, key, queue[wave][q], lane, k);
-      } else {
-        const float s = bl_dist_sq(a[q], b);
-        const bool p = valid && !(s > bnd[q]);
-        if (__ballot(p) == 0) continue;
-        const float d = __all(!p || bl_sqrt_fast_ok(s)) ? bl_sqrt_rn_fast<1>(s) : sqrtf(s);
-        const unsigned long long key = bl_key<false>(d, j);
-        top[q].push(p && key < top[q].thr, key, queue[wave][q], lane, k);
-        bnd[q] = bl_sq_bound(top[q].thr);
-      }
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < KNN_QPW; ++q) {
-    if (q >= nq) break;
-    top[q].finish(queue[wave][q], lane, k);
-    const size_t r = (size_t)(r0 + q);
-    if (n_split == 1) {
-      knn_emit<KW, COSINE>(top[q], lane, k, r, a[q], pa[q], vecs, prep, out_index, out_value);
-    } else {
-      unsigned long long *dst = part + (r * n_split + blockIdx.y) * k;
-#pragma unroll
-      for (int w = 0; w < KW; ++w)
-        if (w * 64 + lane < k) dst[w * 64 + lane] = w == 0 ? top[q].e0 : top[q].e1;
-    }
-  }
-}
-
-/* k_knn_merge of the cross form: the values come from the query array again */
-template <int KW, bool COSINE>
-__global__ __launch_bounds__(256) void k_knn_cross_merge(const float4 *__restrict__ qvecs,
-                                                         const double2 *__restrict__ qprep,
-                                                         const float4 *__restrict__ vecs,
-                                                         const double2 *__restrict__ prep, int n_rows, int k, int n_split,
-                                                         const unsigned long long *__restrict__ part,
-                                                         int32_t *__restrict__ out_index, float *__restrict__ out_value) {
-  __shared__ unsigned long long queue[KNN_WAVES][64];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int r = blockIdx.x * KNN_WAVES + wave;
-  if (r >= n_rows) return;
-  const unsigned long long *src = part + (size_t)r * n_split * k;
-  const int total = n_split * k;
-  knn_top<KW> top;
-  top.init();
-  for (int o = 0; o < total; o += 4 * 64) {
-    unsigned long long key[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int i = o + u * 64 + lane;
-      key[u] = i < total ? src[i] : BL_KEY_EMPTY;
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) top.push(key[u] < top.thr, key[u], queue[wave], lane, k);
-  }
-  top.finish(queue[wave], lane, k);
-  knn_emit<KW, COSINE>(top, lane, k, (size_t)r, qvecs[r], COSINE ? qprep[r] : make_double2(0.0, 0.0), vecs, prep,
+  const int row = (CROSS ? 0 : row_begin) + r;
+  knn_emit<KW, COSINE>(top, lane, k, (size_t)r, qvecs[row], COSINE ? qprep[row] : make_double2(0.0, 0.0), vecs, prep,
                        out_index, out_value);
 }
 
@@ -940,18 +849,25 @@ template <bool COSINE> __device__ __forceinline__ bool radius_within(float m, fl
   return COSINE ? m >= bound : m <= bound;
 }
 
-/* the hit lanes of query `row` among the columns j0 .. j0 + 63; vmask: the lanes whose column exists */
-template <bool COSINE>
+/* the hit lanes of query `row` among the columns j0 .. j0 + 63; vmask: the lanes whose column exists.  CROSS: no
+ * column is the query's own, so the hits are the ballot under the tail mask alone */
+template <bool COSINE, bool CROSS>
 __device__ __forceinline__ unsigned long long radius_hits(float m, float bound, unsigned long long vmask, int row, int j0) {
   unsigned long long hits = __ballot(radius_within<COSINE>(m, bound)) & vmask;
-  const unsigned self = (unsigned)(row - j0);
-  if (self < 64u) hits &= ~(1ull << self);
+  if (!CROSS) {
+    const unsigned self = (unsigned)(row - j0);
+    if (self < 64u) hits &= ~(1ull << self);
+  }
   return hits;
 }
 
-/* grid (query tiles of RAD_WAVES * RAD_QPW rows, n_split); part[row * n_split + split] = hits of the split */
-template <bool COSINE>
-__global__ __launch_bounds__(256) void k_radius_count(const float4 *__restrict__ vecs, const double2 *__restrict__ prep,
+/* grid (query tiles of RAD_WAVES * RAD_QPW rows, n_split); part[row * n_split + split] = hits of the split.  Query r
+ * is qvecs[row_begin + r] with its prep qprep[row_begin + r], as in k_knn: the self form (CROSS = false) is launched
+ * with the library as its own query array; the cross form's queries (bl_amd_cross_radius_*_device) start at row 0.
+ * k_radius_offsets and k_radius_split_scan serve both forms. */
+template <bool COSINE, bool CROSS>
+__global__ __launch_bounds__(256) void k_radius_count(const float4 *__restrict__ qvecs, const double2 *__restrict__ qprep,
+                                                      const float4 *__restrict__ vecs, const double2 *__restrict__ prep,
                                                       int n, int row_begin, int n_rows, int cols, int n_split,
                                                       float bound, unsigned *__restrict__ part) {
   const int lane = threadIdx.x & 63;
@@ -960,9 +876,10 @@ __global__ __launch_bounds__(256) void k_radius_count(const float4 *__restrict__
   if (r0 >= n_rows) return;
   const int nq = min(RAD_QPW, n_rows - r0);
   const int c0 = blockIdx.y * cols, c1 = min(n, c0 + cols);
+  const int q0 = (CROSS ? 0 : row_begin) + r0; /* the wave's first row in qvecs */
   float4 a[RAD_QPW];
   double2 pa[RAD_QPW];
-  radius_load_queries<COSINE>(vecs, prep, row_begin + r0, nq, a, pa);
+  radius_load_queries<COSINE>(qvecs, qprep, q0, nq, a, pa);
   unsigned cnt[RAD_QPW];
 #pragma unroll
   for (int q = 0; q < RAD_QPW; ++q) cnt[q] = 0;
@@ -978,8 +895,8 @@ __global__ __launch_bounds__(256) void k_radius_count(const float4 *__restrict__
     const unsigned long long vmask = __ballot(j0 + lane < c1);
 #pragma unroll
     for (int q = 0; q < RAD_QPW; ++q) /* rows past nq repeat the last query; their counts are not stored */
-      cnt[q] += __popcll(radius_hits<COSINE>(bl_measure<COSINE>(a[q], pa[q], bc, pbc), bound, vmask,
-                                             row_begin + r0 + q, j0));
+      cnt[q] += __popcll(radius_hits<COSINE, CROSS>(bl_measure<COSINE>(a[q], pa[q], bc, pbc), bound, vmask,
+                                                    q0 + q, j0));
   }
   if (lane == 0) {
 #pragma unroll
@@ -1040,8 +957,9 @@ __global__ __launch_bounds__(256) void k_radius_split_scan(unsigned *__restrict_
 
 /* grid as k_radius_count; row r's hits of split y go to out_*[offset[r] + before[r * n_split + y] ...] in ascending
  * song order (before == nullptr: one split).  The stored value is computed from the measure that decided the hit. */
-template <bool COSINE, bool VALUES>
-__global__ __launch_bounds__(256) void k_radius_fill(const float4 *__restrict__ vecs, const double2 *__restrict__ prep,
+template <bool COSINE, bool VALUES, bool CROSS>
+__global__ __launch_bounds__(256) void k_radius_fill(const float4 *__restrict__ qvecs, const double2 *__restrict__ qprep,
+                                                     const float4 *__restrict__ vecs, const double2 *__restrict__ prep,
                                                      int n, int row_begin, int n_rows, int cols, int n_split, float bound,
                                                      const unsigned *__restrict__ before,
                                                      const long long *__restrict__ offset, int32_t *__restrict__ out_index,
@@ -1052,9 +970,10 @@ __global__ __launch_bounds__(256) void k_radius_fill(const float4 *__restrict__ 
   if (r0 >= n_rows) return;
   const int nq = min(RAD_QPW, n_rows - r0);
   const int c0 = blockIdx.y * cols, c1 = min(n, c0 + cols);
+  const int q0 = (CROSS ? 0 : row_begin) + r0; /* the wave's first row in qvecs */
   float4 a[RAD_QPW];
   double2 pa[RAD_QPW];
-  radius_load_queries<COSINE>(vecs, prep, row_begin + r0, nq, a, pa);
+  radius_load_queries<COSINE>(qvecs, qprep, q0, nq, a, pa);
   long long base[RAD_QPW];
 #pragma unroll
   for (int q = 0; q < RAD_QPW; ++q) {
@@ -1076,105 +995,7 @@ __global__ __launch_bounds__(256) void k_radius_fill(const float4 *__restrict__ 
     for (int q = 0; q < RAD_QPW; ++q) {
       if (q >= nq) break;
       const float m = bl_measure<COSINE>(a[q], pa[q], bc, pbc);
-      const unsigned long long hits = radius_hits<COSINE>(m, bound, vmask, row_begin + r0 + q, j0);
-      if (hits == 0) continue;
-      if ((hits >> lane) & 1ull) {
-        const long long pos = base[q] + __popcll(hits & below);
-        out_index[pos] = j0 + lane;
-        if (VALUES) out_value[pos] = bl_value_of<COSINE>(m);
-      }
-      base[q] += __popcll(hits);
-    }
-  }
-}
-
-/* Queries that are no songs of the library (bl_amd_cross_radius_*_device): siblings of k_radius_count and
- * k_radius_fill over the same pieces.  Query r is qvecs[r] with its prep qprep[r] (radius_load_queries reads them as it
- * reads songs), and no column is the query's own, so a step's hits are the ballot under the tail mask alone.
- * k_radius_offsets and k_radius_split_scan serve both forms.  qvecs may alias vecs: nothing here writes either. */
-template <bool COSINE>
-__device__ __forceinline__ unsigned long long radius_hits_all(float m, float bound, unsigned long long vmask) {
-  return __ballot(radius_within<COSINE>(m, bound)) & vmask;
-}
-
-template <bool COSINE>
-__global__ __launch_bounds__(256) void k_radius_cross_count(const float4 *__restrict__ qvecs,
-                                                            const double2 *__restrict__ qprep,
-                                                            const float4 *__restrict__ vecs,
-                                                            const double2 *__restrict__ prep, int n, int n_rows, int cols,
-                                                            int n_split, float bound, unsigned *__restrict__ part) {
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int r0 = (blockIdx.x * RAD_WAVES + wave) * RAD_QPW;
-  if (r0 >= n_rows) return;
-  const int nq = min(RAD_QPW, n_rows - r0);
-  const int c0 = blockIdx.y * cols, c1 = min(n, c0 + cols);
-  float4 a[RAD_QPW];
-  double2 pa[RAD_QPW];
-  radius_load_queries<COSINE>(qvecs, qprep, r0, nq, a, pa);
-  unsigned cnt[RAD_QPW];
-#pragma unroll
-  for (int q = 0; q < RAD_QPW; ++q) cnt[q] = 0;
-  int jn = min(c0 + lane, c1 - 1);
-  float4 b = vecs[jn];
-  double2 pb = COSINE ? prep[jn] : make_double2(0.0, 0.0);
-  for (int j0 = c0; j0 < c1; j0 += 64) {
-    const float4 bc = b;
-    const double2 pbc = pb;
-    jn = min(j0 + 64 + lane, c1 - 1); /* the next step's column, fetched under this step's arithmetic */
-    b = vecs[jn];
-    if (COSINE) pb = prep[jn];
-    const unsigned long long vmask = __ballot(j0 + lane < c1);
-#pragma unroll
-    for (int q = 0; q < RAD_QPW; ++q) /* rows past nq repeat the last query; their counts are not stored */
-      cnt[q] += __popcll(radius_hits_all<COSINE>(bl_measure<COSINE>(a[q], pa[q], bc, pbc), bound, vmask));
-  }
-  if (lane == 0) {
-#pragma unroll
-    for (int q = 0; q < RAD_QPW; ++q)
-      if (q < nq) part[(size_t)(r0 + q) * n_split + blockIdx.y] = cnt[q];
-  }
-}
-
-template <bool COSINE, bool VALUES>
-__global__ __launch_bounds__(256) void k_radius_cross_fill(const float4 *__restrict__ qvecs,
-                                                           const double2 *__restrict__ qprep,
-                                                           const float4 *__restrict__ vecs,
-                                                           const double2 *__restrict__ prep, int n, int n_rows, int cols,
-                                                           int n_split, float bound, const unsigned *__restrict__ before,
-                                                           const long long *__restrict__ offset,
-                                                           int32_t *__restrict__ out_index, float *__restrict__ out_value) {
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int r0 = (blockIdx.x * RAD_WAVES + wave) * RAD_QPW;
-  if (r0 >= n_rows) return;
-  const int nq = min(RAD_QPW, n_rows - r0);
-  const int c0 = blockIdx.y * cols, c1 = min(n, c0 + cols);
-  float4 a[RAD_QPW];
-  double2 pa[RAD_QPW];
-  radius_load_queries<COSINE>(qvecs, qprep, r0, nq, a, pa);
-  long long base[RAD_QPW];
-#pragma unroll
-  for (int q = 0; q < RAD_QPW; ++q) {
-    const size_t r = (size_t)(r0 + min(q, nq - 1));
-    base[q] = offset[r] + (before ? (long long)before[r * n_split + blockIdx.y] : 0);
-  }
-  const unsigned long long below = (1ull << lane) - 1ull;
-  int jn = min(c0 + lane, c1 - 1);
-  float4 b = vecs[jn];
-  double2 pb = COSINE ? prep[jn] : make_double2(0.0, 0.0);
-  for (int j0 = c0; j0 < c1; j0 += 64) {
-    const float4 bc = b;
-    const double2 pbc = pb;
-    jn = min(j0 + 64 + lane, c1 - 1);
-    b = vecs[jn];
-    if (COSINE) pb = prep[jn];
-    const unsigned long long vmask = __ballot(j0 + lane < c1);
-#pragma unroll
-    for (int q = 0; q < RAD_QPW; ++q) {
-      if (q >= nq) break;
-      const float m = bl_measure<COSINE>(a[q], pa[q], bc, pbc);
-      const unsigned long long hits = radius_hits_all<COSINE>(m, bound, vmask);
+      const unsigned long long hits = radius_hits<COSINE, CROSS>(m, bound, vmask, q0 + q, j0);
       if (hits == 0) continue;
       if ((hits >> lane) & 1ull) {
         const long long pos = base[q] + __popcll(hits & below);
@@ -1347,41 +1168,36 @@ size_t blk_knn_cross_scratch_bytes(int n, int n_queries, int k, bool cosine, int
   return blk_knn_scratch_bytes(n, n_queries, k, cosine, n_cu) + prep_bytes(n_queries, cosine);
 }
 
-/* q == nullptr: the self kernels over rows [row_begin, row_begin + n_rows) of v; else the cross kernels over q[0 .. n_rows) */
-template <int KW, bool COSINE>
+/* The queries are q[row_begin .. row_begin + n_rows).  CROSS = false: q is v, the library as its own query array, and
+ * p.qprep is p.prep; the kernels only read through either name, so the same array under two __restrict__ pointers is
+ * as sound as a cross call whose queries alias the library.  CROSS = true: vectors outside the library, row_begin = 0. */
+template <int KW, bool COSINE, bool CROSS>
 static void knn_launch(hipStream_t s, const float4 *q, const float4 *v, const query_preps &p, int n, int row_begin,
                        int n_rows, int k, int n_split, int cols, unsigned long long *part, int32_t *d_index,
                        float *d_value) {
   const int per_block = KNN_WAVES * KNN_QPW;
   const dim3 grid((n_rows + per_block - 1) / per_block, n_split), merge_grid((n_rows + KNN_WAVES - 1) / KNN_WAVES);
   const dim3 block(64 * KNN_WAVES);
-  if (q) {
-    hipLaunchKernelGGL((k_knn_cross<KW, COSINE>), grid, block, 0, s, q, p.qprep, v, p.prep, n, n_rows, k, cols, n_split,
-                       part, d_index, d_value);
-    if (n_split > 1)
-      hipLaunchKernelGGL((k_knn_cross_merge<KW, COSINE>), merge_grid, block, 0, s, q, p.qprep, v, p.prep, n_rows, k,
-                         n_split, part, d_index, d_value);
-    return;
-  }
-  hipLaunchKernelGGL((k_knn<KW, COSINE>), grid, block, 0, s, v, p.prep, n, row_begin, n_rows, k, cols, n_split, part,
-                     d_index, d_value);
+  hipLaunchKernelGGL((k_knn<KW, COSINE, CROSS>), grid, block, 0, s, q, p.qprep, v, p.prep, n, row_begin, n_rows, k, cols,
+                     n_split, part, d_index, d_value);
   if (n_split > 1)
-    hipLaunchKernelGGL((k_knn_merge<KW, COSINE>), merge_grid, block, 0, s, v, p.prep, row_begin, n_rows, k, n_split,
-                       part, d_index, d_value);
+    hipLaunchKernelGGL((k_knn_merge<KW, COSINE, CROSS>), merge_grid, block, 0, s, q, p.qprep, v, p.prep, row_begin,
+                       n_rows, k, n_split, part, d_index, d_value);
 }
 
+template <bool CROSS>
 static int knn_run(hipStream_t s, const float4 *q, const float4 *v, int n, int row_begin, int n_rows, int k, bool cosine,
                    int n_cu, void *d_scratch, int32_t *d_index, float *d_value) {
   int n_split, cols;
   blk_split_plan(n, n_rows, n_cu, KNN_QPW, KNN_SPLIT_MIN_COLS, &n_split, &cols);
-  const query_preps p = launch_preps(s, q, n_rows, v, n, cosine, d_scratch);
+  const query_preps p = launch_preps(s, CROSS ? q : nullptr, n_rows, v, n, cosine, d_scratch);
   unsigned long long *part = n_split > 1 ? reinterpret_cast<unsigned long long *>(p.rest) : nullptr;
   if (k > 64) {
-    if (cosine) knn_launch<2, true>(s, q, v, p, n, row_begin, n_rows, k, n_split, cols, part, d_index, d_value);
-    else knn_launch<2, false>(s, q, v, p, n, row_begin, n_rows, k, n_split, cols, part, d_index, d_value);
+    if (cosine) knn_launch<2, true, CROSS>(s, q, v, p, n, row_begin, n_rows, k, n_split, cols, part, d_index, d_value);
+    else knn_launch<2, false, CROSS>(s, q, v, p, n, row_begin, n_rows, k, n_split, cols, part, d_index, d_value);
   } else {
-    if (cosine) knn_launch<1, true>(s, q, v, p, n, row_begin, n_rows, k, n_split, cols, part, d_index, d_value);
-    else knn_launch<1, false>(s, q, v, p, n, row_begin, n_rows, k, n_split, cols, part, d_index, d_value);
+    if (cosine) knn_launch<1, true, CROSS>(s, q, v, p, n, row_begin, n_rows, k, n_split, cols, part, d_index, d_value);
+    else knn_launch<1, false, CROSS>(s, q, v, p, n, row_begin, n_rows, k, n_split, cols, part, d_index, d_value);
   }
   BL_HIP_CHECK(hipGetLastError());
   return BL_OK;
@@ -1389,15 +1205,15 @@ static int knn_run(hipStream_t s, const float4 *q, const float4 *v, int n, int r
 
 int blk_knn(hipStream_t s, const struct force_vector_s *d_vecs, int n, int row_begin, int n_rows, int k,
             bool cosine, int n_cu, void *d_scratch, int32_t *d_index, float *d_value) {
-  return knn_run(s, nullptr, reinterpret_cast<const float4 *>(d_vecs), n, row_begin, n_rows, k, cosine, n_cu, d_scratch,
-                 d_index, d_value);
+  const float4 *v = reinterpret_cast<const float4 *>(d_vecs);
+  return knn_run<false>(s, v, v, n, row_begin, n_rows, k, cosine, n_cu, d_scratch, d_index, d_value);
 }
 
 int blk_knn_cross(hipStream_t s, const struct force_vector_s *d_queries, int n_queries,
                   const struct force_vector_s *d_vecs, int n, int k, bool cosine, int n_cu, void *d_scratch,
                   int32_t *d_index, float *d_value) {
-  return knn_run(s, reinterpret_cast<const float4 *>(d_queries), reinterpret_cast<const float4 *>(d_vecs), n, 0,
-                 n_queries, k, cosine, n_cu, d_scratch, d_index, d_value);
+  return knn_run<true>(s, reinterpret_cast<const float4 *>(d_queries), reinterpret_cast<const float4 *>(d_vecs), n, 0,
+                       n_queries, k, cosine, n_cu, d_scratch, d_index, d_value);
 }
 
 /* Shape of a chain call (see k_chain).  Column split (2) when the corpus is large enough for a step's scan by one
@@ -1558,27 +1374,24 @@ static dim3 radius_grid(int n_rows, int n_split) {
   return dim3((n_rows + per_block - 1) / per_block, n_split);
 }
 
-/* the per-(row, split) counts into p.rest, which is returned; q as in knn_launch */
-template <bool COSINE>
+/* the per-(row, split) counts into p.rest, which is returned; q and CROSS as in knn_launch */
+template <bool COSINE, bool CROSS>
 static unsigned *radius_count_launch(hipStream_t s, const float4 *q, const float4 *v, const query_preps &p, int n,
                                      int row_begin, int n_rows, float bound, int n_split, int cols) {
   unsigned *part = reinterpret_cast<unsigned *>(p.rest);
-  if (q)
-    hipLaunchKernelGGL((k_radius_cross_count<COSINE>), radius_grid(n_rows, n_split), dim3(64 * RAD_WAVES), 0, s, q,
-                       p.qprep, v, p.prep, n, n_rows, cols, n_split, bound, part);
-  else
-    hipLaunchKernelGGL((k_radius_count<COSINE>), radius_grid(n_rows, n_split), dim3(64 * RAD_WAVES), 0, s, v, p.prep, n,
-                       row_begin, n_rows, cols, n_split, bound, part);
+  hipLaunchKernelGGL((k_radius_count<COSINE, CROSS>), radius_grid(n_rows, n_split), dim3(64 * RAD_WAVES), 0, s, q,
+                     p.qprep, v, p.prep, n, row_begin, n_rows, cols, n_split, bound, part);
   return part;
 }
 
+template <bool CROSS>
 static int radius_count_run(hipStream_t s, const float4 *q, const float4 *v, int n, int row_begin, int n_rows,
                             bool cosine, float bound, int n_cu, void *d_scratch, long long *d_offset) {
   int n_split, cols;
   blk_split_plan(n, n_rows, n_cu, RAD_QPW, RAD_SPLIT_MIN_COLS, &n_split, &cols);
-  const query_preps p = launch_preps(s, q, n_rows, v, n, cosine, d_scratch);
-  unsigned *part = cosine ? radius_count_launch<true>(s, q, v, p, n, row_begin, n_rows, bound, n_split, cols)
-                          : radius_count_launch<false>(s, q, v, p, n, row_begin, n_rows, bound, n_split, cols);
+  const query_preps p = launch_preps(s, CROSS ? q : nullptr, n_rows, v, n, cosine, d_scratch);
+  unsigned *part = cosine ? radius_count_launch<true, CROSS>(s, q, v, p, n, row_begin, n_rows, bound, n_split, cols)
+                          : radius_count_launch<false, CROSS>(s, q, v, p, n, row_begin, n_rows, bound, n_split, cols);
   const unsigned *counts = part;
   if (n_split > 1) {
     unsigned *rowsum = part + (size_t)n_rows * n_split;
@@ -1592,58 +1405,48 @@ static int radius_count_run(hipStream_t s, const float4 *q, const float4 *v, int
 
 int blk_radius_count(hipStream_t s, const struct force_vector_s *d_vecs, int n, int row_begin, int n_rows, bool cosine,
                      float bound, int n_cu, void *d_scratch, long long *d_offset) {
-  return radius_count_run(s, nullptr, reinterpret_cast<const float4 *>(d_vecs), n, row_begin, n_rows, cosine, bound, n_cu,
-                          d_scratch, d_offset);
+  const float4 *v = reinterpret_cast<const float4 *>(d_vecs);
+  return radius_count_run<false>(s, v, v, n, row_begin, n_rows, cosine, bound, n_cu, d_scratch, d_offset);
 }
 
 int blk_radius_cross_count(hipStream_t s, const struct force_vector_s *d_queries, int n_queries,
                            const struct force_vector_s *d_vecs, int n, bool cosine, float bound, int n_cu,
                            void *d_scratch, long long *d_offset) {
-  return radius_count_run(s, reinterpret_cast<const float4 *>(d_queries), reinterpret_cast<const float4 *>(d_vecs), n, 0,
-                          n_queries, cosine, bound, n_cu, d_scratch, d_offset);
-}
-
-template <bool COSINE, bool VALUES>
-static void radius_fill_launch(hipStream_t s, const float4 *q, const float4 *v, const query_preps &p, int n,
-                               int row_begin, int n_rows, int n_split, int cols, float bound, const unsigned *before,
-                               const long long *d_offset, int32_t *d_index, float *d_value) {
-  if (q)
-    hipLaunchKernelGGL((k_radius_cross_fill<COSINE, VALUES>), radius_grid(n_rows, n_split), dim3(64 * RAD_WAVES), 0, s,
-                       q, p.qprep, v, p.prep, n, n_rows, cols, n_split, bound, before, d_offset, d_index, d_value);
-  else
-    hipLaunchKernelGGL((k_radius_fill<COSINE, VALUES>), radius_grid(n_rows, n_split), dim3(64 * RAD_WAVES), 0, s, v,
-                       p.prep, n, row_begin, n_rows, cols, n_split, bound, before, d_offset, d_index, d_value);
+  return radius_count_run<true>(s, reinterpret_cast<const float4 *>(d_queries),
+                                reinterpret_cast<const float4 *>(d_vecs), n, 0, n_queries, cosine, bound, n_cu, d_scratch,
+                                d_offset);
 }
 
 /* One split: a row's list starts at its offset, nothing else is needed.  Column split: the per-split counts are
  * computed again here (the scratch may have served another call since the count), so fill depends on nothing but
  * its arguments. */
-template <bool COSINE>
+template <bool COSINE, bool CROSS>
 static void radius_fill_run(hipStream_t s, const float4 *q, const float4 *v, int n, int row_begin, int n_rows,
                             float bound, int n_cu, void *d_scratch, const long long *d_offset, int32_t *d_index,
                             float *d_value) {
   int n_split, cols;
   blk_split_plan(n, n_rows, n_cu, RAD_QPW, RAD_SPLIT_MIN_COLS, &n_split, &cols);
-  const query_preps p = launch_preps(s, q, n_rows, v, n, COSINE, d_scratch);
+  const query_preps p = launch_preps(s, CROSS ? q : nullptr, n_rows, v, n, COSINE, d_scratch);
   unsigned *before = nullptr;
   if (n_split > 1) {
-    before = radius_count_launch<COSINE>(s, q, v, p, n, row_begin, n_rows, bound, n_split, cols);
+    before = radius_count_launch<COSINE, CROSS>(s, q, v, p, n, row_begin, n_rows, bound, n_split, cols);
     hipLaunchKernelGGL(k_radius_split_scan, dim3((n_rows + 3) / 4), dim3(256), 0, s, before, n_rows, n_split,
                        before + (size_t)n_rows * n_split);
   }
+  const dim3 grid = radius_grid(n_rows, n_split), block(64 * RAD_WAVES);
   if (d_value)
-    radius_fill_launch<COSINE, true>(s, q, v, p, n, row_begin, n_rows, n_split, cols, bound, before, d_offset, d_index,
-                                     d_value);
+    hipLaunchKernelGGL((k_radius_fill<COSINE, true, CROSS>), grid, block, 0, s, q, p.qprep, v, p.prep, n, row_begin,
+                       n_rows, cols, n_split, bound, before, d_offset, d_index, d_value);
   else
-    radius_fill_launch<COSINE, false>(s, q, v, p, n, row_begin, n_rows, n_split, cols, bound, before, d_offset, d_index,
-                                      d_value);
+    hipLaunchKernelGGL((k_radius_fill<COSINE, false, CROSS>), grid, block, 0, s, q, p.qprep, v, p.prep, n, row_begin,
+                       n_rows, cols, n_split, bound, before, d_offset, d_index, d_value);
 }
 
 int blk_radius_fill(hipStream_t s, const struct force_vector_s *d_vecs, int n, int row_begin, int n_rows, bool cosine,
                     float bound, int n_cu, void *d_scratch, const long long *d_offset, int32_t *d_index, float *d_value) {
   const float4 *v = reinterpret_cast<const float4 *>(d_vecs);
-  if (cosine) radius_fill_run<true>(s, nullptr, v, n, row_begin, n_rows, bound, n_cu, d_scratch, d_offset, d_index, d_value);
-  else radius_fill_run<false>(s, nullptr, v, n, row_begin, n_rows, bound, n_cu, d_scratch, d_offset, d_index, d_value);
+  if (cosine) radius_fill_run<true, false>(s, v, v, n, row_begin, n_rows, bound, n_cu, d_scratch, d_offset, d_index, d_value);
+  else radius_fill_run<false, false>(s, v, v, n, row_begin, n_rows, bound, n_cu, d_scratch, d_offset, d_index, d_value);
   BL_HIP_CHECK(hipGetLastError());
   return BL_OK;
 }
@@ -1652,8 +1455,8 @@ int blk_radius_cross_fill(hipStream_t s, const struct force_vector_s *d_queries,
                           const struct force_vector_s *d_vecs, int n, bool cosine, float bound, int n_cu, void *d_scratch,
                           const long long *d_offset, int32_t *d_index, float *d_value) {
   const float4 *q = reinterpret_cast<const float4 *>(d_queries), *v = reinterpret_cast<const float4 *>(d_vecs);
-  if (cosine) radius_fill_run<true>(s, q, v, n, 0, n_queries, bound, n_cu, d_scratch, d_offset, d_index, d_value);
-  else radius_fill_run<false>(s, q, v, n, 0, n_queries, bound, n_cu, d_scratch, d_offset, d_index, d_value);
+  if (cosine) radius_fill_run<true, true>(s, q, v, n, 0, n_queries, bound, n_cu, d_scratch, d_offset, d_index, d_value);
+  else radius_fill_run<false, true>(s, q, v, n, 0, n_queries, bound, n_cu, d_scratch, d_offset, d_index, d_value);
   BL_HIP_CHECK(hipGetLastError());
   return BL_OK;
 }

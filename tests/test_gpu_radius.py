@@ -244,6 +244,27 @@ def test_fill_variants_null_values_side_stream_and_two_contexts(gpu_lib, metric)
 
 
 @pytest.mark.parametrize("metric", ["distance", "cosine"])
+def test_one_split_with_and_without_values(gpu_lib, oracle, metric):
+    """n = 1 027 is below twice RAD_SPLIT_MIN_COLS and no multiple of 64, so every call runs as one split, which the
+    larger shapes of this file never do: all rows and a row range, with values and with d_value = NULL"""
+    import torch
+    n = 1027
+    v = (np.random.default_rng(9).standard_normal((n, 4)) * 8).astype(np.float32)
+    v[n - 1] = v[3]                                     # a duplicate in the last column
+    mat = oracle.distance_matrix(v) if metric == "distance" else oracle.cosine_matrix(v)
+    r = 6.0 if metric == "distance" else 0.9
+    d = torch.from_numpy(v).cuda()
+    for a, b in ((0, n), (500, 541), (n - 1, n)):
+        rows = np.arange(a, b)
+        want = expected(mat[a:b], rows, r, metric)
+        assert want[0][-1] > 0
+        assert_same(bliss_amd.radius_device(d, r, metric=metric, row_begin=a, n_rows=b - a), want)
+        off, idx, val = bliss_amd.radius_device(d, r, metric=metric, row_begin=a, n_rows=b - a, values=False)
+        assert val is None
+        assert np.array_equal(off.cpu().numpy(), want[0]) and np.array_equal(idx.cpu().numpy(), want[1])
+
+
+@pytest.mark.parametrize("metric", ["distance", "cosine"])
 def test_an_empty_total(gpu_lib, metric):
     """a radius below every entry: offsets all 0, fill writes nothing (and is given zero-length lists' worth of room)"""
     import torch

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Do two source trees compile to the same gfx950 kernels?
 
-    tools/kernel_asm_diff.py OLD NEW [--make VAR=VALUE ...] [--keep DIR]
+    tools/kernel_asm_diff.py OLD NEW [--make VAR=VALUE ...] [--keep DIR] [--map OLD=NEW ...] [--margin N]
 
 OLD and NEW are each a checkout (a directory with bliss_amd/csrc/Makefile) or anything `git archive` accepts
 (a commit, a tag, HEAD).  Every bliss_amd/csrc/*.hip file with a __global__ in it is compiled device-only to
@@ -19,6 +19,13 @@ Prints the kernels that differ or exist on one side only and exits 1 if there ar
 --make VAR=VALUE (repeatable) is handed to both Makefiles, so the other builds can be compared too: --make MEASURE=1
 is the measurement build (every k_env_windows3 priority table, every k_pairwise root), --make XDEFS=-DBL_AMD_CHECKED_HIST
 the one with the range-tested histogram adds.
+
+--map 'OLD=NEW' (repeatable) pairs a kernel that was renamed: OLD is a regular expression that must match the whole
+demangled name of a kernel of OLD without its argument list (`k_knn_cross<1, false>`), NEW the name it has in NEW, with
+\\1 ... for OLD's groups: --map 'k_knn_cross<(.*)>=k_knn<\\1, true>'.  A mapped pair is not compared line by line (its
+arguments differ).  Its line counts, report fields and differing descriptor fields are printed side by side, and the pair
+fails when NumVgprs, NumAgprs, ScratchSize, LDSByteSize or Occupancy differ, when TotalNumSgprs rose, or when NEW has
+more than --margin lines more than OLD (default 4).  --map 'OLD~NEW' is the same with the line counts only reported.
 """
 import argparse
 import os
@@ -122,7 +129,46 @@ def demangle(syms):
         return {s: s for s in syms}
 
 
-def compare(old, new):
+def short(nice):
+    """`void k<1, false>(float4 const*, int)` -> `k<1, false>`"""
+    return re.sub(r"^void ", "", nice).split("(", 1)[0].strip()
+
+
+def mapped_pairs(fo, fn, nice, maps, margin):
+    """prints the renamed pairs, takes them out of fo / fn, returns how many fail"""
+    by_name = {short(nice[s]): s for s in fn}
+    bad, used = 0, set()
+    for spec in maps:
+        sep = "=" if "=" in spec else "~"
+        pat, _, to = spec.partition(sep)
+        hits = [s for s in sorted(fo) if fo[s]["desc"] and re.fullmatch(pat, short(nice[s]))]
+        if not hits:
+            sys.exit(f"--map {spec}: no kernel of OLD matches")
+        for so in hits:
+            name = re.fullmatch(pat, short(nice[so])).expand(to)
+            sn = by_name.get(name)
+            if sn is None:
+                sys.exit(f"--map {spec}: NEW has no kernel {name}")
+            a, b = fo.pop(so), fn[sn]
+            used.add(sn)
+            why = [f"{k}: {a['report'].get(k)} vs {b['report'].get(k)}" for k in REPORT[1:]
+                   if a["report"].get(k) != b["report"].get(k)]
+            if int(b["report"]["TotalNumSgprs"]) > int(a["report"]["TotalNumSgprs"]):
+                why.append("TotalNumSgprs rose")
+            if sep == "=" and len(b["text"]) - len(a["text"]) > margin:
+                why.append(f"more than {margin} lines longer")
+            desc = [f"{k} {a['desc'].get(k)} -> {b['desc'].get(k)}" for k in sorted(set(a["desc"]) | set(b["desc"]))
+                    if a["desc"].get(k) != b["desc"].get(k)]
+            print(f"{'FAIL' if why else 'PAIR'} {short(nice[so])} -> {name}\n     lines {len(a['text'])} -> {len(b['text'])}"
+                  + "".join(f", {k} {a['report'].get(k)} -> {b['report'].get(k)}" for k in REPORT)
+                  + ("\n     " + "; ".join(desc) if desc else "") + ("\n     " + "; ".join(why) if why else ""))
+            bad += bool(why)
+    for sn in used:  # a NEW kernel may stand for several OLD ones, so it leaves only now
+        del fn[sn]
+    return bad
+
+
+def compare(old, new, maps=(), margin=4):
     fo, fn = {}, {}
     for side, dst in ((old, fo), (new, fn)):
         for stem, asm in side.items():
@@ -130,7 +176,7 @@ def compare(old, new):
                 f["file"] = stem + ".hip"
                 dst[sym] = f
     nice = demangle(sorted(set(fo) | set(fn)))
-    bad = 0
+    bad = mapped_pairs(fo, fn, nice, maps, margin)
     for sym in sorted(set(fo) | set(fn)):
         a, b = fo.get(sym), fn.get(sym)
         why = []
@@ -163,6 +209,10 @@ def main():
     ap.add_argument("--make", action="append", default=[], metavar="VAR=VALUE", dest="make_vars",
                     help="a make variable for both trees' Makefiles (repeatable), e.g. MEASURE=1")
     ap.add_argument("--keep", metavar="DIR", help="leave the assembly files here")
+    ap.add_argument("--map", action="append", default=[], metavar="OLD=NEW", dest="maps",
+                    help="a renamed kernel: regex on OLD's demangled name = its name in NEW (OLD~NEW: line counts "
+                         "reported, not capped); repeatable")
+    ap.add_argument("--margin", type=int, default=4, help="lines a mapped kernel of NEW may be longer by (default 4)")
     a = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmp:
         work = a.keep or tmp
@@ -172,7 +222,7 @@ def main():
             wd = os.path.join(work, name)
             os.makedirs(wd, exist_ok=True)
             sides.append((tree, wd))
-        bad = compare(device_asm(*sides[0], a.make_vars), device_asm(*sides[1], a.make_vars))
+        bad = compare(device_asm(*sides[0], a.make_vars), device_asm(*sides[1], a.make_vars), a.maps, a.margin)
     sys.exit(1 if bad else 0)
 
 
