@@ -501,6 +501,27 @@ def _knn_check(k, metric, shape):
     return _metric_check(metric, shape)
 
 
+def _knn_host_call(name, args, rows, k):
+    """(index, value) of shape (rows, k) from the kNN host entry point `name`, called with `args` and the two outputs"""
+    lib = _lib.load()
+    index = np.empty((rows, k), dtype=np.int32)
+    value = np.empty((rows, k), dtype=np.float32)
+    rc = getattr(lib, name)(*args, index.ctypes.data_as(C.POINTER(C.c_int32)), value.ctypes.data_as(C.POINTER(C.c_float)))
+    _check(rc, name)
+    return index, value
+
+
+def _knn_device_call(name, args, v, rows, k, stream):
+    """The same for a device entry point, on the device of the library tensor v and on `stream`"""
+    import torch
+    lib = _lib.load()
+    index = torch.empty((rows, k), dtype=torch.int32, device=v.device)
+    value = torch.empty((rows, k), dtype=torch.float32, device=v.device)
+    with _on_device_of(lib, v, stream) as cur:
+        _check(getattr(lib, name)(*args, index.data_ptr(), value.data_ptr(), C.c_void_p(cur.cuda_stream)), name)
+    return index, value
+
+
 def knn(vecs, k, metric="distance"):
     """The k nearest songs of every song of (n, 4) force vectors: (index (n, k) int32, value (n, k) float32).
     Values have the bits of bl_distance ("distance", nearest = smallest) or bl_cosine_similarity ("cosine",
@@ -508,33 +529,20 @@ def knn(vecs, k, metric="distance"):
     (ref python/examples/make_m3u_playlist.py:62-72 for every seed).  Slots past n - 1 hold -1 and NaN."""
     v = np.ascontiguousarray(vecs, dtype=np.float32)
     m = _knn_check(k, metric, v.shape)
-    lib = _lib.load()
     n = v.shape[0]
-    index = np.empty((n, k), dtype=np.int32)
-    value = np.empty((n, k), dtype=np.float32)
-    rc = lib.bl_amd_knn_host(v.ctypes.data_as(C.POINTER(_lib.ForceVector)), n, int(k), m,
-                             index.ctypes.data_as(C.POINTER(C.c_int32)), value.ctypes.data_as(C.POINTER(C.c_float)))
-    _check(rc, "bl_amd_knn_host")
-    return index, value
+    return _knn_host_call("bl_amd_knn_host", (v.ctypes.data_as(C.POINTER(_lib.ForceVector)), n, int(k), m), n, k)
 
 
 def knn_device(d_vecs, k, metric="distance", row_begin=0, n_rows=None, stream=None):
     """knn() for the queries d_vecs[row_begin:row_begin + n_rows] against all of d_vecs, a float32 (n, 4) CUDA
     tensor; returns (index, value) CUDA tensors of shape (n_rows, k) on its device, asynchronously on `stream`
     (default: the current stream of that device)."""
-    import torch
     m = _knn_check(k, metric, tuple(d_vecs.shape))
     _device_vecs_check(d_vecs)
     n = d_vecs.shape[0]
     n_rows = _rows_check(n, row_begin, n_rows)
-    lib = _lib.load()
-    v = d_vecs
-    index = torch.empty((n_rows, k), dtype=torch.int32, device=v.device)
-    value = torch.empty((n_rows, k), dtype=torch.float32, device=v.device)
-    with _on_device_of(lib, v, stream) as cur:
-        _check(lib.bl_amd_knn_device(v.data_ptr(), n, int(row_begin), int(n_rows), int(k), m, index.data_ptr(),
-                                     value.data_ptr(), C.c_void_p(cur.cuda_stream)), "bl_amd_knn_device")
-    return index, value
+    return _knn_device_call("bl_amd_knn_device", (d_vecs.data_ptr(), n, int(row_begin), int(n_rows), int(k), m), d_vecs,
+                            n_rows, k, stream)
 
 
 def _chain_check(seeds, length, metric, shape, n_limit):
@@ -729,22 +737,16 @@ def _radius_check(r, metric, shape):
     return m, float(r32)
 
 
-def radius(vecs, r, metric="distance"):
-    """The songs within radius r of every song of (n, 4) force vectors, as compressed sparse row lists:
-    (offsets int64 (n + 1,), index int32 (total,), value float32 (total,)); row i is index[offsets[i]:offsets[i + 1]],
-    in ascending song index, and never lists i.  Within means bl_distance <= r ("distance") or bl_cosine_similarity
-    >= r ("cosine") on the f32 matrix entry, whose bits `value` holds; a NaN entry is never within."""
-    v = np.ascontiguousarray(vecs, dtype=np.float32)
-    m, r = _radius_check(r, metric, v.shape)
+def _radius_host_call(name, args, rows):
+    """(offsets, index, value) of `rows` queries from the radius host entry point `name`, called with `args` and the
+    three outputs; the two blocks the library allocates are copied and freed"""
     lib = _lib.load()
-    n = v.shape[0]
-    offsets = np.empty(n + 1, dtype=np.int64)
+    offsets = np.empty(rows + 1, dtype=np.int64)
     p_index, p_value = C.POINTER(C.c_int32)(), C.POINTER(C.c_float)()
-    rc = lib.bl_amd_radius_host(v.ctypes.data_as(C.POINTER(_lib.ForceVector)), n, m, r,
-                                offsets.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(p_index), C.byref(p_value))
-    _check(rc, "bl_amd_radius_host")
+    rc = getattr(lib, name)(*args, offsets.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(p_index), C.byref(p_value))
+    _check(rc, name)
     try:
-        total = int(offsets[n])
+        total = int(offsets[rows])
         index = np.ctypeslib.as_array(p_index, shape=(total,)).copy() if total else np.empty(0, dtype=np.int32)
         value = np.ctypeslib.as_array(p_value, shape=(total,)).copy() if total else np.empty(0, dtype=np.float32)
     finally:
@@ -753,31 +755,46 @@ def radius(vecs, r, metric="distance"):
     return offsets, index, value
 
 
+def _radius_device_call(count, fill, args, v, rows, values, stream):
+    """The same from the device entry points `count` and `fill`, both called with `args` and their outputs on the
+    device of the library tensor v: count, read the total back (the one synchronisation), fill"""
+    import torch
+    lib = _lib.load()
+    with _on_device_of(lib, v, stream) as cur, torch.cuda.stream(cur):
+        s = C.c_void_p(cur.cuda_stream)
+        offsets = torch.empty(rows + 1, dtype=torch.int64, device=v.device)
+        _check(getattr(lib, count)(*args, offsets.data_ptr(), s), count)
+        total = int(offsets[-1].item())
+        # one slot at least: an empty result still goes through the fill call, which then writes nothing
+        index = torch.empty(max(total, 1), dtype=torch.int32, device=v.device)
+        value = torch.empty(max(total, 1), dtype=torch.float32, device=v.device) if values else None
+        _check(getattr(lib, fill)(*args, offsets.data_ptr(), index.data_ptr(), value.data_ptr() if values else None, s),
+               fill)
+    return offsets, index[:total], value[:total] if values else None
+
+
+def radius(vecs, r, metric="distance"):
+    """The songs within radius r of every song of (n, 4) force vectors, as compressed sparse row lists:
+    (offsets int64 (n + 1,), index int32 (total,), value float32 (total,)); row i is index[offsets[i]:offsets[i + 1]],
+    in ascending song index, and never lists i.  Within means bl_distance <= r ("distance") or bl_cosine_similarity
+    >= r ("cosine") on the f32 matrix entry, whose bits `value` holds; a NaN entry is never within."""
+    v = np.ascontiguousarray(vecs, dtype=np.float32)
+    m, r = _radius_check(r, metric, v.shape)
+    n = v.shape[0]
+    return _radius_host_call("bl_amd_radius_host", (v.ctypes.data_as(C.POINTER(_lib.ForceVector)), n, m, r), n)
+
+
 def radius_device(d_vecs, r, metric="distance", row_begin=0, n_rows=None, values=True, stream=None):
     """radius() for the queries d_vecs[row_begin:row_begin + n_rows] against all of d_vecs, a contiguous float32
     (n, 4) CUDA tensor.  Returns (offsets int64 (n_rows + 1,), index int32 (total,), value float32 (total,) or None
     without `values`) as CUDA tensors on its device.  Count and fill run on `stream` (default: the current stream of
     that device); between them the total is read back, which is the one synchronisation."""
-    import torch
     m, r = _radius_check(r, metric, tuple(d_vecs.shape))
     _device_vecs_check(d_vecs)
     n = d_vecs.shape[0]
     n_rows = _rows_check(n, row_begin, n_rows)
-    lib = _lib.load()
-    v = d_vecs
-    with _on_device_of(lib, v, stream) as cur, torch.cuda.stream(cur):
-        s = C.c_void_p(cur.cuda_stream)
-        offsets = torch.empty(n_rows + 1, dtype=torch.int64, device=v.device)
-        _check(lib.bl_amd_radius_count_device(v.data_ptr(), n, int(row_begin), int(n_rows), m, r, offsets.data_ptr(), s),
-               "bl_amd_radius_count_device")
-        total = int(offsets[-1].item())
-        # one slot at least: an empty result still goes through the fill call, which then writes nothing
-        index = torch.empty(max(total, 1), dtype=torch.int32, device=v.device)
-        value = torch.empty(max(total, 1), dtype=torch.float32, device=v.device) if values else None
-        _check(lib.bl_amd_radius_fill_device(v.data_ptr(), n, int(row_begin), int(n_rows), m, r, offsets.data_ptr(),
-                                             index.data_ptr(), value.data_ptr() if values else None, s),
-               "bl_amd_radius_fill_device")
-    return offsets, index[:total], value[:total] if values else None
+    return _radius_device_call("bl_amd_radius_count_device", "bl_amd_radius_fill_device",
+                               (d_vecs.data_ptr(), n, int(row_begin), int(n_rows), m, r), d_vecs, n_rows, values, stream)
 
 
 def duplicate_groups(vecs, r, metric="distance"):
@@ -850,16 +867,10 @@ def knn_cross(queries, vecs, k, metric="distance"):
     out: a query equal to library song 7 lists song 7 first, at distance 0.  Slots past n hold -1 and NaN."""
     m_code = _knn_check(k, metric, (1, 4))   # the shapes are checked per side below
     q, v = _cross_host_vecs(queries, vecs)
-    lib = _lib.load()
     m = q.shape[0]
-    index = np.empty((m, k), dtype=np.int32)
-    value = np.empty((m, k), dtype=np.float32)
     fv = C.POINTER(_lib.ForceVector)
-    rc = lib.bl_amd_cross_knn_host(q.ctypes.data_as(fv), m, v.ctypes.data_as(fv), v.shape[0], int(k), m_code,
-                                   index.ctypes.data_as(C.POINTER(C.c_int32)),
-                                   value.ctypes.data_as(C.POINTER(C.c_float)))
-    _check(rc, "bl_amd_cross_knn_host")
-    return index, value
+    return _knn_host_call("bl_amd_cross_knn_host",
+                          (q.ctypes.data_as(fv), m, v.ctypes.data_as(fv), v.shape[0], int(k), m_code), m, k)
 
 
 def knn_cross_device(d_queries, d_vecs, k, metric="distance", stream=None):
@@ -867,19 +878,12 @@ def knn_cross_device(d_queries, d_vecs, k, metric="distance", stream=None):
     d_queries may be a view into d_vecs and needs 16-byte alignment only.  Returns (index, value) CUDA tensors of
     shape (m, k), asynchronously on `stream` (default: the current stream of that device).  Queries are independent:
     shard by slicing d_queries."""
-    import torch
     m_code = _knn_check(k, metric, (1, 4))
     _cross_device_check(d_queries, d_vecs)
-    lib = _lib.load()
     q, v = d_queries, d_vecs
     m = q.shape[0]
-    index = torch.empty((m, k), dtype=torch.int32, device=v.device)
-    value = torch.empty((m, k), dtype=torch.float32, device=v.device)
-    with _on_device_of(lib, v, stream) as cur:
-        _check(lib.bl_amd_cross_knn_device(q.data_ptr(), m, v.data_ptr(), v.shape[0], int(k), m_code,
-                                           index.data_ptr(), value.data_ptr(), C.c_void_p(cur.cuda_stream)),
-               "bl_amd_cross_knn_device")
-    return index, value
+    return _knn_device_call("bl_amd_cross_knn_device", (q.data_ptr(), m, v.data_ptr(), v.shape[0], int(k), m_code), v, m,
+                            k, stream)
 
 
 def _radius_cross_check(r, metric):
@@ -892,46 +896,22 @@ def radius_cross(queries, vecs, r, metric="distance"):
     orders a row.  Unlike radius() nothing is left out: with r = 0 a query that is in the library finds its copy."""
     m_code, r = _radius_cross_check(r, metric)
     q, v = _cross_host_vecs(queries, vecs)
-    lib = _lib.load()
     m = q.shape[0]
-    offsets = np.empty(m + 1, dtype=np.int64)
-    p_index, p_value = C.POINTER(C.c_int32)(), C.POINTER(C.c_float)()
     fv = C.POINTER(_lib.ForceVector)
-    rc = lib.bl_amd_cross_radius_host(q.ctypes.data_as(fv), m, v.ctypes.data_as(fv), v.shape[0], m_code, r,
-                                      offsets.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(p_index), C.byref(p_value))
-    _check(rc, "bl_amd_cross_radius_host")
-    try:
-        total = int(offsets[m])
-        index = np.ctypeslib.as_array(p_index, shape=(total,)).copy() if total else np.empty(0, dtype=np.int32)
-        value = np.ctypeslib.as_array(p_value, shape=(total,)).copy() if total else np.empty(0, dtype=np.float32)
-    finally:
-        _libc_free(p_index)
-        _libc_free(p_value)
-    return offsets, index, value
+    return _radius_host_call("bl_amd_cross_radius_host",
+                             (q.ctypes.data_as(fv), m, v.ctypes.data_as(fv), v.shape[0], m_code, r), m)
 
 
 def radius_cross_device(d_queries, d_vecs, r, metric="distance", values=True, stream=None):
     """radius_cross() on the device, tensors as for knn_cross_device().  Returns (offset int64 (m + 1,), index int32
     (total,), value float32 (total,) or None without `values`) as CUDA tensors.  Count and fill run on `stream`;
     between them the total is read back, which is the one synchronisation."""
-    import torch
     m_code, r = _radius_cross_check(r, metric)
     _cross_device_check(d_queries, d_vecs)
-    lib = _lib.load()
     q, v = d_queries, d_vecs
     m, n = q.shape[0], v.shape[0]
-    with _on_device_of(lib, v, stream) as cur, torch.cuda.stream(cur):
-        s = C.c_void_p(cur.cuda_stream)
-        offsets = torch.empty(m + 1, dtype=torch.int64, device=v.device)
-        _check(lib.bl_amd_cross_radius_count_device(q.data_ptr(), m, v.data_ptr(), n, m_code, r, offsets.data_ptr(), s),
-               "bl_amd_cross_radius_count_device")
-        total = int(offsets[-1].item())
-        index = torch.empty(max(total, 1), dtype=torch.int32, device=v.device)   # as in radius_device
-        value = torch.empty(max(total, 1), dtype=torch.float32, device=v.device) if values else None
-        _check(lib.bl_amd_cross_radius_fill_device(q.data_ptr(), m, v.data_ptr(), n, m_code, r, offsets.data_ptr(),
-                                                   index.data_ptr(), value.data_ptr() if values else None, s),
-               "bl_amd_cross_radius_fill_device")
-    return offsets, index[:total], value[:total] if values else None
+    return _radius_device_call("bl_amd_cross_radius_count_device", "bl_amd_cross_radius_fill_device",
+                               (q.data_ptr(), m, v.data_ptr(), n, m_code, r), v, m, values, stream)
 
 
 def playlist_vec(vecs, seed_vec):

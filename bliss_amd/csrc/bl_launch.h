@@ -4,8 +4,9 @@
  * bl_stats_kernels.hip, bl_freq_kernels.hip and bl_env_kernels.hip; bl_level_kernels.hip the signal
  * levels, bl_matrix_kernels.hip the pairwise matrix, bl_query_kernels.hip the vector queries,
  * bl_rs_kernels.hip the rate converter)
- * and the runtime (bl_runtime.hip: contexts, workspaces, streams, the C-ABI of
- * include/bliss_amd.h; bl_multi.hip: the multi-device corpus path).  Also BL_HIP_CHECK, which
+ * and the runtime (bl_runtime.hip: contexts, workspaces, streams, the analysis C-ABI of
+ * include/bliss_amd.h; bl_query_api.hip: its matrix, playlist and vector-query C-ABI; bl_multi.hip: the multi-device
+ * corpus path).  Also BL_HIP_CHECK, which
  * every .hip file uses.  C++ only, not installed.
  */
 #ifndef BL_LAUNCH_H_
@@ -209,17 +210,17 @@ int blk_query_configure_device(void);                  /* dynamic-LDS attributes
 /* Column split shared by the queries: waves of `qpw` query rows, splits of at least `min_cols` columns; *cols is a
  * multiple of 64 and *n_split the number of blockIdx.y slices.  Not static so that it can be checked on the host. */
 void blk_split_plan(int n, int n_rows, int n_cu, int qpw, int min_cols, int *n_split, int *cols);
-/* the k nearest songs of rows [row_begin, row_begin + n_rows) (bl_amd_knn_device); d_scratch: at least
- * blk_knn_scratch_bytes(n, n_rows, k, cosine, n_cu) bytes, 256-byte aligned */
-size_t blk_knn_scratch_bytes(int n, int n_rows, int k, bool cosine, int n_cu);
-int blk_knn(hipStream_t s, const struct force_vector_s *d_vecs, int n, int row_begin, int n_rows, int k,
-            bool cosine, int n_cu, void *d_scratch, int32_t *d_index, float *d_value);
-/* the k nearest of all n songs to each of d_queries[0 .. n_queries), vectors outside the library that may alias it
- * (bl_amd_cross_knn_device): no candidate is excluded.  The split plan is blk_split_plan(n, n_queries, ...). */
-size_t blk_knn_cross_scratch_bytes(int n, int n_queries, int k, bool cosine, int n_cu);
-int blk_knn_cross(hipStream_t s, const struct force_vector_s *d_queries, int n_queries,
-                  const struct force_vector_s *d_vecs, int n, int k, bool cosine, int n_cu, void *d_scratch,
-                  int32_t *d_index, float *d_value);
+/* kNN and radius take the query array beside the library.  d_queries == nullptr: the queries are rows
+ * [row_begin, row_begin + n_rows) of d_vecs, and a row is no candidate of its own (bl_amd_knn_device,
+ * bl_amd_radius_*_device).  Otherwise they are d_queries[0 .. n_rows), vectors of their own that may alias the library,
+ * row_begin must be 0 and no candidate is excluded (bl_amd_cross_*_device).  The split plan is
+ * blk_split_plan(n, n_rows, ...) either way.  Query scratch, 256-byte aligned, front to back: the library's cosine prep,
+ * the queries' own (cross and cosine only), then a column split's partial results.  The *_scratch_bytes functions
+ * take d_queries only to tell the two forms apart. */
+/* the k nearest songs of each query; d_scratch: at least blk_knn_scratch_bytes(d_queries, n, n_rows, k, cosine, n_cu) */
+size_t blk_knn_scratch_bytes(const struct force_vector_s *d_queries, int n, int n_rows, int k, bool cosine, int n_cu);
+int blk_knn(hipStream_t s, const struct force_vector_s *d_queries, const struct force_vector_s *d_vecs, int n,
+            int row_begin, int n_rows, int k, bool cosine, int n_cu, void *d_scratch, int32_t *d_index, float *d_value);
 /* song-to-song chains (bl_amd_chain_device).  blk_chain_shape: 1 = one workgroup per chain, 2 = column split with one
  * launch per step; force: 0 = the launch layer's rule, 1 / 2 = that shape.  d_scratch: at least
  * blk_chain_scratch_bytes(...) bytes for the same (n, n_chains, cosine, n_cu, force), 256-byte aligned; it is
@@ -234,23 +235,17 @@ size_t blk_mix_scratch_bytes(int n, int n_chains, bool cosine, int n_cu, int for
 int blk_mix(hipStream_t s, const struct force_vector_s *d_vecs, int n, const int32_t *d_seeds,
             const struct force_vector_s *d_seed_vecs, int n_chains, int length, bool cosine, const int32_t *d_tags,
             int gap, const uint8_t *d_exclude, int n_cu, int force, void *d_scratch, int32_t *d_order, float *d_value);
-/* the songs within a radius of rows [row_begin, row_begin + n_rows) (bl_amd_radius_*_device).  bound: the largest
- * squared sum whose correctly rounded root is <= the radius (distance) or the radius itself (cosine).  d_scratch: at
- * least blk_radius_scratch_bytes(n, n_rows, cosine, n_cu) bytes, 256-byte aligned; count and fill both rewrite it, and
- * fill needs nothing of what count left there.  d_offset: n_rows + 1 entries. */
-size_t blk_radius_scratch_bytes(int n, int n_rows, bool cosine, int n_cu);
-int blk_radius_count(hipStream_t s, const struct force_vector_s *d_vecs, int n, int row_begin, int n_rows, bool cosine,
-                     float bound, int n_cu, void *d_scratch, long long *d_offset);
-int blk_radius_fill(hipStream_t s, const struct force_vector_s *d_vecs, int n, int row_begin, int n_rows, bool cosine,
-                    float bound, int n_cu, void *d_scratch, const long long *d_offset, int32_t *d_index, float *d_value);
-/* the same for d_queries[0 .. n_queries) outside the library (bl_amd_cross_radius_*_device); d_offset: n_queries + 1 */
-size_t blk_radius_cross_scratch_bytes(int n, int n_queries, bool cosine, int n_cu);
-int blk_radius_cross_count(hipStream_t s, const struct force_vector_s *d_queries, int n_queries,
-                           const struct force_vector_s *d_vecs, int n, bool cosine, float bound, int n_cu,
-                           void *d_scratch, long long *d_offset);
-int blk_radius_cross_fill(hipStream_t s, const struct force_vector_s *d_queries, int n_queries,
-                          const struct force_vector_s *d_vecs, int n, bool cosine, float bound, int n_cu, void *d_scratch,
-                          const long long *d_offset, int32_t *d_index, float *d_value);
+/* the songs within a radius of each query.  bound: the largest squared sum whose correctly rounded root is <= the
+ * radius (distance) or the radius itself (cosine).  d_scratch: at least blk_radius_scratch_bytes(d_queries, n, n_rows,
+ * cosine, n_cu) bytes; count and fill both rewrite it, and fill needs nothing of what count left there.  d_offset:
+ * n_rows + 1 entries. */
+size_t blk_radius_scratch_bytes(const struct force_vector_s *d_queries, int n, int n_rows, bool cosine, int n_cu);
+int blk_radius_count(hipStream_t s, const struct force_vector_s *d_queries, const struct force_vector_s *d_vecs, int n,
+                     int row_begin, int n_rows, bool cosine, float bound, int n_cu, void *d_scratch,
+                     long long *d_offset);
+int blk_radius_fill(hipStream_t s, const struct force_vector_s *d_queries, const struct force_vector_s *d_vecs, int n,
+                    int row_begin, int n_rows, bool cosine, float bound, int n_cu, void *d_scratch,
+                    const long long *d_offset, int32_t *d_index, float *d_value);
 /* duplicate groups (bl_amd_groups_device): d_group[i] = the smallest index of i's component; d_scratch: the cosine prep */
 size_t blk_groups_scratch_bytes(int n, bool cosine);
 int blk_groups(hipStream_t s, const struct force_vector_s *d_vecs, int n, bool cosine, float bound, int n_cu,

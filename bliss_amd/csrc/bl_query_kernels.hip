@@ -1137,83 +1137,74 @@ static double2 *launch_prep(hipStream_t s, const float4 *v, int n, bool cosine, 
   return prep;
 }
 
-/* A cross query (q != nullptr: n_q vectors outside the library) keeps the queries' prep behind the library's; the
- * self forms have q == nullptr and the library's prep is the queries' too.  Fills what the cosine needs and returns
- * where the rest of the scratch begins. */
+/* The two sides of a query.  The queries are q[row_begin .. row_begin + n_rows).  A cross query (d_queries != nullptr:
+ * n_q vectors outside the library, row_begin = 0) keeps the queries' prep behind the library's.  The self forms have
+ * d_queries == nullptr: q is v, the library as its own query array, and qprep is prep; the kernels only read through
+ * either name, so the same array under two __restrict__ pointers is as sound as a cross call whose queries alias the
+ * library.  `cross` picks the kernels' CROSS instantiation and is derived here, nowhere else. */
 struct query_preps {
+  const float4 *q;
   const double2 *prep, *qprep;
   char *rest;
+  bool cross;
 };
 
-static size_t cross_prep_bytes(const float4 *q, int n_q, bool cosine) { return q ? prep_bytes(n_q, cosine) : 0; }
+static size_t cross_prep_bytes(const void *d_queries, int n_q, bool cosine) {
+  return d_queries ? prep_bytes(n_q, cosine) : 0;
+}
 
-static query_preps launch_preps(hipStream_t s, const float4 *q, int n_q, const float4 *v, int n, bool cosine,
-                                void *d_scratch) {
+/* fills what the cosine needs and returns where the rest of the scratch begins */
+static query_preps launch_preps(hipStream_t s, const struct force_vector_s *d_queries, int n_q, const float4 *v, int n,
+                                bool cosine, void *d_scratch) {
   query_preps p;
   char *base = static_cast<char *>(d_scratch);
+  p.cross = d_queries != nullptr;
+  p.q = p.cross ? reinterpret_cast<const float4 *>(d_queries) : v;
   p.prep = launch_prep(s, v, n, cosine, base);
-  p.qprep = q ? launch_prep(s, q, n_q, cosine, base + prep_bytes(n, cosine)) : p.prep;
-  p.rest = base + prep_bytes(n, cosine) + cross_prep_bytes(q, n_q, cosine);
+  p.qprep = p.cross ? launch_prep(s, p.q, n_q, cosine, base + prep_bytes(n, cosine)) : p.prep;
+  p.rest = base + prep_bytes(n, cosine) + cross_prep_bytes(d_queries, n_q, cosine);
   return p;
 }
 
-size_t blk_knn_scratch_bytes(int n, int n_rows, int k, bool cosine, int n_cu) {
+size_t blk_knn_scratch_bytes(const struct force_vector_s *d_queries, int n, int n_rows, int k, bool cosine, int n_cu) {
   int n_split, cols;
   blk_split_plan(n, n_rows, n_cu, KNN_QPW, KNN_SPLIT_MIN_COLS, &n_split, &cols);
   const size_t part = n_split > 1 ? sizeof(unsigned long long) * (size_t)n_rows * n_split * k : 0;
-  return prep_bytes(n, cosine) + part;
+  return prep_bytes(n, cosine) + cross_prep_bytes(d_queries, n_rows, cosine) + part;
 }
 
-size_t blk_knn_cross_scratch_bytes(int n, int n_queries, int k, bool cosine, int n_cu) {
-  return blk_knn_scratch_bytes(n, n_queries, k, cosine, n_cu) + prep_bytes(n_queries, cosine);
-}
-
-/* The queries are q[row_begin .. row_begin + n_rows).  CROSS = false: q is v, the library as its own query array, and
- * p.qprep is p.prep; the kernels only read through either name, so the same array under two __restrict__ pointers is
- * as sound as a cross call whose queries alias the library.  CROSS = true: vectors outside the library, row_begin = 0. */
-template <int KW, bool COSINE, bool CROSS>
-static void knn_launch(hipStream_t s, const float4 *q, const float4 *v, const query_preps &p, int n, int row_begin,
-                       int n_rows, int k, int n_split, int cols, unsigned long long *part, int32_t *d_index,
-                       float *d_value) {
+template <int KW, bool COSINE>
+static void knn_launch(hipStream_t s, const float4 *v, const query_preps &p, int n, int row_begin, int n_rows, int k,
+                       int n_split, int cols, unsigned long long *part, int32_t *d_index, float *d_value) {
   const int per_block = KNN_WAVES * KNN_QPW;
   const dim3 grid((n_rows + per_block - 1) / per_block, n_split), merge_grid((n_rows + KNN_WAVES - 1) / KNN_WAVES);
   const dim3 block(64 * KNN_WAVES);
-  hipLaunchKernelGGL((k_knn<KW, COSINE, CROSS>), grid, block, 0, s, q, p.qprep, v, p.prep, n, row_begin, n_rows, k, cols,
-                     n_split, part, d_index, d_value);
+  const auto knn = p.cross ? k_knn<KW, COSINE, true> : k_knn<KW, COSINE, false>;
+  const auto merge = p.cross ? k_knn_merge<KW, COSINE, true> : k_knn_merge<KW, COSINE, false>;
+  hipLaunchKernelGGL(knn, grid, block, 0, s, p.q, p.qprep, v, p.prep, n, row_begin, n_rows, k, cols, n_split, part,
+                     d_index, d_value);
   if (n_split > 1)
-    hipLaunchKernelGGL((k_knn_merge<KW, COSINE, CROSS>), merge_grid, block, 0, s, q, p.qprep, v, p.prep, row_begin,
-                       n_rows, k, n_split, part, d_index, d_value);
+    hipLaunchKernelGGL(merge, merge_grid, block, 0, s, p.q, p.qprep, v, p.prep, row_begin, n_rows, k, n_split, part,
+                       d_index, d_value);
 }
 
-template <bool CROSS>
-static int knn_run(hipStream_t s, const float4 *q, const float4 *v, int n, int row_begin, int n_rows, int k, bool cosine,
-                   int n_cu, void *d_scratch, int32_t *d_index, float *d_value) {
+int blk_knn(hipStream_t s, const struct force_vector_s *d_queries, const struct force_vector_s *d_vecs, int n,
+            int row_begin, int n_rows, int k, bool cosine, int n_cu, void *d_scratch, int32_t *d_index, float *d_value) {
+  if (d_queries && row_begin) return BL_UNEXPECTED;
+  const float4 *v = reinterpret_cast<const float4 *>(d_vecs);
   int n_split, cols;
   blk_split_plan(n, n_rows, n_cu, KNN_QPW, KNN_SPLIT_MIN_COLS, &n_split, &cols);
-  const query_preps p = launch_preps(s, CROSS ? q : nullptr, n_rows, v, n, cosine, d_scratch);
+  const query_preps p = launch_preps(s, d_queries, n_rows, v, n, cosine, d_scratch);
   unsigned long long *part = n_split > 1 ? reinterpret_cast<unsigned long long *>(p.rest) : nullptr;
   if (k > 64) {
-    if (cosine) knn_launch<2, true, CROSS>(s, q, v, p, n, row_begin, n_rows, k, n_split, cols, part, d_index, d_value);
-    else knn_launch<2, false, CROSS>(s, q, v, p, n, row_begin, n_rows, k, n_split, cols, part, d_index, d_value);
+    if (cosine) knn_launch<2, true>(s, v, p, n, row_begin, n_rows, k, n_split, cols, part, d_index, d_value);
+    else knn_launch<2, false>(s, v, p, n, row_begin, n_rows, k, n_split, cols, part, d_index, d_value);
   } else {
-    if (cosine) knn_launch<1, true, CROSS>(s, q, v, p, n, row_begin, n_rows, k, n_split, cols, part, d_index, d_value);
-    else knn_launch<1, false, CROSS>(s, q, v, p, n, row_begin, n_rows, k, n_split, cols, part, d_index, d_value);
+    if (cosine) knn_launch<1, true>(s, v, p, n, row_begin, n_rows, k, n_split, cols, part, d_index, d_value);
+    else knn_launch<1, false>(s, v, p, n, row_begin, n_rows, k, n_split, cols, part, d_index, d_value);
   }
   BL_HIP_CHECK(hipGetLastError());
   return BL_OK;
-}
-
-int blk_knn(hipStream_t s, const struct force_vector_s *d_vecs, int n, int row_begin, int n_rows, int k,
-            bool cosine, int n_cu, void *d_scratch, int32_t *d_index, float *d_value) {
-  const float4 *v = reinterpret_cast<const float4 *>(d_vecs);
-  return knn_run<false>(s, v, v, n, row_begin, n_rows, k, cosine, n_cu, d_scratch, d_index, d_value);
-}
-
-int blk_knn_cross(hipStream_t s, const struct force_vector_s *d_queries, int n_queries,
-                  const struct force_vector_s *d_vecs, int n, int k, bool cosine, int n_cu, void *d_scratch,
-                  int32_t *d_index, float *d_value) {
-  return knn_run<true>(s, reinterpret_cast<const float4 *>(d_queries), reinterpret_cast<const float4 *>(d_vecs), n, 0,
-                       n_queries, k, cosine, n_cu, d_scratch, d_index, d_value);
 }
 
 /* Shape of a chain call (see k_chain).  Column split (2) when the corpus is large enough for a step's scan by one
@@ -1358,15 +1349,12 @@ int blk_mix(hipStream_t s, const struct force_vector_s *d_vecs, int n, const int
   return BL_OK;
 }
 
-size_t blk_radius_scratch_bytes(int n, int n_rows, bool cosine, int n_cu) {
+size_t blk_radius_scratch_bytes(const struct force_vector_s *d_queries, int n, int n_rows, bool cosine, int n_cu) {
   int n_split, cols;
   blk_split_plan(n, n_rows, n_cu, RAD_QPW, RAD_SPLIT_MIN_COLS, &n_split, &cols);
   /* counts per (row, split), and with a column split the rows' sums behind them */
-  return prep_bytes(n, cosine) + sizeof(unsigned) * (size_t)n_rows * (n_split + (n_split > 1 ? 1 : 0));
-}
-
-size_t blk_radius_cross_scratch_bytes(int n, int n_queries, bool cosine, int n_cu) {
-  return blk_radius_scratch_bytes(n, n_queries, cosine, n_cu) + prep_bytes(n_queries, cosine);
+  return prep_bytes(n, cosine) + cross_prep_bytes(d_queries, n_rows, cosine) +
+         sizeof(unsigned) * (size_t)n_rows * (n_split + (n_split > 1 ? 1 : 0));
 }
 
 static dim3 radius_grid(int n_rows, int n_split) {
@@ -1374,24 +1362,27 @@ static dim3 radius_grid(int n_rows, int n_split) {
   return dim3((n_rows + per_block - 1) / per_block, n_split);
 }
 
-/* the per-(row, split) counts into p.rest, which is returned; q and CROSS as in knn_launch */
-template <bool COSINE, bool CROSS>
-static unsigned *radius_count_launch(hipStream_t s, const float4 *q, const float4 *v, const query_preps &p, int n,
-                                     int row_begin, int n_rows, float bound, int n_split, int cols) {
+/* the per-(row, split) counts into p.rest, which is returned */
+template <bool COSINE>
+static unsigned *radius_count_launch(hipStream_t s, const float4 *v, const query_preps &p, int n, int row_begin,
+                                     int n_rows, float bound, int n_split, int cols) {
   unsigned *part = reinterpret_cast<unsigned *>(p.rest);
-  hipLaunchKernelGGL((k_radius_count<COSINE, CROSS>), radius_grid(n_rows, n_split), dim3(64 * RAD_WAVES), 0, s, q,
-                     p.qprep, v, p.prep, n, row_begin, n_rows, cols, n_split, bound, part);
+  const auto count = p.cross ? k_radius_count<COSINE, true> : k_radius_count<COSINE, false>;
+  hipLaunchKernelGGL(count, radius_grid(n_rows, n_split), dim3(64 * RAD_WAVES), 0, s, p.q, p.qprep, v, p.prep, n,
+                     row_begin, n_rows, cols, n_split, bound, part);
   return part;
 }
 
-template <bool CROSS>
-static int radius_count_run(hipStream_t s, const float4 *q, const float4 *v, int n, int row_begin, int n_rows,
-                            bool cosine, float bound, int n_cu, void *d_scratch, long long *d_offset) {
+int blk_radius_count(hipStream_t s, const struct force_vector_s *d_queries, const struct force_vector_s *d_vecs, int n,
+                     int row_begin, int n_rows, bool cosine, float bound, int n_cu, void *d_scratch,
+                     long long *d_offset) {
+  if (d_queries && row_begin) return BL_UNEXPECTED;
+  const float4 *v = reinterpret_cast<const float4 *>(d_vecs);
   int n_split, cols;
   blk_split_plan(n, n_rows, n_cu, RAD_QPW, RAD_SPLIT_MIN_COLS, &n_split, &cols);
-  const query_preps p = launch_preps(s, CROSS ? q : nullptr, n_rows, v, n, cosine, d_scratch);
-  unsigned *part = cosine ? radius_count_launch<true, CROSS>(s, q, v, p, n, row_begin, n_rows, bound, n_split, cols)
-                          : radius_count_launch<false, CROSS>(s, q, v, p, n, row_begin, n_rows, bound, n_split, cols);
+  const query_preps p = launch_preps(s, d_queries, n_rows, v, n, cosine, d_scratch);
+  unsigned *part = cosine ? radius_count_launch<true>(s, v, p, n, row_begin, n_rows, bound, n_split, cols)
+                          : radius_count_launch<false>(s, v, p, n, row_begin, n_rows, bound, n_split, cols);
   const unsigned *counts = part;
   if (n_split > 1) {
     unsigned *rowsum = part + (size_t)n_rows * n_split;
@@ -1403,60 +1394,36 @@ static int radius_count_run(hipStream_t s, const float4 *q, const float4 *v, int
   return BL_OK;
 }
 
-int blk_radius_count(hipStream_t s, const struct force_vector_s *d_vecs, int n, int row_begin, int n_rows, bool cosine,
-                     float bound, int n_cu, void *d_scratch, long long *d_offset) {
-  const float4 *v = reinterpret_cast<const float4 *>(d_vecs);
-  return radius_count_run<false>(s, v, v, n, row_begin, n_rows, cosine, bound, n_cu, d_scratch, d_offset);
-}
-
-int blk_radius_cross_count(hipStream_t s, const struct force_vector_s *d_queries, int n_queries,
-                           const struct force_vector_s *d_vecs, int n, bool cosine, float bound, int n_cu,
-                           void *d_scratch, long long *d_offset) {
-  return radius_count_run<true>(s, reinterpret_cast<const float4 *>(d_queries),
-                                reinterpret_cast<const float4 *>(d_vecs), n, 0, n_queries, cosine, bound, n_cu, d_scratch,
-                                d_offset);
-}
-
 /* One split: a row's list starts at its offset, nothing else is needed.  Column split: the per-split counts are
  * computed again here (the scratch may have served another call since the count), so fill depends on nothing but
  * its arguments. */
-template <bool COSINE, bool CROSS>
-static void radius_fill_run(hipStream_t s, const float4 *q, const float4 *v, int n, int row_begin, int n_rows,
-                            float bound, int n_cu, void *d_scratch, const long long *d_offset, int32_t *d_index,
-                            float *d_value) {
+template <bool COSINE>
+static void radius_fill_run(hipStream_t s, const struct force_vector_s *d_queries, const float4 *v, int n, int row_begin,
+                            int n_rows, float bound, int n_cu, void *d_scratch, const long long *d_offset,
+                            int32_t *d_index, float *d_value) {
   int n_split, cols;
   blk_split_plan(n, n_rows, n_cu, RAD_QPW, RAD_SPLIT_MIN_COLS, &n_split, &cols);
-  const query_preps p = launch_preps(s, CROSS ? q : nullptr, n_rows, v, n, COSINE, d_scratch);
+  const query_preps p = launch_preps(s, d_queries, n_rows, v, n, COSINE, d_scratch);
   unsigned *before = nullptr;
   if (n_split > 1) {
-    before = radius_count_launch<COSINE, CROSS>(s, q, v, p, n, row_begin, n_rows, bound, n_split, cols);
+    before = radius_count_launch<COSINE>(s, v, p, n, row_begin, n_rows, bound, n_split, cols);
     hipLaunchKernelGGL(k_radius_split_scan, dim3((n_rows + 3) / 4), dim3(256), 0, s, before, n_rows, n_split,
                        before + (size_t)n_rows * n_split);
   }
   const dim3 grid = radius_grid(n_rows, n_split), block(64 * RAD_WAVES);
-  if (d_value)
-    hipLaunchKernelGGL((k_radius_fill<COSINE, true, CROSS>), grid, block, 0, s, q, p.qprep, v, p.prep, n, row_begin,
-                       n_rows, cols, n_split, bound, before, d_offset, d_index, d_value);
-  else
-    hipLaunchKernelGGL((k_radius_fill<COSINE, false, CROSS>), grid, block, 0, s, q, p.qprep, v, p.prep, n, row_begin,
-                       n_rows, cols, n_split, bound, before, d_offset, d_index, d_value);
+  const auto fill = d_value ? (p.cross ? k_radius_fill<COSINE, true, true> : k_radius_fill<COSINE, true, false>)
+                            : (p.cross ? k_radius_fill<COSINE, false, true> : k_radius_fill<COSINE, false, false>);
+  hipLaunchKernelGGL(fill, grid, block, 0, s, p.q, p.qprep, v, p.prep, n, row_begin, n_rows, cols, n_split, bound, before,
+                     d_offset, d_index, d_value);
 }
 
-int blk_radius_fill(hipStream_t s, const struct force_vector_s *d_vecs, int n, int row_begin, int n_rows, bool cosine,
-                    float bound, int n_cu, void *d_scratch, const long long *d_offset, int32_t *d_index, float *d_value) {
+int blk_radius_fill(hipStream_t s, const struct force_vector_s *d_queries, const struct force_vector_s *d_vecs, int n,
+                    int row_begin, int n_rows, bool cosine, float bound, int n_cu, void *d_scratch,
+                    const long long *d_offset, int32_t *d_index, float *d_value) {
+  if (d_queries && row_begin) return BL_UNEXPECTED;
   const float4 *v = reinterpret_cast<const float4 *>(d_vecs);
-  if (cosine) radius_fill_run<true, false>(s, v, v, n, row_begin, n_rows, bound, n_cu, d_scratch, d_offset, d_index, d_value);
-  else radius_fill_run<false, false>(s, v, v, n, row_begin, n_rows, bound, n_cu, d_scratch, d_offset, d_index, d_value);
-  BL_HIP_CHECK(hipGetLastError());
-  return BL_OK;
-}
-
-int blk_radius_cross_fill(hipStream_t s, const struct force_vector_s *d_queries, int n_queries,
-                          const struct force_vector_s *d_vecs, int n, bool cosine, float bound, int n_cu, void *d_scratch,
-                          const long long *d_offset, int32_t *d_index, float *d_value) {
-  const float4 *q = reinterpret_cast<const float4 *>(d_queries), *v = reinterpret_cast<const float4 *>(d_vecs);
-  if (cosine) radius_fill_run<true, true>(s, q, v, n, 0, n_queries, bound, n_cu, d_scratch, d_offset, d_index, d_value);
-  else radius_fill_run<false, true>(s, q, v, n, 0, n_queries, bound, n_cu, d_scratch, d_offset, d_index, d_value);
+  if (cosine) radius_fill_run<true>(s, d_queries, v, n, row_begin, n_rows, bound, n_cu, d_scratch, d_offset, d_index, d_value);
+  else radius_fill_run<false>(s, d_queries, v, n, row_begin, n_rows, bound, n_cu, d_scratch, d_offset, d_index, d_value);
   BL_HIP_CHECK(hipGetLastError());
   return BL_OK;
 }

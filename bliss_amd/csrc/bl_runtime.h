@@ -1,6 +1,7 @@
 /*
  * bl_runtime.h — internal: the per-device context behind include/bliss_amd.h, shared by
- * bl_runtime.hip (single-device C-ABI) and bl_multi.hip (multi-device corpus path).
+ * bl_runtime.hip (contexts and the single-device analysis C-ABI), bl_query_api.hip (the matrix, playlist and
+ * vector-query C-ABI) and bl_multi.hip (multi-device corpus path).
  * C++ only, not installed.
  */
 #ifndef BL_RUNTIME_H_
@@ -96,5 +97,68 @@ int blr_analyze_device(bl_amd_ctx *c, const int16_t *d_pcm, const bl_amd_song_de
 int blr_analyze_host(bl_amd_ctx *c, const void *const *h_pcm, int pcm_is_s32, const int32_t *n_samples,
                      const int32_t *channels, const uint64_t *duration, int n_songs, int in_rate,
                      bl_amd_song_result *h_results, bl_amd_song_result **d_res_out);
+
+/* makes the context's device current for the duration of a call and puts the caller's back:
+ * the current device is per-thread state shared with whoever else uses HIP in this thread
+ * (torch, the caller's own code) */
+struct DevGuard {
+  int prev = -1;
+  bool changed = false;
+  bool ok = true;
+  explicit DevGuard(int dev) {
+    if (hipGetDevice(&prev) != hipSuccess) { prev = -1; (void)hipGetLastError(); }
+    if (prev != dev) {
+      ok = hipSetDevice(dev) == hipSuccess;
+      changed = ok && prev >= 0;
+    }
+  }
+  ~DevGuard() {
+    if (changed) (void)hipSetDevice(prev);
+  }
+};
+
+/* a device block of the *_host entry points, freed when the call returns; zero bytes: no block, p stays nullptr.
+ * Every step answers "did it work", so a call is one && chain and any failure is BL_UNEXPECTED. */
+struct DevMem {
+  void *p = nullptr;
+  size_t bytes;
+  explicit DevMem(size_t n) : bytes(n) {
+    if (n && hipMalloc(&p, n) != hipSuccess) p = nullptr;
+  }
+  ~DevMem() {
+    if (p) (void)hipFree(p);
+  }
+  DevMem(const DevMem &) = delete;
+  DevMem &operator=(const DevMem &) = delete;
+  bool ok() const { return p || !bytes; }
+  bool up(const void *h) const { return p && hipMemcpy(p, h, bytes, hipMemcpyHostToDevice) == hipSuccess; }
+  bool down(void *h, size_t n) const { return ok() && hipMemcpy(h, p, n, hipMemcpyDeviceToHost) == hipSuccess; }
+  bool down(void *h) const { return down(h, bytes); }
+  template <class T> T *as() const { return static_cast<T *>(p); }
+};
+
+/* the metric and the row range of a vector query (bl_amd_knn_*, bl_amd_chain_*, bl_amd_radius_*, bl_amd_groups_*) */
+inline bool metric_ok(int metric) { return metric == BL_AMD_KNN_DISTANCE || metric == BL_AMD_KNN_COSINE; }
+inline bool rows_ok(int n, int row_begin, int n_rows) {
+  return row_begin >= 0 && n_rows > 0 && row_begin < n && n_rows <= n - row_begin;
+}
+
+/* one query on context c: `launch(stream, scratch)` runs with the context locked, its device current, the workspace's
+ * last user waited for on `stream` and `buf` grown to `bytes`; then the stream's position becomes the hand-over point */
+template <class Launch>
+int query_call(bl_amd_ctx *c, void *stream, bl_buf &buf, size_t bytes, Launch launch) {
+  std::lock_guard<std::mutex> lk(c->mu);
+  DevGuard dg(c->device);
+  if (!dg.ok) return BL_UNEXPECTED;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (c->ws_used) BL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_ws, 0));
+  if (blr_ensure(buf, bytes) != BL_OK || launch(s, buf.p) != BL_OK) return BL_UNEXPECTED;
+  BL_HIP_CHECK(hipEventRecord(c->ev_ws, s));
+  c->ws_used = true;
+  return BL_OK;
+}
+
+/* the profiling callback of the launchers (blk_mark_fn); user: the context */
+void mark_cb(void *user, int k, hipStream_t s, int begin);
 
 #endif /* BL_RUNTIME_H_ */

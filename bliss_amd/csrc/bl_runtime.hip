@@ -1,6 +1,6 @@
 /*
  * bl_runtime.hip — contexts, workspaces, streams and the single-device C-ABI of
- * include/bliss_amd.h.  Host code only (compiled by hipcc for the HIP runtime API); every
+ * include/bliss_amd.h, but for the matrix, playlists and vector queries (bl_query_api.hip).  Host code only (compiled by hipcc for the HIP runtime API); every
  * kernel lives in a bl_*kernels.hip file and is reached through the launchers of bl_launch.h.
  *
  * Contexts.  A bl_amd_ctx owns one device's scratch workspace, internal streams and pinned
@@ -15,8 +15,6 @@
  * 32 768 songs follow each other on the stream, and the shared workspace is handed from one
  * batch to the next by an event, not by a host synchronisation.
  */
-#include <float.h>
-#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -38,70 +36,10 @@ std::atomic<int> g_process_device{-1};
 thread_local int tl_device = -1;
 std::atomic<int> g_host_mode{-1}; /* -1: from BL_AMD_HOST_MODE or staged */
 
-/* makes the context's device current for the duration of a call and puts the caller's back:
- * the current device is per-thread state shared with whoever else uses HIP in this thread
- * (torch, the caller's own code) */
-struct DevGuard {
-  int prev = -1;
-  bool changed = false;
-  bool ok = true;
-  explicit DevGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) { prev = -1; (void)hipGetLastError(); }
-    if (prev != dev) {
-      ok = hipSetDevice(dev) == hipSuccess;
-      changed = ok && prev >= 0;
-    }
-  }
-  ~DevGuard() {
-    if (changed) (void)hipSetDevice(prev);
-  }
-};
-
 void release_buf(bl_buf &b) {
   if (b.p) (void)hipFree(b.p);
   b.p = nullptr;
   b.cap = 0;
-}
-
-/* a device block of the *_host entry points, freed when the call returns; zero bytes: no block, p stays nullptr.
- * Every step answers "did it work", so a call is one && chain and any failure is BL_UNEXPECTED. */
-struct DevMem {
-  void *p = nullptr;
-  size_t bytes;
-  explicit DevMem(size_t n) : bytes(n) {
-    if (n && hipMalloc(&p, n) != hipSuccess) p = nullptr;
-  }
-  ~DevMem() {
-    if (p) (void)hipFree(p);
-  }
-  DevMem(const DevMem &) = delete;
-  DevMem &operator=(const DevMem &) = delete;
-  bool ok() const { return p || !bytes; }
-  bool up(const void *h) const { return p && hipMemcpy(p, h, bytes, hipMemcpyHostToDevice) == hipSuccess; }
-  bool down(void *h, size_t n) const { return ok() && hipMemcpy(h, p, n, hipMemcpyDeviceToHost) == hipSuccess; }
-  bool down(void *h) const { return down(h, bytes); }
-  template <class T> T *as() const { return static_cast<T *>(p); }
-};
-
-/* the metric and the row range of a vector query (bl_amd_knn_*, bl_amd_chain_*, bl_amd_radius_*, bl_amd_groups_*) */
-bool metric_ok(int metric) { return metric == BL_AMD_KNN_DISTANCE || metric == BL_AMD_KNN_COSINE; }
-bool rows_ok(int n, int row_begin, int n_rows) {
-  return row_begin >= 0 && n_rows > 0 && row_begin < n && n_rows <= n - row_begin;
-}
-
-/* one query on context c: `launch(stream, scratch)` runs with the context locked, its device current, the workspace's
- * last user waited for on `stream` and `buf` grown to `bytes`; then the stream's position becomes the hand-over point */
-template <class Launch>
-int query_call(bl_amd_ctx *c, void *stream, bl_buf &buf, size_t bytes, Launch launch) {
-  std::lock_guard<std::mutex> lk(c->mu);
-  DevGuard dg(c->device);
-  if (!dg.ok) return BL_UNEXPECTED;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (c->ws_used) BL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_ws, 0));
-  if (blr_ensure(buf, bytes) != BL_OK || launch(s, buf.p) != BL_OK) return BL_UNEXPECTED;
-  BL_HIP_CHECK(hipEventRecord(c->ev_ws, s));
-  c->ws_used = true;
-  return BL_OK;
 }
 
 int ctx_init(bl_amd_ctx *c, int device) {
@@ -210,25 +148,6 @@ int current_device(void) {
   return d >= 0 ? d : 0;
 }
 
-void mark_cb(void *user, int k, hipStream_t s, int begin) {
-  bl_amd_ctx *c = static_cast<bl_amd_ctx *>(user);
-  if (!c->prof) return;
-  if (begin) {
-    bl_amd_ctx::Ev e{k, nullptr, nullptr};
-    if (hipEventCreate(&e.a) != hipSuccess || hipEventCreate(&e.b) != hipSuccess) return;
-    (void)hipEventRecord(e.a, s);
-    c->open.push_back(e);
-  } else {
-    for (size_t i = c->open.size(); i-- > 0;)
-      if (c->open[i].k == k) {
-        (void)hipEventRecord(c->open[i].b, s);
-        c->events.push_back(c->open[i]);
-        c->open.erase(c->open.begin() + (long)i);
-        break;
-      }
-  }
-}
-
 /* pinned slot of at least `bytes`; blocks only when BL_PIN_SLOTS batches are still in flight */
 int ring_get(bl_amd_ctx *c, size_t bytes, bl_pin_slot **out) {
   bl_pin_slot &s = c->ring[c->ring_next];
@@ -297,6 +216,25 @@ void fill_group(const bl_amd_song_desc *desc, int n_songs, bl_dsong *out, long l
 }
 
 } // namespace
+
+void mark_cb(void *user, int k, hipStream_t s, int begin) {
+  bl_amd_ctx *c = static_cast<bl_amd_ctx *>(user);
+  if (!c->prof) return;
+  if (begin) {
+    bl_amd_ctx::Ev e{k, nullptr, nullptr};
+    if (hipEventCreate(&e.a) != hipSuccess || hipEventCreate(&e.b) != hipSuccess) return;
+    (void)hipEventRecord(e.a, s);
+    c->open.push_back(e);
+  } else {
+    for (size_t i = c->open.size(); i-- > 0;)
+      if (c->open[i].k == k) {
+        (void)hipEventRecord(c->open[i].b, s);
+        c->events.push_back(c->open[i]);
+        c->open.erase(c->open.begin() + (long)i);
+        break;
+      }
+  }
+}
 
 int blr_ensure(bl_buf &b, size_t bytes) {
   if (bytes <= b.cap) return BL_OK;
@@ -915,6 +853,7 @@ int bl_amd_synth_pcm_device(int16_t *d_pcm, const bl_amd_song_desc *h_desc, int 
   if (!c) return BL_UNEXPECTED;
   std::lock_guard<std::mutex> lk(c->mu);
   DevGuard dg(c->device);
+  if (!dg.ok) return BL_UNEXPECTED;
   hipStream_t s = static_cast<hipStream_t>(stream);
   for (int i = 0; i < n_songs; ++i)
     if (validate_desc(h_desc[i], i) != BL_OK) return BL_UNEXPECTED;
@@ -941,486 +880,6 @@ int bl_amd_synth_pcm_device(int16_t *d_pcm, const bl_amd_song_desc *h_desc, int 
   BL_HIP_CHECK(hipEventRecord(c->ev_ws, s));
   c->ws_used = true;
   return BL_OK;
-}
-
-static int matrix_device(const struct force_vector_s *d_vecs, int n, int row_begin, int n_rows,
-                         float *d_out, void *stream, bool cosine) {
-  if (n <= 0 || n_rows <= 0 || row_begin < 0 || row_begin + n_rows > n || !d_vecs || !d_out)
-    return BL_UNEXPECTED;
-  bl_amd_ctx *c = blr_default_ctx();
-  if (!c) return BL_UNEXPECTED;
-  std::lock_guard<std::mutex> lk(c->mu);
-  DevGuard dg(c->device);
-  return blk_pairwise(static_cast<hipStream_t>(stream), d_vecs, n, row_begin, n_rows, d_out, cosine,
-                      c->prof ? mark_cb : nullptr, c);
-}
-
-int bl_amd_distance_matrix_device(const struct force_vector_s *d_vecs, int n, int row_begin,
-                                  int n_rows, float *d_out, void *stream) {
-  return matrix_device(d_vecs, n, row_begin, n_rows, d_out, stream, false);
-}
-
-int bl_amd_cosine_matrix_device(const struct force_vector_s *d_vecs, int n, int row_begin,
-                                int n_rows, float *d_out, void *stream) {
-  return matrix_device(d_vecs, n, row_begin, n_rows, d_out, stream, true);
-}
-
-int bl_amd_playlist_device(const struct force_vector_s *d_vecs, int n, int seed_index,
-                           int32_t *d_order, float *d_dist, void *stream) {
-  if (n <= 0 || seed_index < 0 || seed_index >= n || !d_vecs || !d_order || !d_dist)
-    return BL_UNEXPECTED;
-  bl_amd_ctx *c = blr_default_ctx();
-  if (!c) return BL_UNEXPECTED;
-  DevGuard dg(c->device);
-  return blk_playlist(static_cast<hipStream_t>(stream), d_vecs, n, seed_index, d_order, d_dist);
-}
-
-int bl_amd_playlist_host(const struct force_vector_s *h_vecs, int n, int seed_index,
-                         int32_t *h_order, float *h_dist) {
-  if (n <= 0 || !h_vecs || !h_order) return BL_UNEXPECTED;
-  bl_amd_ctx *c = blr_default_ctx();
-  if (!c) return BL_UNEXPECTED;
-  DevGuard dg(c->device);
-  DevMem dv(sizeof(struct force_vector_s) * (size_t)n), dord(sizeof(int32_t) * (size_t)n), dd(sizeof(float) * (size_t)n);
-  return dv.up(h_vecs) && dord.ok() && dd.ok() &&
-                 bl_amd_playlist_device(dv.as<struct force_vector_s>(), n, seed_index, dord.as<int32_t>(), dd.as<float>(),
-                                        nullptr) == BL_OK &&
-                 dord.down(h_order) && (!h_dist || dd.down(h_dist))
-             ? BL_OK
-             : BL_UNEXPECTED;
-}
-
-int bl_amd_playlist_vec_device(const struct force_vector_s *d_vecs, int n, struct force_vector_s seed,
-                               int32_t *d_order, float *d_dist, void *stream) {
-  if (n <= 0 || !d_vecs || !d_order || !d_dist) return BL_UNEXPECTED;
-  bl_amd_ctx *c = blr_default_ctx();
-  if (!c) return BL_UNEXPECTED;
-  DevGuard dg(c->device);
-  return blk_playlist_vec(static_cast<hipStream_t>(stream), d_vecs, n, seed, d_order, d_dist);
-}
-
-int bl_amd_playlist_vec_host(const struct force_vector_s *h_vecs, int n, struct force_vector_s seed,
-                             int32_t *h_order, float *h_dist) {
-  if (n <= 0 || !h_vecs || !h_order) return BL_UNEXPECTED;
-  bl_amd_ctx *c = blr_default_ctx();
-  if (!c) return BL_UNEXPECTED;
-  DevGuard dg(c->device);
-  DevMem dv(sizeof(struct force_vector_s) * (size_t)n), dord(sizeof(int32_t) * (size_t)n), dd(sizeof(float) * (size_t)n);
-  return dv.up(h_vecs) && dord.ok() && dd.ok() &&
-                 bl_amd_playlist_vec_device(dv.as<struct force_vector_s>(), n, seed, dord.as<int32_t>(), dd.as<float>(),
-                                            nullptr) == BL_OK &&
-                 dord.down(h_order) && (!h_dist || dd.down(h_dist))
-             ? BL_OK
-             : BL_UNEXPECTED;
-}
-
-/* Vector queries (bl_query_kernels.hip): k nearest songs, song-to-song chains, radius lists, duplicate groups.  Every
- * argument is checked before any device work, so a rejected call leaves the outputs untouched, and the default-context
- * wrappers check before they fetch the context.  The scratch (cosine prep, a column split's partial results) is the
- * context's workspace, handed from call to call by ev_ws like the analysis workspace: nothing here waits for the
- * device. */
-static bool knn_args_ok(const void *vecs, int n, int row_begin, int n_rows, int k, int metric, const void *index,
-                        const void *value) {
-  return vecs && index && value && n > 0 && k >= 1 && k <= BL_AMD_KNN_MAX_K && metric_ok(metric) &&
-         rows_ok(n, row_begin, n_rows);
-}
-
-int bl_amd_knn_device(const struct force_vector_s *d_vecs, int n, int row_begin, int n_rows, int k, int metric,
-                      int32_t *d_index, float *d_value, void *stream) {
-  if (!knn_args_ok(d_vecs, n, row_begin, n_rows, k, metric, d_index, d_value)) return BL_UNEXPECTED;
-  bl_amd_ctx *c = blr_default_ctx();
-  if (!c) return BL_UNEXPECTED;
-  const bool cosine = metric == BL_AMD_KNN_COSINE;
-  return query_call(c, stream, c->knn, blk_knn_scratch_bytes(n, n_rows, k, cosine, c->n_cu),
-                    [&](hipStream_t s, void *scratch) {
-                      return blk_knn(s, d_vecs, n, row_begin, n_rows, k, cosine, c->n_cu, scratch, d_index, d_value);
-                    });
-}
-
-int bl_amd_knn_host(const struct force_vector_s *h_vecs, int n, int k, int metric, int32_t *h_index,
-                    float *h_value) {
-  if (!knn_args_ok(h_vecs, n, 0, n, k, metric, h_index, h_index /* h_value may be NULL */)) return BL_UNEXPECTED;
-  bl_amd_ctx *c = blr_default_ctx();
-  if (!c) return BL_UNEXPECTED;
-  DevGuard dg(c->device);
-  if (!dg.ok) return BL_UNEXPECTED;
-  const size_t out = (size_t)n * k;
-  DevMem dv(sizeof(struct force_vector_s) * (size_t)n), di(sizeof(int32_t) * out), dd(sizeof(float) * out);
-  return dv.up(h_vecs) && di.ok() && dd.ok() &&
-                 bl_amd_knn_device(dv.as<struct force_vector_s>(), n, 0, n, k, metric, di.as<int32_t>(), dd.as<float>(),
-                                   nullptr) == BL_OK &&
-                 di.down(h_index) && (!h_value || dd.down(h_value))
-             ? BL_OK
-             : BL_UNEXPECTED;
-}
-
-/* Cross forms: the queries are n_queries vectors of their own, and no candidate is excluded */
-static bool knn_cross_args_ok(const void *queries, int n_queries, const void *vecs, int n, int k, int metric,
-                              const void *index, const void *value) {
-  return queries && n_queries > 0 && knn_args_ok(vecs, n, 0, n, k, metric, index, value);
-}
-
-int bl_amd_cross_knn_device(const struct force_vector_s *d_queries, int n_queries, const struct force_vector_s *d_vecs,
-                            int n, int k, int metric, int32_t *d_index, float *d_value, void *stream) {
-  if (!knn_cross_args_ok(d_queries, n_queries, d_vecs, n, k, metric, d_index, d_value)) return BL_UNEXPECTED;
-  bl_amd_ctx *c = blr_default_ctx();
-  if (!c) return BL_UNEXPECTED;
-  const bool cosine = metric == BL_AMD_KNN_COSINE;
-  return query_call(c, stream, c->knn, blk_knn_cross_scratch_bytes(n, n_queries, k, cosine, c->n_cu),
-                    [&](hipStream_t s, void *scratch) {
-                      return blk_knn_cross(s, d_queries, n_queries, d_vecs, n, k, cosine, c->n_cu, scratch, d_index,
-                                           d_value);
-                    });
-}
-
-int bl_amd_cross_knn_host(const struct force_vector_s *h_queries, int n_queries, const struct force_vector_s *h_vecs,
-                          int n, int k, int metric, int32_t *h_index, float *h_value) {
-  if (!knn_cross_args_ok(h_queries, n_queries, h_vecs, n, k, metric, h_index, h_index /* h_value may be NULL */))
-    return BL_UNEXPECTED;
-  bl_amd_ctx *c = blr_default_ctx();
-  if (!c) return BL_UNEXPECTED;
-  DevGuard dg(c->device);
-  if (!dg.ok) return BL_UNEXPECTED;
-  const size_t out = (size_t)n_queries * k;
-  DevMem dq(sizeof(struct force_vector_s) * (size_t)n_queries), dv(sizeof(struct force_vector_s) * (size_t)n);
-  DevMem di(sizeof(int32_t) * out), dd(sizeof(float) * out);
-  return dq.up(h_queries) && dv.up(h_vecs) && di.ok() && dd.ok() &&
-                 bl_amd_cross_knn_device(dq.as<struct force_vector_s>(), n_queries, dv.as<struct force_vector_s>(), n, k,
-                                         metric, di.as<int32_t>(), dd.as<float>(), nullptr) == BL_OK &&
-                 di.down(h_index) && (!h_value || dd.down(h_value))
-             ? BL_OK
-             : BL_UNEXPECTED;
-}
-
-static std::atomic<int> g_chain_force{BL_AMD_CHAIN_AUTO};
-
-static bool chain_args_ok(const void *vecs, int n, const void *seeds, int n_chains, int length, int metric,
-                          const void *order, const void *value) {
-  return vecs && seeds && order && value && n > 0 && n_chains > 0 && length > 0 && metric_ok(metric);
-}
-
-int bl_amd_ctx_chain_device(bl_amd_ctx *c, const struct force_vector_s *d_vecs, int n, const int32_t *d_seeds,
-                            int n_chains, int length, int metric, int32_t *d_order, float *d_value, void *stream) {
-  if (!chain_args_ok(d_vecs, n, d_seeds, n_chains, length, metric, d_order, d_value) || !c) return BL_UNEXPECTED;
-  const bool cosine = metric == BL_AMD_KNN_COSINE;
-  const int force = g_chain_force.load();
-  return query_call(c, stream, c->chain, blk_chain_scratch_bytes(n, n_chains, cosine, c->n_cu, force),
-                    [&](hipStream_t s, void *scratch) {
-                      return blk_chain(s, d_vecs, n, d_seeds, n_chains, length, cosine, c->n_cu, force, scratch, d_order,
-                                       d_value);
-                    });
-}
-
-int bl_amd_chain_device(const struct force_vector_s *d_vecs, int n, const int32_t *d_seeds, int n_chains, int length,
-                        int metric, int32_t *d_order, float *d_value, void *stream) {
-  if (!chain_args_ok(d_vecs, n, d_seeds, n_chains, length, metric, d_order, d_value)) return BL_UNEXPECTED;
-  return bl_amd_ctx_chain_device(blr_default_ctx(), d_vecs, n, d_seeds, n_chains, length, metric, d_order, d_value,
-                                 stream);
-}
-
-int bl_amd_chain_host(const struct force_vector_s *h_vecs, int n, const int32_t *h_seeds, int n_chains, int length,
-                      int metric, int32_t *h_order, float *h_value) {
-  if (!chain_args_ok(h_vecs, n, h_seeds, n_chains, length, metric, h_order, h_order /* h_value may be NULL */))
-    return BL_UNEXPECTED;
-  for (int c = 0; c < n_chains; ++c)
-    if (h_seeds[c] < 0 || h_seeds[c] >= n) return BL_UNEXPECTED;
-  bl_amd_ctx *c = blr_default_ctx();
-  if (!c) return BL_UNEXPECTED;
-  DevGuard dg(c->device);
-  if (!dg.ok) return BL_UNEXPECTED;
-  const size_t out = (size_t)n_chains * length;
-  DevMem dv(sizeof(struct force_vector_s) * (size_t)n), ds(sizeof(int32_t) * (size_t)n_chains), di(sizeof(int32_t) * out), dd(sizeof(float) * out);
-  return dv.up(h_vecs) && ds.up(h_seeds) && di.ok() && dd.ok() &&
-                 bl_amd_chain_device(dv.as<struct force_vector_s>(), n, ds.as<int32_t>(), n_chains, length, metric,
-                                     di.as<int32_t>(), dd.as<float>(), nullptr) == BL_OK &&
-                 di.down(h_order) && (!h_value || dd.down(h_value))
-             ? BL_OK
-             : BL_UNEXPECTED;
-}
-
-/* Chains under rules: the chain's workspace, shape switch and call path */
-static bool mix_args_ok(const void *vecs, int n, const void *seeds, const void *seed_vecs, int n_chains, int length,
-                        int metric, const void *tags, int gap, const void *order, const void *value) {
-  return vecs && order && value && n > 0 && n_chains > 0 && length > 0 && metric_ok(metric) &&
-         (seeds != nullptr) != (seed_vecs != nullptr) && gap >= 0 && gap <= BL_AMD_MIX_MAX_GAP && (gap == 0 || tags);
-}
-
-int bl_amd_ctx_mix_device(bl_amd_ctx *c, const struct force_vector_s *d_vecs, int n, const int32_t *d_seeds,
-                          const struct force_vector_s *d_seed_vecs, int n_chains, int length, int metric,
-                          const int32_t *d_tags, int gap, const uint8_t *d_exclude, int32_t *d_order, float *d_value,
-                          void *stream) {
-  if (!mix_args_ok(d_vecs, n, d_seeds, d_seed_vecs, n_chains, length, metric, d_tags, gap, d_order, d_value) || !c)
-    return BL_UNEXPECTED;
-  const bool cosine = metric == BL_AMD_KNN_COSINE;
-  const int force = g_chain_force.load();
-  return query_call(c, stream, c->chain, blk_mix_scratch_bytes(n, n_chains, cosine, c->n_cu, force),
-                    [&](hipStream_t s, void *scratch) {
-                      return blk_mix(s, d_vecs, n, d_seeds, d_seed_vecs, n_chains, length, cosine, d_tags, gap, d_exclude,
-                                     c->n_cu, force, scratch, d_order, d_value);
-                    });
-}
-
-int bl_amd_mix_device(const struct force_vector_s *d_vecs, int n, const int32_t *d_seeds,
-                      const struct force_vector_s *d_seed_vecs, int n_chains, int length, int metric,
-                      const int32_t *d_tags, int gap, const uint8_t *d_exclude, int32_t *d_order, float *d_value,
-                      void *stream) {
-  if (!mix_args_ok(d_vecs, n, d_seeds, d_seed_vecs, n_chains, length, metric, d_tags, gap, d_order, d_value))
-    return BL_UNEXPECTED;
-  return bl_amd_ctx_mix_device(blr_default_ctx(), d_vecs, n, d_seeds, d_seed_vecs, n_chains, length, metric, d_tags, gap,
-                               d_exclude, d_order, d_value, stream);
-}
-
-int bl_amd_mix_host(const struct force_vector_s *h_vecs, int n, const int32_t *h_seeds,
-                    const struct force_vector_s *h_seed_vecs, int n_chains, int length, int metric,
-                    const int32_t *h_tags, int gap, const uint8_t *h_exclude, int32_t *h_order, float *h_value) {
-  if (!mix_args_ok(h_vecs, n, h_seeds, h_seed_vecs, n_chains, length, metric, h_tags, gap, h_order,
-                   h_order /* h_value may be NULL */))
-    return BL_UNEXPECTED;
-  for (int c = 0; h_seeds && c < n_chains; ++c)
-    if (h_seeds[c] < 0 || h_seeds[c] >= n) return BL_UNEXPECTED;
-  bl_amd_ctx *c = blr_default_ctx();
-  if (!c) return BL_UNEXPECTED;
-  DevGuard dg(c->device);
-  if (!dg.ok) return BL_UNEXPECTED;
-  const bool use_tags = gap > 0;
-  const size_t out = (size_t)n_chains * length;
-  DevMem dv(sizeof(struct force_vector_s) * (size_t)n), ds(h_seeds ? sizeof(int32_t) * (size_t)n_chains : 0);
-  DevMem dq(h_seed_vecs ? sizeof(struct force_vector_s) * (size_t)n_chains : 0);
-  DevMem dt(use_tags ? sizeof(int32_t) * (size_t)n : 0), dx(h_exclude ? (size_t)n : 0);
-  DevMem di(sizeof(int32_t) * out), dd(sizeof(float) * out);
-  return dv.up(h_vecs) && (!h_seeds || ds.up(h_seeds)) && (!h_seed_vecs || dq.up(h_seed_vecs)) &&
-                 (!use_tags || dt.up(h_tags)) && (!h_exclude || dx.up(h_exclude)) && di.ok() && dd.ok() &&
-                 bl_amd_mix_device(dv.as<struct force_vector_s>(), n, ds.as<int32_t>(), dq.as<struct force_vector_s>(),
-                                   n_chains, length, metric, dt.as<int32_t>(), gap, dx.as<uint8_t>(), di.as<int32_t>(),
-                                   dd.as<float>(), nullptr) == BL_OK &&
-                 di.down(h_order) && (!h_value || dd.down(h_value))
-             ? BL_OK
-             : BL_UNEXPECTED;
-}
-
-/* Radius queries and duplicate groups: the distance is compared on the squared sum against
- * bl_amd_radius_bound(radius), computed here once per call. */
-float bl_amd_radius_bound(float radius) {
-  if (radius != radius) return radius;
-  if (radius < 0.f) return -INFINITY;       /* no root is negative; -0 is not below 0 */
-  if (radius == INFINITY) return INFINITY;  /* an overflowed sum has the root +inf */
-  float s = radius * radius;
-  if (!(s <= FLT_MAX)) s = FLT_MAX;
-  while (s > 0.f && (float)sqrt((double)s) > radius) s = nextafterf(s, 0.f);
-  while (s < FLT_MAX) {
-    const float up = nextafterf(s, INFINITY);
-    if ((float)sqrt((double)up) > radius) break;
-    s = up;
-  }
-  return s;
-}
-
-static bool radius_args_ok(const void *vecs, int n, int row_begin, int n_rows, int metric, float radius,
-                           const void *out) {
-  return vecs && out && n > 0 && metric_ok(metric) && radius == radius && rows_ok(n, row_begin, n_rows);
-}
-
-static float radius_kernel_bound(int metric, float radius) {
-  return metric == BL_AMD_KNN_COSINE ? radius : bl_amd_radius_bound(radius);
-}
-
-int bl_amd_ctx_radius_count_device(bl_amd_ctx *c, const struct force_vector_s *d_vecs, int n, int row_begin, int n_rows,
-                                   int metric, float radius, int64_t *d_offset, void *stream) {
-  if (!radius_args_ok(d_vecs, n, row_begin, n_rows, metric, radius, d_offset) || !c) return BL_UNEXPECTED;
-  const bool cosine = metric == BL_AMD_KNN_COSINE;
-  return query_call(c, stream, c->radius, blk_radius_scratch_bytes(n, n_rows, cosine, c->n_cu),
-                    [&](hipStream_t s, void *scratch) {
-                      return blk_radius_count(s, d_vecs, n, row_begin, n_rows, cosine, radius_kernel_bound(metric, radius),
-                                              c->n_cu, scratch, reinterpret_cast<long long *>(d_offset));
-                    });
-}
-
-int bl_amd_radius_count_device(const struct force_vector_s *d_vecs, int n, int row_begin, int n_rows, int metric,
-                               float radius, int64_t *d_offset, void *stream) {
-  if (!radius_args_ok(d_vecs, n, row_begin, n_rows, metric, radius, d_offset)) return BL_UNEXPECTED;
-  return bl_amd_ctx_radius_count_device(blr_default_ctx(), d_vecs, n, row_begin, n_rows, metric, radius, d_offset,
-                                        stream);
-}
-
-int bl_amd_ctx_radius_fill_device(bl_amd_ctx *c, const struct force_vector_s *d_vecs, int n, int row_begin, int n_rows,
-                                  int metric, float radius, const int64_t *d_offset, int32_t *d_index, float *d_value,
-                                  void *stream) {
-  if (!radius_args_ok(d_vecs, n, row_begin, n_rows, metric, radius, d_offset) || !d_index || !c) return BL_UNEXPECTED;
-  const bool cosine = metric == BL_AMD_KNN_COSINE;
-  return query_call(c, stream, c->radius, blk_radius_scratch_bytes(n, n_rows, cosine, c->n_cu),
-                    [&](hipStream_t s, void *scratch) {
-                      return blk_radius_fill(s, d_vecs, n, row_begin, n_rows, cosine, radius_kernel_bound(metric, radius),
-                                             c->n_cu, scratch, reinterpret_cast<const long long *>(d_offset), d_index,
-                                             d_value);
-                    });
-}
-
-int bl_amd_radius_fill_device(const struct force_vector_s *d_vecs, int n, int row_begin, int n_rows, int metric,
-                              float radius, const int64_t *d_offset, int32_t *d_index, float *d_value, void *stream) {
-  if (!radius_args_ok(d_vecs, n, row_begin, n_rows, metric, radius, d_offset) || !d_index) return BL_UNEXPECTED;
-  return bl_amd_ctx_radius_fill_device(blr_default_ctx(), d_vecs, n, row_begin, n_rows, metric, radius, d_offset,
-                                       d_index, d_value, stream);
-}
-
-int bl_amd_radius_host(const struct force_vector_s *h_vecs, int n, int metric, float radius, int64_t *h_offset,
-                       int32_t **h_index, float **h_value) {
-  if (!radius_args_ok(h_vecs, n, 0, n, metric, radius, h_offset) || !h_index) return BL_UNEXPECTED;
-  bl_amd_ctx *c = blr_default_ctx();
-  if (!c) return BL_UNEXPECTED;
-  DevGuard dg(c->device);
-  if (!dg.ok) return BL_UNEXPECTED;
-  std::vector<int64_t> off((size_t)n + 1);
-  DevMem dv(sizeof(struct force_vector_s) * (size_t)n), doff(sizeof(int64_t) * off.size());
-  if (!(dv.up(h_vecs) && doff.ok() &&
-        bl_amd_radius_count_device(dv.as<struct force_vector_s>(), n, 0, n, metric, radius, doff.as<int64_t>(),
-                                   nullptr) == BL_OK &&
-        doff.down(off.data())))
-    return BL_UNEXPECTED;
-  const size_t total = (size_t)off[(size_t)n], slots = total ? total : 1; /* an empty result is still a free()-able block */
-  int32_t *hi = static_cast<int32_t *>(malloc(sizeof(int32_t) * slots));
-  float *hv = h_value ? static_cast<float *>(malloc(sizeof(float) * slots)) : nullptr;
-  DevMem di(sizeof(int32_t) * slots), dd(h_value ? sizeof(float) * slots : 0);
-  if (!(hi && (hv || !h_value) && di.ok() && dd.ok() &&
-        bl_amd_radius_fill_device(dv.as<struct force_vector_s>(), n, 0, n, metric, radius, doff.as<int64_t>(),
-                                  di.as<int32_t>(), dd.as<float>(), nullptr) == BL_OK &&
-        di.down(hi, sizeof(int32_t) * total) && (!h_value || dd.down(hv, sizeof(float) * total)))) {
-    free(hi);
-    free(hv);
-    return BL_UNEXPECTED;
-  }
-  memcpy(h_offset, off.data(), sizeof(int64_t) * off.size());
-  *h_index = hi;
-  if (h_value) *h_value = hv;
-  return BL_OK;
-}
-
-static bool radius_cross_args_ok(const void *queries, int n_queries, const void *vecs, int n, int metric, float radius,
-                                 const void *out) {
-  return queries && n_queries > 0 && radius_args_ok(vecs, n, 0, n, metric, radius, out);
-}
-
-int bl_amd_ctx_cross_radius_count_device(bl_amd_ctx *c, const struct force_vector_s *d_queries, int n_queries,
-                                         const struct force_vector_s *d_vecs, int n, int metric, float radius,
-                                         int64_t *d_offset, void *stream) {
-  if (!radius_cross_args_ok(d_queries, n_queries, d_vecs, n, metric, radius, d_offset) || !c) return BL_UNEXPECTED;
-  const bool cosine = metric == BL_AMD_KNN_COSINE;
-  return query_call(c, stream, c->radius, blk_radius_cross_scratch_bytes(n, n_queries, cosine, c->n_cu),
-                    [&](hipStream_t s, void *scratch) {
-                      return blk_radius_cross_count(s, d_queries, n_queries, d_vecs, n, cosine,
-                                                    radius_kernel_bound(metric, radius), c->n_cu, scratch,
-                                                    reinterpret_cast<long long *>(d_offset));
-                    });
-}
-
-int bl_amd_cross_radius_count_device(const struct force_vector_s *d_queries, int n_queries,
-                                     const struct force_vector_s *d_vecs, int n, int metric, float radius,
-                                     int64_t *d_offset, void *stream) {
-  if (!radius_cross_args_ok(d_queries, n_queries, d_vecs, n, metric, radius, d_offset)) return BL_UNEXPECTED;
-  return bl_amd_ctx_cross_radius_count_device(blr_default_ctx(), d_queries, n_queries, d_vecs, n, metric, radius,
-                                              d_offset, stream);
-}
-
-int bl_amd_ctx_cross_radius_fill_device(bl_amd_ctx *c, const struct force_vector_s *d_queries, int n_queries,
-                                        const struct force_vector_s *d_vecs, int n, int metric, float radius,
-                                        const int64_t *d_offset, int32_t *d_index, float *d_value, void *stream) {
-  if (!radius_cross_args_ok(d_queries, n_queries, d_vecs, n, metric, radius, d_offset) || !d_index || !c)
-    return BL_UNEXPECTED;
-  const bool cosine = metric == BL_AMD_KNN_COSINE;
-  return query_call(c, stream, c->radius, blk_radius_cross_scratch_bytes(n, n_queries, cosine, c->n_cu),
-                    [&](hipStream_t s, void *scratch) {
-                      return blk_radius_cross_fill(s, d_queries, n_queries, d_vecs, n, cosine,
-                                                   radius_kernel_bound(metric, radius), c->n_cu, scratch,
-                                                   reinterpret_cast<const long long *>(d_offset), d_index, d_value);
-                    });
-}
-
-int bl_amd_cross_radius_fill_device(const struct force_vector_s *d_queries, int n_queries,
-                                    const struct force_vector_s *d_vecs, int n, int metric, float radius,
-                                    const int64_t *d_offset, int32_t *d_index, float *d_value, void *stream) {
-  if (!radius_cross_args_ok(d_queries, n_queries, d_vecs, n, metric, radius, d_offset) || !d_index) return BL_UNEXPECTED;
-  return bl_amd_ctx_cross_radius_fill_device(blr_default_ctx(), d_queries, n_queries, d_vecs, n, metric, radius,
-                                             d_offset, d_index, d_value, stream);
-}
-
-int bl_amd_cross_radius_host(const struct force_vector_s *h_queries, int n_queries, const struct force_vector_s *h_vecs,
-                             int n, int metric, float radius, int64_t *h_offset, int32_t **h_index, float **h_value) {
-  if (!radius_cross_args_ok(h_queries, n_queries, h_vecs, n, metric, radius, h_offset) || !h_index) return BL_UNEXPECTED;
-  bl_amd_ctx *c = blr_default_ctx();
-  if (!c) return BL_UNEXPECTED;
-  DevGuard dg(c->device);
-  if (!dg.ok) return BL_UNEXPECTED;
-  std::vector<int64_t> off((size_t)n_queries + 1);
-  DevMem dq(sizeof(struct force_vector_s) * (size_t)n_queries), dv(sizeof(struct force_vector_s) * (size_t)n);
-  DevMem doff(sizeof(int64_t) * off.size());
-  if (!(dq.up(h_queries) && dv.up(h_vecs) && doff.ok() &&
-        bl_amd_cross_radius_count_device(dq.as<struct force_vector_s>(), n_queries, dv.as<struct force_vector_s>(), n,
-                                         metric, radius, doff.as<int64_t>(), nullptr) == BL_OK &&
-        doff.down(off.data())))
-    return BL_UNEXPECTED;
-  const size_t total = (size_t)off[(size_t)n_queries], slots = total ? total : 1; /* as in bl_amd_radius_host */
-  int32_t *hi = static_cast<int32_t *>(malloc(sizeof(int32_t) * slots));
-  float *hv = h_value ? static_cast<float *>(malloc(sizeof(float) * slots)) : nullptr;
-  DevMem di(sizeof(int32_t) * slots), dd(h_value ? sizeof(float) * slots : 0);
-  if (!(hi && (hv || !h_value) && di.ok() && dd.ok() &&
-        bl_amd_cross_radius_fill_device(dq.as<struct force_vector_s>(), n_queries, dv.as<struct force_vector_s>(), n,
-                                        metric, radius, doff.as<int64_t>(), di.as<int32_t>(), dd.as<float>(),
-                                        nullptr) == BL_OK &&
-        di.down(hi, sizeof(int32_t) * total) && (!h_value || dd.down(hv, sizeof(float) * total)))) {
-    free(hi);
-    free(hv);
-    return BL_UNEXPECTED;
-  }
-  memcpy(h_offset, off.data(), sizeof(int64_t) * off.size());
-  *h_index = hi;
-  if (h_value) *h_value = hv;
-  return BL_OK;
-}
-
-static bool groups_args_ok(const void *vecs, int n, int metric, float radius, const void *group) {
-  return vecs && group && n > 0 && metric_ok(metric) && radius == radius;
-}
-
-int bl_amd_ctx_groups_device(bl_amd_ctx *c, const struct force_vector_s *d_vecs, int n, int metric, float radius,
-                             int32_t *d_group, void *stream) {
-  if (!groups_args_ok(d_vecs, n, metric, radius, d_group) || !c) return BL_UNEXPECTED;
-  const bool cosine = metric == BL_AMD_KNN_COSINE;
-  return query_call(c, stream, c->radius, blk_groups_scratch_bytes(n, cosine), [&](hipStream_t s, void *scratch) {
-    return blk_groups(s, d_vecs, n, cosine, radius_kernel_bound(metric, radius), c->n_cu, scratch, d_group);
-  });
-}
-
-int bl_amd_groups_device(const struct force_vector_s *d_vecs, int n, int metric, float radius, int32_t *d_group,
-                         void *stream) {
-  if (!groups_args_ok(d_vecs, n, metric, radius, d_group)) return BL_UNEXPECTED;
-  return bl_amd_ctx_groups_device(blr_default_ctx(), d_vecs, n, metric, radius, d_group, stream);
-}
-
-int bl_amd_groups_host(const struct force_vector_s *h_vecs, int n, int metric, float radius, int32_t *h_group) {
-  if (!groups_args_ok(h_vecs, n, metric, radius, h_group)) return BL_UNEXPECTED;
-  bl_amd_ctx *c = blr_default_ctx();
-  if (!c) return BL_UNEXPECTED;
-  DevGuard dg(c->device);
-  if (!dg.ok) return BL_UNEXPECTED;
-  DevMem dv(sizeof(struct force_vector_s) * (size_t)n), dgrp(sizeof(int32_t) * (size_t)n);
-  return dv.up(h_vecs) && dgrp.ok() &&
-                 bl_amd_groups_device(dv.as<struct force_vector_s>(), n, metric, radius, dgrp.as<int32_t>(), nullptr) ==
-                     BL_OK &&
-                 dgrp.down(h_group)
-             ? BL_OK
-             : BL_UNEXPECTED;
-}
-
-int bl_amd_chain_shape(int n, int n_chains) {
-  if (n < 1 || n_chains < 1) return BL_UNEXPECTED;
-  bl_amd_ctx *c = blr_default_ctx();
-  if (!c) return BL_UNEXPECTED;
-  return blk_chain_shape(n, n_chains, c->n_cu, g_chain_force.load());
-}
-
-int bl_amd_chain_force_shape(int shape) {
-  if (shape != BL_AMD_CHAIN_AUTO && shape != BL_AMD_CHAIN_PER_CHAIN && shape != BL_AMD_CHAIN_SPLIT)
-    return BL_UNEXPECTED;
-  return g_chain_force.exchange(shape);
 }
 
 int bl_amd_selftest_sqrt(uint64_t counts[3]) {
@@ -1461,26 +920,6 @@ int bl_amd_selftest_cos(uint64_t counts[6], uint64_t triples) {
   }
   (void)hipFree(d);
   return rc;
-}
-
-static int matrix_host(const struct force_vector_s *h_vecs, int n, float *h_out, bool cosine) {
-  if (n <= 0 || !h_vecs || !h_out) return BL_UNEXPECTED;
-  bl_amd_ctx *c = blr_default_ctx();
-  if (!c) return BL_UNEXPECTED;
-  DevGuard dg(c->device);
-  DevMem dv(sizeof(struct force_vector_s) * (size_t)n), dout(sizeof(float) * (size_t)n * n);
-  return dv.up(h_vecs) && dout.ok() &&
-                 matrix_device(dv.as<struct force_vector_s>(), n, 0, n, dout.as<float>(), nullptr, cosine) == BL_OK &&
-                 dout.down(h_out)
-             ? BL_OK
-             : BL_UNEXPECTED;
-}
-
-int bl_amd_distance_matrix_host(const struct force_vector_s *h_vecs, int n, float *h_out) {
-  return matrix_host(h_vecs, n, h_out, false);
-}
-int bl_amd_cosine_matrix_host(const struct force_vector_s *h_vecs, int n, float *h_out) {
-  return matrix_host(h_vecs, n, h_out, true);
 }
 
 int bl_amd_set_host_transfer(int mode) {
