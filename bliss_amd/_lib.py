@@ -17,6 +17,7 @@ BL_LOUD, BL_CALM, BL_UNKNOWN, BL_UNEXPECTED, BL_OK = 0, 1, 2, -2, 0
 BL_AMD_KNN_DISTANCE, BL_AMD_KNN_COSINE, BL_AMD_KNN_MAX_K = 0, 1, 128  # include/bliss_amd.h
 BL_AMD_CHAIN_AUTO, BL_AMD_CHAIN_PER_CHAIN, BL_AMD_CHAIN_SPLIT = 0, 1, 2  # include/bliss_amd.h
 BL_AMD_MIX_MAX_GAP = 16  # include/bliss_amd.h
+BL_AMD_PART_SPECTRUM, BL_AMD_PART_SUMS, BL_AMD_PART_HIST = 1, 2, 4  # include/bliss_amd.h
 
 
 class ForceVector(C.Structure):  # ref include/bliss.h:26-31
@@ -191,6 +192,8 @@ SYMBOLS = {
     "bl_amd_profile_reset": (None, []),
     "bl_amd_profile_ms": (C.c_double, [C.c_char_p, _P(C.c_int)]),
     "bl_amd_last_energies": (C.c_longlong, [_P(C.c_float), C.c_longlong]),
+    "bl_amd_last_freq_stats": (C.c_int, [C.c_int, _P(C.c_float), _P(C.c_longlong), _P(C.c_ulonglong), _P(C.c_uint),
+                                         _P(C.c_int)]),
     "bl_amd_shutdown": (None, []),
 }
 

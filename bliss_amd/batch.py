@@ -222,6 +222,28 @@ def analyze_batch_host(pcm_list, channels, durations):
     return results_to_numpy(bytes(out))
 
 
+def last_freq_stats():
+    """Diagnostic (bl_amd_last_freq_stats): what the frequency and statistics passes of the default context's most
+    recent launch group left in the workspace, in the caller's song order.  Returns a dict: n_songs, parts (the
+    BL_AMD_PART_* bits of what that group wrote; the rest is left over from earlier calls), spectrum (n, 256) float32
+    (bin 0 unspecified), sum (n,) int64, sumsq (n,) uint64, hist (n, 4096) uint32.  Waits for the device."""
+    lib = _lib.load()
+    parts = C.c_int(0)
+    n = lib.bl_amd_last_freq_stats(0, None, None, None, None, C.byref(parts))
+    if n < 0:
+        raise RuntimeError("bl_amd_last_freq_stats failed; see stderr")
+    spectrum = np.zeros((n, 256), dtype=np.float32)
+    total = np.zeros(n, dtype=np.int64)
+    sumsq = np.zeros(n, dtype=np.uint64)
+    hist = np.zeros((n, 4096), dtype=np.uint32)
+    if n and lib.bl_amd_last_freq_stats(n, spectrum.ctypes.data_as(C.POINTER(C.c_float)),
+                                        total.ctypes.data_as(C.POINTER(C.c_longlong)),
+                                        sumsq.ctypes.data_as(C.POINTER(C.c_ulonglong)),
+                                        hist.ctypes.data_as(C.POINTER(C.c_uint)), C.byref(parts)) != n:
+        raise RuntimeError("bl_amd_last_freq_stats failed; see stderr")
+    return dict(n_songs=n, parts=parts.value, spectrum=spectrum, sum=total, sumsq=sumsq, hist=hist)
+
+
 def levels_batch_host(pcm_list, channels, silence=0):
     """Signal levels of songs in host memory (bl_amd_levels_batch_host): pcm_list a list of 1-D int16 arrays
     (interleaved), channels per song or one for all.  Returns the structured array of levels_to_numpy()."""

@@ -133,17 +133,21 @@ int blk_configure_device(void) {
   return BL_OK;
 }
 
+/* sum, sum of squares, histogram, trim, mean and variance: the amplitude reads the histogram and the trim, the envelope
+ * mean and variance; the frequency analysis (what == 2, bl_frequency_sort) nothing of it */
+static bool wants_statistics(int what) { return (what & 5) != 0; }
+
 /* analysis of one launch group (n_songs <= 32768: gridDim.y) */
 int blk_analyze(const blk_analyze_args &a) {
   const int n_songs = a.n_songs, what = a.what;
   hipStream_t stream = a.stream;
   blk_stats_init(a);
   /* With all three analyzers asked for, the statistics ride along with the frequency pass (k_freq_scan): two
-   * passes over the PCM instead of three. */
+   * passes over the PCM instead of three.  The frequency analysis alone reads none of them: no statistics pass. */
   const bool fused = blk_freq_scan_fused(what);
   if (fused) blk_freq_scan(a);
-  else if (blk_pcm_scan(a) != BL_OK) return BL_UNEXPECTED;
-  blk_song_prep(a);
+  else if (wants_statistics(what) && blk_pcm_scan(a) != BL_OK) return BL_UNEXPECTED;
+  if (wants_statistics(what)) blk_song_prep(a);
   /* Order: the envelope windows first, then the serial envelope tail (three latency-bound waves per 64 songs: it
    * leaves the chip free) beside what is left — the amplitude kernel and, when the statistics were not fused into
    * it, the frequency pass; k_force joins the two.  The tail's 143 KB workgroups only reach a CU when the dispatcher
@@ -218,6 +222,11 @@ int blk_analyze(const blk_analyze_args &a) {
   if (what == 7) blk_force(a);
   BL_HIP_CHECK(hipGetLastError());
   return BL_OK;
+}
+
+/* what blk_analyze(what) writes of a.spectrum, a.stats and a.hist (bl_amd_last_freq_stats) */
+int blk_analyze_parts(int what) {
+  return (wants_statistics(what) ? BL_AMD_PART_SUMS | BL_AMD_PART_HIST : 0) | ((what & 2) ? BL_AMD_PART_SPECTRUM : 0);
 }
 
 int blk_synth(hipStream_t s, int16_t *pcm, const bl_dsong *d_songs, int n_songs, int max_n,

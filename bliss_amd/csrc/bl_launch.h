@@ -137,6 +137,7 @@ struct blk_analyze_args {
   void *mark_user;
 };
 int blk_analyze(const blk_analyze_args &a);             /* bl_kernels.hip: the launch order of the stages below */
+int blk_analyze_parts(int what);                        /* BL_AMD_PART_* bits of the scratch that launch order writes */
 
 /* ---- the stages of blk_analyze, one translation unit each --------------------- */
 /* Each launches on a.stream unless it takes a stream, for all a.n_songs songs unless it takes a range. */

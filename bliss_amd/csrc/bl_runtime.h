@@ -45,6 +45,8 @@ struct bl_amd_ctx {
   hipEvent_t ev_ws = nullptr; /* end of the last launch group that used the workspace */
   bool ws_used = false;
   long long last_env_total = 0;
+  /* bl_amd_last_freq_stats: the last launch group's first record in `songs`, its song count, the parts it wrote */
+  int last_first = 0, last_songs = 0, last_parts = 0;
   bl_tables tb{};
   void *tables_mem = nullptr;
   bl_buf songs, stats, hist, spectrum, energies, lc, results, misc;

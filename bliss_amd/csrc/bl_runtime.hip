@@ -344,6 +344,9 @@ int blr_analyze_device(bl_amd_ctx *c, const int16_t *d_pcm, const bl_amd_song_de
     a.mark_user = c;
     if (blk_analyze(a) != BL_OK) return BL_UNEXPECTED;
     c->last_env_total = env_total[gi];
+    c->last_first = b;
+    c->last_songs = cnt;
+    c->last_parts = blk_analyze_parts(what);
   }
   BL_HIP_CHECK(hipEventRecord(c->ev_ws, stream));
   c->ws_used = true;
@@ -1210,6 +1213,9 @@ int bld_mean_variance_host(const int16_t *h_pcm, int n, int have_mean, int mean_
   const int16_t *d_pcm = static_cast<const int16_t *>(c->arena[0].p);
   if (blk_scan_one(s, d_pcm, d_songs, d_stats, static_cast<unsigned *>(c->hist.p), n, c->n_cu) != BL_OK)
     return BL_UNEXPECTED;
+  c->last_first = 0;
+  c->last_songs = 1;
+  c->last_parts = BL_AMD_PART_SUMS | BL_AMD_PART_HIST;
   bl_dstats st;
   BL_HIP_CHECK(hipMemcpyAsync(&st, d_stats, sizeof st, hipMemcpyDeviceToHost, s));
   BL_HIP_CHECK(hipStreamSynchronize(s));
@@ -1241,6 +1247,47 @@ long long bl_amd_last_energies(float *h_out, long long max_elems) {
   const long long n = c->last_env_total < max_elems ? c->last_env_total : max_elems;
   if (hipDeviceSynchronize() != hipSuccess) return -1;
   if (hipMemcpy(h_out, c->energies.p, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess)
+    return -1;
+  return n;
+}
+
+/* diagnostic: the summed spectrum, the raw sums and the raw histogram of the most recent launch group, un-permuted
+ * from the workspace's processing order (slot = block index) to the caller's through the records' out_idx */
+int bl_amd_last_freq_stats(int max_songs, float *h_spectrum, long long *h_sum, unsigned long long *h_sumsq,
+                           unsigned *h_hist, int *parts) {
+  bl_amd_ctx *c = blr_default_ctx();
+  if (!c) return -1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DevGuard dg(c->device);
+  if (!dg.ok) return -1;
+  const int n = c->last_songs;
+  if (parts) *parts = n > 0 ? c->last_parts : 0;
+  if (n <= 0) return 0;
+  if (hipDeviceSynchronize() != hipSuccess) return -1;
+  std::vector<bl_dsong> songs((size_t)n);
+  if (hipMemcpy(songs.data(), static_cast<const bl_dsong *>(c->songs.p) + c->last_first, sizeof(bl_dsong) * (size_t)n,
+                hipMemcpyDeviceToHost) != hipSuccess)
+    return -1;
+  for (int i = 0; i < n; ++i)
+    if (songs[i].out_idx < 0 || songs[i].out_idx >= n) return -1;
+  /* one workspace at a time through a staging block, rows scattered to the caller's order */
+  auto fetch = [&](const bl_buf &ws, size_t row_bytes, void *out, size_t out_off, size_t out_bytes) -> bool {
+    if (!out) return true;
+    if (!ws.p || ws.cap < row_bytes * (size_t)n) return false;
+    std::vector<unsigned char> tmp(row_bytes * (size_t)n);
+    if (hipMemcpy(tmp.data(), ws.p, tmp.size(), hipMemcpyDeviceToHost) != hipSuccess) return false;
+    for (int i = 0; i < n; ++i) {
+      const int to = songs[i].out_idx;
+      if (to < max_songs)
+        memcpy(static_cast<unsigned char *>(out) + out_bytes * (size_t)to, tmp.data() + row_bytes * (size_t)i + out_off,
+               out_bytes);
+    }
+    return true;
+  };
+  if (!fetch(c->spectrum, sizeof(float) * 256, h_spectrum, 0, sizeof(float) * 256) ||
+      !fetch(c->stats, sizeof(bl_dstats), h_sum, offsetof(bl_dstats, sum), sizeof(long long)) ||
+      !fetch(c->stats, sizeof(bl_dstats), h_sumsq, offsetof(bl_dstats, sumsq), sizeof(unsigned long long)) ||
+      !fetch(c->hist, sizeof(unsigned) * BL_HIST_BINS, h_hist, 0, sizeof(unsigned) * BL_HIST_BINS))
     return -1;
   return n;
 }

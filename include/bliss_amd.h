@@ -524,6 +524,29 @@ double bl_amd_profile_ms(const char *name, int *launches);
  * max_elems floats to h_out; returns the number copied, 0 if none, -1 on error. */
 long long bl_amd_last_energies(float *h_out, long long max_elems);
 
+/* Diagnostic: what the frequency and statistics passes left in the default context's workspace for the most recent
+ * launch group, read-only and in the CALLER's song order (the workspace itself is in processing order, longest song
+ * first in a mixed-length batch).  Returns the number of songs of that group, 0 if nothing has run, -1 on error, and
+ * fills, for the songs whose index is below max_songs, whichever of these is not NULL:
+ *   h_spectrum  256 floats per song: the ordered f32 sum over the frames of re*re + im*im per bin (ps[] of ref
+ *               src/frequency_sort.c:88-93, before the square root).  Bins 1..255 are the reference's; bin 0 is
+ *               unspecified (the reference overwrites ps[0] every frame and never reads it, the kernels sum it);
+ *   h_sum       the sum of all samples of the song (exact, not the reference's wrapping int32);
+ *   h_sumsq     the sum of their squares;
+ *   h_hist      4096 counts per song: samples of value s in [-2048, 2048) at index s + 2048, over ALL samples (the
+ *               trimmed silence is taken off bin 2048 later, by the amplitude kernel).
+ * *parts (may be NULL) receives the BL_AMD_PART_* bits of what that group's launches wrote; anything else is left
+ * over from an earlier call or cleared.  bl_analyze and the batch calls write all three; bl_frequency_sort the spectrum
+ * alone (it reads no statistics, so no statistics pass runs); bl_amplitude_sort and bl_envelope_sort the sums and the
+ * histogram alone, and so do bl_mean / bl_variance, as a group of one song.
+ * Waits for the device like bl_amd_last_energies.  A call that is split into several launch groups (BL_AMD_GROUP_SONGS,
+ * or the waves of a host batch) leaves only its last group here. */
+#define BL_AMD_PART_SPECTRUM 1
+#define BL_AMD_PART_SUMS 2
+#define BL_AMD_PART_HIST 4
+int bl_amd_last_freq_stats(int max_songs, float *h_spectrum, long long *h_sum, unsigned long long *h_sumsq,
+                           unsigned *h_hist, int *parts);
+
 /* Releases every default context (workspaces, streams, pinned staging) and the multi-device
  * state.  Explicit contexts are released by bl_amd_ctx_destroy. */
 void bl_amd_shutdown(void);

@@ -62,6 +62,8 @@ class Oracle:
         L.orc_cosine_matrix.argtypes = [C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_float)]
         L.orc_synth_fill.restype = None
         L.orc_synth_fill.argtypes = [i16p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
+        L.orc_rdft512_f32.restype = None
+        L.orc_rdft512_f32.argtypes = [C.POINTER(C.c_float)]
         L.orc_set_fft_variant.restype = None
         L.orc_set_fft_variant.argtypes = [C.c_int]
 
@@ -77,6 +79,12 @@ class Oracle:
     def frequency(self, pcm, channels):
         pcm = np.ascontiguousarray(pcm, dtype=np.int16)
         return float(self.lib.orc_frequency(self._p(pcm), pcm.size, channels, None))
+
+    def rdft512_f32(self, x):
+        """the 512-point f32 real DFT orc_frequency runs on a frame, in place on a contiguous float32 array of 512
+        (FFmpeg's packed layout: x[2 d], x[2 d + 1] = re, im of bin d)"""
+        assert x.dtype == np.float32 and x.size == 512 and x.flags.c_contiguous
+        self.lib.orc_rdft512_f32(x.ctypes.data_as(C.POINTER(C.c_float)))
 
     def synth(self, seed, rate, channels, n):
         out = np.empty(n, dtype=np.int16)

@@ -298,7 +298,8 @@ def test_quiet_sparse_and_clipped_material_bit_for_bit(gpu_lib, oracle):
     a few LSB loud (frames of tiny values: the power terms sit ~20 orders of magnitude below a loud song's, nowhere near
     the subnormals), isolated impulses in digital silence (almost every frame all zero, single Hann-weighted samples
     otherwise), full-scale square waves (the largest sums the transform can see), and a mono and a stereo song whose
-    length leaves every remainder of the 64-frame iteration."""
+    lengths leave two remainders of the 64-frame iteration, 5 and 37 (every remainder, and every bin of the summed
+    spectrum instead of the one scalar: tests/test_gpu_freq_spectrum.py)."""
     rate = 22050
     rng = np.random.default_rng(66)
     songs, chans, secs = [], [], []
