@@ -14,7 +14,7 @@ from .batch import (Context, DeviceCorpus, analyze_batch_host, analyze_files, an
                     duplicate_groups, duplicate_groups_device, radius, radius_device,
                     resample_batch_device,
                     resample_host, results_to_numpy,
-                    gapless_links, levels_batch_host, levels_db, levels_to_numpy, last_freq_stats)
+                    gapless_links, levels_batch_host, levels_db, levels_to_numpy, last_freq_stats, tail_from_envelope)
 from .bl_song import bl_song
 
 __all__ = ["_lib", "load", "BlSong", "ForceVector", "EnvelopeResult", "SongDesc", "SongResult",
@@ -24,7 +24,7 @@ __all__ = ["_lib", "load", "BlSong", "ForceVector", "EnvelopeResult", "SongDesc"
            "radius", "radius_device", "knn_cross", "knn_cross_device", "radius_cross", "radius_cross_device", "playlist_vec",
            "duplicate_groups", "duplicate_groups_device",
            "SongLevels", "levels_batch_host", "levels_to_numpy", "levels_db", "gapless_links",
-           "last_freq_stats", "resample_host", "resample_batch_device", "bl_song", "distance", "version"]
+           "last_freq_stats", "tail_from_envelope", "resample_host", "resample_batch_device", "bl_song", "distance", "version"]
 
 
 def __getattr__(name):

@@ -194,6 +194,7 @@ SYMBOLS = {
     "bl_amd_last_energies": (C.c_longlong, [_P(C.c_float), C.c_longlong]),
     "bl_amd_last_freq_stats": (C.c_int, [C.c_int, _P(C.c_float), _P(C.c_longlong), _P(C.c_ulonglong), _P(C.c_uint),
                                          _P(C.c_int)]),
+    "bl_amd_tail_from_envelope": (C.c_int, [_P(SongDesc), C.c_int, _P(C.c_double), C.c_longlong, _P(SongResult)]),
     "bl_amd_shutdown": (None, []),
 }
 

@@ -244,6 +244,24 @@ def last_freq_stats():
     return dict(n_songs=n, parts=parts.value, spectrum=spectrum, sum=total, sumsq=sumsq, hist=hist)
 
 
+def tail_from_envelope(n_samples, durations, envelopes):
+    """Diagnostic (bl_amd_tail_from_envelope): the envelope tail kernel on compressed envelopes of the caller's, one
+    launch group.  n_samples / durations per song; envelopes: per song a float64 array of 2 * (n_samples // 512)
+    slots (the last two are never read).  Returns the structured results: nb_frames, n_windows, beat, atk_sum, tempo,
+    attack and status are filled, the rest is zero."""
+    lib = _lib.load()
+    n = len(n_samples)
+    durations = [durations] * n if np.isscalar(durations) else list(durations)
+    desc = (_lib.SongDesc * n)()
+    for i, (ln, du) in enumerate(zip(n_samples, durations)):
+        desc[i].pcm_offset, desc[i].n_samples, desc[i].channels, desc[i].duration = 0, int(ln), 1, int(du)
+    env = np.ascontiguousarray(np.concatenate([np.asarray(e, dtype=np.float64).reshape(-1) for e in envelopes]))
+    out = (_lib.SongResult * n)()
+    _check(lib.bl_amd_tail_from_envelope(desc, n, env.ctypes.data_as(C.POINTER(C.c_double)), env.size, out),
+           "bl_amd_tail_from_envelope")
+    return results_to_numpy(bytes(out))
+
+
 def levels_batch_host(pcm_list, channels, silence=0):
     """Signal levels of songs in host memory (bl_amd_levels_batch_host): pcm_list a list of 1-D int16 arrays
     (interleaved), channels per song or one for all.  Returns the structured array of levels_to_numpy()."""

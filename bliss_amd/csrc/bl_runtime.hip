@@ -1292,6 +1292,51 @@ int bl_amd_last_freq_stats(int max_songs, float *h_spectrum, long long *h_sum, u
   return n;
 }
 
+/* diagnostic: k_env_tail on a compressed envelope the caller supplies.  The group is the product's own (fill_group:
+ * env_off, n_windows, longest first) and so is the launch (blk_env_tail); of the workspace only `lc` is written —
+ * descriptors and records live in blocks of their own, so bl_amd_last_energies and bl_amd_last_freq_stats answer what
+ * they answered before. */
+int bl_amd_tail_from_envelope(const bl_amd_song_desc *h_desc, int n_songs, const double *h_env, long long n_env,
+                              bl_amd_song_result *h_results) {
+  if (!h_desc || !h_env || !h_results || n_songs <= 0 || n_songs > BL_GROUP_SONGS_MAX) return BL_UNEXPECTED;
+  for (int i = 0; i < n_songs; ++i)
+    if (validate_desc(h_desc[i], i) != BL_OK || h_desc[i].channels != 1 || h_desc[i].pcm_offset != 0) return BL_UNEXPECTED;
+  bl_amd_ctx *c = blr_default_ctx();
+  if (!c) return BL_UNEXPECTED;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DevGuard dg(c->device);
+  if (!dg.ok) return BL_UNEXPECTED;
+  std::vector<bl_dsong> hs((size_t)n_songs);
+  long long env_total = 0;
+  int max_n = 0;
+  fill_group(h_desc, n_songs, hs.data(), env_total, max_n);
+  if (env_total != n_env) return BL_UNEXPECTED;
+  /* whatever used the workspace last has finished before lc is overwritten */
+  BL_HIP_CHECK(hipDeviceSynchronize());
+  if (blr_ensure(c->lc, sizeof(double) * (size_t)env_total) != BL_OK) return BL_UNEXPECTED;
+  DevMem d_songs(sizeof(bl_dsong) * (size_t)n_songs), d_res(sizeof(bl_amd_song_result) * (size_t)n_songs);
+  if (!d_songs.up(hs.data()) || !d_res.ok()) return BL_UNEXPECTED;
+  BL_HIP_CHECK(hipMemset(d_res.p, 0, d_res.bytes));
+  BL_HIP_CHECK(hipMemcpy(c->lc.p, h_env, sizeof(double) * (size_t)env_total, hipMemcpyHostToDevice));
+  blk_analyze_args a{};
+  a.songs = d_songs.as<bl_dsong>();
+  a.lc = static_cast<double *>(c->lc.p);
+  a.results = d_res.as<bl_amd_song_result>();
+  a.n_songs = n_songs;
+  a.max_n = max_n;
+  blk_env_tail(a, nullptr, 0, n_songs);
+  BL_HIP_CHECK(hipGetLastError());
+  BL_HIP_CHECK(hipDeviceSynchronize());
+  if (!d_res.down(h_results)) return BL_UNEXPECTED;
+  for (int i = 0; i < n_songs; ++i) { /* the geometry the other kernels write into a record */
+    bl_amd_song_result &r = h_results[hs[i].out_idx];
+    r.nb_frames = hs[i].nb_frames;
+    r.n_windows = hs[i].n_windows;
+    r.status = BL_OK;
+  }
+  return BL_OK;
+}
+
 void bl_multi_shutdown(void); /* bl_multi.hip */
 
 void bl_amd_shutdown(void) {

@@ -547,6 +547,19 @@ long long bl_amd_last_energies(float *h_out, long long max_elems);
 int bl_amd_last_freq_stats(int max_songs, float *h_spectrum, long long *h_sum, unsigned long long *h_sumsq,
                            unsigned *h_hist, int *parts);
 
+/* Diagnostic: the envelope tail (k_env_tail: recurrence, onset weighting, the two box filters, the peak count; ref
+ * src/tempo_atk_sort.c:201-284) of the default context on a compressed envelope the CALLER supplies instead of the one
+ * the window kernel leaves, as one launch group of n_songs songs.  h_desc: n_samples and duration per song (channels 1,
+ * pcm_offset 0; no PCM is read); h_env: nb_frames = 2 * (n_samples / 512) doubles per song, songs concatenated in the
+ * caller's order — slot w < nb_frames - 2 is log(1 + mu f_w) / log(1 + mu) of window w, the last two slots of a song are
+ * never read; n_env: their total count, anything but the sum of nb_frames is BL_UNEXPECTED.  The group is laid out as
+ * a batch call lays it out (longest song first in a mixed-length group) and runs the same launch.  h_results (host,
+ * n_songs records, caller's order) gets nb_frames, n_windows, beat, atk_sum, v.tempo, v.attack and status; every other
+ * field is zero.  Read-only towards the other diagnostics: what bl_amd_last_energies and bl_amd_last_freq_stats answer
+ * is unchanged.  Blocking. */
+int bl_amd_tail_from_envelope(const bl_amd_song_desc *h_desc, int n_songs, const double *h_env, long long n_env,
+                              bl_amd_song_result *h_results);
+
 /* Releases every default context (workspaces, streams, pinned staging) and the multi-device
  * state.  Explicit contexts are released by bl_amd_ctx_destroy. */
 void bl_amd_shutdown(void);

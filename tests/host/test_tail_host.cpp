@@ -9,10 +9,8 @@
 #include "../../bliss_amd/csrc/bl_tail.h"
 #include "../../oracle/bliss_oracle.h"
 
-static int check(unsigned seed, unsigned rate, unsigned ch, unsigned secs, unsigned extra, bool use_fast = true) {
-  unsigned n = rate * ch * secs + extra;
-  std::vector<int16_t> pcm(n);
-  orc_synth_fill(pcm.data(), n, seed, rate, ch);
+static int check_pcm(const std::vector<int16_t> &pcm, unsigned seed, unsigned secs, bool use_fast, bool quiet) {
+  const unsigned n = (unsigned)pcm.size();
   orc_result r;
   memset(&r, 0, sizeof r);
   std::vector<float> en(2 * (n / 512) + 4, 0.f);
@@ -61,9 +59,44 @@ static int check(unsigned seed, unsigned rate, unsigned ch, unsigned secs, unsig
     if (!ok2) printf("  three-stage: beat %d atk %.17g taken %d MISMATCH\n", c.beat(), ab.atk, c.taken);
     ok &= ok2;
   }
-  printf("seed %u n %u: beat %d/%d atk %.17g/%.17g tempo %g attack %g %s\n", seed, n, t.beat(),
-         r.beat, t.atk, r.atk_sum, tempo, attack, ok ? "ok" : "MISMATCH");
+  if (!quiet || !ok)
+    printf("seed %u n %u: beat %d/%d atk %.17g/%.17g tempo %g attack %g %s\n", seed, n, t.beat(),
+           r.beat, t.atk, r.atk_sum, tempo, attack, ok ? "ok" : "MISMATCH");
   return ok;
+}
+
+static int check(unsigned seed, unsigned rate, unsigned ch, unsigned secs, unsigned extra, bool use_fast = true) {
+  unsigned n = rate * ch * secs + extra;
+  std::vector<int16_t> pcm(n);
+  orc_synth_fill(pcm.data(), n, seed, rate, ch);
+  return check_pcm(pcm, seed, secs, use_fast, false);
+}
+
+// Every m = floor(n / 512) from 10 to 124 — two periods (57) of (N mod 38, n_blocks mod 6) — with a varying n % 512,
+// on noise gated at a period of 2200..5200 samples over a quiet floor (the generator's own songs have 1-5 beats in
+// these lengths, these up to a dozen or two): both forms, with and without the register chunks.
+static int check_sweep() {
+  unsigned long long st = 0x9E3779B97F4A7C15ull;
+  auto next = [&]() { st ^= st << 13; st ^= st >> 7; st ^= st << 17; return st; };
+  int ok = 1, max_beat = 0;
+  for (unsigned m = 10; m <= 124; ++m) {
+    const unsigned n = 512 * m + (unsigned)(next() % 512);
+    const unsigned period = 2200 + (unsigned)(next() % 3001), on = period * (15 + (unsigned)(next() % 36)) / 100;
+    const unsigned phase = (unsigned)(next() % period);
+    std::vector<int16_t> pcm(n);
+    for (unsigned i = 0; i < n; ++i) {
+      const unsigned long long v = next();
+      pcm[i] = (i + phase) % period < on ? (int16_t)((int)(v % 24001) - 12000) : (int16_t)((int)(v % 81) - 40);
+    }
+    orc_result r;
+    memset(&r, 0, sizeof r);
+    orc_envelope(pcm.data(), (int)n, 1 + m % 7, &r, NULL);
+    if (r.beat > max_beat) max_beat = r.beat;
+    ok &= check_pcm(pcm, m, 1 + m % 7, true, true);
+    ok &= check_pcm(pcm, m, 1 + m % 7, false, true);
+  }
+  printf("sweep m = 10..124: %s, up to %d beats\n", ok ? "ok" : "MISMATCH", max_beat);
+  return ok && max_beat >= 8;
 }
 
 // bl_div_const must agree with IEEE division bit for bit
@@ -94,6 +127,7 @@ int main() {
   ok &= check(7, 22050, 2, 7, 0, false);  // generic path only
   ok &= check(8, 13312, 1, 1, 0);     // N = 52
   ok &= check(9, 14000, 1, 1, 0);     // N = 54
+  ok &= check_sweep();
   puts(ok ? "OK" : "FAIL");
   return ok ? 0 : 1;
 }

@@ -79,6 +79,10 @@ def test_no_device_fails_loudly(lib):
         bliss_amd.analyze_batch_host([pcm], 1, 1)
     ctx = C.c_void_p()
     assert lib.bl_amd_ctx_create(0, C.byref(ctx)) == _lib.BL_UNEXPECTED and not ctx.value
+    desc = (_lib.SongDesc * 1)(_lib.SongDesc(0, 8192, 1, 1))
+    env, rec = np.zeros(32), (_lib.SongResult * 1)()
+    assert lib.bl_amd_tail_from_envelope(desc, 1, env.ctypes.data_as(C.POINTER(C.c_double)), env.size,
+                                         rec) == _lib.BL_UNEXPECTED
 
 
 def test_analyze_files_fails_loudly_without_a_device(lib, tmp_path):
