@@ -6,7 +6,7 @@ All computation happens in libbliss_amd.so (hand-written HIP kernels for gfx950)
 """
 from . import _lib
 from ._lib import (BL_CALM, BL_LOUD, BL_OK, BL_UNEXPECTED, BL_UNKNOWN, BlSong, EnvelopeResult,
-                   ForceVector, SongDesc, SongLevels, SongResult, load)
+                   ForceVector, FrameTimbre, SongDesc, SongLevels, SongResult, SongTimbre, load)
 from . import distance, version
 from .batch import (Context, DeviceCorpus, analyze_batch_host, analyze_files, analyze_batch_host_rate, analyze_batch_host_s32,
                     analyze_corpus_multi, analyze_corpus_multi_device, chain, chain_device, mix, mix_device, cosine_matrix, distance_matrix, knn, knn_device,
@@ -14,7 +14,8 @@ from .batch import (Context, DeviceCorpus, analyze_batch_host, analyze_files, an
                     duplicate_groups, duplicate_groups_device, radius, radius_device,
                     resample_batch_device,
                     resample_host, results_to_numpy,
-                    gapless_links, levels_batch_host, levels_db, levels_to_numpy, last_freq_stats, tail_from_envelope)
+                    gapless_links, levels_batch_host, levels_db, levels_to_numpy, last_freq_stats, tail_from_envelope,
+                    timbre_batch_host, timbre_hz, timbre_to_numpy)
 from .bl_song import bl_song
 
 __all__ = ["_lib", "load", "BlSong", "ForceVector", "EnvelopeResult", "SongDesc", "SongResult",
@@ -24,6 +25,7 @@ __all__ = ["_lib", "load", "BlSong", "ForceVector", "EnvelopeResult", "SongDesc"
            "radius", "radius_device", "knn_cross", "knn_cross_device", "radius_cross", "radius_cross_device", "playlist_vec",
            "duplicate_groups", "duplicate_groups_device",
            "SongLevels", "levels_batch_host", "levels_to_numpy", "levels_db", "gapless_links",
+           "SongTimbre", "FrameTimbre", "timbre_batch_host", "timbre_to_numpy", "timbre_hz",
            "last_freq_stats", "tail_from_envelope", "resample_host", "resample_batch_device", "bl_song", "distance", "version"]
 
 

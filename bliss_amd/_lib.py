@@ -64,6 +64,17 @@ class SongLevels(C.Structure):  # include/bliss_amd.h bl_amd_song_levels
                 ("frames", C.c_int32), ("status", C.c_int32), ("head", C.c_int16 * 2), ("tail", C.c_int16 * 2)]
 
 
+class FrameTimbre(C.Structure):  # include/bliss_amd.h bl_amd_frame_timbre
+    _fields_ = [("energy", C.c_uint64), ("moment", C.c_uint64), ("rolloff", C.c_int32), ("peak", C.c_int32)]
+
+
+class SongTimbre(C.Structure):  # include/bliss_amd.h bl_amd_song_timbre
+    _fields_ = [("centroid_sum", C.c_uint64), ("centroid_sumsq", C.c_uint64), ("rolloff_sum", C.c_uint64),
+                ("rolloff_sumsq", C.c_uint64), ("peak_sum", C.c_uint64), ("peak_sumsq", C.c_uint64),
+                ("energy_max", C.c_uint64), ("frames", C.c_int32), ("used", C.c_int32), ("status", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 class Shard(C.Structure):  # include/bliss_amd.h bl_amd_shard
     _fields_ = [("device", C.c_int32), ("n_songs", C.c_int32), ("d_pcm", C.c_void_p),
                 ("h_desc", C.POINTER(SongDesc)), ("d_results", C.c_void_p), ("d_rows", C.c_void_p)]
@@ -185,6 +196,16 @@ SYMBOLS = {
     "bl_amd_gapless_host": (C.c_int, [_P(SongLevels), C.c_int, _P(C.c_uint8)]),
     "bl_amd_levels_peak_db": (C.c_double, [_P(SongLevels), C.c_int]),
     "bl_amd_levels_rms_db": (C.c_double, [_P(SongLevels), C.c_int]),
+    "bl_amd_timbre_frames": (C.c_int, [C.c_int, C.c_int]),
+    "bl_amd_timbre_batch_device": (C.c_int, [C.c_void_p, _P(SongDesc), C.c_int, C.c_int, C.c_uint64, C.c_void_p,
+                                             C.c_void_p, C.c_longlong, C.c_void_p]),
+    "bl_amd_ctx_timbre_batch_device": (C.c_int, [C.c_void_p, C.c_void_p, _P(SongDesc), C.c_int, C.c_int, C.c_uint64,
+                                                 C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "bl_amd_timbre_batch_host": (C.c_int, [_P(C.c_void_p), _P(C.c_int32), _P(C.c_int32), C.c_int, C.c_int, C.c_uint64,
+                                           _P(SongTimbre), _P(FrameTimbre)]),
+    "bl_amd_timbre_centroid_hz": (C.c_double, [_P(SongTimbre), C.c_int, _P(C.c_double)]),
+    "bl_amd_timbre_rolloff_hz": (C.c_double, [_P(SongTimbre), C.c_int, _P(C.c_double)]),
+    "bl_amd_timbre_peak_hz": (C.c_double, [_P(SongTimbre), C.c_int, _P(C.c_double)]),
     "bl_amd_synth_pcm_device": (C.c_int, [C.c_void_p, _P(SongDesc), C.c_int, C.c_uint32, C.c_uint32, C.c_void_p]),
     "bl_amd_set_fir_mode": (C.c_int, [C.c_int]),
     "bl_amd_fir_mode": (C.c_int, []),

@@ -37,6 +37,53 @@ def levels_to_numpy(raw):
     return np.frombuffer(bytes(raw), dtype=LEVELS_DTYPE).copy()
 
 
+TIMBRE_FRAME_DTYPE = np.dtype([("energy", "<u8"), ("moment", "<u8"), ("rolloff", "<i4"), ("peak", "<i4")], align=True)
+TIMBRE_SONG_DTYPE = np.dtype([
+    ("centroid_sum", "<u8"), ("centroid_sumsq", "<u8"), ("rolloff_sum", "<u8"), ("rolloff_sumsq", "<u8"),
+    ("peak_sum", "<u8"), ("peak_sumsq", "<u8"), ("energy_max", "<u8"), ("frames", "<i4"), ("used", "<i4"),
+    ("status", "<i4"), ("reserved", "<i4")], align=True)
+assert TIMBRE_FRAME_DTYPE.itemsize == C.sizeof(_lib.FrameTimbre) == 24
+assert TIMBRE_SONG_DTYPE.itemsize == C.sizeof(_lib.SongTimbre) == 72
+
+TIMBRE_HZ_DTYPE = np.dtype([("centroid_hz", "<f8"), ("centroid_std_hz", "<f8"), ("rolloff_hz", "<f8"),
+                            ("rolloff_std_hz", "<f8"), ("peak_hz", "<f8"), ("peak_std_hz", "<f8")])
+
+
+def timbre_to_numpy(raw_songs, raw_frames=None):
+    """bytes / uint8 arrays of bl_amd_song_timbre (and bl_amd_frame_timbre) records -> structured numpy arrays with the
+    header's field names.  Returns the song array, or (songs, frames) when raw_frames is given."""
+    songs = np.frombuffer(bytes(raw_songs), dtype=TIMBRE_SONG_DTYPE).copy()
+    if raw_frames is None:
+        return songs
+    return songs, np.frombuffer(bytes(raw_frames), dtype=TIMBRE_FRAME_DTYPE).copy()
+
+
+def _timbre_params_check(pct, min_energy):
+    if isinstance(pct, bool) or not isinstance(pct, (int, np.integer)) or not 1 <= pct <= 100:
+        raise ValueError(f"pct must be an integer in [1, 100], got {pct!r}")
+    if isinstance(min_energy, bool) or not isinstance(min_energy, (int, np.integer)) or not 0 <= min_energy < 2 ** 64:
+        raise ValueError(f"min_energy must be an integer in [0, 2^64), got {min_energy!r}")
+    return int(pct), int(min_energy)
+
+
+def _timbre_songs_check(lengths, channels):
+    """per-song channel list and frame counts, once there is a song and every song has 1 or 2 channels and a frame"""
+    n = len(lengths)
+    if n < 1:
+        raise ValueError("at least one song is needed")
+    channels = [channels] * n if np.isscalar(channels) else list(channels)
+    if len(channels) != n:
+        raise ValueError(f"{n} songs but {len(channels)} channel counts")
+    frames = []
+    for ln, ch in zip(lengths, channels):
+        if isinstance(ch, bool) or not isinstance(ch, (int, np.integer)) or ch not in (1, 2):
+            raise ValueError(f"channels must be 1 or 2, got {ch!r}")
+        if int(ln) // int(ch) // 512 < 1:
+            raise ValueError(f"a song needs at least one frame of 512 samples per channel, got {int(ln)} samples")
+        frames.append(int(ln) // int(ch) // 512)
+    return [int(ch) for ch in channels], frames
+
+
 def _silence_check(silence):
     if isinstance(silence, bool) or not isinstance(silence, (int, np.integer)) or not 0 <= silence <= 32767:
         raise ValueError(f"silence must be an integer in [0, 32767], got {silence!r}")
@@ -168,6 +215,43 @@ class DeviceCorpus:
         self.torch.cuda.synchronize(self.device)
         return levels_to_numpy(self.levels_raw.cpu().numpy().tobytes())
 
+    def timbre(self, pct=85, min_energy=0, frames=True, ctx=None):
+        """Enqueue the spectral timbre of every song (bl_amd_timbre_batch_device) on torch's current stream; returns
+        the uint8 CUDA tensors (song records, frame records or None) this corpus owns (fetch_timbre() reads them).
+        pct: the rolloff percentage, 1..100; min_energy: a frame enters the song's sums iff its energy is above 0 and
+        at least this; frames: also keep every frame's record.  ctx: an explicit Context."""
+        pct, min_energy = _timbre_params_check(pct, min_energy)
+        _, nfr = _timbre_songs_check([d.n_samples for d in self.desc], [d.channels for d in self.desc])
+        total = sum(nfr)
+        with self.torch.cuda.device(self.device):
+            if getattr(self, "timbre_raw", None) is None:
+                self.timbre_raw = self.torch.zeros(self.n_songs * C.sizeof(_lib.SongTimbre), dtype=self.torch.uint8,
+                                                   device=self.device)
+            if frames and getattr(self, "timbre_frames_raw", None) is None:
+                self.timbre_frames_raw = self.torch.zeros(total * C.sizeof(_lib.FrameTimbre), dtype=self.torch.uint8,
+                                                          device=self.device)
+        if not frames:
+            self.timbre_frames_raw = None
+        fr = C.c_void_p(self.timbre_frames_raw.data_ptr()) if frames else C.c_void_p()
+        args = (C.c_void_p(self.pcm.data_ptr()), self.desc, self.n_songs, pct, min_energy,
+                C.c_void_p(self.timbre_raw.data_ptr()), fr, total, self._stream())
+        if ctx is None:
+            _check(self.lib.bl_amd_timbre_batch_device(*args), "bl_amd_timbre_batch_device")
+        else:
+            _check(self.lib.bl_amd_ctx_timbre_batch_device(ctx.handle, *args), "bl_amd_ctx_timbre_batch_device")
+        return self.timbre_raw, self.timbre_frames_raw
+
+    def fetch_timbre(self):
+        """Wait for the device and return what the last timbre() call computed: (songs, frames) structured arrays,
+        frames None if that call kept none.  Song i's frames start at the sum of the earlier songs' `frames`."""
+        if getattr(self, "timbre_raw", None) is None:
+            raise RuntimeError("timbre() has not been called on this corpus")
+        self.torch.cuda.synchronize(self.device)
+        songs = timbre_to_numpy(self.timbre_raw.cpu().numpy().tobytes())
+        if self.timbre_frames_raw is None:
+            return songs, None
+        return timbre_to_numpy(self.timbre_raw.cpu().numpy().tobytes(), self.timbre_frames_raw.cpu().numpy().tobytes())
+
     def force_vectors(self):
         """(n_songs, 4) float32 CUDA tensor view-copy of the force vectors."""
         rec = self.results.view(self.n_songs, C.sizeof(_lib.SongResult))
@@ -276,6 +360,44 @@ def levels_batch_host(pcm_list, channels, silence=0):
     out = (_lib.SongLevels * n)()
     _check(lib.bl_amd_levels_batch_host(ptrs, ns, chs, n, silence, out), "bl_amd_levels_batch_host")
     return levels_to_numpy(bytes(out))
+
+
+def timbre_batch_host(pcm_list, channels, pct=85, min_energy=0, frames=True):
+    """Spectral timbre of songs in host memory (bl_amd_timbre_batch_host): pcm_list a list of 1-D int16 arrays
+    (interleaved), channels per song or one for all.  Returns (songs, frames): the structured arrays of
+    timbre_to_numpy(), frames None unless asked for."""
+    pct, min_energy = _timbre_params_check(pct, min_energy)
+    arrs = [np.ascontiguousarray(p, dtype=np.int16).reshape(-1) for p in pcm_list]
+    channels, nfr = _timbre_songs_check([a.size for a in arrs], channels)
+    lib = _lib.load()
+    n = len(arrs)
+    ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in arrs])
+    ns = (C.c_int32 * n)(*[a.size for a in arrs])
+    chs = (C.c_int32 * n)(*channels)
+    out = (_lib.SongTimbre * n)()
+    fout = (_lib.FrameTimbre * sum(nfr))() if frames else None
+    _check(lib.bl_amd_timbre_batch_host(ptrs, ns, chs, n, pct, min_energy, out, fout), "bl_amd_timbre_batch_host")
+    if not frames:
+        return timbre_to_numpy(bytes(out)), None
+    return timbre_to_numpy(bytes(out), bytes(fout))
+
+
+def timbre_hz(songs, rate=22050):
+    """What a user reads off the integers (bl_amd_timbre_centroid_hz, _rolloff_hz, _peak_hz): mean and population
+    standard deviation over the used frames, in Hz, as a structured array; NaN where a song has no used frame."""
+    st = np.ascontiguousarray(songs)
+    if st.dtype != TIMBRE_SONG_DTYPE or st.ndim != 1 or st.size < 1:
+        raise ValueError("songs must be a non-empty 1-D array of bl_amd_song_timbre records (timbre_to_numpy)")
+    lib = _lib.load()
+    out = np.empty(st.size, dtype=TIMBRE_HZ_DTYPE)
+    recs = st.ctypes.data_as(C.POINTER(_lib.SongTimbre))
+    std = C.c_double()
+    for i in range(st.size):
+        for name, fn in (("centroid", lib.bl_amd_timbre_centroid_hz), ("rolloff", lib.bl_amd_timbre_rolloff_hz),
+                         ("peak", lib.bl_amd_timbre_peak_hz)):
+            out[name + "_hz"][i] = fn(C.byref(recs[i]), int(rate), C.byref(std))
+            out[name + "_std_hz"][i] = std.value
+    return out
 
 
 def _levels_array(levels):

@@ -238,3 +238,42 @@ double bl_amd_levels_rms_db(const bl_amd_song_levels *lv, int channel) {
   if (!lv || channel < 0 || channel > 1 || lv->frames < 1) return NAN;
   return 10.0 * log10((double)lv->sum_sq[channel] / ((double)lv->frames * 1073741824.0));
 }
+
+/* ---- spectral timbre: the host arithmetic over bl_amd_song_timbre (include/bliss_amd.h) ---- */
+
+/* F = (n_samples / channels) / 512, ref src/frequency_sort.c:50 */
+int bl_amd_timbre_frames(int n_samples, int channels) {
+  if (n_samples < 0 || (channels != 1 && channels != 2)) return -1;
+  return (n_samples / channels) / 512;
+}
+
+/* mean and population standard deviation of a quantity whose sum and sum of squares over `used` frames are given, in
+ * units of `unit`.  used * sumsq - sum^2 is taken exactly (it is below 2^22 * 2^62), so the variance loses nothing to
+ * cancellation before it becomes a double. */
+static double timbre_mean_std(uint64_t sum, uint64_t sumsq, int used, double unit, double *std_out) {
+  if (used < 1) {
+    if (std_out) *std_out = NAN;
+    return NAN;
+  }
+  if (std_out) {
+    const unsigned __int128 n = (unsigned __int128)(unsigned)used * sumsq, s2 = (unsigned __int128)sum * sum;
+    const double var = n > s2 ? (double)(n - s2) / ((double)used * (double)used) : 0.0;
+    *std_out = sqrt(var) * unit;
+  }
+  return (double)sum / (double)used * unit;
+}
+
+double bl_amd_timbre_centroid_hz(const bl_amd_song_timbre *st, int rate, double *std_hz) {
+  if (!st) { if (std_hz) *std_hz = NAN; return NAN; }
+  return timbre_mean_std(st->centroid_sum, st->centroid_sumsq, st->used, (double)rate / 512.0 / 4096.0, std_hz);
+}
+
+double bl_amd_timbre_rolloff_hz(const bl_amd_song_timbre *st, int rate, double *std_hz) {
+  if (!st) { if (std_hz) *std_hz = NAN; return NAN; }
+  return timbre_mean_std(st->rolloff_sum, st->rolloff_sumsq, st->used, (double)rate / 512.0, std_hz);
+}
+
+double bl_amd_timbre_peak_hz(const bl_amd_song_timbre *st, int rate, double *std_hz) {
+  if (!st) { if (std_hz) *std_hz = NAN; return NAN; }
+  return timbre_mean_std(st->peak_sum, st->peak_sumsq, st->used, (double)rate / 512.0, std_hz);
+}

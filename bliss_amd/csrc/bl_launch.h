@@ -2,8 +2,8 @@
  * bl_launch.h — internal seam between the kernel translation units (device code + launch
  * geometry: bl_kernels.hip the launch order of the per-song analysis, whose stages are
  * bl_stats_kernels.hip, bl_freq_kernels.hip and bl_env_kernels.hip; bl_level_kernels.hip the signal
- * levels, bl_matrix_kernels.hip the pairwise matrix, bl_query_kernels.hip the vector queries,
- * bl_rs_kernels.hip the rate converter)
+ * levels, bl_timbre_kernels.hip the per-frame spectral timbre, bl_matrix_kernels.hip the pairwise matrix,
+ * bl_query_kernels.hip the vector queries, bl_rs_kernels.hip the rate converter)
  * and the runtime (bl_runtime.hip: contexts, workspaces, streams, the analysis C-ABI of
  * include/bliss_amd.h; bl_query_api.hip: its matrix, playlist and vector-query C-ABI; bl_multi.hip: the multi-device
  * corpus path).  Also BL_HIP_CHECK, which
@@ -176,6 +176,22 @@ struct bl_level_song { /* what the level kernels read of a bl_amd_song_desc; rec
 /* bl_amd_levels_batch_device: zeroes d_levels, then fills every field of its n_songs records; max_n: the longest n */
 int blk_levels(hipStream_t s, const int16_t *d_pcm, const bl_level_song *d_songs, int n_songs, int max_n, int silence,
                int n_cu, bl_amd_song_levels *d_levels);
+
+/* ---- per-frame spectral timbre (bl_timbre_kernels.hip) -------------------------- */
+
+struct bl_timbre_song { /* one workgroup's song; the records are sorted longest first */
+  unsigned long long pcm_off; /* int16 elements from the arena base, a multiple of 8 */
+  long long frame_off;        /* the song's first record in d_frames: the sum of F over the songs before it in the
+                                 caller's order */
+  int n_frames, channels;     /* F >= 1, 1 | 2 */
+  int out_idx;                /* position in the caller's order: its record in d_songs_out */
+  int reserved;
+};
+int blk_timbre_configure_device(void);                 /* dynamic-LDS attribute, once per device */
+/* bl_amd_timbre_batch_device: one workgroup per record of d_songs; writes every field of the n_songs song records and,
+ * unless d_frames is nullptr, of every frame record */
+int blk_timbre(hipStream_t s, const int16_t *d_pcm, const bl_timbre_song *d_songs, int n_songs, const bl_tables &tb,
+               int pct, unsigned long long min_energy, bl_amd_song_timbre *d_songs_out, bl_amd_frame_timbre *d_frames);
 
 /* ---- benchmark corpus and sample narrowing (bl_kernels.hip) -------------------- */
 

@@ -84,6 +84,8 @@ struct bl_amd_ctx {
   bl_buf radius;
   /* bl_amd_levels_batch_device: the songs' records (bl_level_song) */
   bl_buf level_songs;
+  /* bl_amd_timbre_batch_device: the songs' records (bl_timbre_song), longest first */
+  bl_buf timbre_songs;
 };
 
 /* bl_runtime.hip */

@@ -65,7 +65,8 @@ int ctx_init(bl_amd_ctx *c, int device) {
   BL_HIP_CHECK(hipMalloc(&c->tables_mem, h.size()));
   BL_HIP_CHECK(hipMemcpy(c->tables_mem, h.data(), h.size(), hipMemcpyHostToDevice));
   c->tb = blk_tables_bind(c->tables_mem);
-  if (blk_configure_device() != BL_OK || blk_query_configure_device() != BL_OK) return BL_UNEXPECTED;
+  if (blk_configure_device() != BL_OK || blk_query_configure_device() != BL_OK || blk_timbre_configure_device() != BL_OK)
+    return BL_UNEXPECTED;
   {
     /* songs per launch group; lowered by the tests to exercise the multi-group path */
     const char *gs = getenv("BL_AMD_GROUP_SONGS");
@@ -109,7 +110,7 @@ void ctx_release(bl_amd_ctx *c) {
   prof_collect(c);
   bl_buf *bufs[] = {&c->songs,   &c->stats,   &c->hist, &c->spectrum, &c->energies, &c->lc,
                     &c->results, &c->misc,    &c->arena[0], &c->arena[1], &c->arena22[0], &c->arena22[1],
-                    &c->rs_songs, &c->rs_bank, &c->mx_my, &c->mx_gath, &c->mx_all, &c->mx_order, &c->mx_rows, &c->knn, &c->chain, &c->radius, &c->level_songs};
+                    &c->rs_songs, &c->rs_bank, &c->mx_my, &c->mx_gath, &c->mx_all, &c->mx_order, &c->mx_rows, &c->knn, &c->chain, &c->radius, &c->level_songs, &c->timbre_songs};
   for (bl_buf *b : bufs) release_buf(*b);
   for (int k = 0; k < 2; ++k) {
     unregister_wave(c, k);
@@ -844,6 +845,121 @@ int bl_amd_levels_batch_host(const int16_t *const *h_pcm, const int32_t *n_sampl
                                    nullptr) != BL_OK ||
         !out.down(h_levels + b))
       return BL_UNEXPECTED;
+    b = e;
+  }
+  return BL_OK;
+}
+
+/* ---- per-frame spectral timbre (bl_timbre_kernels.hip) ------------------------ */
+
+/* bl_amd_timbre_frames (bl_api.c) */
+static bool timbre_song_ok(unsigned long long pcm_offset, int n_samples, int channels) {
+  return bl_amd_timbre_frames(n_samples, channels) >= 1 && !(pcm_offset & 7);
+}
+
+/* everything that can be said without a device; *n_frames: the sum of F over the songs */
+static bool timbre_args_ok(const void *d_pcm, const bl_amd_song_desc *h_desc, int n_songs, int pct,
+                           const void *d_songs_out, const void *d_frames_out, long long n_frame_records) {
+  if (!d_pcm || ((uintptr_t)d_pcm & 15) || !h_desc || !d_songs_out || ((uintptr_t)d_songs_out & 7) ||
+      ((uintptr_t)d_frames_out & 7) || n_songs < 1 || pct < 1 || pct > 100)
+    return false;
+  long long total = 0;
+  for (int i = 0; i < n_songs; ++i) {
+    if (!timbre_song_ok(h_desc[i].pcm_offset, h_desc[i].n_samples, h_desc[i].channels)) return false;
+    total += bl_amd_timbre_frames(h_desc[i].n_samples, h_desc[i].channels);
+  }
+  return !d_frames_out || n_frame_records == total;
+}
+
+int bl_amd_ctx_timbre_batch_device(bl_amd_ctx *c, const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs,
+                                   int pct, uint64_t min_energy, bl_amd_song_timbre *d_songs_out,
+                                   bl_amd_frame_timbre *d_frames_out, long long n_frame_records, void *stream) {
+  if (!timbre_args_ok(d_pcm, h_desc, n_songs, pct, d_songs_out, d_frames_out, n_frame_records) || !c)
+    return BL_UNEXPECTED;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DevGuard dg(c->device);
+  if (!dg.ok) return BL_UNEXPECTED;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  /* the records go through a pinned slot, as bl_amd_ctx_levels_batch_device's: copied when this returns */
+  const size_t bytes = sizeof(bl_timbre_song) * (size_t)n_songs;
+  bl_pin_slot *slot = nullptr;
+  if (ring_get(c, bytes, &slot) != BL_OK) return BL_UNEXPECTED;
+  bl_timbre_song *hs = static_cast<bl_timbre_song *>(slot->p);
+  long long frame_off = 0;
+  for (int i = 0; i < n_songs; ++i) {
+    hs[i].pcm_off = h_desc[i].pcm_offset;
+    hs[i].frame_off = frame_off;
+    hs[i].n_frames = bl_amd_timbre_frames(h_desc[i].n_samples, h_desc[i].channels);
+    hs[i].channels = h_desc[i].channels;
+    hs[i].out_idx = i;
+    hs[i].reserved = 0;
+    frame_off += hs[i].n_frames;
+  }
+  /* one workgroup per song, the longest first, as the analysis lays its songs out: the long songs start while there
+   * are short ones left to fill the chip behind them */
+  std::stable_sort(hs, hs + n_songs,
+                   [](const bl_timbre_song &a, const bl_timbre_song &b) { return a.n_frames > b.n_frames; });
+  if (c->ws_used) BL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_ws, 0));
+  if (blr_ensure(c->timbre_songs, bytes) != BL_OK) return BL_UNEXPECTED;
+  bl_timbre_song *d_songs = static_cast<bl_timbre_song *>(c->timbre_songs.p);
+  BL_HIP_CHECK(hipMemcpyAsync(d_songs, hs, bytes, hipMemcpyHostToDevice, s));
+  BL_HIP_CHECK(hipEventRecord(slot->ev, s));
+  slot->busy = true;
+  if (blk_timbre(s, d_pcm, d_songs, n_songs, c->tb, pct, min_energy, d_songs_out, d_frames_out) != BL_OK)
+    return BL_UNEXPECTED;
+  BL_HIP_CHECK(hipEventRecord(c->ev_ws, s));
+  c->ws_used = true;
+  return BL_OK;
+}
+
+int bl_amd_timbre_batch_device(const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs, int pct,
+                               uint64_t min_energy, bl_amd_song_timbre *d_songs_out,
+                               bl_amd_frame_timbre *d_frames_out, long long n_frame_records, void *stream) {
+  if (!timbre_args_ok(d_pcm, h_desc, n_songs, pct, d_songs_out, d_frames_out, n_frame_records)) return BL_UNEXPECTED;
+  return bl_amd_ctx_timbre_batch_device(blr_default_ctx(), d_pcm, h_desc, n_songs, pct, min_energy, d_songs_out,
+                                        d_frames_out, n_frame_records, stream);
+}
+
+int bl_amd_timbre_batch_host(const int16_t *const *h_pcm, const int32_t *n_samples, const int32_t *channels,
+                             int n_songs, int pct, uint64_t min_energy, bl_amd_song_timbre *h_songs_out,
+                             bl_amd_frame_timbre *h_frames_out) {
+  if (!h_pcm || !n_samples || !channels || !h_songs_out || n_songs < 1 || pct < 1 || pct > 100) return BL_UNEXPECTED;
+  for (int i = 0; i < n_songs; ++i)
+    if (!h_pcm[i] || !timbre_song_ok(0, n_samples[i], channels[i])) return BL_UNEXPECTED;
+  bl_amd_ctx *c = blr_default_ctx();
+  if (!c) return BL_UNEXPECTED;
+  DevGuard dg(c->device);
+  if (!dg.ok) return BL_UNEXPECTED;
+  std::vector<bl_amd_song_desc> desc;
+  for (int b = 0; b < n_songs;) {
+    /* one wave, as bl_amd_levels_batch_host's: songs [b, e), every one at a multiple of 8 samples */
+    desc.clear();
+    size_t total = 0;
+    long long frames = 0;
+    int e = b;
+    while (e < n_songs && (e == b || total + (size_t)n_samples[e] <= BL_LEVELS_WAVE_SAMPLES)) {
+      bl_amd_song_desc d;
+      d.pcm_offset = total;
+      d.n_samples = n_samples[e];
+      d.channels = channels[e];
+      d.duration = 0;
+      desc.push_back(d);
+      total += ((size_t)n_samples[e] + 7) & ~(size_t)7;
+      frames += bl_amd_timbre_frames(n_samples[e], channels[e]);
+      ++e;
+    }
+    DevMem arena(sizeof(int16_t) * total), out(sizeof(bl_amd_song_timbre) * (size_t)(e - b)),
+        fout(h_frames_out ? sizeof(bl_amd_frame_timbre) * (size_t)frames : 0);
+    if (!arena.ok() || !out.ok() || !fout.ok()) return BL_UNEXPECTED;
+    for (int i = b; i < e; ++i)
+      BL_HIP_CHECK(hipMemcpy(arena.as<int16_t>() + desc[i - b].pcm_offset, h_pcm[i],
+                             sizeof(int16_t) * (size_t)n_samples[i], hipMemcpyHostToDevice));
+    if (bl_amd_timbre_batch_device(arena.as<int16_t>(), desc.data(), e - b, pct, min_energy,
+                                   out.as<bl_amd_song_timbre>(), fout.as<bl_amd_frame_timbre>(), frames,
+                                   nullptr) != BL_OK ||
+        !out.down(h_songs_out + b) || (h_frames_out && !fout.down(h_frames_out)))
+      return BL_UNEXPECTED;
+    if (h_frames_out) h_frames_out += frames;
     b = e;
   }
   return BL_OK;

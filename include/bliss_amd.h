@@ -489,6 +489,67 @@ int bl_amd_gapless_host(const bl_amd_song_levels *h_levels, int n_songs, uint8_t
 double bl_amd_levels_peak_db(const bl_amd_song_levels *lv, int channel);
 double bl_amd_levels_rms_db(const bl_amd_song_levels *lv, int channel);
 
+/* Spectral timbre: per frame of the frequency analysis, where the power sits (centroid), where it stops (rolloff) and
+ * its strongest bin (peak), summarised over the song.  The reference's author lists "spectral centroid" and "spectral
+ * rolloff" in ROADMAP.md ("Timbral features"); none of it is in the reference's API.  Every field is an exact integer.
+ * Frames are those of ref src/frequency_sort.c:50,67-80: F = (n_samples / channels) / 512, frame t is samples
+ * [512 channels t, 512 channels (t + 1)), stereo averaged with C's truncating / 2, Hann-windowed, libavcodec's
+ * 512-point f32 transform; P_t[d], d = 1..255, is re*re + im*im (unfused): bit for bit what the frequency pass adds
+ * into its spectrum.  Bins 0 and 256 take no part.  Per frame, with Q_t[d] = floor(16 P_t[d]) as a uint64 (power in
+ * sixteenths; the sum over d stays below 2^50):
+ *   energy   sum of Q_t[d];   moment   sum of d Q_t[d]
+ *   rolloff  the smallest d in 1..255 with 100 * (Q_t[1] + .. + Q_t[d]) >= pct * energy (pct = 100: the last
+ *            non-zero bin; energy = 0: 1)
+ *   peak     the smallest d that maximises Q_t[d] (an all-zero frame: 1)
+ *   centroid floor(4096 moment / energy), for energy > 0: in 1/4096 of a bin; one bin is rate / 512 Hz
+ * Per song: a frame is USED iff energy > 0 and energy >= min_energy; the sums and sums of squares of centroid, rolloff
+ * and peak run over the used frames. */
+typedef struct bl_amd_frame_timbre { /* 24 bytes */
+  uint64_t energy, moment;
+  int32_t rolloff, peak;
+} bl_amd_frame_timbre;
+typedef struct bl_amd_song_timbre { /* 72 bytes */
+  uint64_t centroid_sum, centroid_sumsq;
+  uint64_t rolloff_sum, rolloff_sumsq;
+  uint64_t peak_sum, peak_sumsq;
+  uint64_t energy_max; /* over ALL frames */
+  int32_t frames;      /* F */
+  int32_t used;
+  int32_t status;      /* BL_OK */
+  int32_t reserved;    /* 0 */
+} bl_amd_song_timbre;
+/* bl_amd_timbre_frames: F of a song, plain host arithmetic; -1 for n_samples < 0 or channels outside {1, 2}.
+ * bl_amd_timbre_batch_device: the timbre of n_songs songs whose PCM sits in device memory.  The descriptors are those
+ * of bl_amd_analyze_batch_device with other limits: pcm_offset a multiple of 8, channels 1 or 2, F >= 1 (not the
+ * analysers' 5120 samples), duration ignored; d_pcm 16-byte aligned.  1 <= pct <= 100, n_songs >= 1.  d_songs_out:
+ * n_songs records in the caller's order.  d_frames_out may be NULL (n_frame_records is then ignored); otherwise it
+ * receives every frame's record, songs concatenated in the caller's order, song i at the sum of F_j over j < i, and
+ * n_frame_records must equal the sum of all F_j.  Neither output needs zeroing.  A rejected call returns
+ * BL_UNEXPECTED and writes nothing.  Asynchronous on `stream`; h_desc is copied before the call returns.  Calls of
+ * one context are ordered on the device like its batches.  A song's records are a pure function of its samples,
+ * `channels`, pct and min_energy: they depend neither on the other songs, n_songs, the order, the launch shape nor on
+ * whether d_frames_out is NULL, and no sample outside the song's whole frames is read.  Read-only towards
+ * bl_amd_last_energies and bl_amd_last_freq_stats.
+ *   bl_amd_timbre_batch_host: the same from host memory, blocking: the songs are uploaded and analysed in waves;
+ *     h_frames_out may be NULL.
+ *   bl_amd_timbre_centroid_hz / _rolloff_hz / _peak_hz: plain host arithmetic in double from the exact integers, no
+ *     device.  Each returns the mean over the used frames in Hz (sum / used, the centroid divided by 4096, times
+ *     rate / 512) and stores the population standard deviation in *std_hz if that is not NULL; used == 0 gives NaN
+ *     for both. */
+int bl_amd_timbre_frames(int n_samples, int channels);
+int bl_amd_timbre_batch_device(const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs, int pct,
+                               uint64_t min_energy, bl_amd_song_timbre *d_songs_out,
+                               bl_amd_frame_timbre *d_frames_out, long long n_frame_records, void *stream);
+int bl_amd_ctx_timbre_batch_device(bl_amd_ctx *ctx, const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs,
+                                   int pct, uint64_t min_energy, bl_amd_song_timbre *d_songs_out,
+                                   bl_amd_frame_timbre *d_frames_out, long long n_frame_records, void *stream);
+int bl_amd_timbre_batch_host(const int16_t *const *h_pcm, const int32_t *n_samples, const int32_t *channels,
+                             int n_songs, int pct, uint64_t min_energy, bl_amd_song_timbre *h_songs_out,
+                             bl_amd_frame_timbre *h_frames_out);
+double bl_amd_timbre_centroid_hz(const bl_amd_song_timbre *st, int rate, double *std_hz);
+double bl_amd_timbre_rolloff_hz(const bl_amd_song_timbre *st, int rate, double *std_hz);
+double bl_amd_timbre_peak_hz(const bl_amd_song_timbre *st, int rate, double *std_hz);
+
 /* Integer-only synthetic PCM (the benchmark corpus of BASELINE.json),
  * generated in place on the device: song i = seed_base + i, written at
  * h_desc[i].pcm_offset.  Byte-identical to oracle/orc_synth.c. */
