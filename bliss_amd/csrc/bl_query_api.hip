@@ -1,7 +1,8 @@
 /*
  * bl_query_api.hip — the C-ABI of include/bliss_amd.h over force vectors: the pairwise matrix, playlists and the
  * vector queries (k nearest songs, song-to-song chains, radius lists, duplicate groups).  Host code only; contexts,
- * query_call, DevGuard and DevMem come from bl_runtime.hip through bl_runtime.h, the kernels from bl_launch.h.
+ * query_call, call_ctx, CtxGuard, DevGuard and DevMem come from bl_runtime.hip through bl_runtime.h, the kernels from
+ * bl_launch.h.
  *
  * One static body per query holds its argument check, workspace choice and blk_ call; the public entry points call it
  * in one line, for the default context or a given one (`dflt`) and for the library's own rows or vectors outside it
@@ -19,18 +20,14 @@
 
 #include "bl_runtime.h"
 
-/* the context of a call: the calling thread's default one, or the one it was given */
-static bl_amd_ctx *call_ctx(bl_amd_ctx *c, bool dflt) { return dflt ? blr_default_ctx() : c; }
-
 static int matrix_device(const struct force_vector_s *d_vecs, int n, int row_begin, int n_rows,
                          float *d_out, void *stream, bool cosine) {
   if (n <= 0 || n_rows <= 0 || row_begin < 0 || row_begin + n_rows > n || !d_vecs || !d_out)
     return BL_UNEXPECTED;
   bl_amd_ctx *c = blr_default_ctx();
   if (!c) return BL_UNEXPECTED;
-  std::lock_guard<std::mutex> lk(c->mu);
-  DevGuard dg(c->device);
-  if (!dg.ok) return BL_UNEXPECTED;
+  CtxGuard g(c);
+  if (!g.ok()) return BL_UNEXPECTED;
   return blk_pairwise(static_cast<hipStream_t>(stream), d_vecs, n, row_begin, n_rows, d_out, cosine,
                       c->prof ? mark_cb : nullptr, c);
 }
@@ -40,6 +37,7 @@ static int matrix_host(const struct force_vector_s *h_vecs, int n, float *h_out,
   bl_amd_ctx *c = blr_default_ctx();
   if (!c) return BL_UNEXPECTED;
   DevGuard dg(c->device);
+  if (!dg.ok) return BL_UNEXPECTED;
   DevMem dv(sizeof(struct force_vector_s) * (size_t)n), dout(sizeof(float) * (size_t)n * n);
   return dv.up(h_vecs) && dout.ok() &&
                  matrix_device(dv.as<struct force_vector_s>(), n, 0, n, dout.as<float>(), nullptr, cosine) == BL_OK &&
@@ -69,6 +67,7 @@ static int playlist_host(const struct force_vector_s *h_vecs, int n, int seed_in
   bl_amd_ctx *c = blr_default_ctx();
   if (!c) return BL_UNEXPECTED;
   DevGuard dg(c->device);
+  if (!dg.ok) return BL_UNEXPECTED;
   DevMem dv(sizeof(struct force_vector_s) * (size_t)n), dord(sizeof(int32_t) * (size_t)n), dd(sizeof(float) * (size_t)n);
   return dv.up(h_vecs) && dord.ok() && dd.ok() &&
                  playlist_device(dv.as<struct force_vector_s>(), n, seed_index, seed, dord.as<int32_t>(), dd.as<float>(),

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "bl_launch.h"
+#include "bl_resample.h"
 
 #define BL_MAX_DEVICES 16
 #define BL_GROUP_SONGS_MAX 32768 /* gridDim.y of the (blocks, songs) launch grids */
@@ -49,7 +50,7 @@ struct bl_amd_ctx {
   int last_first = 0, last_songs = 0, last_parts = 0;
   bl_tables tb{};
   void *tables_mem = nullptr;
-  bl_buf songs, stats, hist, spectrum, energies, lc, results, misc;
+  bl_buf songs, stats, hist, spectrum, energies, lc, results;
   bl_pin_slot ring[BL_PIN_SLOTS];
   int ring_next = 0;
   /* profiling */
@@ -74,7 +75,7 @@ struct bl_amd_ctx {
   int rs_rate = 0, rs_kind = -1, rs_bank_lds = 0;
   bl_rs_geom rs_geom{};
   size_t rs_lds = 0;
-  int rs_taps = 0, rs_phases = 0, rs_src_incr = 0, rs_dst_incr = 0;
+  bl_rs_plan rs_plan{}; /* the uploaded plan's geometry, for bl_rs_out_frames; the bank pointers are null */
   /* bl_amd_knn_device: the cosine prep of the vectors and the column splits' partial lists */
   bl_buf knn;
   /* bl_amd_chain_device, bl_amd_mix_device: cosine prep, the column split's per-chain state and played bits (or the
@@ -121,6 +122,30 @@ struct DevGuard {
   }
 };
 
+/* a call that uses context c's workspace: the context locked and its device current until the call returns */
+struct CtxGuard {
+  std::lock_guard<std::mutex> lk;
+  DevGuard dg;
+  explicit CtxGuard(bl_amd_ctx *c) : lk(c->mu), dg(c->device) {}
+  bool ok() const { return dg.ok; }
+};
+
+/* the context of a call: the calling thread's default one, or the one it was given */
+inline bl_amd_ctx *call_ctx(bl_amd_ctx *c, bool dflt) { return dflt ? blr_default_ctx() : c; }
+
+/* The workspace is shared by every call on a context, whatever stream it is enqueued on: a call waits, on the device,
+ * for the previous user before anything of it writes a workspace block (ws_wait), and leaves its stream's position
+ * behind as the hand-over point after its last launch (ws_pass).  The mutex only orders the enqueues. */
+inline int ws_wait(bl_amd_ctx *c, hipStream_t s) {
+  if (c->ws_used) BL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_ws, 0));
+  return BL_OK;
+}
+inline int ws_pass(bl_amd_ctx *c, hipStream_t s) {
+  BL_HIP_CHECK(hipEventRecord(c->ev_ws, s));
+  c->ws_used = true;
+  return BL_OK;
+}
+
 /* a device block of the *_host entry points, freed when the call returns; zero bytes: no block, p stays nullptr.
  * Every step answers "did it work", so a call is one && chain and any failure is BL_UNEXPECTED. */
 struct DevMem {
@@ -151,15 +176,11 @@ inline bool rows_ok(int n, int row_begin, int n_rows) {
  * last user waited for on `stream` and `buf` grown to `bytes`; then the stream's position becomes the hand-over point */
 template <class Launch>
 int query_call(bl_amd_ctx *c, void *stream, bl_buf &buf, size_t bytes, Launch launch) {
-  std::lock_guard<std::mutex> lk(c->mu);
-  DevGuard dg(c->device);
-  if (!dg.ok) return BL_UNEXPECTED;
+  CtxGuard g(c);
+  if (!g.ok()) return BL_UNEXPECTED;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (c->ws_used) BL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_ws, 0));
-  if (blr_ensure(buf, bytes) != BL_OK || launch(s, buf.p) != BL_OK) return BL_UNEXPECTED;
-  BL_HIP_CHECK(hipEventRecord(c->ev_ws, s));
-  c->ws_used = true;
-  return BL_OK;
+  if (ws_wait(c, s) != BL_OK || blr_ensure(buf, bytes) != BL_OK || launch(s, buf.p) != BL_OK) return BL_UNEXPECTED;
+  return ws_pass(c, s);
 }
 
 /* the profiling callback of the launchers (blk_mark_fn); user: the context */

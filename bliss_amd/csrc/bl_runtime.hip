@@ -13,7 +13,14 @@
  * Asynchrony.  bl_amd_analyze_batch_device() only enqueues: descriptors go through a ring of
  * pinned slots (hipMemcpyAsync from pinned memory does not block), launch groups of more than
  * 32 768 songs follow each other on the stream, and the shared workspace is handed from one
- * batch to the next by an event, not by a host synchronisation.
+ * batch to the next by an event, not by a host synchronisation.  Every entry point that uploads
+ * per-song records (analysis, rate conversion, levels, timbre, synthesis, bld_mean_variance_host)
+ * does so through record_call, the one place that knows this protocol; the vector queries have
+ * query_call (bl_runtime.h), which shares the hand-over (ws_wait, ws_pass) with it.
+ *
+ * Guards.  An entry point that uses the workspace takes a CtxGuard (context lock + device guard);
+ * the *_host forms, the selftests and bl_amd_narrow_s32_device use no workspace themselves and
+ * take a DevGuard alone.  Either way a device that cannot be made current ends the call.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -41,6 +48,11 @@ void release_buf(bl_buf &b) {
   b.p = nullptr;
   b.cap = 0;
 }
+
+/* the streams and events a context owns from ctx_init to ctx_release (streams[] of the host batch come on first use) */
+hipStream_t bl_amd_ctx::*const kCtxStreams[] = {&bl_amd_ctx::side, &bl_amd_ctx::side2};
+hipEvent_t bl_amd_ctx::*const kCtxEvents[] = {&bl_amd_ctx::ev_env, &bl_amd_ctx::ev_tail, &bl_amd_ctx::ev_head,
+                                              &bl_amd_ctx::ev_tail2, &bl_amd_ctx::ev_ws};
 
 int ctx_init(bl_amd_ctx *c, int device) {
   int count = 0;
@@ -73,13 +85,8 @@ int ctx_init(bl_amd_ctx *c, int device) {
     int g = gs ? atoi(gs) : BL_GROUP_SONGS_MAX;
     c->group_songs = g < 1 ? 1 : (g > BL_GROUP_SONGS_MAX ? BL_GROUP_SONGS_MAX : g);
   }
-  BL_HIP_CHECK(hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
-  BL_HIP_CHECK(hipStreamCreateWithFlags(&c->side2, hipStreamNonBlocking));
-  BL_HIP_CHECK(hipEventCreateWithFlags(&c->ev_env, hipEventDisableTiming));
-  BL_HIP_CHECK(hipEventCreateWithFlags(&c->ev_tail, hipEventDisableTiming));
-  BL_HIP_CHECK(hipEventCreateWithFlags(&c->ev_head, hipEventDisableTiming));
-  BL_HIP_CHECK(hipEventCreateWithFlags(&c->ev_tail2, hipEventDisableTiming));
-  BL_HIP_CHECK(hipEventCreateWithFlags(&c->ev_ws, hipEventDisableTiming));
+  for (auto m : kCtxStreams) BL_HIP_CHECK(hipStreamCreateWithFlags(&(c->*m), hipStreamNonBlocking));
+  for (auto m : kCtxEvents) BL_HIP_CHECK(hipEventCreateWithFlags(&(c->*m), hipEventDisableTiming));
   for (int k = 0; k < BL_PIN_SLOTS; ++k)
     BL_HIP_CHECK(hipEventCreateWithFlags(&c->ring[k].ev, hipEventDisableTiming));
   return BL_OK;
@@ -109,7 +116,7 @@ void ctx_release(bl_amd_ctx *c) {
   (void)hipDeviceSynchronize();
   prof_collect(c);
   bl_buf *bufs[] = {&c->songs,   &c->stats,   &c->hist, &c->spectrum, &c->energies, &c->lc,
-                    &c->results, &c->misc,    &c->arena[0], &c->arena[1], &c->arena22[0], &c->arena22[1],
+                    &c->results, &c->arena[0], &c->arena[1], &c->arena22[0], &c->arena22[1],
                     &c->rs_songs, &c->rs_bank, &c->mx_my, &c->mx_gath, &c->mx_all, &c->mx_order, &c->mx_rows, &c->knn, &c->chain, &c->radius, &c->level_songs, &c->timbre_songs};
   for (bl_buf *b : bufs) release_buf(*b);
   for (int k = 0; k < 2; ++k) {
@@ -127,17 +134,14 @@ void ctx_release(bl_amd_ctx *c) {
   }
   if (c->tables_mem) (void)hipFree(c->tables_mem);
   c->tables_mem = nullptr;
-  if (c->side) (void)hipStreamDestroy(c->side);
-  if (c->side2) (void)hipStreamDestroy(c->side2);
-  if (c->ev_env) (void)hipEventDestroy(c->ev_env);
-  if (c->ev_tail) (void)hipEventDestroy(c->ev_tail);
-  if (c->ev_head) (void)hipEventDestroy(c->ev_head);
-  if (c->ev_tail2) (void)hipEventDestroy(c->ev_tail2);
-  c->side2 = nullptr;
-  c->ev_head = c->ev_tail2 = nullptr;
-  if (c->ev_ws) (void)hipEventDestroy(c->ev_ws);
-  c->side = nullptr;
-  c->ev_env = c->ev_tail = c->ev_ws = nullptr;
+  for (auto m : kCtxStreams) {
+    if (c->*m) (void)hipStreamDestroy(c->*m);
+    c->*m = nullptr;
+  }
+  for (auto m : kCtxEvents) {
+    if (c->*m) (void)hipEventDestroy(c->*m);
+    c->*m = nullptr;
+  }
   c->ws_used = false;
   c->rs_rate = 0;
   c->rs_kind = -1;
@@ -167,6 +171,29 @@ int ring_get(bl_amd_ctx *c, size_t bytes, bl_pin_slot **out) {
   }
   *out = &s;
   return BL_OK;
+}
+
+/* One call that uploads n per-song records of type T into `block` and launches on them; the caller holds c->mu and has
+ * made c->device current.  `fill(T *h)` writes the records into a pinned slot (BL_OK, or BL_UNEXPECTED to refuse the
+ * call), `launch(const T *h, T *d)` enqueues the kernels on `s` and grows whatever other workspace they need.
+ * The caller's own descriptors are read by `fill` alone, so they are the caller's again when the call returns, and
+ * hipMemcpyAsync from pinned memory does not block, so nothing here waits for the device.  The order is the protocol:
+ * the wait for the workspace's last user is on `s` before the copy (the record block is workspace); the slot counts as
+ * in flight only once its event is recorded behind the copy, so a call that fails before that leaves the slot free
+ * and the hand-over untouched; the hand-over point moves behind the last launch. */
+template <class T, class Fill, class Launch>
+int record_call(bl_amd_ctx *c, hipStream_t s, bl_buf &block, int n, Fill fill, Launch launch) {
+  const size_t bytes = sizeof(T) * (size_t)n;
+  bl_pin_slot *slot = nullptr;
+  if (ring_get(c, bytes, &slot) != BL_OK) return BL_UNEXPECTED;
+  T *h = static_cast<T *>(slot->p);
+  if (fill(h) != BL_OK || ws_wait(c, s) != BL_OK || blr_ensure(block, bytes) != BL_OK) return BL_UNEXPECTED;
+  T *d = static_cast<T *>(block.p);
+  BL_HIP_CHECK(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s));
+  BL_HIP_CHECK(hipEventRecord(slot->ev, s));
+  slot->busy = true;
+  if (launch(h, d) != BL_OK) return BL_UNEXPECTED;
+  return ws_pass(c, s);
 }
 
 int validate_desc(const bl_amd_song_desc &d, int i) {
@@ -276,82 +303,74 @@ int blr_analyze_device(bl_amd_ctx *c, const int16_t *d_pcm, const bl_amd_song_de
     if (validate_desc(h_desc[i], i) != BL_OK) return BL_UNEXPECTED;
   const int G = c->group_songs;
   const int n_groups = (n_songs + G - 1) / G;
-  /* all descriptors of the call in one pinned slot, one asynchronous copy */
-  bl_pin_slot *slot = nullptr;
-  if (ring_get(c, sizeof(bl_dsong) * (size_t)n_songs, &slot) != BL_OK) return BL_UNEXPECTED;
-  bl_dsong *hs = static_cast<bl_dsong *>(slot->p);
   std::vector<long long> env_total(n_groups);
   std::vector<int> max_n(n_groups);
-  long long env_max = 0;
-  for (int gi = 0; gi < n_groups; ++gi) {
-    const int b = gi * G, cnt = std::min(G, n_songs - b);
-    fill_group(h_desc + b, cnt, hs + b, env_total[gi], max_n[gi]);
-    env_max = std::max(env_max, env_total[gi]);
-  }
-  const int gmax = std::min(G, n_songs);
-  /* the workspace is shared by every call on this context: a batch enqueued on another
-   * stream waits (on the device) for the previous user; the mutex only orders the enqueues */
-  if (c->ws_used) BL_HIP_CHECK(hipStreamWaitEvent(stream, c->ev_ws, 0));
-  if (blr_ensure(c->songs, sizeof(bl_dsong) * (size_t)n_songs) != BL_OK) return BL_UNEXPECTED;
-  if (blr_ensure(c->stats, sizeof(bl_dstats) * (size_t)gmax) != BL_OK) return BL_UNEXPECTED;
-  if (blr_ensure(c->hist, sizeof(unsigned) * BL_HIST_BINS * (size_t)gmax) != BL_OK) return BL_UNEXPECTED;
-  if (blr_ensure(c->spectrum, sizeof(float) * 256 * (size_t)gmax) != BL_OK) return BL_UNEXPECTED;
-  if (blr_ensure(c->energies, sizeof(float) * (size_t)env_max) != BL_OK) return BL_UNEXPECTED;
-  if (blr_ensure(c->lc, sizeof(double) * (size_t)env_max) != BL_OK) return BL_UNEXPECTED;
-  bl_dsong *d_songs = static_cast<bl_dsong *>(c->songs.p);
-  BL_HIP_CHECK(hipMemcpyAsync(d_songs, hs, sizeof(bl_dsong) * (size_t)n_songs, hipMemcpyHostToDevice,
-                              stream));
-  BL_HIP_CHECK(hipEventRecord(slot->ev, stream));
-  slot->busy = true;
-  for (int gi = 0; gi < n_groups; ++gi) {
-    const int b = gi * G, cnt = std::min(G, n_songs - b);
-    blk_analyze_args a;
-    a.pcm = d_pcm;
-    a.songs = d_songs + b;
-    a.stats = static_cast<bl_dstats *>(c->stats.p);
-    a.hist = static_cast<unsigned *>(c->hist.p);
-    a.spectrum = static_cast<float *>(c->spectrum.p);
-    a.energies = static_cast<float *>(c->energies.p);
-    a.lc = static_cast<double *>(c->lc.p);
-    a.results = d_results + b;
-    a.n_songs = cnt;
-    a.max_n = max_n[gi];
-    /* a mixed-length group (sorted longest first by fill_group): the songs longer than a quarter of the longest
-     * go first, in whole waves of the tail kernel, if both parts stay wide enough to fill the chip */
-    if (cnt >= 1024 && hs[b].n != hs[b + cnt - 1].n) {
-      int k = 0;
-      while (k < cnt && hs[b + k].n > max_n[gi] / 4) ++k;
-      k = (k + 63) / 64 * 64;
-      if (k >= 256 && k <= cnt - 256) {
-        a.n_head = k;
-        a.max_n_rest = hs[b + k].n;
-      }
+  /* all descriptors of the call in one pinned slot, one asynchronous copy */
+  auto fill = [&](bl_dsong *hs) {
+    for (int gi = 0; gi < n_groups; ++gi) {
+      const int b = gi * G, cnt = std::min(G, n_songs - b);
+      fill_group(h_desc + b, cnt, hs + b, env_total[gi], max_n[gi]);
     }
-    a.what = what;
-    a.n_cu = c->n_cu;
-    a.tb = c->tb;
-    a.stream = stream;
+    return BL_OK;
+  };
+  auto launch = [&](const bl_dsong *hs, bl_dsong *d_songs) {
+    const size_t gmax = (size_t)std::min(G, n_songs);
+    size_t env_max = 0;
+    for (long long t : env_total) env_max = std::max(env_max, (size_t)t);
+    if (blr_ensure(c->stats, sizeof(bl_dstats) * gmax) != BL_OK) return BL_UNEXPECTED;
+    if (blr_ensure(c->hist, sizeof(unsigned) * BL_HIST_BINS * gmax) != BL_OK) return BL_UNEXPECTED;
+    if (blr_ensure(c->spectrum, sizeof(float) * 256 * gmax) != BL_OK) return BL_UNEXPECTED;
+    if (blr_ensure(c->energies, sizeof(float) * env_max) != BL_OK) return BL_UNEXPECTED;
+    if (blr_ensure(c->lc, sizeof(double) * env_max) != BL_OK) return BL_UNEXPECTED;
+    for (int gi = 0; gi < n_groups; ++gi) {
+      const int b = gi * G, cnt = std::min(G, n_songs - b);
+      blk_analyze_args a;
+      a.pcm = d_pcm;
+      a.songs = d_songs + b;
+      a.stats = static_cast<bl_dstats *>(c->stats.p);
+      a.hist = static_cast<unsigned *>(c->hist.p);
+      a.spectrum = static_cast<float *>(c->spectrum.p);
+      a.energies = static_cast<float *>(c->energies.p);
+      a.lc = static_cast<double *>(c->lc.p);
+      a.results = d_results + b;
+      a.n_songs = cnt;
+      a.max_n = max_n[gi];
+      /* a mixed-length group (sorted longest first by fill_group): the songs longer than a quarter of the longest
+       * go first, in whole waves of the tail kernel, if both parts stay wide enough to fill the chip */
+      if (cnt >= 1024 && hs[b].n != hs[b + cnt - 1].n) {
+        int k = 0;
+        while (k < cnt && hs[b + k].n > max_n[gi] / 4) ++k;
+        k = (k + 63) / 64 * 64;
+        if (k >= 256 && k <= cnt - 256) {
+          a.n_head = k;
+          a.max_n_rest = hs[b + k].n;
+        }
+      }
+      a.what = what;
+      a.n_cu = c->n_cu;
+      a.tb = c->tb;
+      a.stream = stream;
 #ifdef BL_AMD_MEASURE
-    a.side = getenv("BL_AMD_NO_SIDE") ? nullptr : c->side; /* measurement builds only: serialise the tail */
+      a.side = getenv("BL_AMD_NO_SIDE") ? nullptr : c->side; /* measurement builds only: serialise the tail */
 #else
-    a.side = c->side;
+      a.side = c->side;
 #endif
-    a.ev_env = c->ev_env;
-    a.ev_tail = c->ev_tail;
-    a.side2 = a.side ? c->side2 : nullptr;
-    a.ev_head = c->ev_head;
-    a.ev_tail2 = c->ev_tail2;
-    a.mark = c->prof ? mark_cb : nullptr;
-    a.mark_user = c;
-    if (blk_analyze(a) != BL_OK) return BL_UNEXPECTED;
-    c->last_env_total = env_total[gi];
-    c->last_first = b;
-    c->last_songs = cnt;
-    c->last_parts = blk_analyze_parts(what);
-  }
-  BL_HIP_CHECK(hipEventRecord(c->ev_ws, stream));
-  c->ws_used = true;
-  return BL_OK;
+      a.ev_env = c->ev_env;
+      a.ev_tail = c->ev_tail;
+      a.side2 = a.side ? c->side2 : nullptr;
+      a.ev_head = c->ev_head;
+      a.ev_tail2 = c->ev_tail2;
+      a.mark = c->prof ? mark_cb : nullptr;
+      a.mark_user = c;
+      if (blk_analyze(a) != BL_OK) return BL_UNEXPECTED;
+      c->last_env_total = env_total[gi];
+      c->last_first = b;
+      c->last_songs = cnt;
+      c->last_parts = blk_analyze_parts(what);
+    }
+    return BL_OK;
+  };
+  return record_call<bl_dsong>(c, stream, c->songs, n_songs, fill, launch);
 }
 
 /* ---- device rate conversion (bl_rs_kernels.hip), shared by the C-ABI and the host batch ---- */
@@ -379,7 +398,7 @@ static int rs_prepare(bl_amd_ctx *c, int in_rate, int in_is_s32) {
   std::vector<int32_t> host(elems);
   if (in_is_s32) memcpy(host.data(), p.fbank, elems * sizeof(float));
   else for (size_t i = 0; i < elems; ++i) host[i] = p.ibank[i];
-  bl_rs_plan_free(&p);
+  bl_rs_plan_free(&p); /* p stays as the geometry, its bank pointers null */
   /* a plan change is rare; kernels of the previous plan may still be reading the old bank */
   BL_HIP_CHECK(hipDeviceSynchronize());
   c->rs_rate = 0;
@@ -389,10 +408,7 @@ static int rs_prepare(bl_amd_ctx *c, int in_rate, int in_is_s32) {
   c->rs_geom = g;
   c->rs_lds = lds;
   c->rs_bank_lds = bank_lds;
-  c->rs_taps = p.taps;
-  c->rs_phases = p.phase_count;
-  c->rs_src_incr = p.src_incr;
-  c->rs_dst_incr = p.dst_incr;
+  c->rs_plan = p;
   c->rs_rate = in_rate;
   c->rs_kind = in_is_s32;
   return BL_OK;
@@ -404,55 +420,43 @@ int blr_resample_device(bl_amd_ctx *c, const void *d_in, int in_is_s32, const bl
                         int n_songs, int in_rate, int16_t *d_out, hipStream_t s) {
   in_is_s32 = in_is_s32 != 0;
   if (rs_prepare(c, in_rate, in_is_s32) != BL_OK) return BL_UNEXPECTED;
-  bl_rs_plan geo;
-  memset(&geo, 0, sizeof geo);
-  geo.taps = c->rs_taps;
-  geo.phase_count = c->rs_phases;
-  geo.src_incr = c->rs_src_incr;
-  geo.dst_incr = c->rs_dst_incr;
-  bl_pin_slot *slot = nullptr;
-  if (ring_get(c, sizeof(bl_rs_dsong) * (size_t)n_songs, &slot) != BL_OK) return BL_UNEXPECTED;
-  bl_rs_dsong *hs = static_cast<bl_rs_dsong *>(slot->p);
-  for (int i = 0; i < n_songs; ++i) {
-    const bl_amd_resample_desc &d = h_desc[i];
-    size_t refl = 0;
-    const size_t of = d.frames > 0 ? bl_rs_out_frames(&geo, (size_t)d.frames, &refl) : 0;
-    if (of == 0 || of > (size_t)INT32_MAX / 2 || (d.channels != 1 && d.channels != 2) ||
-        (d.out_offset & 1) || (d.channels == 2 && (d.in_offset & 1))) {
-      fprintf(stderr,
-              "bliss_amd: resample: song %d rejected (frames=%d channels=%d in_offset=%llu out_offset=%llu): "
-              "need frames > filter length (%d), channels 1|2, even offsets\n",
-              i, d.frames, d.channels, (unsigned long long)d.in_offset, (unsigned long long)d.out_offset,
-              c->rs_taps);
-      return BL_UNEXPECTED;
+  auto fill = [&](bl_rs_dsong *hs) {
+    for (int i = 0; i < n_songs; ++i) {
+      const bl_amd_resample_desc &d = h_desc[i];
+      size_t refl = 0;
+      const size_t of = d.frames > 0 ? bl_rs_out_frames(&c->rs_plan, (size_t)d.frames, &refl) : 0;
+      if (of == 0 || of > (size_t)INT32_MAX / 2 || (d.channels != 1 && d.channels != 2) ||
+          (d.out_offset & 1) || (d.channels == 2 && (d.in_offset & 1))) {
+        fprintf(stderr,
+                "bliss_amd: resample: song %d rejected (frames=%d channels=%d in_offset=%llu out_offset=%llu): "
+                "need frames > filter length (%d), channels 1|2, even offsets\n",
+                i, d.frames, d.channels, (unsigned long long)d.in_offset, (unsigned long long)d.out_offset,
+                c->rs_plan.taps);
+        return BL_UNEXPECTED;
+      }
+      hs[i].in_off = d.in_offset;
+      hs[i].out_off = d.out_offset;
+      hs[i].frames = d.frames;
+      hs[i].channels = d.channels;
+      hs[i].out_frames = (int)of;
+      hs[i].refl = (int)refl;
     }
-    hs[i].in_off = d.in_offset;
-    hs[i].out_off = d.out_offset;
-    hs[i].frames = d.frames;
-    hs[i].channels = d.channels;
-    hs[i].out_frames = (int)of;
-    hs[i].refl = (int)refl;
-  }
-  if (c->ws_used) BL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_ws, 0));
-  if (blr_ensure(c->rs_songs, sizeof(bl_rs_dsong) * (size_t)n_songs) != BL_OK) return BL_UNEXPECTED;
-  bl_rs_dsong *d_songs = static_cast<bl_rs_dsong *>(c->rs_songs.p);
-  BL_HIP_CHECK(hipMemcpyAsync(d_songs, hs, sizeof(bl_rs_dsong) * (size_t)n_songs, hipMemcpyHostToDevice, s));
-  BL_HIP_CHECK(hipEventRecord(slot->ev, s));
-  slot->busy = true;
-  const int G = BL_GROUP_SONGS_MAX;
-  for (int b = 0; b < n_songs; b += G) {
-    const int cnt = std::min(G, n_songs - b);
-    int max_out = 0;
-    for (int i = 0; i < cnt; ++i) max_out = std::max(max_out, hs[b + i].out_frames);
-    if (blk_resample(s, d_in, in_is_s32, d_songs + b, cnt, max_out, c->rs_bank.p, c->rs_geom, c->rs_lds,
-                     c->rs_bank_lds, d_out) != BL_OK)
-      return BL_UNEXPECTED;
-  }
-  BL_HIP_CHECK(hipEventRecord(c->ev_ws, s));
-  c->ws_used = true;
-  return BL_OK;
+    return BL_OK;
+  };
+  auto launch = [&](const bl_rs_dsong *hs, bl_rs_dsong *d_songs) {
+    const int G = BL_GROUP_SONGS_MAX;
+    for (int b = 0; b < n_songs; b += G) {
+      const int cnt = std::min(G, n_songs - b);
+      int max_out = 0;
+      for (int i = 0; i < cnt; ++i) max_out = std::max(max_out, hs[b + i].out_frames);
+      if (blk_resample(s, d_in, in_is_s32, d_songs + b, cnt, max_out, c->rs_bank.p, c->rs_geom, c->rs_lds,
+                       c->rs_bank_lds, d_out) != BL_OK)
+        return BL_UNEXPECTED;
+    }
+    return BL_OK;
+  };
+  return record_call<bl_rs_dsong>(c, s, c->rs_songs, n_songs, fill, launch);
 }
-
 
 /* ---- host-memory batch: pinned staging, copy/compute overlap on 2 streams ---- */
 #ifndef BL_STAGE_THREADS
@@ -657,6 +661,59 @@ int blr_analyze_host(bl_amd_ctx *c, const void *const *h_pcm, int pcm_is_s32, co
   return rc;
 }
 
+/* ---- host forms of the signal levels and the spectral timbre: what the two share ---- */
+
+/* samples per wave of bl_amd_levels_batch_host and bl_amd_timbre_batch_host: the songs are uploaded, analysed and
+ * fetched 256 MiB of PCM at a time (a song longer than that is a wave of its own) */
+#define BL_HOST_WAVE_SAMPLES ((size_t)128 << 20)
+
+/* The host songs in waves: songs [b, e) laid out in a device arena, every one at a multiple of 8 samples, as many as
+ * fit BL_HOST_WAVE_SAMPLES but at least one, copied there, and `wave(d_arena, desc, b, e)` called on them with
+ * desc[i - b] the place of song i.  The arena is freed when `wave` returns, so `wave` fetches what it computed. */
+template <class Wave>
+static int host_waves(const int16_t *const *h_pcm, const int32_t *n_samples, const int32_t *channels, int n_songs,
+                      Wave wave) {
+  std::vector<bl_amd_song_desc> desc;
+  for (int b = 0, e; b < n_songs; b = e) {
+    desc.clear();
+    size_t total = 0;
+    for (e = b; e < n_songs; ++e) {
+      const size_t padded = ((size_t)n_samples[e] + 7) & ~(size_t)7;
+      if (e > b && total + padded > BL_HOST_WAVE_SAMPLES) break;
+      bl_amd_song_desc d;
+      d.pcm_offset = total;
+      d.n_samples = n_samples[e];
+      d.channels = channels[e];
+      d.duration = 0;
+      desc.push_back(d);
+      total += padded;
+    }
+    DevMem arena(sizeof(int16_t) * total);
+    if (!arena.ok()) return BL_UNEXPECTED;
+    for (int i = b; i < e; ++i)
+      BL_HIP_CHECK(hipMemcpy(arena.as<int16_t>() + desc[i - b].pcm_offset, h_pcm[i],
+                             sizeof(int16_t) * (size_t)n_samples[i], hipMemcpyHostToDevice));
+    if (wave(arena.as<int16_t>(), desc.data(), b, e) != BL_OK) return BL_UNEXPECTED;
+  }
+  return BL_OK;
+}
+
+/* the device sweeps behind the selftests: `sweep(d, n_cu)` adds to n zeroed counters on the device */
+template <class Sweep>
+static int selftest(uint64_t *counts, int n, Sweep sweep) {
+  unsigned long long h[6];
+  bl_amd_ctx *c = counts ? blr_default_ctx() : nullptr;
+  if (!c) return BL_UNEXPECTED;
+  DevGuard dg(c->device);
+  if (!dg.ok) return BL_UNEXPECTED;
+  DevMem d(sizeof(unsigned long long) * (size_t)n);
+  if (!d.ok() || hipMemset(d.p, 0, d.bytes) != hipSuccess || sweep(d.as<unsigned long long>(), c->n_cu) != BL_OK ||
+      !d.down(h))
+    return BL_UNEXPECTED;
+  for (int k = 0; k < n; ++k) counts[k] = h[k];
+  return BL_OK;
+}
+
 /* ========================================================================= */
 /* C-ABI                                                                      */
 
@@ -717,8 +774,8 @@ void bl_amd_profile(int enable) {
 void bl_amd_profile_reset(void) {
   bl_amd_ctx *c = blr_default_ctx();
   if (!c) return;
-  std::lock_guard<std::mutex> lk(c->mu);
-  DevGuard dg(c->device);
+  CtxGuard g(c);
+  if (!g.ok()) return;
   prof_collect(c);
   for (int k = 0; k < PK_COUNT; ++k) { c->prof_ms[k] = 0; c->prof_n[k] = 0; }
 }
@@ -729,8 +786,8 @@ double bl_amd_profile_ms(const char *name, int *launches) {
   if (launches) *launches = 0;
   bl_amd_ctx *c = blr_default_ctx();
   if (!c || !name) return -1.0;
-  std::lock_guard<std::mutex> lk(c->mu);
-  DevGuard dg(c->device);
+  CtxGuard g(c);
+  if (!g.ok()) return -1.0;
   prof_collect(c);
   for (int k = 0; k < PK_COUNT; ++k)
     if (!strcmp(name, kProfNames[k])) {
@@ -743,9 +800,8 @@ double bl_amd_profile_ms(const char *name, int *launches) {
 int bl_amd_ctx_analyze_batch_device(bl_amd_ctx *ctx, const int16_t *d_pcm, const bl_amd_song_desc *h_desc,
                                     int n_songs, bl_amd_song_result *d_results, void *stream) {
   if (!ctx || n_songs <= 0 || !d_pcm || !h_desc || !d_results) return BL_UNEXPECTED;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  DevGuard dg(ctx->device);
-  if (!dg.ok) return BL_UNEXPECTED;
+  CtxGuard g(ctx);
+  if (!g.ok()) return BL_UNEXPECTED;
   return blr_analyze_device(ctx, d_pcm, h_desc, n_songs, d_results, static_cast<hipStream_t>(stream), 7);
 }
 
@@ -756,58 +812,42 @@ int bl_amd_analyze_batch_device(const int16_t *d_pcm, const bl_amd_song_desc *h_
 
 /* ---- signal levels (bl_level_kernels.hip) ---------------------------------- */
 
-/* samples per wave of bl_amd_levels_batch_host: the songs are uploaded, analysed and fetched 256 MiB of PCM at a
- * time (a song longer than that is a wave of its own) */
-#define BL_LEVELS_WAVE_SAMPLES ((size_t)128 << 20)
-
 static bool levels_song_ok(unsigned long long pcm_offset, int n_samples, int channels) {
   return n_samples >= 2 && (channels == 1 || channels == 2) && !(pcm_offset & 7);
 }
 
-static bool levels_args_ok(const void *d_pcm, const bl_amd_song_desc *h_desc, int n_songs, int silence,
-                           const void *d_levels) {
+static int levels_device(bl_amd_ctx *c, bool dflt, const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs,
+                         int silence, bl_amd_song_levels *d_levels, void *stream) {
   if (!d_pcm || ((uintptr_t)d_pcm & 15) || !h_desc || !d_levels || n_songs < 1 || silence < 0 || silence > 32767)
-    return false;
+    return BL_UNEXPECTED;
   for (int i = 0; i < n_songs; ++i)
-    if (!levels_song_ok(h_desc[i].pcm_offset, h_desc[i].n_samples, h_desc[i].channels)) return false;
-  return true;
+    if (!levels_song_ok(h_desc[i].pcm_offset, h_desc[i].n_samples, h_desc[i].channels)) return BL_UNEXPECTED;
+  if (!(c = call_ctx(c, dflt))) return BL_UNEXPECTED;
+  CtxGuard g(c);
+  if (!g.ok()) return BL_UNEXPECTED;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  int max_n = 0;
+  return record_call<bl_level_song>(c, s, c->level_songs, n_songs, [&](bl_level_song *hs) {
+    for (int i = 0; i < n_songs; ++i) {
+      hs[i].pcm_off = h_desc[i].pcm_offset;
+      hs[i].n = h_desc[i].n_samples;
+      hs[i].channels = h_desc[i].channels;
+      max_n = std::max(max_n, h_desc[i].n_samples);
+    }
+    return BL_OK;
+  }, [&](const bl_level_song *, bl_level_song *d_songs) {
+    return blk_levels(s, d_pcm, d_songs, n_songs, max_n, silence, c->n_cu, d_levels);
+  });
 }
 
 int bl_amd_ctx_levels_batch_device(bl_amd_ctx *c, const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs,
                                    int silence, bl_amd_song_levels *d_levels, void *stream) {
-  if (!levels_args_ok(d_pcm, h_desc, n_songs, silence, d_levels) || !c) return BL_UNEXPECTED;
-  std::lock_guard<std::mutex> lk(c->mu);
-  DevGuard dg(c->device);
-  if (!dg.ok) return BL_UNEXPECTED;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  /* the records go through a pinned slot, as blr_analyze_device uploads its own: copied when this returns */
-  const size_t bytes = sizeof(bl_level_song) * (size_t)n_songs;
-  bl_pin_slot *slot = nullptr;
-  if (ring_get(c, bytes, &slot) != BL_OK) return BL_UNEXPECTED;
-  bl_level_song *hs = static_cast<bl_level_song *>(slot->p);
-  int max_n = 0;
-  for (int i = 0; i < n_songs; ++i) {
-    hs[i].pcm_off = h_desc[i].pcm_offset;
-    hs[i].n = h_desc[i].n_samples;
-    hs[i].channels = h_desc[i].channels;
-    max_n = std::max(max_n, h_desc[i].n_samples);
-  }
-  if (c->ws_used) BL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_ws, 0));
-  if (blr_ensure(c->level_songs, bytes) != BL_OK) return BL_UNEXPECTED;
-  bl_level_song *d_songs = static_cast<bl_level_song *>(c->level_songs.p);
-  BL_HIP_CHECK(hipMemcpyAsync(d_songs, hs, bytes, hipMemcpyHostToDevice, s));
-  BL_HIP_CHECK(hipEventRecord(slot->ev, s));
-  slot->busy = true;
-  if (blk_levels(s, d_pcm, d_songs, n_songs, max_n, silence, c->n_cu, d_levels) != BL_OK) return BL_UNEXPECTED;
-  BL_HIP_CHECK(hipEventRecord(c->ev_ws, s));
-  c->ws_used = true;
-  return BL_OK;
+  return levels_device(c, false, d_pcm, h_desc, n_songs, silence, d_levels, stream);
 }
 
 int bl_amd_levels_batch_device(const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs, int silence,
                                bl_amd_song_levels *d_levels, void *stream) {
-  if (!levels_args_ok(d_pcm, h_desc, n_songs, silence, d_levels)) return BL_UNEXPECTED;
-  return bl_amd_ctx_levels_batch_device(blr_default_ctx(), d_pcm, h_desc, n_songs, silence, d_levels, stream);
+  return levels_device(nullptr, true, d_pcm, h_desc, n_songs, silence, d_levels, stream);
 }
 
 int bl_amd_levels_batch_host(const int16_t *const *h_pcm, const int32_t *n_samples, const int32_t *channels,
@@ -820,34 +860,16 @@ int bl_amd_levels_batch_host(const int16_t *const *h_pcm, const int32_t *n_sampl
   if (!c) return BL_UNEXPECTED;
   DevGuard dg(c->device);
   if (!dg.ok) return BL_UNEXPECTED;
-  std::vector<bl_amd_song_desc> desc;
-  for (int b = 0; b < n_songs;) {
-    /* one wave: songs [b, e), every one at a multiple of 8 samples */
-    desc.clear();
-    size_t total = 0;
-    int e = b;
-    while (e < n_songs && (e == b || total + (size_t)n_samples[e] <= BL_LEVELS_WAVE_SAMPLES)) {
-      bl_amd_song_desc d;
-      d.pcm_offset = total;
-      d.n_samples = n_samples[e];
-      d.channels = channels[e];
-      d.duration = 0;
-      desc.push_back(d);
-      total += ((size_t)n_samples[e] + 7) & ~(size_t)7;
-      ++e;
-    }
-    DevMem arena(sizeof(int16_t) * total), out(sizeof(bl_amd_song_levels) * (size_t)(e - b));
-    if (!arena.ok() || !out.ok()) return BL_UNEXPECTED;
-    for (int i = b; i < e; ++i)
-      BL_HIP_CHECK(hipMemcpy(arena.as<int16_t>() + desc[i - b].pcm_offset, h_pcm[i],
-                             sizeof(int16_t) * (size_t)n_samples[i], hipMemcpyHostToDevice));
-    if (bl_amd_levels_batch_device(arena.as<int16_t>(), desc.data(), e - b, silence, out.as<bl_amd_song_levels>(),
-                                   nullptr) != BL_OK ||
-        !out.down(h_levels + b))
-      return BL_UNEXPECTED;
-    b = e;
-  }
-  return BL_OK;
+  return host_waves(h_pcm, n_samples, channels, n_songs,
+                    [&](const int16_t *d_pcm, const bl_amd_song_desc *desc, int b, int e) {
+                      DevMem out(sizeof(bl_amd_song_levels) * (size_t)(e - b));
+                      return out.ok() &&
+                                     levels_device(nullptr, true, d_pcm, desc, e - b, silence,
+                                                   out.as<bl_amd_song_levels>(), nullptr) == BL_OK &&
+                                     out.down(h_levels + b)
+                                 ? BL_OK
+                                 : BL_UNEXPECTED;
+                    });
 }
 
 /* ---- per-frame spectral timbre (bl_timbre_kernels.hip) ------------------------ */
@@ -857,67 +879,54 @@ static bool timbre_song_ok(unsigned long long pcm_offset, int n_samples, int cha
   return bl_amd_timbre_frames(n_samples, channels) >= 1 && !(pcm_offset & 7);
 }
 
-/* everything that can be said without a device; *n_frames: the sum of F over the songs */
-static bool timbre_args_ok(const void *d_pcm, const bl_amd_song_desc *h_desc, int n_songs, int pct,
-                           const void *d_songs_out, const void *d_frames_out, long long n_frame_records) {
+static int timbre_device(bl_amd_ctx *c, bool dflt, const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs,
+                         int pct, uint64_t min_energy, bl_amd_song_timbre *d_songs_out,
+                         bl_amd_frame_timbre *d_frames_out, long long n_frame_records, void *stream) {
   if (!d_pcm || ((uintptr_t)d_pcm & 15) || !h_desc || !d_songs_out || ((uintptr_t)d_songs_out & 7) ||
       ((uintptr_t)d_frames_out & 7) || n_songs < 1 || pct < 1 || pct > 100)
-    return false;
-  long long total = 0;
+    return BL_UNEXPECTED;
+  long long total = 0; /* the sum of F over the songs */
   for (int i = 0; i < n_songs; ++i) {
-    if (!timbre_song_ok(h_desc[i].pcm_offset, h_desc[i].n_samples, h_desc[i].channels)) return false;
+    if (!timbre_song_ok(h_desc[i].pcm_offset, h_desc[i].n_samples, h_desc[i].channels)) return BL_UNEXPECTED;
     total += bl_amd_timbre_frames(h_desc[i].n_samples, h_desc[i].channels);
   }
-  return !d_frames_out || n_frame_records == total;
+  if ((d_frames_out && n_frame_records != total) || !(c = call_ctx(c, dflt))) return BL_UNEXPECTED;
+  CtxGuard g(c);
+  if (!g.ok()) return BL_UNEXPECTED;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return record_call<bl_timbre_song>(c, s, c->timbre_songs, n_songs, [&](bl_timbre_song *hs) {
+    long long frame_off = 0;
+    for (int i = 0; i < n_songs; ++i) {
+      hs[i].pcm_off = h_desc[i].pcm_offset;
+      hs[i].frame_off = frame_off;
+      hs[i].n_frames = bl_amd_timbre_frames(h_desc[i].n_samples, h_desc[i].channels);
+      hs[i].channels = h_desc[i].channels;
+      hs[i].out_idx = i;
+      hs[i].reserved = 0;
+      frame_off += hs[i].n_frames;
+    }
+    /* one workgroup per song, the longest first, as the analysis lays its songs out: the long songs start while there
+     * are short ones left to fill the chip behind them */
+    std::stable_sort(hs, hs + n_songs,
+                     [](const bl_timbre_song &a, const bl_timbre_song &b) { return a.n_frames > b.n_frames; });
+    return BL_OK;
+  }, [&](const bl_timbre_song *, bl_timbre_song *d_songs) {
+    return blk_timbre(s, d_pcm, d_songs, n_songs, c->tb, pct, min_energy, d_songs_out, d_frames_out);
+  });
 }
 
 int bl_amd_ctx_timbre_batch_device(bl_amd_ctx *c, const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs,
                                    int pct, uint64_t min_energy, bl_amd_song_timbre *d_songs_out,
                                    bl_amd_frame_timbre *d_frames_out, long long n_frame_records, void *stream) {
-  if (!timbre_args_ok(d_pcm, h_desc, n_songs, pct, d_songs_out, d_frames_out, n_frame_records) || !c)
-    return BL_UNEXPECTED;
-  std::lock_guard<std::mutex> lk(c->mu);
-  DevGuard dg(c->device);
-  if (!dg.ok) return BL_UNEXPECTED;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  /* the records go through a pinned slot, as bl_amd_ctx_levels_batch_device's: copied when this returns */
-  const size_t bytes = sizeof(bl_timbre_song) * (size_t)n_songs;
-  bl_pin_slot *slot = nullptr;
-  if (ring_get(c, bytes, &slot) != BL_OK) return BL_UNEXPECTED;
-  bl_timbre_song *hs = static_cast<bl_timbre_song *>(slot->p);
-  long long frame_off = 0;
-  for (int i = 0; i < n_songs; ++i) {
-    hs[i].pcm_off = h_desc[i].pcm_offset;
-    hs[i].frame_off = frame_off;
-    hs[i].n_frames = bl_amd_timbre_frames(h_desc[i].n_samples, h_desc[i].channels);
-    hs[i].channels = h_desc[i].channels;
-    hs[i].out_idx = i;
-    hs[i].reserved = 0;
-    frame_off += hs[i].n_frames;
-  }
-  /* one workgroup per song, the longest first, as the analysis lays its songs out: the long songs start while there
-   * are short ones left to fill the chip behind them */
-  std::stable_sort(hs, hs + n_songs,
-                   [](const bl_timbre_song &a, const bl_timbre_song &b) { return a.n_frames > b.n_frames; });
-  if (c->ws_used) BL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_ws, 0));
-  if (blr_ensure(c->timbre_songs, bytes) != BL_OK) return BL_UNEXPECTED;
-  bl_timbre_song *d_songs = static_cast<bl_timbre_song *>(c->timbre_songs.p);
-  BL_HIP_CHECK(hipMemcpyAsync(d_songs, hs, bytes, hipMemcpyHostToDevice, s));
-  BL_HIP_CHECK(hipEventRecord(slot->ev, s));
-  slot->busy = true;
-  if (blk_timbre(s, d_pcm, d_songs, n_songs, c->tb, pct, min_energy, d_songs_out, d_frames_out) != BL_OK)
-    return BL_UNEXPECTED;
-  BL_HIP_CHECK(hipEventRecord(c->ev_ws, s));
-  c->ws_used = true;
-  return BL_OK;
+  return timbre_device(c, false, d_pcm, h_desc, n_songs, pct, min_energy, d_songs_out, d_frames_out, n_frame_records,
+                       stream);
 }
 
 int bl_amd_timbre_batch_device(const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs, int pct,
                                uint64_t min_energy, bl_amd_song_timbre *d_songs_out,
                                bl_amd_frame_timbre *d_frames_out, long long n_frame_records, void *stream) {
-  if (!timbre_args_ok(d_pcm, h_desc, n_songs, pct, d_songs_out, d_frames_out, n_frame_records)) return BL_UNEXPECTED;
-  return bl_amd_ctx_timbre_batch_device(blr_default_ctx(), d_pcm, h_desc, n_songs, pct, min_energy, d_songs_out,
-                                        d_frames_out, n_frame_records, stream);
+  return timbre_device(nullptr, true, d_pcm, h_desc, n_songs, pct, min_energy, d_songs_out, d_frames_out,
+                       n_frame_records, stream);
 }
 
 int bl_amd_timbre_batch_host(const int16_t *const *h_pcm, const int32_t *n_samples, const int32_t *channels,
@@ -930,39 +939,20 @@ int bl_amd_timbre_batch_host(const int16_t *const *h_pcm, const int32_t *n_sampl
   if (!c) return BL_UNEXPECTED;
   DevGuard dg(c->device);
   if (!dg.ok) return BL_UNEXPECTED;
-  std::vector<bl_amd_song_desc> desc;
-  for (int b = 0; b < n_songs;) {
-    /* one wave, as bl_amd_levels_batch_host's: songs [b, e), every one at a multiple of 8 samples */
-    desc.clear();
-    size_t total = 0;
-    long long frames = 0;
-    int e = b;
-    while (e < n_songs && (e == b || total + (size_t)n_samples[e] <= BL_LEVELS_WAVE_SAMPLES)) {
-      bl_amd_song_desc d;
-      d.pcm_offset = total;
-      d.n_samples = n_samples[e];
-      d.channels = channels[e];
-      d.duration = 0;
-      desc.push_back(d);
-      total += ((size_t)n_samples[e] + 7) & ~(size_t)7;
-      frames += bl_amd_timbre_frames(n_samples[e], channels[e]);
-      ++e;
-    }
-    DevMem arena(sizeof(int16_t) * total), out(sizeof(bl_amd_song_timbre) * (size_t)(e - b)),
-        fout(h_frames_out ? sizeof(bl_amd_frame_timbre) * (size_t)frames : 0);
-    if (!arena.ok() || !out.ok() || !fout.ok()) return BL_UNEXPECTED;
-    for (int i = b; i < e; ++i)
-      BL_HIP_CHECK(hipMemcpy(arena.as<int16_t>() + desc[i - b].pcm_offset, h_pcm[i],
-                             sizeof(int16_t) * (size_t)n_samples[i], hipMemcpyHostToDevice));
-    if (bl_amd_timbre_batch_device(arena.as<int16_t>(), desc.data(), e - b, pct, min_energy,
-                                   out.as<bl_amd_song_timbre>(), fout.as<bl_amd_frame_timbre>(), frames,
-                                   nullptr) != BL_OK ||
-        !out.down(h_songs_out + b) || (h_frames_out && !fout.down(h_frames_out)))
-      return BL_UNEXPECTED;
-    if (h_frames_out) h_frames_out += frames;
-    b = e;
-  }
-  return BL_OK;
+  return host_waves(h_pcm, n_samples, channels, n_songs,
+                    [&](const int16_t *d_pcm, const bl_amd_song_desc *desc, int b, int e) {
+                      long long frames = 0;
+                      for (int i = b; i < e; ++i) frames += bl_amd_timbre_frames(n_samples[i], channels[i]);
+                      DevMem out(sizeof(bl_amd_song_timbre) * (size_t)(e - b)),
+                          fout(h_frames_out ? sizeof(bl_amd_frame_timbre) * (size_t)frames : 0);
+                      if (!out.ok() || !fout.ok() ||
+                          timbre_device(nullptr, true, d_pcm, desc, e - b, pct, min_energy, out.as<bl_amd_song_timbre>(),
+                                        fout.as<bl_amd_frame_timbre>(), frames, nullptr) != BL_OK ||
+                          !out.down(h_songs_out + b) || (h_frames_out && !fout.down(h_frames_out)))
+                        return BL_UNEXPECTED;
+                      if (h_frames_out) h_frames_out += frames;
+                      return BL_OK;
+                    });
 }
 
 int bl_amd_synth_pcm_device(int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs,
@@ -970,75 +960,41 @@ int bl_amd_synth_pcm_device(int16_t *d_pcm, const bl_amd_song_desc *h_desc, int 
   if (n_songs <= 0 || !d_pcm || !h_desc) return BL_UNEXPECTED;
   bl_amd_ctx *c = blr_default_ctx();
   if (!c) return BL_UNEXPECTED;
-  std::lock_guard<std::mutex> lk(c->mu);
-  DevGuard dg(c->device);
-  if (!dg.ok) return BL_UNEXPECTED;
+  CtxGuard g(c);
+  if (!g.ok()) return BL_UNEXPECTED;
   hipStream_t s = static_cast<hipStream_t>(stream);
   for (int i = 0; i < n_songs; ++i)
     if (validate_desc(h_desc[i], i) != BL_OK) return BL_UNEXPECTED;
-  /* the descriptor block of the workspace is shared with the analysis: same hand-over */
-  if (c->ws_used) BL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_ws, 0));
-  if (blr_ensure(c->songs, sizeof(bl_dsong) * (size_t)n_songs) != BL_OK) return BL_UNEXPECTED;
-  bl_pin_slot *slot = nullptr;
-  if (ring_get(c, sizeof(bl_dsong) * (size_t)n_songs, &slot) != BL_OK) return BL_UNEXPECTED;
-  bl_dsong *hs = static_cast<bl_dsong *>(slot->p);
   const int G = BL_GROUP_SONGS_MAX;
   std::vector<int> max_n((n_songs + G - 1) / G);
-  for (int b = 0, gi = 0; b < n_songs; b += G, ++gi) {
-    long long env_total;
-    fill_group(h_desc + b, std::min(G, n_songs - b), hs + b, env_total, max_n[gi]);
-  }
-  bl_dsong *d_songs = static_cast<bl_dsong *>(c->songs.p);
-  BL_HIP_CHECK(hipMemcpyAsync(d_songs, hs, sizeof(bl_dsong) * (size_t)n_songs, hipMemcpyHostToDevice, s));
-  BL_HIP_CHECK(hipEventRecord(slot->ev, s));
-  slot->busy = true;
-  for (int b = 0, gi = 0; b < n_songs; b += G, ++gi)
-    if (blk_synth(s, d_pcm, d_songs + b, std::min(G, n_songs - b), max_n[gi], c->n_cu,
-                  seed_base + (uint32_t)b, sample_rate) != BL_OK)
-      return BL_UNEXPECTED;
-  BL_HIP_CHECK(hipEventRecord(c->ev_ws, s));
-  c->ws_used = true;
-  return BL_OK;
+  /* the descriptor block of the workspace is shared with the analysis */
+  return record_call<bl_dsong>(c, s, c->songs, n_songs, [&](bl_dsong *hs) {
+    for (int b = 0, gi = 0; b < n_songs; b += G, ++gi) {
+      long long env_total;
+      fill_group(h_desc + b, std::min(G, n_songs - b), hs + b, env_total, max_n[gi]);
+    }
+    return BL_OK;
+  }, [&](const bl_dsong *, bl_dsong *d_songs) {
+    for (int b = 0, gi = 0; b < n_songs; b += G, ++gi)
+      if (blk_synth(s, d_pcm, d_songs + b, std::min(G, n_songs - b), max_n[gi], c->n_cu, seed_base + (uint32_t)b,
+                    sample_rate) != BL_OK)
+        return BL_UNEXPECTED;
+    return BL_OK;
+  });
 }
 
 int bl_amd_selftest_sqrt(uint64_t counts[3]) {
-  if (!counts) return BL_UNEXPECTED;
-  bl_amd_ctx *c = blr_default_ctx();
-  if (!c) return BL_UNEXPECTED;
-  DevGuard dg(c->device);
-  unsigned long long *d = nullptr;
-  BL_HIP_CHECK(hipMalloc(&d, 3 * sizeof(unsigned long long)));
-  int rc = BL_UNEXPECTED;
-  unsigned long long h[3] = {0, 0, 0};
-  if (hipMemset(d, 0, sizeof h) == hipSuccess &&
-      blk_sqrt_sweep(nullptr, 0ull, 1ull << 32, d, c->n_cu) == BL_OK &&   /* every f32 bit pattern */
-      hipMemcpy(h, d, sizeof h, hipMemcpyDeviceToHost) == hipSuccess) {
-    for (int k = 0; k < 3; ++k) counts[k] = h[k];
-    rc = BL_OK;
-  }
-  (void)hipFree(d);
-  return rc;
+  return selftest(counts, 3, [](unsigned long long *d, int n_cu) {
+    return blk_sqrt_sweep(nullptr, 0ull, 1ull << 32, d, n_cu); /* every f32 bit pattern */
+  });
 }
 
 int bl_amd_selftest_cos(uint64_t counts[6], uint64_t triples) {
-  if (!counts) return BL_UNEXPECTED;
-  bl_amd_ctx *c = blr_default_ctx();
-  if (!c) return BL_UNEXPECTED;
-  DevGuard dg(c->device);
-  unsigned long long *d = nullptr;
-  BL_HIP_CHECK(hipMalloc(&d, 6 * sizeof(unsigned long long)));
-  int rc = BL_UNEXPECTED;
-  unsigned long long h[6] = {0, 0, 0, 0, 0, 0};
-  const unsigned long long threads = (unsigned long long)c->n_cu * 8 * 256;
-  const int per_thread = (int)std::min<unsigned long long>((triples / 8 + threads - 1) / threads, 1u << 24);
-  if (hipMemset(d, 0, sizeof h) == hipSuccess &&
-      blk_cos_sweep(nullptr, 0x5eedc05ull, std::max(per_thread, 1), d, c->n_cu) == BL_OK &&
-      hipMemcpy(h, d, sizeof h, hipMemcpyDeviceToHost) == hipSuccess) {
-    for (int k = 0; k < 6; ++k) counts[k] = h[k];
-    rc = BL_OK;
-  }
-  (void)hipFree(d);
-  return rc;
+  return selftest(counts, 6, [&](unsigned long long *d, int n_cu) {
+    const unsigned long long threads = (unsigned long long)n_cu * 8 * 256;
+    const int per_thread = (int)std::min<unsigned long long>((triples / 8 + threads - 1) / threads, 1u << 24);
+    return blk_cos_sweep(nullptr, 0x5eedc05ull, std::max(per_thread, 1), d, n_cu);
+  });
 }
 
 int bl_amd_set_host_transfer(int mode) {
@@ -1047,23 +1003,29 @@ int bl_amd_set_host_transfer(int mode) {
   return BL_OK;
 }
 
+/* the host batch on the default context (`dflt`) or a given one: blr_analyze_host with the context locked */
+static int analyze_host(bl_amd_ctx *c, bool dflt, const void *const *h_pcm, int pcm_is_s32, const int32_t *n_samples,
+                        const int32_t *channels, const uint64_t *duration, int n_songs, int in_rate,
+                        bl_amd_song_result *h_results) {
+  if (n_songs <= 0 || !h_pcm || !n_samples || !channels || !duration || !h_results || !(c = call_ctx(c, dflt)))
+    return BL_UNEXPECTED;
+  CtxGuard g(c);
+  if (!g.ok()) return BL_UNEXPECTED;
+  return blr_analyze_host(c, h_pcm, pcm_is_s32, n_samples, channels, duration, n_songs, in_rate, h_results, nullptr);
+}
+
 int bl_amd_ctx_analyze_batch_host(bl_amd_ctx *ctx, const int16_t *const *h_pcm, const int32_t *n_samples,
                                   const int32_t *channels, const uint64_t *duration, int n_songs,
                                   bl_amd_song_result *h_results) {
-  if (!ctx || n_songs <= 0 || !h_pcm || !n_samples || !channels || !duration || !h_results)
-    return BL_UNEXPECTED;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  DevGuard dg(ctx->device);
-  if (!dg.ok) return BL_UNEXPECTED;
-  return blr_analyze_host(ctx, reinterpret_cast<const void *const *>(h_pcm), 0, n_samples, channels,
-                          duration, n_songs, 0, h_results, nullptr);
+  return analyze_host(ctx, false, reinterpret_cast<const void *const *>(h_pcm), 0, n_samples, channels, duration,
+                      n_songs, 0, h_results);
 }
 
 int bl_amd_analyze_batch_host(const int16_t *const *h_pcm, const int32_t *n_samples,
                               const int32_t *channels, const uint64_t *duration, int n_songs,
                               bl_amd_song_result *h_results) {
-  return bl_amd_ctx_analyze_batch_host(blr_default_ctx(), h_pcm, n_samples, channels, duration, n_songs,
-                                       h_results);
+  return analyze_host(nullptr, true, reinterpret_cast<const void *const *>(h_pcm), 0, n_samples, channels, duration,
+                      n_songs, 0, h_results);
 }
 
 /* The corpus loop of ref python/examples/make_m3u_playlist.py:51-72 / examples/analyze.c:17 as one
@@ -1160,14 +1122,8 @@ int bl_amd_analyze_files(const char *const *filenames, int n_files, struct bl_so
     cv.notify_all();
     if (!idx.empty()) {
       res.assign(idx.size(), bl_amd_song_result());
-      int rc;
-      {
-        std::lock_guard<std::mutex> lk(c->mu);
-        DevGuard dg(c->device);
-        rc = dg.ok ? blr_analyze_host(c, pcm.data(), 0, ns.data(), ch.data(), du.data(), (int)idx.size(), 0,
-                                      res.data(), nullptr)
-                   : BL_UNEXPECTED;
-      }
+      const int rc = analyze_host(c, false, pcm.data(), 0, ns.data(), ch.data(), du.data(), (int)idx.size(), 0,
+                                  res.data());
       if (rc != BL_OK) rc_all = BL_UNEXPECTED;
       for (size_t k = 0; k < idx.size(); ++k) {
         struct bl_song &sg = songs[idx[k]];
@@ -1209,27 +1165,16 @@ int bl_amd_analyze_files(const char *const *filenames, int n_files, struct bl_so
 int bl_amd_analyze_batch_host_s32(const int32_t *const *h_pcm, const int32_t *n_samples,
                                   const int32_t *channels, const uint64_t *duration, int n_songs,
                                   bl_amd_song_result *h_results) {
-  if (n_songs <= 0 || !h_pcm || !n_samples || !channels || !duration || !h_results) return BL_UNEXPECTED;
-  bl_amd_ctx *c = blr_default_ctx();
-  if (!c) return BL_UNEXPECTED;
-  std::lock_guard<std::mutex> lk(c->mu);
-  DevGuard dg(c->device);
-  return blr_analyze_host(c, reinterpret_cast<const void *const *>(h_pcm), 1, n_samples, channels,
-                          duration, n_songs, 0, h_results, nullptr);
+  return analyze_host(nullptr, true, reinterpret_cast<const void *const *>(h_pcm), 1, n_samples, channels, duration,
+                      n_songs, 0, h_results);
 }
 
 int bl_amd_analyze_batch_host_rate(const void *const *h_pcm, int pcm_is_s32, const int32_t *n_samples,
                                    const int32_t *channels, const uint64_t *duration, int n_songs,
                                    int sample_rate, bl_amd_song_result *h_results) {
-  if (n_songs <= 0 || !h_pcm || !n_samples || !channels || !duration || !h_results || sample_rate <= 0)
-    return BL_UNEXPECTED;
-  bl_amd_ctx *c = blr_default_ctx();
-  if (!c) return BL_UNEXPECTED;
-  std::lock_guard<std::mutex> lk(c->mu);
-  DevGuard dg(c->device);
-  if (!dg.ok) return BL_UNEXPECTED;
-  return blr_analyze_host(c, h_pcm, pcm_is_s32 != 0, n_samples, channels, duration, n_songs, sample_rate,
-                          h_results, nullptr);
+  if (sample_rate <= 0) return BL_UNEXPECTED;
+  return analyze_host(nullptr, true, h_pcm, pcm_is_s32 != 0, n_samples, channels, duration, n_songs, sample_rate,
+                      h_results);
 }
 
 int bl_amd_narrow_s32_device(const int32_t *d_in, int16_t *d_out, size_t n, void *stream) {
@@ -1238,6 +1183,7 @@ int bl_amd_narrow_s32_device(const int32_t *d_in, int16_t *d_out, size_t n, void
   bl_amd_ctx *c = blr_default_ctx();
   if (!c) return BL_UNEXPECTED;
   DevGuard dg(c->device);
+  if (!dg.ok) return BL_UNEXPECTED;
   return blk_narrow_s32(static_cast<hipStream_t>(stream), d_in, d_out, n, c->n_cu);
 }
 
@@ -1260,9 +1206,8 @@ int bl_amd_ctx_resample_batch_device(bl_amd_ctx *c, const void *d_in, int in_is_
                                      int16_t *d_out, void *stream) {
   if (!c || !d_in || !d_out || !h_desc || n_songs <= 0 || in_rate <= 0 || (in_is_s32 != 0 && in_is_s32 != 1))
     return BL_UNEXPECTED; /* float sources: host form only */
-  std::lock_guard<std::mutex> lk(c->mu);
-  DevGuard dg(c->device);
-  if (!dg.ok) return BL_UNEXPECTED;
+  CtxGuard g(c);
+  if (!g.ok()) return BL_UNEXPECTED;
   return blr_resample_device(c, d_in, in_is_s32, h_desc, n_songs, in_rate, d_out, static_cast<hipStream_t>(stream));
 }
 
@@ -1279,14 +1224,15 @@ int bld_analyze_one_host(const int16_t *h_pcm, int n, int channels, uint64_t dur
   if (!h_pcm || !res) return BL_UNEXPECTED;
   bl_amd_ctx *c = blr_default_ctx();
   if (!c) return BL_UNEXPECTED;
-  std::lock_guard<std::mutex> lk(c->mu);
-  DevGuard dg(c->device);
+  CtxGuard g(c);
+  if (!g.ok()) return BL_UNEXPECTED;
   if (!c->streams[0]) BL_HIP_CHECK(hipStreamCreateWithFlags(&c->streams[0], hipStreamNonBlocking));
   hipStream_t s = c->streams[0];
   const size_t elems = ((size_t)n + 7) & ~(size_t)7;
   if (blr_ensure(c->arena[0], elems * 2 + 64) != BL_OK) return BL_UNEXPECTED;
   if (blr_ensure(c->results, sizeof(bl_amd_song_result)) != BL_OK) return BL_UNEXPECTED;
-  if (c->ws_used) BL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_ws, 0));
+  /* the copies below come before blr_analyze_device's own wait, so the previous user is waited for here */
+  if (ws_wait(c, s) != BL_OK) return BL_UNEXPECTED;
   BL_HIP_CHECK(hipMemcpyAsync(c->arena[0].p, h_pcm, (size_t)n * 2, hipMemcpyHostToDevice, s));
   BL_HIP_CHECK(hipMemsetAsync(c->results.p, 0, sizeof(bl_amd_song_result), s));
   bl_amd_song_desc d;
@@ -1304,52 +1250,45 @@ int bld_mean_variance_host(const int16_t *h_pcm, int n, int have_mean, int mean_
   if (!h_pcm || n <= 0) return BL_UNEXPECTED;
   bl_amd_ctx *c = blr_default_ctx();
   if (!c) return BL_UNEXPECTED;
-  std::lock_guard<std::mutex> lk(c->mu);
-  DevGuard dg(c->device);
+  CtxGuard g(c);
+  if (!g.ok()) return BL_UNEXPECTED;
   if (!c->streams[0]) BL_HIP_CHECK(hipStreamCreateWithFlags(&c->streams[0], hipStreamNonBlocking));
   hipStream_t s = c->streams[0];
   const size_t elems = ((size_t)n + 7) & ~(size_t)7;
   if (blr_ensure(c->arena[0], elems * 2 + 64) != BL_OK) return BL_UNEXPECTED;
-  if (blr_ensure(c->songs, sizeof(bl_dsong)) != BL_OK) return BL_UNEXPECTED;
   if (blr_ensure(c->stats, sizeof(bl_dstats)) != BL_OK) return BL_UNEXPECTED;
   if (blr_ensure(c->hist, sizeof(unsigned) * BL_HIST_BINS) != BL_OK) return BL_UNEXPECTED;
-  /* same workspace as the batches: wait for the previous user on the device, hand it on after */
-  if (c->ws_used) BL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_ws, 0));
-  BL_HIP_CHECK(hipMemcpyAsync(c->arena[0].p, h_pcm, (size_t)n * 2, hipMemcpyHostToDevice, s));
-  bl_pin_slot *slot = nullptr;
-  if (ring_get(c, sizeof(bl_dsong), &slot) != BL_OK) return BL_UNEXPECTED;
-  bl_dsong *hs = static_cast<bl_dsong *>(slot->p);
-  memset(hs, 0, sizeof *hs);
-  hs->n = n; hs->channels = 1; hs->duration = 1;
-  BL_HIP_CHECK(hipMemcpyAsync(c->songs.p, hs, sizeof *hs, hipMemcpyHostToDevice, s));
-  BL_HIP_CHECK(hipEventRecord(slot->ev, s));
-  slot->busy = true;
-  bl_dstats *d_stats = static_cast<bl_dstats *>(c->stats.p);
-  const bl_dsong *d_songs = static_cast<const bl_dsong *>(c->songs.p);
-  const int16_t *d_pcm = static_cast<const int16_t *>(c->arena[0].p);
-  if (blk_scan_one(s, d_pcm, d_songs, d_stats, static_cast<unsigned *>(c->hist.p), n, c->n_cu) != BL_OK)
-    return BL_UNEXPECTED;
-  c->last_first = 0;
-  c->last_songs = 1;
-  c->last_parts = BL_AMD_PART_SUMS | BL_AMD_PART_HIST;
-  bl_dstats st;
-  BL_HIP_CHECK(hipMemcpyAsync(&st, d_stats, sizeof st, hipMemcpyDeviceToHost, s));
-  BL_HIP_CHECK(hipStreamSynchronize(s));
-  /* ref helpers.c:30-37 */
-  const int mean = have_mean ? mean_in : (int)(unsigned)(st.sum & 0xFFFFFFFFull) / n;
-  if (mean_out) *mean_out = mean;
-  if (variance_out) {
-    /* always the exact wrapping form (ref helpers.c:39-49) for the stand-alone helper */
-    st.mean = mean; st.wrap_pass = 1; st.wrap_acc = 0;
-    BL_HIP_CHECK(hipMemcpyAsync(d_stats, &st, sizeof st, hipMemcpyHostToDevice, s));
-    if (blk_variance_wrap_one(s, d_pcm, d_songs, d_stats, n, c->n_cu) != BL_OK) return BL_UNEXPECTED;
+  /* same workspace as the batches, same hand-over; the song goes up behind the wait for the previous user */
+  return record_call<bl_dsong>(c, s, c->songs, 1, [&](bl_dsong *hs) {
+    memset(hs, 0, sizeof *hs);
+    hs->n = n; hs->channels = 1; hs->duration = 1;
+    return BL_OK;
+  }, [&](const bl_dsong *, bl_dsong *d_songs) {
+    BL_HIP_CHECK(hipMemcpyAsync(c->arena[0].p, h_pcm, (size_t)n * 2, hipMemcpyHostToDevice, s));
+    bl_dstats *d_stats = static_cast<bl_dstats *>(c->stats.p);
+    const int16_t *d_pcm = static_cast<const int16_t *>(c->arena[0].p);
+    if (blk_scan_one(s, d_pcm, d_songs, d_stats, static_cast<unsigned *>(c->hist.p), n, c->n_cu) != BL_OK)
+      return BL_UNEXPECTED;
+    c->last_first = 0;
+    c->last_songs = 1;
+    c->last_parts = BL_AMD_PART_SUMS | BL_AMD_PART_HIST;
+    bl_dstats st;
     BL_HIP_CHECK(hipMemcpyAsync(&st, d_stats, sizeof st, hipMemcpyDeviceToHost, s));
     BL_HIP_CHECK(hipStreamSynchronize(s));
-    *variance_out = (int)(st.wrap_acc / n);
-  }
-  BL_HIP_CHECK(hipEventRecord(c->ev_ws, s));
-  c->ws_used = true;
-  return BL_OK;
+    /* ref helpers.c:30-37 */
+    const int mean = have_mean ? mean_in : (int)(unsigned)(st.sum & 0xFFFFFFFFull) / n;
+    if (mean_out) *mean_out = mean;
+    if (variance_out) {
+      /* always the exact wrapping form (ref helpers.c:39-49) for the stand-alone helper */
+      st.mean = mean; st.wrap_pass = 1; st.wrap_acc = 0;
+      BL_HIP_CHECK(hipMemcpyAsync(d_stats, &st, sizeof st, hipMemcpyHostToDevice, s));
+      if (blk_variance_wrap_one(s, d_pcm, d_songs, d_stats, n, c->n_cu) != BL_OK) return BL_UNEXPECTED;
+      BL_HIP_CHECK(hipMemcpyAsync(&st, d_stats, sizeof st, hipMemcpyDeviceToHost, s));
+      BL_HIP_CHECK(hipStreamSynchronize(s));
+      *variance_out = (int)(st.wrap_acc / n);
+    }
+    return BL_OK;
+  });
 }
 
 /* diagnostic: the per-window energies (ref tempo_atk_sort.c:150, filtered_array) of the
@@ -1357,8 +1296,8 @@ int bld_mean_variance_host(const int16_t *h_pcm, int n, int have_mean, int mean_
 long long bl_amd_last_energies(float *h_out, long long max_elems) {
   bl_amd_ctx *c = blr_default_ctx();
   if (!c) return -1;
-  std::lock_guard<std::mutex> lk(c->mu);
-  DevGuard dg(c->device);
+  CtxGuard g(c);
+  if (!g.ok()) return -1;
   if (!c->energies.p || c->last_env_total <= 0) return 0;
   const long long n = c->last_env_total < max_elems ? c->last_env_total : max_elems;
   if (hipDeviceSynchronize() != hipSuccess) return -1;
@@ -1373,9 +1312,8 @@ int bl_amd_last_freq_stats(int max_songs, float *h_spectrum, long long *h_sum, u
                            unsigned *h_hist, int *parts) {
   bl_amd_ctx *c = blr_default_ctx();
   if (!c) return -1;
-  std::lock_guard<std::mutex> lk(c->mu);
-  DevGuard dg(c->device);
-  if (!dg.ok) return -1;
+  CtxGuard g(c);
+  if (!g.ok()) return -1;
   const int n = c->last_songs;
   if (parts) *parts = n > 0 ? c->last_parts : 0;
   if (n <= 0) return 0;
@@ -1419,9 +1357,8 @@ int bl_amd_tail_from_envelope(const bl_amd_song_desc *h_desc, int n_songs, const
     if (validate_desc(h_desc[i], i) != BL_OK || h_desc[i].channels != 1 || h_desc[i].pcm_offset != 0) return BL_UNEXPECTED;
   bl_amd_ctx *c = blr_default_ctx();
   if (!c) return BL_UNEXPECTED;
-  std::lock_guard<std::mutex> lk(c->mu);
-  DevGuard dg(c->device);
-  if (!dg.ok) return BL_UNEXPECTED;
+  CtxGuard g(c);
+  if (!g.ok()) return BL_UNEXPECTED;
   std::vector<bl_dsong> hs((size_t)n_songs);
   long long env_total = 0;
   int max_n = 0;

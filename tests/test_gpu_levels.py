@@ -176,6 +176,34 @@ def test_host_form_equals_the_device_form(batch):
         assert bliss_amd.levels_batch_host(songs, chans, silence=sil).tobytes() == got[sil].tobytes()
 
 
+def test_host_form_over_two_waves(gpu_lib):
+    """levels_batch_host uploads at most 2^27 samples at a time, every song at a multiple of 8.  Padded, the first two
+    songs come to 125 829 128 <= 2^27 and the third passes it: the waves are songs {0, 1} and song {2}.  Byte for byte
+    the records of one device call on one corpus, which is never split; each song is a block of 65 536 random samples
+    of its own seed tiled to length, so a swapped or shifted wave shows."""
+    lengths, chans = (62_914_563, 62_914_560, 20_971_527), (1, 2, 1)
+    padded = [(n + 7) & ~7 for n in lengths]
+    assert padded[0] + padded[1] <= 1 << 27 < sum(padded)
+    songs = [np.resize(np.random.default_rng(9100 + i).integers(-32768, 32768, 65536).astype(np.int16), n)
+             for i, n in enumerate(lengths)]
+    corpus = bliss_amd.DeviceCorpus(lengths, chans, 1)
+    corpus.pcm.fill_(32767)
+    for i, s in enumerate(songs):
+        corpus.upload(i, s)
+    for sil in SILENCES:
+        corpus.levels(silence=sil)
+        want = corpus.fetch_levels()
+        assert bliss_amd.levels_batch_host(songs, chans, silence=sil).tobytes() == want.tobytes(), sil
+    for i, (s, ch) in enumerate(zip(songs, chans)):   # the device call itself, by what numpy gives without 64-bit copies
+        F = s.size // ch
+        assert want["frames"][i] == F and want["status"][i] == _lib.BL_OK
+        assert want["head"][i].tolist() == s[:2].tolist() and want["tail"][i].tolist() == s[-2:].tolist()
+        for c in range(2):
+            v = s[c:F * ch:ch] if c < ch else s[:0]
+            assert want["sum"][i][c] == int(v.sum(dtype=np.int64)), (i, c)
+            assert want["peak"][i][c] == (max(int(v.max()), -int(v.min())) if c < ch else 0), (i, c)
+
+
 def test_lead_and_trail_agree_with_the_trim_of_the_analysis(gpu_lib):
     """for songs the analysers accept and silence 0: lead = start // channels, trail = F - 1 - end // channels"""
     rng = np.random.default_rng(5)

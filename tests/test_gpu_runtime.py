@@ -73,6 +73,54 @@ def test_two_contexts_from_two_threads(gpu_lib, oracle):
             check_song(out[t][i], oracle.analyze(p, c, d), ("ctx", t, i))
 
 
+def test_entry_points_interleaved_on_two_streams_without_host_sync(gpu_lib, oracle):
+    """Synthesis, analysis, levels and timbre of two corpora on the default context, issued twice in a row with the
+    stream alternating from call to call and no host synchronisation but the last: twelve record uploads through the
+    four pinned slots, and every call takes the workspace over from a call on the other stream.  Every output equals
+    what the same calls give with a device synchronisation after each."""
+    import torch
+    dev = torch.device("cuda", 0)
+    xs = _songs(oracle, 4500, 9)
+    X = bliss_amd.DeviceCorpus([p.size for p, _, _ in xs], [c for _, c, _ in xs], [d for _, _, d in xs])
+    for i, (p, _, _) in enumerate(xs):
+        X.upload(i, p)
+    ych = [1 + i % 2 for i in range(7)]
+    ysec = [6 + (i * 2) % 5 for i in range(7)]
+    Y = bliss_amd.DeviceCorpus([22050 * c * s + 8 * (i % 3) for i, (c, s) in enumerate(zip(ych, ysec))], ych, ysec)
+    calls = [lambda: Y.synth(seed_base=4600, sample_rate=22050), X.analyze, X.levels, X.timbre, Y.analyze, Y.levels]
+
+    def outputs():
+        return [Y.pcm, X.results, X.levels_raw, X.timbre_raw, X.timbre_frames_raw, Y.results, Y.levels_raw]
+
+    def fetch():
+        torch.cuda.synchronize()
+        y_pcm = Y.pcm.cpu().numpy()   # the songs, not the gaps between them: nothing writes those
+        y_pcm = np.concatenate([y_pcm[int(d.pcm_offset):int(d.pcm_offset) + d.n_samples] for d in Y.desc])
+        ts, tf = X.fetch_timbre()
+        return {"Y.pcm": y_pcm, "X.levels": X.fetch_levels(), "X.timbre": ts, "X.frames": tf,
+                "Y.levels": Y.fetch_levels()}, {"X": X.fetch(), "Y": Y.fetch()}
+
+    for f in calls:
+        f()
+        torch.cuda.synchronize()
+    want, want_res = fetch()
+    for t in outputs():
+        t.view(torch.uint8).fill_(0xAB)
+    torch.cuda.synchronize()
+    streams = [torch.cuda.Stream(dev), torch.cuda.Stream(dev)]
+    for k, f in enumerate(calls + calls):
+        with torch.cuda.stream(streams[k % 2]):
+            f()
+    got, got_res = fetch()
+    for name in want:
+        assert got[name].tobytes() == want[name].tobytes(), name
+    for name in want_res:   # field by field: the analysis records carry padding nothing writes
+        for k in want_res[name].dtype.names:
+            assert got_res[name][k].tobytes() == want_res[name][k].tobytes(), (name, k)
+    assert int(want_res["Y"]["status"].max()) == 0 and int(want["Y.levels"]["frames"].min()) > 0
+    check_song(got_res["X"][0], oracle.analyze(*xs[0]), "X, song 0")
+
+
 def test_launch_groups_and_async_enqueue(oracle, tmp_path):
     """More songs than one launch group holds (group size lowered through the environment for a
     fresh process) give the same records as a single group; and the device entry point returns

@@ -421,3 +421,36 @@ def test_host_form_and_python_wrappers(gpu_lib, ref, parameter_songs):
         assert hz["centroid_std_hz"][i] == pytest.approx(c.std(), rel=1e-9, abs=1e-9 * c.mean())
         assert hz["rolloff_hz"][i] == pytest.approx(r.mean(), rel=1e-12)
         assert hz["rolloff_std_hz"][i] == pytest.approx(r.std(), rel=1e-9, abs=1e-9 * r.mean())
+
+
+def test_host_form_over_two_waves(gpu_lib, ref):
+    """timbre_batch_host uploads at most 2^27 samples at a time, every song at a multiple of 8.  Padded, the first two
+    songs come to 125 829 128 <= 2^27 and the third passes it: the waves are songs {0, 1} and song {2}, and the frame
+    output advances from one wave to the next.  Equal to one device call on one corpus, which is never split.  Each song
+    is a block of 65 536 random samples of its own seed tiled to length, so a swapped or shifted wave shows; the block
+    is 128 frames mono and 64 stereo, and the first period of every song is held against the reference."""
+    lengths, chans = (62_914_563, 62_914_560, 20_971_527), (1, 2, 1)
+    padded = [(n + 7) & ~7 for n in lengths]
+    assert padded[0] + padded[1] <= 1 << 27 < sum(padded)
+    blocks = [np.random.default_rng(9200 + i).integers(-32768, 32768, 65536).astype(np.int16) for i in range(3)]
+    pcms = [np.resize(b, n) for b, n in zip(blocks, lengths)]
+    corpus = bliss_amd.DeviceCorpus(lengths, chans, 1)
+    corpus.pcm.fill_(32767)
+    for i, p in enumerate(pcms):
+        corpus.upload(i, p)
+    corpus.timbre()
+    cs, cf = corpus.fetch_timbre()
+    hs, hf = bliss_amd.timbre_batch_host(pcms, chans)
+    assert hs.tobytes() == cs.tobytes() and hf.tobytes() == cf.tobytes()
+    hs2, none = bliss_amd.timbre_batch_host(pcms, chans, frames=False)
+    assert none is None and hs2.tobytes() == cs.tobytes()
+    at = 0
+    for i, (block, n, ch) in enumerate(zip(blocks, lengths, chans)):
+        period = 65536 // (W * ch)
+        frames, _ = ref.records(block, ch)
+        assert len(frames) == period and int(hs["frames"][i]) == frames_of(n, ch) >= 2 * period
+        for k, name in enumerate(FRAME_FIELDS):
+            assert [int(x) for x in hf[name][at:at + period]] == [f[k] for f in frames], (i, name)
+            assert np.array_equal(hf[name][at + period:at + 2 * period], hf[name][at:at + period]), (i, name)
+        at += frames_of(n, ch)
+    assert at == hf.size

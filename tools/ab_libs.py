@@ -84,6 +84,7 @@ def main():
                           if any(k in x["ms"] for x in r)},
             "env_windows_ms_all": [round(x["ms"].get("env_windows", 0.0), 3) for x in r],
             "wall_ms_median": round(float(np.median([x["wall_ms"] for x in r])), 3),
+            "wall_ms_all": [round(x["wall_ms"], 3) for x in r],
             "records_identical_to_first": all(x["records_sha256"] == base for x in r),
             "status_max": max(x["status_max"] for x in r)}
     b = rep["libs"][os.path.relpath(libs[0], ROOT)]["ms_median"]
