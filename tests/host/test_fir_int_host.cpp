@@ -11,7 +11,13 @@
 //   (d) with bl_fft_tan.h's lane code behind it, as the kernel calls it (halved input, no quarter in the split,
 //       4 x the middle term): the window energies of the songs tests/test_gpu_fir_int.py analyses against the
 //       oracle's — none more than one f32 ulp apart; the count of moved energies is printed and must stay within the
-//       two that GPU test allows (its seeds were chosen so that it is 0).
+//       two that GPU test allows (its seeds were chosen so that it is 0);
+//   (e) the route the shipped kernel takes since it transforms the sums unscaled: the integers Y themselves through the
+//       same lane code and bl_fft512_power1_sq with the song's kappa, 2 kappa for the middle term (as in the kernel and
+//       in test_fft_sq_host.cpp), on the same songs; its count is printed beside (d)'s.
+// With arguments — pairs of a channel count and a file of raw s16 PCM (native byte order, 44.1 kHz) — the program runs
+// (d) and (e) on those files instead and prints, per file, how many energies differ from the oracle's and the largest
+// step in f32 ulps; the caller (tests/test_fir_int_host.py) holds the numbers to the project's allowance.
 // Build: g++ -O2 -std=c++17 -ffp-contract=off, linked with the oracle's C sources.
 #include <cmath>
 #include <cstdint>
@@ -123,7 +129,7 @@ static void check_block(const int16_t *s, int mean) {
 
 /* ---- (d): whole songs through FIR mode 2 and the tan-form DFT ---- */
 static bl_fft_tan_lane<double> g_lanes[16];
-static bl_c2<double> g_tw512t[128];
+static bl_c2<double> g_tw512t[128], g_cs512[128];
 static void kernel_power(const double *x, double *pw) { /* x: the halved filter output, as the kernel holds it */
   double re[16][16], im[16][16];
   for (int n0 = 0; n0 < 16; ++n0)
@@ -143,22 +149,58 @@ static void kernel_power(const double *x, double *pw) { /* x: the halved filter 
   pw[128] = 4.0 * bl_fma(mr, mr, mi * mi);
 }
 
-static long g_windows = 0, g_moved = 0, g_far = 0;
-static void check_song(const std::vector<int16_t> &pcm, const char *name) {
+/* (e) Y: the unscaled integer sums; the split from the squares with the song's constants, 2 kappa x the middle term */
+static void shipped_power(const double *Y, double kappa, double *pw) {
+  double re[16][16], im[16][16];
+  for (int n0 = 0; n0 < 16; ++n0)
+    for (int m1 = 0; m1 < 16; ++m1) { re[n0][m1] = Y[2 * (16 * m1 + n0)]; im[n0][m1] = Y[2 * (16 * m1 + n0) + 1]; }
+  for (int l = 0; l < 16; ++l) bl_fft512_pass1_tan<double>(re[l], im[l], g_lanes[l].t1);
+  double tr[16][16], ti[16][16];
+  for (int k1 = 0; k1 < 16; ++k1)
+    for (int n0 = 0; n0 < 16; ++n0) { tr[k1][n0] = re[n0][bl_pos16(k1)]; ti[k1][n0] = im[n0][bl_pos16(k1)]; }
+  for (int l = 0; l < 16; ++l) bl_fft16_folded<double>(tr[l], ti[l], g_lanes[l].fold);
+  for (int l = 0; l < 16; ++l)
+    for (int k0 = 0; k0 < 8; ++k0) {
+      const int pl = l ? 16 - l : 0, pk = l ? 15 - k0 : (k0 ? 16 - k0 : 0);
+      const bl_c2<double> cs = bl_fft_sq_consts<double>(g_cs512[l + 16 * k0], kappa); /* what the kernel keeps in LDS */
+      bl_fft512_power1_sq<double>(tr[l][bl_pos16(k0)], ti[l][bl_pos16(k0)], tr[pl][bl_pos16(pk)], ti[pl][bl_pos16(pk)],
+                                  cs, kappa, pw[l + 16 * k0], pw[256 - l - 16 * k0]);
+    }
+  const double mr = tr[0][bl_pos16(8)], mi = ti[0][bl_pos16(8)];
+  pw[128] = (2.0 * kappa) * bl_fma(mr, mr, mi * mi);
+}
+
+static long g_windows = 0, g_moved = 0, g_far = 0, g_moved_sq = 0, g_far_sq = 0, g_step = 0, g_step_sq = 0;
+static void check_song(const std::vector<int16_t> &pcm, const char *name, int channels = 1) {
   const int n = (int)pcm.size();
   orc_result r;
   memset(&r, 0, sizeof r);
   const int nb_frames = (n - (n % 512)) * 2 / 512, n_windows = nb_frames - 2;
   std::vector<float> en(nb_frames);
-  orc_envelope(pcm.data(), n, 1, &r, en.data());
+  const int secs = n / (44100 * channels);
+  orc_envelope(pcm.data(), n, secs > 0 ? secs : 1, &r, en.data());
   const int mean = orc_mean(pcm.data(), n), var = orc_variance(pcm.data(), n, mean);
   /* k_song_prep */
   const double v2 = 2.0 * ((double)var / 32768.0), rcp = 1.0 / v2, rcp_lo = bl_fma(-rcp, v2, 1.0) / v2;
-  const double sc = bl_firi_scale(rcp, rcp_lo);
-  long moved = 0;
+  const double sc = bl_firi_scale(rcp, rcp_lo), kappa = bl_firi_power_scale(rcp, rcp_lo);
+  long moved = 0, moved_sq = 0, step = 0, step_sq = 0;
   for (int w = 0; w < n_windows; ++w) {
-    double x[512], pw[257];
-    for (int j = 0; j < 512; ++j) x[j] = (double)conv64(pcm.data(), 256 * w + j, mean, 256 * w) * sc;
+    double Y[512], x[512], pw[257];
+    for (int j = 0; j < 512; ++j) {
+      Y[j] = (double)conv64(pcm.data(), 256 * w + j, mean, 256 * w);
+      x[j] = Y[j] * sc;
+    }
+    {
+      shipped_power(Y, kappa, pw);
+      float e = 0;
+      for (int k = 0; k <= 256; ++k) e = (float)((double)e + pw[k]);
+      int32_t a, b;
+      memcpy(&a, &e, 4); memcpy(&b, &en[w], 4);
+      const long d = labs((long)a - (long)b);
+      moved_sq += d != 0;
+      if (d > step_sq) step_sq = d;
+      if (d > 1) { if (g_far_sq++ < 5) printf("(e) %s window %d: %.9g, oracle %.9g\n", name, w, e, en[w]); }
+    }
     kernel_power(x, pw);
     float e = 0;
     for (int k = 0; k <= 256; ++k) e = (float)((double)e + pw[k]);
@@ -166,14 +208,44 @@ static void check_song(const std::vector<int16_t> &pcm, const char *name) {
     memcpy(&a, &e, 4); memcpy(&b, &en[w], 4);
     const long d = labs((long)a - (long)b);
     moved += d != 0;
+    if (d > step) step = d;
     if (d > 1) { if (g_far++ < 5) printf("(d) %s window %d: %.9g, oracle %.9g\n", name, w, e, en[w]); }
   }
   printf("(d) %-12s %6d samples, %5d windows, mean %6d: %ld energies moved\n", name, n, n_windows, mean, moved);
+  printf("(e) %-12s %d channel(s), %5d windows: shipped route %ld differ, largest step %ld ulp; scaled route %ld differ, "
+         "largest step %ld ulp\n", name, channels, n_windows, moved_sq, step_sq, moved, step);
   g_windows += n_windows;
   g_moved += moved;
+  g_moved_sq += moved_sq;
+  if (step > g_step) g_step = step;
+  if (step_sq > g_step_sq) g_step_sq = step_sq;
 }
 
-int main() {
+/* (d), (e) on files of raw s16 PCM: argv = pairs of channel count and path */
+static int run_files(int argc, char **argv) {
+  if (argc < 3 || (argc - 1) % 2) { fprintf(stderr, "usage: %s [CHANNELS FILE]...\n", argv[0]); return 2; }
+  for (int i = 1; i + 1 < argc; i += 2) {
+    const int ch = atoi(argv[i]);
+    FILE *f = fopen(argv[i + 1], "rb");
+    if ((ch != 1 && ch != 2) || !f) { fprintf(stderr, "cannot read %s as %s-channel PCM\n", argv[i + 1], argv[i]); return 2; }
+    std::vector<int16_t> pcm;
+    int16_t buf[4096];
+    size_t got;
+    while ((got = fread(buf, 2, 4096, f)) > 0) pcm.insert(pcm.end(), buf, buf + got);
+    fclose(f);
+    if (pcm.size() < 5120) { fprintf(stderr, "%s: fewer than 5120 samples\n", argv[i + 1]); return 2; }
+    const char *base = strrchr(argv[i + 1], '/');
+    check_song(pcm, base ? base + 1 : argv[i + 1], ch);
+  }
+  printf("files: %ld windows; shipped route %ld differ, largest step %ld ulp; scaled route %ld differ, largest step %ld ulp\n",
+         g_windows, g_moved_sq, g_step_sq, g_moved, g_step);
+  return 0;
+}
+
+int main(int argc, char **argv) {
+  bl_fft_tan_fill(g_lanes, g_tw512t);
+  bl_fft_sq_fill(g_cs512);
+  if (argc > 1) return run_files(argc, argv);
   for (int b = 0; b < 16; ++b)
     for (int kb = 0; kb < 4; ++kb) {
       bl_firi_tap_planes(b, kb, g_cp[b][kb]);
@@ -223,14 +295,13 @@ int main() {
          g_amax[0], g_amax[1], g_amax[2], g_amax[3], g_amax[4], g_amax[5], g_amax[6]);
 
   /* (d) the songs of tests/test_gpu_fir_int.py: (seed, channels, samples), 44.1 kHz; then its two built songs */
-  bl_fft_tan_fill(g_lanes, g_tw512t);
   static const struct { unsigned seed, ch, n; const char *name; } songs[] = {
       {81001, 2, 176400, "stereo 2 s"}, {81002, 1, 132812, "mono 3 s"}, {81003, 2, 529200, "stereo 6 s"},
       {81004, 1, 5120, "shortest"},     {81005, 2, 265134, "stereo 3 s"}};
   for (const auto &sg : songs) {
     std::vector<int16_t> pcm(sg.n);
     orc_synth_fill(pcm.data(), sg.n, sg.seed, 44100, sg.ch);
-    check_song(pcm, sg.name);
+    check_song(pcm, sg.name, (int)sg.ch);
   }
   {
     std::vector<int16_t> pcm(88533); /* DC offset: |mean| > 13 571 */
@@ -244,6 +315,8 @@ int main() {
     check_song(pcm, "square");
   }
   printf("(d) %ld windows, %ld energies moved against the oracle, %ld by more than one ulp\n", g_windows, g_moved, g_far);
+  printf("(e) %ld windows, shipped route: %ld energies moved against the oracle, %ld by more than one ulp\n", g_windows,
+         g_moved_sq, g_far_sq);
   const bool ok = g_fail == 0 && g_far == 0 && g_moved <= 2;
   printf(ok ? "OK\n" : "FAIL\n");
   return ok ? 0 : 1;

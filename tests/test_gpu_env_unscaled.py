@@ -10,19 +10,16 @@ blocks filtered in front of a run here are main-loop blocks there); samples with
 scale, kappa ~ 1e-6); a full-scale square wave (the smallest scale of real material); means of +-32 000 with a few LSB of
 noise (the largest constant in the matrix products' initial values, the variance from the wrap pass); and a constant
 song, which keeps its status."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
-import bliss_amd
 from bliss_amd import _lib
 from tests.test_gpu_parity import check_song
+from tests.window_reference import analyze as _analyze_songs, grid_x as _grid_x, run_starts as _run_starts
 
 pytestmark = pytest.mark.gpu
 
 RATE = 44100
-EV_CWAVES = 7   # compute waves per workgroup of k_env_windows3
 I_20S = 3       # position of the 20-s song in _songs()
 
 
@@ -46,21 +43,7 @@ def _secs(pcm):
 
 
 def _analyze(lib, songs, mode):
-    """Records and window energies (one array per song) of `songs` analysed as one batch in FIR mode `mode`."""
-    corpus = bliss_amd.DeviceCorpus([len(p) for p in songs], [1] * len(songs), [_secs(p) for p in songs])
-    for i, p in enumerate(songs):
-        corpus.upload(i, p)
-    try:
-        assert lib.bl_amd_set_fir_mode(mode) == 0
-        corpus.analyze()
-        got = corpus.fetch()
-        total = int(sum(int(g["nb_frames"]) for g in got))
-        en = np.zeros(total, dtype=np.float32)
-        assert lib.bl_amd_last_energies(en.ctypes.data_as(C.POINTER(C.c_float)), total) == total
-    finally:
-        lib.bl_amd_set_fir_mode(-1)
-    offs = np.concatenate([[0], np.cumsum(got["nb_frames"].astype(np.int64))])
-    return got, [en[offs[i]:offs[i] + int(got[i]["n_windows"])].copy() for i in range(len(songs))]
+    return _analyze_songs(lib, [(p, 1) for p in songs], mode)
 
 
 @pytest.fixture(scope="module")
@@ -98,17 +81,6 @@ def test_mode2_energies_are_mode0s_up_to_one_ulp(runs):
         assert d.max() <= 1, (i, int(d.max()))
         moved += int(np.count_nonzero(d))
     assert moved <= 2, moved   # the project's allowance for a batch
-
-
-def _run_starts(n_windows, gx):
-    n_rounds = (n_windows + 3) // 4
-    return {n_rounds * u // (EV_CWAVES * gx) for u in range(EV_CWAVES * gx + 1)}
-
-
-def _grid_x(maxn, count, n_cu):
-    """blk_env_windows' grid_x_for: blocks per song."""
-    units_max = max(1, (2 * (maxn // 512)) // (4 * 4 * EV_CWAVES))
-    return max(1, min((2 * n_cu + count - 1) // count, units_max, 65535))
 
 
 def test_the_20s_song_alone_and_beside_the_60s_one_gives_the_same_bits(runs):

@@ -8,20 +8,17 @@ full-scale square wave; a song with a DC offset beyond |mean| = 13 571.  n_windo
 n_windows mod 4 takes its two possible values, 0 and 2; a song with fewer than four windows is below the shortest
 input.  The seeds are the ones tests/host/test_fir_int_host.cpp runs on the CPU: no energy moves against the oracle
 there."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
-import bliss_amd
 from bliss_amd import _lib
 from tests.test_gpu_parity import check_song
+from tests.window_reference import analyze as _analyze, grid_x as _grid_x, run_starts as _run_starts
 
 pytestmark = pytest.mark.gpu
 
 RATE = 44100
 SYNTH = [(81001, 2, 176400), (81002, 1, 132812), (81003, 2, 529200), (81004, 1, 5120), (81005, 2, 265134)]
-EV_CWAVES = 7   # compute waves per workgroup of k_env_windows3
 
 
 def _songs(oracle):
@@ -37,24 +34,6 @@ def _songs(oracle):
 
 def _secs(pcm, ch):
     return max(1, len(pcm) // (RATE * ch))
-
-
-def _analyze(lib, songs, mode):
-    """Records and window energies (one array per song) of `songs` analysed as one batch in FIR mode `mode`."""
-    corpus = bliss_amd.DeviceCorpus([len(p) for p, _ in songs], [c for _, c in songs], [_secs(p, c) for p, c in songs])
-    for i, (p, _) in enumerate(songs):
-        corpus.upload(i, p)
-    try:
-        assert lib.bl_amd_set_fir_mode(mode) == 0
-        corpus.analyze()
-        got = corpus.fetch()
-        total = int(sum(int(g["nb_frames"]) for g in got))
-        en = np.zeros(total, dtype=np.float32)
-        assert lib.bl_amd_last_energies(en.ctypes.data_as(C.POINTER(C.c_float)), total) == total
-    finally:
-        lib.bl_amd_set_fir_mode(-1)
-    offs = np.concatenate([[0], np.cumsum(got["nb_frames"].astype(np.int64))])
-    return got, [en[offs[i]:offs[i] + int(got[i]["n_windows"])].copy() for i in range(len(songs))]
 
 
 @pytest.fixture(scope="module")
@@ -97,17 +76,6 @@ def test_mode2_energies_are_mode0s_up_to_one_ulp(runs):
         assert d.max() <= 1, (i, int(d.max()))
         moved += int(np.count_nonzero(d))
     assert moved <= 2, moved   # the project's cap for a file; the CPU run of the same songs shows none
-
-
-def _run_starts(n_windows, gx):
-    n_rounds = (n_windows + 3) // 4
-    return {n_rounds * u // (EV_CWAVES * gx) for u in range(EV_CWAVES * gx + 1)}
-
-
-def _grid_x(maxn, count, n_cu):
-    """blk_env_windows' grid_x_for: blocks per song."""
-    units_max = max(1, (2 * (maxn // 512)) // (4 * 4 * EV_CWAVES))
-    return max(1, min((2 * n_cu + count - 1) // count, units_max, 65535))
 
 
 def test_a_song_alone_and_in_the_batch_gives_the_same_bits(runs):
