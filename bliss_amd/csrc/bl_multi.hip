@@ -191,13 +191,6 @@ void rank_exchange(const Call &c, int rank, bl_amd_ctx *ctx, ncclComm_t comm, hi
   c.bar->wait(); /* nobody returns (and lets a later call reuse its buffers) while a peer may still write */
 }
 
-/* the rank's internal stream 0, created on first use */
-hipStream_t rank_stream(bl_amd_ctx *ctx) {
-  if (!ctx->streams[0] && hipStreamCreateWithFlags(&ctx->streams[0], hipStreamNonBlocking) != hipSuccess)
-    return nullptr;
-  return ctx->streams[0];
-}
-
 struct HostJob {
   const std::vector<int> *mine; /* caller indices of this rank's songs */
   const int16_t *const *h_pcm;
@@ -223,7 +216,7 @@ void rank_main_host(const Call *c, int rank, bl_amd_ctx *ctx, ncclComm_t comm, H
     ok = blr_analyze_host(ctx, pcm.data(), 0, ns.data(), ch.data(), du.data(), cnt, 0, res.data(), &d_res) == BL_OK;
   if (ok)
     for (int i = 0; i < cnt; ++i) j.h_results[(*j.mine)[i]] = res[i];
-  hipStream_t s = ok ? rank_stream(ctx) : nullptr;
+  hipStream_t s = ok ? blr_stream(ctx, 0) : nullptr;
   rank_exchange(*c, rank, ctx, comm, s, d_res, cnt, nullptr, ok && s);
 }
 
@@ -231,7 +224,7 @@ void rank_main_device(const Call *c, int rank, bl_amd_ctx *ctx, ncclComm_t comm,
                       bl_amd_song_result *h_results_block) {
   int ok = hipSetDevice(sh->device) == hipSuccess;
   std::unique_lock<std::mutex> lk(ctx->mu);
-  hipStream_t s = ok ? rank_stream(ctx) : nullptr;
+  hipStream_t s = ok ? blr_stream(ctx, 0) : nullptr;
   ok = ok && s;
   bl_amd_song_result *d_res = sh->d_results;
   if (ok && !d_res && sh->n_songs > 0) { /* the caller keeps no device copy: the context's buffer */

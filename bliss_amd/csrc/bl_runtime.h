@@ -1,7 +1,8 @@
 /*
  * bl_runtime.h — internal: the per-device context behind include/bliss_amd.h, shared by
- * bl_runtime.hip (contexts and the single-device analysis C-ABI), bl_query_api.hip (the matrix, playlist and
- * vector-query C-ABI) and bl_multi.hip (multi-device corpus path).
+ * bl_runtime.hip (contexts and the single-device analysis C-ABI), bl_host_batch.hip (songs from host memory: the host
+ * batch, bl_amd_analyze_files, the *_host forms), bl_query_api.hip (the matrix, playlist and vector-query C-ABI) and
+ * bl_multi.hip (multi-device corpus path).
  * C++ only, not installed.
  */
 #ifndef BL_RUNTIME_H_
@@ -18,6 +19,8 @@
 #define BL_MAX_DEVICES 16
 #define BL_GROUP_SONGS_MAX 32768 /* gridDim.y of the (blocks, songs) launch grids */
 #define BL_PIN_SLOTS 4
+#define BL_RS_OUT_RATE 22050 /* ref src/decode.c:7 SAMPLE_RATE */
+#define BL_HOST_WAVE_MAX ((size_t)2 << 30) /* PCM bytes per wave of the host batch: default and upper bound */
 
 struct bl_buf {
   void *p = nullptr;
@@ -39,6 +42,7 @@ struct bl_amd_ctx {
   int device = 0;
   int n_cu = 256;
   int group_songs = BL_GROUP_SONGS_MAX;
+  size_t host_wave_bytes = BL_HOST_WAVE_MAX;
   hipStream_t side = nullptr; /* envelope tail runs here, beside the frequency pass */
   hipEvent_t ev_env = nullptr, ev_tail = nullptr;
   hipStream_t side2 = nullptr; /* mixed lengths: the tail of the long songs, under the window kernel of the rest */
@@ -93,8 +97,17 @@ struct bl_amd_ctx {
 int blr_ensure(bl_buf &b, size_t bytes);
 /* thread's default context (device chosen by bl_amd_init, default 0); nullptr + message on failure */
 bl_amd_ctx *blr_default_ctx(void);
+/* internal stream k (0 or 1) of the context, created on first use; nullptr + message on failure */
+hipStream_t blr_stream(bl_amd_ctx *c, int k);
+/* what the analysis accepts of song i; BL_UNEXPECTED + message otherwise */
+int blr_validate_desc(const bl_amd_song_desc &d, int i);
 int blr_analyze_device(bl_amd_ctx *c, const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs,
                        bl_amd_song_result *d_results, hipStream_t stream, int what);
+/* enqueue the conversion of n_songs device-resident songs to BL_RS_OUT_RATE on `s` (caller holds c->mu, device current) */
+int blr_resample_device(bl_amd_ctx *c, const void *d_in, int in_is_s32, const bl_amd_resample_desc *h_desc,
+                        int n_songs, int in_rate, int16_t *d_out, hipStream_t s);
+
+/* bl_host_batch.hip */
 /* host-memory batch on one context; pcm_is_s32: h_pcm[i] points at int32 samples that are
  * narrowed with >> 16 while they are staged.  in_rate: 0 / 22 050 = as is; another rate = the songs
  * are converted on the device first (wide sources then travel as int32).  d_res_out (optional) receives the device
@@ -102,6 +115,20 @@ int blr_analyze_device(bl_amd_ctx *c, const int16_t *d_pcm, const bl_amd_song_de
 int blr_analyze_host(bl_amd_ctx *c, const void *const *h_pcm, int pcm_is_s32, const int32_t *n_samples,
                      const int32_t *channels, const uint64_t *duration, int n_songs, int in_rate,
                      bl_amd_song_result *h_results, bl_amd_song_result **d_res_out);
+
+/* drops the registrations (hipHostRegister) the host batch made for its wave slot k */
+inline void blr_unregister_wave(bl_amd_ctx *c, int k) {
+  for (void *p : c->registered[k]) (void)hipHostUnregister(p);
+  c->registered[k].clear();
+}
+
+/* what the levels and the timbre accept of a song, device and host forms alike (bl_amd_timbre_frames: bl_api.c) */
+inline bool levels_song_ok(unsigned long long pcm_offset, int n_samples, int channels) {
+  return n_samples >= 2 && (channels == 1 || channels == 2) && !(pcm_offset & 7);
+}
+inline bool timbre_song_ok(unsigned long long pcm_offset, int n_samples, int channels) {
+  return bl_amd_timbre_frames(n_samples, channels) >= 1 && !(pcm_offset & 7);
+}
 
 /* makes the context's device current for the duration of a call and puts the caller's back:
  * the current device is per-thread state shared with whoever else uses HIP in this thread

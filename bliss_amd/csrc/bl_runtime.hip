@@ -1,6 +1,8 @@
 /*
  * bl_runtime.hip — contexts, workspaces, streams and the single-device C-ABI of
- * include/bliss_amd.h, but for the matrix, playlists and vector queries (bl_query_api.hip).  Host code only (compiled by hipcc for the HIP runtime API); every
+ * include/bliss_amd.h, but for the matrix, playlists and vector queries (bl_query_api.hip) and for everything that feeds
+ * songs from host memory (bl_host_batch.hip: the host batch, bl_amd_analyze_files, the *_host forms of levels and
+ * timbre).  Host code only (compiled by hipcc for the HIP runtime API); every
  * kernel lives in a bl_*kernels.hip file and is reached through the launchers of bl_launch.h.
  *
  * Contexts.  A bl_amd_ctx owns one device's scratch workspace, internal streams and pinned
@@ -19,7 +21,7 @@
  * query_call (bl_runtime.h), which shares the hand-over (ws_wait, ws_pass) with it.
  *
  * Guards.  An entry point that uses the workspace takes a CtxGuard (context lock + device guard);
- * the *_host forms, the selftests and bl_amd_narrow_s32_device use no workspace themselves and
+ * the *_host forms of levels and timbre, the selftests and bl_amd_narrow_s32_device use no workspace themselves and
  * take a DevGuard alone.  Either way a device that cannot be made current ends the call.
  */
 #include <stdio.h>
@@ -28,9 +30,6 @@
 
 #include <algorithm>
 #include <atomic>
-#include <chrono>
-#include <condition_variable>
-#include <thread>
 
 #include "bl_runtime.h"
 #include "bl_resample.h"
@@ -41,7 +40,6 @@ std::mutex g_mu;                       /* guards the default-context table */
 bl_amd_ctx *g_default[BL_MAX_DEVICES]; /* lazily created, one per device */
 std::atomic<int> g_process_device{-1};
 thread_local int tl_device = -1;
-std::atomic<int> g_host_mode{-1}; /* -1: from BL_AMD_HOST_MODE or staged */
 
 void release_buf(bl_buf &b) {
   if (b.p) (void)hipFree(b.p);
@@ -84,6 +82,10 @@ int ctx_init(bl_amd_ctx *c, int device) {
     const char *gs = getenv("BL_AMD_GROUP_SONGS");
     int g = gs ? atoi(gs) : BL_GROUP_SONGS_MAX;
     c->group_songs = g < 1 ? 1 : (g > BL_GROUP_SONGS_MAX ? BL_GROUP_SONGS_MAX : g);
+    /* PCM bytes per wave of the host batch; lowered by the tests to exercise the multi-wave path */
+    const char *wb = getenv("BL_AMD_HOST_WAVE_BYTES");
+    const long long w = wb ? atoll(wb) : (long long)BL_HOST_WAVE_MAX;
+    c->host_wave_bytes = w < 1 ? 1 : (w > (long long)BL_HOST_WAVE_MAX ? BL_HOST_WAVE_MAX : (size_t)w);
   }
   for (auto m : kCtxStreams) BL_HIP_CHECK(hipStreamCreateWithFlags(&(c->*m), hipStreamNonBlocking));
   for (auto m : kCtxEvents) BL_HIP_CHECK(hipEventCreateWithFlags(&(c->*m), hipEventDisableTiming));
@@ -105,11 +107,6 @@ void prof_collect(bl_amd_ctx *c) {
   c->events.clear();
 }
 
-void unregister_wave(bl_amd_ctx *c, int k) {
-  for (void *p : c->registered[k]) (void)hipHostUnregister(p);
-  c->registered[k].clear();
-}
-
 void ctx_release(bl_amd_ctx *c) {
   DevGuard dg(c->device);
   if (!dg.ok) return;
@@ -120,7 +117,7 @@ void ctx_release(bl_amd_ctx *c) {
                     &c->rs_songs, &c->rs_bank, &c->mx_my, &c->mx_gath, &c->mx_all, &c->mx_order, &c->mx_rows, &c->knn, &c->chain, &c->radius, &c->level_songs, &c->timbre_songs};
   for (bl_buf *b : bufs) release_buf(*b);
   for (int k = 0; k < 2; ++k) {
-    unregister_wave(c, k);
+    blr_unregister_wave(c, k);
     if (c->pinned[k]) (void)hipHostFree(c->pinned[k]);
     c->pinned[k] = nullptr;
     c->pinned_cap[k] = 0;
@@ -196,19 +193,6 @@ int record_call(bl_amd_ctx *c, hipStream_t s, bl_buf &block, int n, Fill fill, L
   return ws_pass(c, s);
 }
 
-int validate_desc(const bl_amd_song_desc &d, int i) {
-  if (d.n_samples < 5120 || (d.channels != 1 && d.channels != 2) || d.duration == 0 ||
-      (d.pcm_offset & 7)) {
-    fprintf(stderr,
-            "bliss_amd: song %d rejected (n_samples=%d channels=%d duration=%llu offset=%llu): "
-            "need n_samples >= 5120, channels 1|2, duration > 0, offset %% 8 == 0\n",
-            i, d.n_samples, d.channels, (unsigned long long)d.duration,
-            (unsigned long long)d.pcm_offset);
-    return BL_UNEXPECTED;
-  }
-  return BL_OK;
-}
-
 /* host mirror of the per-song geometry (integer work of ref tempo_atk_sort.c:63-67,
  * frequency_sort.c:50) for one launch group, written to `out` (pinned) */
 void fill_group(const bl_amd_song_desc *desc, int n_songs, bl_dsong *out, long long &env_total,
@@ -245,6 +229,19 @@ void fill_group(const bl_amd_song_desc *desc, int n_songs, bl_dsong *out, long l
 
 } // namespace
 
+int blr_validate_desc(const bl_amd_song_desc &d, int i) {
+  if (d.n_samples < 5120 || (d.channels != 1 && d.channels != 2) || d.duration == 0 ||
+      (d.pcm_offset & 7)) {
+    fprintf(stderr,
+            "bliss_amd: song %d rejected (n_samples=%d channels=%d duration=%llu offset=%llu): "
+            "need n_samples >= 5120, channels 1|2, duration > 0, offset %% 8 == 0\n",
+            i, d.n_samples, d.channels, (unsigned long long)d.duration,
+            (unsigned long long)d.pcm_offset);
+    return BL_UNEXPECTED;
+  }
+  return BL_OK;
+}
+
 void mark_cb(void *user, int k, hipStream_t s, int begin) {
   bl_amd_ctx *c = static_cast<bl_amd_ctx *>(user);
   if (!c->prof) return;
@@ -279,6 +276,14 @@ int blr_ensure(bl_buf &b, size_t bytes) {
   return BL_OK;
 }
 
+hipStream_t blr_stream(bl_amd_ctx *c, int k) {
+  if (!c->streams[k] && hipStreamCreateWithFlags(&c->streams[k], hipStreamNonBlocking) != hipSuccess) {
+    fprintf(stderr, "bliss_amd: hipStreamCreateWithFlags failed (%s:%d)\n", __FILE__, __LINE__);
+    c->streams[k] = nullptr;
+  }
+  return c->streams[k];
+}
+
 bl_amd_ctx *blr_default_ctx(void) {
   const int dev = current_device();
   if (dev < 0 || dev >= BL_MAX_DEVICES) return nullptr;
@@ -300,7 +305,7 @@ bl_amd_ctx *blr_default_ctx(void) {
 int blr_analyze_device(bl_amd_ctx *c, const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs,
                        bl_amd_song_result *d_results, hipStream_t stream, int what) {
   for (int i = 0; i < n_songs; ++i)
-    if (validate_desc(h_desc[i], i) != BL_OK) return BL_UNEXPECTED;
+    if (blr_validate_desc(h_desc[i], i) != BL_OK) return BL_UNEXPECTED;
   const int G = c->group_songs;
   const int n_groups = (n_songs + G - 1) / G;
   std::vector<long long> env_total(n_groups);
@@ -374,7 +379,6 @@ int blr_analyze_device(bl_amd_ctx *c, const int16_t *d_pcm, const bl_amd_song_de
 }
 
 /* ---- device rate conversion (bl_rs_kernels.hip), shared by the C-ABI and the host batch ---- */
-#define BL_RS_OUT_RATE 22050 /* ref src/decode.c:7 SAMPLE_RATE */
 
 /* (re)build and upload the plan of (in_rate, kind); caller holds c->mu, device is current */
 static int rs_prepare(bl_amd_ctx *c, int in_rate, int in_is_s32) {
@@ -456,246 +460,6 @@ int blr_resample_device(bl_amd_ctx *c, const void *d_in, int in_is_s32, const bl
     return BL_OK;
   };
   return record_call<bl_rs_dsong>(c, s, c->rs_songs, n_songs, fill, launch);
-}
-
-/* ---- host-memory batch: pinned staging, copy/compute overlap on 2 streams ---- */
-#ifndef BL_STAGE_THREADS
-#define BL_STAGE_THREADS 8 /* host threads of the staging copy (BL_AMD_STAGE_THREADS overrides) */
-#endif
-
-static int stage_threads(void) {
-  static const int n = [] { /* initialised once, thread-safe (C++11 function-local static) */
-    const char *e = getenv("BL_AMD_STAGE_THREADS");
-    const int v = e ? atoi(e) : BL_STAGE_THREADS;
-    return v < 1 ? 1 : (v > 64 ? 64 : v);
-  }();
-  return n;
-}
-
-static int host_mode(void) {
-  int m = g_host_mode.load();
-  if (m < 0) {
-    const char *e = getenv("BL_AMD_HOST_MODE");
-    m = (e && !strcmp(e, "registered")) ? BL_AMD_HOST_REGISTERED : BL_AMD_HOST_STAGED;
-    g_host_mode.store(m);
-  }
-  return m;
-}
-
-int blr_analyze_host(bl_amd_ctx *c, const void *const *h_pcm, int pcm_is_s32, const int32_t *n_samples,
-                     const int32_t *channels, const uint64_t *duration, int n_songs, int in_rate,
-                     bl_amd_song_result *h_results, bl_amd_song_result **d_res_out) {
-  /* songs at another rate than the analyzers' are converted on the device, wave by wave, between
-   * the transfer and the analysis; wide sources then travel as int32 (the converter's float path
-   * needs all their bits) */
-  const bool convert = in_rate > 0 && in_rate != BL_RS_OUT_RATE;
-  bl_rs_plan geo;
-  memset(&geo, 0, sizeof geo);
-  if (convert && bl_rs_plan_geometry(&geo, BL_RS_OUT_RATE, in_rate)) return BL_UNEXPECTED;
-  const size_t esz = (convert && pcm_is_s32) ? 4 : 2; /* bytes per staged sample */
-  /* reject bad descriptors before anything is staged (a negative length would otherwise
-   * become a ~2^64-byte copy) */
-  for (int i = 0; i < n_songs; ++i) {
-    if (!h_pcm[i]) {
-      fprintf(stderr, "bliss_amd: song %d rejected: NULL sample pointer\n", i);
-      return BL_UNEXPECTED;
-    }
-    bl_amd_song_desc d;
-    d.pcm_offset = 0; d.n_samples = n_samples[i]; d.channels = channels[i]; d.duration = duration[i];
-    if (convert) { /* what the analyzers will see: stereo at 22 050 Hz */
-      if (n_samples[i] <= 0 || (channels[i] != 1 && channels[i] != 2) || n_samples[i] % channels[i]) {
-        fprintf(stderr, "bliss_amd: song %d rejected (n_samples=%d channels=%d)\n", i, n_samples[i], channels[i]);
-        return BL_UNEXPECTED;
-      }
-      const size_t of = bl_rs_out_frames(&geo, (size_t)(n_samples[i] / channels[i]), nullptr);
-      d.n_samples = of > (size_t)INT32_MAX / 2 ? -1 : (int32_t)(2 * of);
-      d.channels = 2;
-    }
-    if (validate_desc(d, i) != BL_OK) return BL_UNEXPECTED;
-  }
-  for (int k = 0; k < 2; ++k)
-    if (!c->streams[k]) BL_HIP_CHECK(hipStreamCreateWithFlags(&c->streams[k], hipStreamNonBlocking));
-  if (blr_ensure(c->results, sizeof(bl_amd_song_result) * (size_t)n_songs) != BL_OK) return BL_UNEXPECTED;
-  bl_amd_song_result *d_res = static_cast<bl_amd_song_result *>(c->results.p);
-  const bool in_place = esz == 2 && !pcm_is_s32 && host_mode() == BL_AMD_HOST_REGISTERED;
-
-  /* waves of songs of at most WAVE_BYTES of PCM each (one song may exceed it): large enough
-   * that the ~20 ms latency of the serial envelope tail (paid once per wave) stays below
-   * the wave's transfer time, small enough for two pinned and two device buffers */
-  const size_t WAVE_BYTES = (size_t)2 << 30;
-  int begin = 0, wave = 0;
-  int rc = BL_OK;
-  /* The scratch workspace is per context, so the waves' kernels follow each other (event chain
-   * inside blr_analyze_device); the copies of wave w+1 overlap the kernels of wave w.  The host
-   * only ever waits for a wave's TRANSFER (its pinned buffer is free again), never for its
-   * kernels: the device arena is reused in stream order.  Waiting for the kernels put the
-   * ~20 ms latency of the serial envelope tail between two transfers (44 instead of 55 GB/s). */
-  hipEvent_t done[2] = {nullptr, nullptr};
-  for (int k = 0; k < 2 && rc == BL_OK; ++k) /* every exit below goes through the cleanup loop */
-    if (hipEventCreateWithFlags(&done[k], hipEventDisableTiming) != hipSuccess) {
-      fprintf(stderr, "bliss_amd: hipEventCreateWithFlags failed (%s:%d)\n", __FILE__, __LINE__);
-      done[k] = nullptr;
-      rc = BL_UNEXPECTED;
-    }
-  bool used[2] = {false, false};
-  while (begin < n_songs && rc == BL_OK) {
-    const int k = wave & 1;
-    size_t elems = 0, elems22 = 0;
-    int end = begin;
-    std::vector<bl_amd_song_desc> desc;   /* the staged songs (native rate when converting) */
-    std::vector<bl_amd_song_desc> desc22; /* converting: the songs as the analysis sees them */
-    std::vector<bl_amd_resample_desc> rdesc;
-    while (end < n_songs) {
-      const size_t need = ((size_t)n_samples[end] + 7) & ~(size_t)7;
-      if (end > begin && (elems + need) * esz > WAVE_BYTES) break;
-      bl_amd_song_desc d;
-      d.pcm_offset = elems; d.n_samples = n_samples[end]; d.channels = channels[end];
-      d.duration = duration[end];
-      desc.push_back(d);
-      if (convert) {
-        const size_t frames = (size_t)(n_samples[end] / channels[end]);
-        const size_t of = bl_rs_out_frames(&geo, frames, nullptr);
-        bl_amd_resample_desc r;
-        r.in_offset = elems; r.out_offset = elems22; r.frames = (int32_t)frames; r.channels = channels[end];
-        rdesc.push_back(r);
-        bl_amd_song_desc d2;
-        d2.pcm_offset = elems22; d2.n_samples = (int32_t)(2 * of); d2.channels = 2; d2.duration = duration[end];
-        desc22.push_back(d2);
-        elems22 += (2 * of + 7) & ~(size_t)7;
-      }
-      elems += need;
-      ++end;
-    }
-    const size_t bytes = elems * esz + 64;
-    const bool trace = getenv("BL_AMD_HOST_TRACE") != nullptr;
-    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t_a = now();
-    if (used[k]) { /* pinned buffer k is free again once the transfer of wave-2 has finished */
-      if (hipEventSynchronize(done[k]) != hipSuccess) { rc = BL_UNEXPECTED; break; }
-      unregister_wave(c, k);
-    }
-    const double t_b = now();
-    if (blr_ensure(c->arena[k], bytes) != BL_OK) { rc = BL_UNEXPECTED; break; }
-    hipStream_t s = c->streams[k];
-    int16_t *d_arena = static_cast<int16_t *>(c->arena[k].p);
-    if (in_place) {
-      /* pin the caller's buffers where they are (hipHostRegister keeps free() valid for the
-       * caller) and copy each song straight to its place in the arena */
-      for (size_t i = 0; i < desc.size() && rc == BL_OK; ++i) {
-        void *hp = const_cast<void *>(h_pcm[begin + i]);
-        const size_t nb = (size_t)desc[i].n_samples * 2;
-        if (hipHostRegister(hp, nb, hipHostRegisterDefault) == hipSuccess) c->registered[k].push_back(hp);
-        else (void)hipGetLastError(); /* already registered / unpinnable: the copy still works, staged by the runtime */
-        if (hipMemcpyAsync(d_arena + desc[i].pcm_offset, hp, nb, hipMemcpyHostToDevice, s) != hipSuccess)
-          rc = BL_UNEXPECTED;
-      }
-      if (rc != BL_OK) break;
-    } else {
-      if (c->pinned_cap[k] < bytes) {
-        if (c->pinned[k]) (void)hipHostFree(c->pinned[k]);
-        c->pinned[k] = nullptr; c->pinned_cap[k] = 0;
-        if (hipHostMalloc(&c->pinned[k], bytes, hipHostMallocDefault) != hipSuccess) { rc = BL_UNEXPECTED; break; }
-        c->pinned_cap[k] = bytes;
-      }
-      unsigned char *stage = static_cast<unsigned char *>(c->pinned[k]);
-      /* staging copy on several host threads: one thread moves ~10 GB/s, the link takes more.
-       * 32-bit sources are narrowed here (>> 16), so the link only ever carries s16. */
-      const int n_thr = (int)std::min<size_t>((size_t)stage_threads(), std::max<size_t>(1, elems * esz / ((size_t)32 << 20)));
-      auto copy_range = [&](int t) {
-        for (size_t i = (size_t)t; i < desc.size(); i += (size_t)n_thr) {
-          const size_t n = (size_t)desc[i].n_samples, padded = (n + 7) & ~(size_t)7;
-          if (esz == 4) { /* wide source on its way to the converter: all 32 bits */
-            int32_t *dst = reinterpret_cast<int32_t *>(stage) + desc[i].pcm_offset;
-            memcpy(dst, h_pcm[begin + i], n * 4);
-            for (size_t z = n; z < padded; ++z) dst[z] = 0;
-            continue;
-          }
-          int16_t *dst = reinterpret_cast<int16_t *>(stage) + desc[i].pcm_offset;
-          if (pcm_is_s32) {
-            const int32_t *src = static_cast<const int32_t *>(h_pcm[begin + i]);
-            for (size_t j = 0; j < n; ++j) dst[j] = (int16_t)(src[j] >> 16);
-          } else {
-            memcpy(dst, h_pcm[begin + i], n * 2);
-          }
-          for (size_t z = n; z < padded; ++z) dst[z] = 0;
-        }
-      };
-      std::vector<std::thread> pool;
-      for (int t = 1; t < n_thr; ++t) pool.emplace_back(copy_range, t);
-      copy_range(0);
-      for (auto &th : pool) th.join();
-      if (trace) fprintf(stderr, "wave %d: wait %.1f ms, stage copy %.1f ms (%zu MB, %d threads)\n", wave,
-                         1e3 * (t_b - t_a), 1e3 * (now() - t_b), elems * esz >> 20, n_thr);
-      if (hipMemcpyAsync(d_arena, stage, elems * esz, hipMemcpyHostToDevice, s) != hipSuccess) { rc = BL_UNEXPECTED; break; }
-    }
-    if (hipEventRecord(done[k], s) != hipSuccess) { rc = BL_UNEXPECTED; break; }
-    const int16_t *d_pcm = d_arena;
-    const bl_amd_song_desc *wave_desc = desc.data();
-    if (convert) { /* native-rate arena -> 22 050 Hz arena of the same wave slot, same stream */
-      if (blr_ensure(c->arena22[k], elems22 * 2 + 64) != BL_OK) { rc = BL_UNEXPECTED; break; }
-      int16_t *d22 = static_cast<int16_t *>(c->arena22[k].p);
-      if (blr_resample_device(c, d_arena, esz == 4, rdesc.data(), (int)rdesc.size(), in_rate, d22, s) != BL_OK) {
-        rc = BL_UNEXPECTED;
-        break;
-      }
-      d_pcm = d22;
-      wave_desc = desc22.data();
-    }
-    if (blr_analyze_device(c, d_pcm, wave_desc, (int)desc.size(), d_res + begin, s, 7) != BL_OK) {
-      rc = BL_UNEXPECTED;
-      break;
-    }
-    used[k] = true;
-    begin = end;
-    ++wave;
-  }
-  for (int k = 0; k < 2; ++k) {
-    if (c->streams[k] && hipStreamSynchronize(c->streams[k]) != hipSuccess) rc = BL_UNEXPECTED;
-    unregister_wave(c, k);
-    if (done[k]) (void)hipEventDestroy(done[k]);
-  }
-  if (rc == BL_OK && h_results &&
-      hipMemcpy(h_results, d_res, sizeof(bl_amd_song_result) * (size_t)n_songs, hipMemcpyDeviceToHost) != hipSuccess)
-    rc = BL_UNEXPECTED;
-  if (d_res_out) *d_res_out = d_res;
-  return rc;
-}
-
-/* ---- host forms of the signal levels and the spectral timbre: what the two share ---- */
-
-/* samples per wave of bl_amd_levels_batch_host and bl_amd_timbre_batch_host: the songs are uploaded, analysed and
- * fetched 256 MiB of PCM at a time (a song longer than that is a wave of its own) */
-#define BL_HOST_WAVE_SAMPLES ((size_t)128 << 20)
-
-/* The host songs in waves: songs [b, e) laid out in a device arena, every one at a multiple of 8 samples, as many as
- * fit BL_HOST_WAVE_SAMPLES but at least one, copied there, and `wave(d_arena, desc, b, e)` called on them with
- * desc[i - b] the place of song i.  The arena is freed when `wave` returns, so `wave` fetches what it computed. */
-template <class Wave>
-static int host_waves(const int16_t *const *h_pcm, const int32_t *n_samples, const int32_t *channels, int n_songs,
-                      Wave wave) {
-  std::vector<bl_amd_song_desc> desc;
-  for (int b = 0, e; b < n_songs; b = e) {
-    desc.clear();
-    size_t total = 0;
-    for (e = b; e < n_songs; ++e) {
-      const size_t padded = ((size_t)n_samples[e] + 7) & ~(size_t)7;
-      if (e > b && total + padded > BL_HOST_WAVE_SAMPLES) break;
-      bl_amd_song_desc d;
-      d.pcm_offset = total;
-      d.n_samples = n_samples[e];
-      d.channels = channels[e];
-      d.duration = 0;
-      desc.push_back(d);
-      total += padded;
-    }
-    DevMem arena(sizeof(int16_t) * total);
-    if (!arena.ok()) return BL_UNEXPECTED;
-    for (int i = b; i < e; ++i)
-      BL_HIP_CHECK(hipMemcpy(arena.as<int16_t>() + desc[i - b].pcm_offset, h_pcm[i],
-                             sizeof(int16_t) * (size_t)n_samples[i], hipMemcpyHostToDevice));
-    if (wave(arena.as<int16_t>(), desc.data(), b, e) != BL_OK) return BL_UNEXPECTED;
-  }
-  return BL_OK;
 }
 
 /* the device sweeps behind the selftests: `sweep(d, n_cu)` adds to n zeroed counters on the device */
@@ -812,10 +576,6 @@ int bl_amd_analyze_batch_device(const int16_t *d_pcm, const bl_amd_song_desc *h_
 
 /* ---- signal levels (bl_level_kernels.hip) ---------------------------------- */
 
-static bool levels_song_ok(unsigned long long pcm_offset, int n_samples, int channels) {
-  return n_samples >= 2 && (channels == 1 || channels == 2) && !(pcm_offset & 7);
-}
-
 static int levels_device(bl_amd_ctx *c, bool dflt, const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs,
                          int silence, bl_amd_song_levels *d_levels, void *stream) {
   if (!d_pcm || ((uintptr_t)d_pcm & 15) || !h_desc || !d_levels || n_songs < 1 || silence < 0 || silence > 32767)
@@ -850,34 +610,7 @@ int bl_amd_levels_batch_device(const int16_t *d_pcm, const bl_amd_song_desc *h_d
   return levels_device(nullptr, true, d_pcm, h_desc, n_songs, silence, d_levels, stream);
 }
 
-int bl_amd_levels_batch_host(const int16_t *const *h_pcm, const int32_t *n_samples, const int32_t *channels,
-                             int n_songs, int silence, bl_amd_song_levels *h_levels) {
-  if (!h_pcm || !n_samples || !channels || !h_levels || n_songs < 1 || silence < 0 || silence > 32767)
-    return BL_UNEXPECTED;
-  for (int i = 0; i < n_songs; ++i)
-    if (!h_pcm[i] || !levels_song_ok(0, n_samples[i], channels[i])) return BL_UNEXPECTED;
-  bl_amd_ctx *c = blr_default_ctx();
-  if (!c) return BL_UNEXPECTED;
-  DevGuard dg(c->device);
-  if (!dg.ok) return BL_UNEXPECTED;
-  return host_waves(h_pcm, n_samples, channels, n_songs,
-                    [&](const int16_t *d_pcm, const bl_amd_song_desc *desc, int b, int e) {
-                      DevMem out(sizeof(bl_amd_song_levels) * (size_t)(e - b));
-                      return out.ok() &&
-                                     levels_device(nullptr, true, d_pcm, desc, e - b, silence,
-                                                   out.as<bl_amd_song_levels>(), nullptr) == BL_OK &&
-                                     out.down(h_levels + b)
-                                 ? BL_OK
-                                 : BL_UNEXPECTED;
-                    });
-}
-
 /* ---- per-frame spectral timbre (bl_timbre_kernels.hip) ------------------------ */
-
-/* bl_amd_timbre_frames (bl_api.c) */
-static bool timbre_song_ok(unsigned long long pcm_offset, int n_samples, int channels) {
-  return bl_amd_timbre_frames(n_samples, channels) >= 1 && !(pcm_offset & 7);
-}
 
 static int timbre_device(bl_amd_ctx *c, bool dflt, const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs,
                          int pct, uint64_t min_energy, bl_amd_song_timbre *d_songs_out,
@@ -929,32 +662,6 @@ int bl_amd_timbre_batch_device(const int16_t *d_pcm, const bl_amd_song_desc *h_d
                        n_frame_records, stream);
 }
 
-int bl_amd_timbre_batch_host(const int16_t *const *h_pcm, const int32_t *n_samples, const int32_t *channels,
-                             int n_songs, int pct, uint64_t min_energy, bl_amd_song_timbre *h_songs_out,
-                             bl_amd_frame_timbre *h_frames_out) {
-  if (!h_pcm || !n_samples || !channels || !h_songs_out || n_songs < 1 || pct < 1 || pct > 100) return BL_UNEXPECTED;
-  for (int i = 0; i < n_songs; ++i)
-    if (!h_pcm[i] || !timbre_song_ok(0, n_samples[i], channels[i])) return BL_UNEXPECTED;
-  bl_amd_ctx *c = blr_default_ctx();
-  if (!c) return BL_UNEXPECTED;
-  DevGuard dg(c->device);
-  if (!dg.ok) return BL_UNEXPECTED;
-  return host_waves(h_pcm, n_samples, channels, n_songs,
-                    [&](const int16_t *d_pcm, const bl_amd_song_desc *desc, int b, int e) {
-                      long long frames = 0;
-                      for (int i = b; i < e; ++i) frames += bl_amd_timbre_frames(n_samples[i], channels[i]);
-                      DevMem out(sizeof(bl_amd_song_timbre) * (size_t)(e - b)),
-                          fout(h_frames_out ? sizeof(bl_amd_frame_timbre) * (size_t)frames : 0);
-                      if (!out.ok() || !fout.ok() ||
-                          timbre_device(nullptr, true, d_pcm, desc, e - b, pct, min_energy, out.as<bl_amd_song_timbre>(),
-                                        fout.as<bl_amd_frame_timbre>(), frames, nullptr) != BL_OK ||
-                          !out.down(h_songs_out + b) || (h_frames_out && !fout.down(h_frames_out)))
-                        return BL_UNEXPECTED;
-                      if (h_frames_out) h_frames_out += frames;
-                      return BL_OK;
-                    });
-}
-
 int bl_amd_synth_pcm_device(int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs,
                             uint32_t seed_base, uint32_t sample_rate, void *stream) {
   if (n_songs <= 0 || !d_pcm || !h_desc) return BL_UNEXPECTED;
@@ -964,7 +671,7 @@ int bl_amd_synth_pcm_device(int16_t *d_pcm, const bl_amd_song_desc *h_desc, int 
   if (!g.ok()) return BL_UNEXPECTED;
   hipStream_t s = static_cast<hipStream_t>(stream);
   for (int i = 0; i < n_songs; ++i)
-    if (validate_desc(h_desc[i], i) != BL_OK) return BL_UNEXPECTED;
+    if (blr_validate_desc(h_desc[i], i) != BL_OK) return BL_UNEXPECTED;
   const int G = BL_GROUP_SONGS_MAX;
   std::vector<int> max_n((n_songs + G - 1) / G);
   /* the descriptor block of the workspace is shared with the analysis */
@@ -995,186 +702,6 @@ int bl_amd_selftest_cos(uint64_t counts[6], uint64_t triples) {
     const int per_thread = (int)std::min<unsigned long long>((triples / 8 + threads - 1) / threads, 1u << 24);
     return blk_cos_sweep(nullptr, 0x5eedc05ull, std::max(per_thread, 1), d, n_cu);
   });
-}
-
-int bl_amd_set_host_transfer(int mode) {
-  if (mode != BL_AMD_HOST_STAGED && mode != BL_AMD_HOST_REGISTERED) return BL_UNEXPECTED;
-  g_host_mode.store(mode);
-  return BL_OK;
-}
-
-/* the host batch on the default context (`dflt`) or a given one: blr_analyze_host with the context locked */
-static int analyze_host(bl_amd_ctx *c, bool dflt, const void *const *h_pcm, int pcm_is_s32, const int32_t *n_samples,
-                        const int32_t *channels, const uint64_t *duration, int n_songs, int in_rate,
-                        bl_amd_song_result *h_results) {
-  if (n_songs <= 0 || !h_pcm || !n_samples || !channels || !duration || !h_results || !(c = call_ctx(c, dflt)))
-    return BL_UNEXPECTED;
-  CtxGuard g(c);
-  if (!g.ok()) return BL_UNEXPECTED;
-  return blr_analyze_host(c, h_pcm, pcm_is_s32, n_samples, channels, duration, n_songs, in_rate, h_results, nullptr);
-}
-
-int bl_amd_ctx_analyze_batch_host(bl_amd_ctx *ctx, const int16_t *const *h_pcm, const int32_t *n_samples,
-                                  const int32_t *channels, const uint64_t *duration, int n_songs,
-                                  bl_amd_song_result *h_results) {
-  return analyze_host(ctx, false, reinterpret_cast<const void *const *>(h_pcm), 0, n_samples, channels, duration,
-                      n_songs, 0, h_results);
-}
-
-int bl_amd_analyze_batch_host(const int16_t *const *h_pcm, const int32_t *n_samples,
-                              const int32_t *channels, const uint64_t *duration, int n_songs,
-                              bl_amd_song_result *h_results) {
-  return analyze_host(nullptr, true, reinterpret_cast<const void *const *>(h_pcm), 0, n_samples, channels, duration,
-                      n_songs, 0, h_results);
-}
-
-/* The corpus loop of ref python/examples/make_m3u_playlist.py:51-72 / examples/analyze.c:17 as one
- * call: `for file: bl_analyze(file, &song)`.  Decoding (bl_audio_decode: FLAC / WAV readers, rate
- * converter) runs on n_threads host threads that stay a bounded number of files ahead; the calling
- * thread takes the decoded songs in file order, wave by wave, through the pinned-staging host path
- * (blr_analyze_host), so that the next wave is being decoded while this one is transferred and
- * analysed.  Every songs[i] ends up exactly as bl_analyze(filenames[i], &songs[i]) leaves it. */
-int bl_amd_analyze_files(const char *const *filenames, int n_files, struct bl_song *songs, int *codes,
-                         int n_threads, int keep_pcm) {
-  if (n_files <= 0 || !filenames || !songs) return BL_UNEXPECTED;
-  bl_amd_ctx *c = blr_default_ctx();
-  if (!c) return BL_UNEXPECTED;
-  if (n_threads <= 0) n_threads = (int)std::min<unsigned>(std::max(1u, std::thread::hardware_concurrency()), 32u);
-  n_threads = std::min(n_threads, n_files);
-  const size_t WAVE_BYTES = (size_t)1 << 30; /* decoded PCM per wave */
-  /* The decoders run ahead of the wave being analysed by at most AHEAD_BYTES of decoded PCM (and AHEAD_FILES
-   * files): a byte bound, because a file bound alone lets 768 ten-minute songs (40 GB) pile up on the host.
-   * The file the consumer is waiting for is always taken, whatever the budget says, so the two cannot deadlock. */
-  const size_t AHEAD_BYTES = 3 * WAVE_BYTES; /* bounds the READ-AHEAD only: with keep_pcm the caller keeps every decoded
-                                               * sample_array (include/bliss_amd.h), and that total is the caller's */
-  const int WAVE_FILES = 512, AHEAD_FILES = 768; /* AHEAD_FILES >= WAVE_FILES: a wave never waits for a file the decoders may not take */
-
-  std::mutex mu;
-  std::condition_variable cv;
-  std::vector<signed char> state((size_t)n_files, 0); /* 0 pending, 1 decoded, -1 failed */
-  int next = 0, limit = std::min(n_files, AHEAD_FILES); /* decoders take indices below `limit` */
-  int want = 0;          /* the file the consumer needs next */
-  size_t ahead_bytes = 0; /* decoded PCM not yet released by the consumer */
-  bool stop = false;
-  auto decoder = [&] {
-    for (;;) {
-      int i;
-      {
-        std::unique_lock<std::mutex> lk(mu);
-        cv.wait(lk, [&] { return stop || next >= n_files || (next < limit && (ahead_bytes < AHEAD_BYTES || next <= want)); });
-        if (stop || next >= n_files) return;
-        i = next++;
-      }
-      /* bl_audio_decode initialises every field of songs[i] itself and fails on a NULL name: the caller's
-       * structs may be uninitialised (ref tests/test_analyze.c:27-28), so it must run for every index */
-      const int rc = bl_audio_decode(filenames[i], &songs[i]);
-      if (rc != BL_OK) fprintf(stderr, "Couldn't decode song\n"); /* ref src/analyze.c:83 */
-      {
-        std::lock_guard<std::mutex> lk(mu);
-        state[(size_t)i] = rc == BL_OK ? 1 : -1;
-        if (rc == BL_OK && songs[i].sample_array) ahead_bytes += (size_t)songs[i].nSamples * 2;
-      }
-      cv.notify_all();
-    }
-  };
-  std::vector<std::thread> pool;
-  for (int t = 0; t < n_threads; ++t) pool.emplace_back(decoder);
-
-  int done = 0, ok_count = 0, rc_all = BL_OK;
-  std::vector<const void *> pcm;
-  std::vector<int32_t> ns, ch;
-  std::vector<uint64_t> du;
-  std::vector<int> idx;
-  std::vector<bl_amd_song_result> res;
-  while (done < n_files) {
-    /* the next wave: files in order until the byte or file budget is reached; wait for each decode */
-    pcm.clear(); ns.clear(); ch.clear(); du.clear(); idx.clear();
-    size_t bytes = 0;
-    int e = done;
-    while (e < n_files && (int)(e - done) < WAVE_FILES && bytes < WAVE_BYTES) {
-      {
-        std::unique_lock<std::mutex> lk(mu);
-        if (state[(size_t)e] == 0) {
-          want = e;
-          cv.notify_all();
-          cv.wait(lk, [&] { return state[(size_t)e] != 0; });
-        }
-      }
-      if (codes) codes[e] = BL_UNEXPECTED;
-      if (state[(size_t)e] == 1) {
-        const struct bl_song &sg = songs[e];
-        /* what run_song() of bl_api.c and validate_desc() accept; anything else is reported per file */
-        if (sg.sample_array && sg.nSamples >= 5120 && (sg.channels == 1 || sg.channels == 2) && sg.duration > 0) {
-          pcm.push_back(sg.sample_array); ns.push_back(sg.nSamples); ch.push_back(sg.channels);
-          du.push_back(sg.duration); idx.push_back(e);
-          bytes += (size_t)sg.nSamples * 2;
-        } else {
-          fprintf(stderr, "bliss_amd: %s not analysable (need >= 5120 s16 samples, 1 or 2 channels, >= 1 s)\n",
-                  filenames[e]);
-        }
-      }
-      ++e;
-    }
-    { /* let the decoders run ahead of the wave that is about to be analysed */
-      std::lock_guard<std::mutex> lk(mu);
-      limit = std::min(n_files, e + AHEAD_FILES);
-    }
-    cv.notify_all();
-    if (!idx.empty()) {
-      res.assign(idx.size(), bl_amd_song_result());
-      const int rc = analyze_host(c, false, pcm.data(), 0, ns.data(), ch.data(), du.data(), (int)idx.size(), 0,
-                                  res.data());
-      if (rc != BL_OK) rc_all = BL_UNEXPECTED;
-      for (size_t k = 0; k < idx.size(); ++k) {
-        struct bl_song &sg = songs[idx[k]];
-        if (rc == BL_OK && res[k].status == BL_OK) {
-          sg.force_vector = res[k].v;            /* ref src/analyze.c:63-66 */
-          sg.force = res[k].force;               /* ref :68-72 */
-          sg.calm_or_loud = res[k].calm_or_loud; /* ref :73-79 */
-          if (codes) codes[idx[k]] = res[k].calm_or_loud;
-          ++ok_count;
-        } else {
-          fprintf(stderr, "Couldn't analyse song on the HIP device\n");
-        }
-      }
-    }
-    size_t released = 0;
-    for (int i = done; i < e; ++i) {
-      if (state[(size_t)i] == 1 && songs[i].sample_array) released += (size_t)songs[i].nSamples * 2;
-      if (!keep_pcm) {
-        free(songs[i].sample_array);
-        songs[i].sample_array = NULL;
-      }
-    }
-    {
-      std::lock_guard<std::mutex> lk(mu);
-      ahead_bytes -= std::min(released, ahead_bytes);
-    }
-    cv.notify_all();
-    done = e;
-  }
-  {
-    std::lock_guard<std::mutex> lk(mu);
-    stop = true;
-  }
-  cv.notify_all();
-  for (auto &t : pool) t.join();
-  return rc_all == BL_OK ? ok_count : BL_UNEXPECTED;
-}
-
-int bl_amd_analyze_batch_host_s32(const int32_t *const *h_pcm, const int32_t *n_samples,
-                                  const int32_t *channels, const uint64_t *duration, int n_songs,
-                                  bl_amd_song_result *h_results) {
-  return analyze_host(nullptr, true, reinterpret_cast<const void *const *>(h_pcm), 1, n_samples, channels, duration,
-                      n_songs, 0, h_results);
-}
-
-int bl_amd_analyze_batch_host_rate(const void *const *h_pcm, int pcm_is_s32, const int32_t *n_samples,
-                                   const int32_t *channels, const uint64_t *duration, int n_songs,
-                                   int sample_rate, bl_amd_song_result *h_results) {
-  if (sample_rate <= 0) return BL_UNEXPECTED;
-  return analyze_host(nullptr, true, h_pcm, pcm_is_s32 != 0, n_samples, channels, duration, n_songs, sample_rate,
-                      h_results);
 }
 
 int bl_amd_narrow_s32_device(const int32_t *d_in, int16_t *d_out, size_t n, void *stream) {
@@ -1226,8 +753,8 @@ int bld_analyze_one_host(const int16_t *h_pcm, int n, int channels, uint64_t dur
   if (!c) return BL_UNEXPECTED;
   CtxGuard g(c);
   if (!g.ok()) return BL_UNEXPECTED;
-  if (!c->streams[0]) BL_HIP_CHECK(hipStreamCreateWithFlags(&c->streams[0], hipStreamNonBlocking));
-  hipStream_t s = c->streams[0];
+  hipStream_t s = blr_stream(c, 0);
+  if (!s) return BL_UNEXPECTED;
   const size_t elems = ((size_t)n + 7) & ~(size_t)7;
   if (blr_ensure(c->arena[0], elems * 2 + 64) != BL_OK) return BL_UNEXPECTED;
   if (blr_ensure(c->results, sizeof(bl_amd_song_result)) != BL_OK) return BL_UNEXPECTED;
@@ -1252,8 +779,8 @@ int bld_mean_variance_host(const int16_t *h_pcm, int n, int have_mean, int mean_
   if (!c) return BL_UNEXPECTED;
   CtxGuard g(c);
   if (!g.ok()) return BL_UNEXPECTED;
-  if (!c->streams[0]) BL_HIP_CHECK(hipStreamCreateWithFlags(&c->streams[0], hipStreamNonBlocking));
-  hipStream_t s = c->streams[0];
+  hipStream_t s = blr_stream(c, 0);
+  if (!s) return BL_UNEXPECTED;
   const size_t elems = ((size_t)n + 7) & ~(size_t)7;
   if (blr_ensure(c->arena[0], elems * 2 + 64) != BL_OK) return BL_UNEXPECTED;
   if (blr_ensure(c->stats, sizeof(bl_dstats)) != BL_OK) return BL_UNEXPECTED;
@@ -1354,7 +881,7 @@ int bl_amd_tail_from_envelope(const bl_amd_song_desc *h_desc, int n_songs, const
                               bl_amd_song_result *h_results) {
   if (!h_desc || !h_env || !h_results || n_songs <= 0 || n_songs > BL_GROUP_SONGS_MAX) return BL_UNEXPECTED;
   for (int i = 0; i < n_songs; ++i)
-    if (validate_desc(h_desc[i], i) != BL_OK || h_desc[i].channels != 1 || h_desc[i].pcm_offset != 0) return BL_UNEXPECTED;
+    if (blr_validate_desc(h_desc[i], i) != BL_OK || h_desc[i].channels != 1 || h_desc[i].pcm_offset != 0) return BL_UNEXPECTED;
   bl_amd_ctx *c = blr_default_ctx();
   if (!c) return BL_UNEXPECTED;
   CtxGuard g(c);

@@ -90,6 +90,7 @@ int bl_amd_ctx_analyze_batch_device(bl_amd_ctx *ctx, const int16_t *d_pcm,
 /* Same from host memory: stages PCM through pinned buffers with
  * hipMemcpyAsync overlapped against the kernels of the previous wave of
  * songs, then copies the results back.  Blocking. */
+/* A wave holds at most BL_AMD_HOST_WAVE_BYTES bytes of PCM (environment, read when a context is created; default 2 GiB). */
 int bl_amd_analyze_batch_host(const int16_t *const *h_pcm, const int32_t *n_samples,
                               const int32_t *channels, const uint64_t *duration, int n_songs,
                               bl_amd_song_result *h_results);

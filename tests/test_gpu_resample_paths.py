@@ -25,7 +25,7 @@ import pytest
 import bliss_amd
 from bliss_amd import _lib
 
-OUT_RATE = 22050          # bl_runtime.hip:354 BL_RS_OUT_RATE
+OUT_RATE = 22050          # bl_runtime.h BL_RS_OUT_RATE
 RS_TILE = 1024            # bl_rs_kernels.hip:37
 RS_LDS_LIMIT = 160 * 1024  # bl_rs_kernels.hip:40
 SENTINEL = -21555         # 0xABCD
@@ -187,7 +187,7 @@ PM_LONG = {"s16": [(2, 0), (1, 0), (2, 2), (2, 4), (2, 6), (1, 2), (1, 4), (1, 6
            "s32": [(2, 0), (2, 2), (2, 4), (2, 6), (1, 0), (1, 5), (1, 2)]}
 GENERIC_LONG = [(2, 0), (1, 3), (2, 6), (1, 0), (2, 2), (1, 7)]
 ALIGN_CASES = [(44100, "s16"), (44100, "s32"), (88200, "s16"), (88200, "s32")]
-# k_resample_1p: every in_offset residue the descriptor check admits (bl_runtime.hip:416-417), out_offset residues
+# k_resample_1p: every in_offset residue the descriptor check admits (blr_resample_device, bl_runtime.hip), out_offset residues
 # 0, 2, 4, 6 three times each and in another pairing for stereo and mono; output frames beyond four whole tiles
 ALIGN_SONGS = [(2, 0, 0, 0), (2, 2, 2, 1), (2, 4, 4, 1023), (2, 6, 6, 517), (1, 0, 2, 3), (1, 1, 4, 0), (1, 2, 6, 1024),
                (1, 3, 0, 2), (1, 4, 4, 5), (1, 5, 6, 515), (1, 6, 0, 7), (1, 7, 2, 9)]

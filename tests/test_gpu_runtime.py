@@ -155,6 +155,106 @@ print(json.dumps({"enqueue": t1 - t0, "total": t2 - t0}))
     assert t["enqueue"] < 0.5 * t["total"], t     # ~14 ms of kernels behind a sub-millisecond enqueue
 
 
+_WAVE_SECS = [1, 1, 2, 1, 3, 1, 1, 2, 1, 1, 3, 1, 1]
+
+
+def _wave_lengths(rate):
+    return [rate * (1 + i % 2) * s + 8 * (i % 3) for i, s in enumerate(_WAVE_SECS)]
+
+
+def _wave_split(lengths, budget):
+    """the rule of bl_waves.h: songs in order, padded to 8, as many as fit `budget` samples but at least one"""
+    waves, total = [[]], 0
+    for i, n in enumerate(lengths):
+        padded = (n + 7) & ~7
+        if waves[-1] and total + padded > budget:
+            waves.append([])
+            total = 0
+        waves[-1].append(i)
+        total += padded
+    return waves
+
+
+def test_host_batch_over_many_waves(oracle, tmp_path):
+    """The host batch, staged and registered, from 16- and 32-bit sources, with and without rate conversion, and the
+    host forms of levels and timbre, on thirteen songs of 1-3 s: a fresh process whose wave budget is lowered to
+    300 000 bytes (6, 9 and 13 waves: both pinned buffers, both arenas and both registration lists are reused, waves of
+    several songs and single songs above the budget both occur) gives what a process with the default budget (one wave)
+    gives, and what the oracle gives."""
+    code = r'''
+import sys
+import numpy as np
+sys.path.insert(0, %r)
+import bliss_amd
+from tests.oracle_py import Oracle
+orc = Oracle()
+secs = %r
+chans = [1 + i %% 2 for i in range(13)]
+def songs(rate):
+    return [orc.synth(7000 + i, rate, chans[i], rate * chans[i] * s + 8 * (i %% 3)) for i, s in enumerate(secs)]
+def mark(name):
+    print("== " + name, file=sys.stderr, flush=True)
+lo, hi = songs(22050), songs(44100)
+rng = np.random.default_rng(5)
+wide = lambda ps: [(p.astype(np.int32) << 16) | rng.integers(0, 65536, p.size, dtype=np.int32) for p in ps]
+out = {}
+mark("staged"); out["staged"] = bliss_amd.analyze_batch_host(lo, chans, secs)
+lib = bliss_amd.load()
+assert lib.bl_amd_set_host_transfer(1) == 0
+mark("registered"); out["registered"] = bliss_amd.analyze_batch_host(lo, chans, secs)
+assert lib.bl_amd_set_host_transfer(0) == 0
+mark("s32"); out["s32"] = bliss_amd.analyze_batch_host_s32(wide(lo), chans, secs)
+mark("rate16"); out["rate16"] = bliss_amd.analyze_batch_host_rate(hi, chans, secs, 44100)
+mark("rate32"); out["rate32"] = bliss_amd.analyze_batch_host_rate(wide(hi), chans, secs, 44100)
+mark("levels"); out["levels"] = bliss_amd.levels_batch_host(hi, chans)
+mark("timbre"); out["timbre"], out["frames"] = bliss_amd.timbre_batch_host(hi, chans, frames=True)
+mark("end")
+for k in ("staged", "registered", "s32", "rate16", "rate32"):
+    assert int(out[k]["status"].max()) == 0, k
+np.savez(sys.argv[1], **out)
+''' % (ROOT, _WAVE_SECS)
+    budget = 300000
+    # the split the lowered process must make: reaches buffer reuse (a slot's third wave is wave 4) and both branches
+    split = {name: _wave_split(_wave_lengths(rate), budget // esz)
+             for name, rate, esz in (("staged", 22050, 2), ("rate16", 44100, 2), ("rate32", 44100, 4))}
+    assert [len(w) for w in split["staged"]] == [3, 2, 2, 2, 2, 2]
+    assert [len(w) for w in split["rate16"]] == [2, 1, 1, 1, 2, 1, 2, 1, 2]
+    assert [len(w) for w in split["rate32"]] == [1] * 13
+    hi = _wave_lengths(44100)
+    assert len(split["rate16"]) >= 5 and any(len(w) >= 2 for w in split["rate16"])
+    assert any(len(w) == 1 and ((hi[w[0]] + 7) & ~7) > budget // 2 for w in split["rate16"])
+    outs, errs = {}, {}
+    for tag, env in (("plain", {}), ("waves", {"BL_AMD_HOST_WAVE_BYTES": str(budget), "BL_AMD_HOST_TRACE": "1"})):
+        f = str(tmp_path / f"{tag}.npz")
+        r = subprocess.run([sys.executable, "-c", code, f], env=dict(os.environ, **env), text=True,
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        outs[tag], errs[tag] = np.load(f), r.stderr
+    for k in ("staged", "registered", "s32", "rate16", "rate32"):
+        _same(outs["plain"][k], outs["waves"][k])
+    for k in ("levels", "timbre", "frames"):
+        assert outs["plain"][k].tobytes() == outs["waves"][k].tobytes(), k
+    _same(outs["waves"]["staged"], outs["waves"]["registered"])
+    _same(outs["waves"]["staged"], outs["waves"]["s32"])
+    for i in (0, 12):
+        ch = 1 + i % 2
+        ref = oracle.analyze(oracle.synth(7000 + i, 22050, ch, _wave_lengths(22050)[i]), ch, _WAVE_SECS[i])
+        check_song(outs["waves"]["staged"][i], ref, f"song {i}, six waves")
+    # the trace lines of each call of the lowered process (the registered form and the levels and timbre print none)
+    traced, call = {}, None
+    for line in errs["waves"].splitlines():
+        if line.startswith("== "):
+            call = line[3:]
+        elif line.startswith("wave "):
+            traced.setdefault(call, []).append(int(line[5:line.index(":")]))
+    assert traced["staged"] == list(range(6)), traced
+    assert traced["s32"] == list(range(6)), traced
+    assert traced["rate16"] == list(range(9)), traced
+    assert traced["rate32"] == list(range(13)), traced
+    assert set(traced) == {"staged", "s32", "rate16", "rate32"}, traced
+    assert "wave 1:" not in errs["plain"]
+
+
 def test_mixed_batch_with_early_tail_equals_the_plain_path(oracle, tmp_path):
     """A mixed-length group of >= 1 024 songs gives its longest songs their own window launch and starts their serial
     tail under the window kernel of the rest (blk_analyze, n_head).  Same records as the same corpus analysed in
