@@ -8,25 +8,31 @@ from . import _lib
 from ._lib import (BL_CALM, BL_LOUD, BL_OK, BL_UNEXPECTED, BL_UNKNOWN, BlSong, EnvelopeResult,
                    ForceVector, FrameTimbre, SongDesc, SongLevels, SongResult, SongTimbre, load)
 from . import distance, version
-from .batch import (Context, DeviceCorpus, analyze_batch_host, analyze_files, analyze_batch_host_rate, analyze_batch_host_s32,
-                    analyze_corpus_multi, analyze_corpus_multi_device, chain, chain_device, mix, mix_device, cosine_matrix, distance_matrix, knn, knn_device,
-                    playlist, knn_cross, knn_cross_device, playlist_vec, radius_cross, radius_cross_device,
-                    duplicate_groups, duplicate_groups_device, radius, radius_device,
-                    resample_batch_device,
-                    resample_host, results_to_numpy,
-                    gapless_links, levels_batch_host, levels_db, levels_to_numpy, last_freq_stats, tail_from_envelope,
-                    timbre_batch_host, timbre_hz, timbre_to_numpy)
+from .batch import (Context, DeviceCorpus, analyze_batch_host, analyze_batch_host_rate, analyze_batch_host_s32,
+                    analyze_corpus_multi, analyze_corpus_multi_device, analyze_files, last_freq_stats, levels_batch_host,
+                    resample_batch_device, resample_host, tail_from_envelope, timbre_batch_host)
+from .queries import (chain, chain_device, cosine_matrix, distance_matrix, duplicate_groups, duplicate_groups_device, knn,
+                      knn_cross, knn_cross_device, knn_device, mix, mix_device, playlist, playlist_vec, radius,
+                      radius_cross, radius_cross_device, radius_device)
+from .records import gapless_links, levels_db, levels_to_numpy, results_to_numpy, timbre_hz, timbre_to_numpy
 from .bl_song import bl_song
 
-__all__ = ["_lib", "load", "BlSong", "ForceVector", "EnvelopeResult", "SongDesc", "SongResult",
-           "BL_LOUD", "BL_CALM", "BL_UNKNOWN", "BL_UNEXPECTED", "BL_OK", "DeviceCorpus",
-           "analyze_batch_host", "analyze_files", "analyze_batch_host_rate", "analyze_batch_host_s32", "analyze_corpus_multi", "analyze_corpus_multi_device", "Context",
-           "distance_matrix", "cosine_matrix", "results_to_numpy", "playlist", "knn", "knn_device", "chain", "chain_device", "mix", "mix_device",
-           "radius", "radius_device", "knn_cross", "knn_cross_device", "radius_cross", "radius_cross_device", "playlist_vec",
-           "duplicate_groups", "duplicate_groups_device",
-           "SongLevels", "levels_batch_host", "levels_to_numpy", "levels_db", "gapless_links",
-           "SongTimbre", "FrameTimbre", "timbre_batch_host", "timbre_to_numpy", "timbre_hz",
-           "last_freq_stats", "tail_from_envelope", "resample_host", "resample_batch_device", "bl_song", "distance", "version"]
+__all__ = [
+    # the C library, its structures and constants
+    "_lib", "load", "BlSong", "ForceVector", "EnvelopeResult", "SongDesc", "SongResult", "SongLevels", "SongTimbre",
+    "FrameTimbre", "BL_LOUD", "BL_CALM", "BL_UNKNOWN", "BL_UNEXPECTED", "BL_OK",
+    # the reference's surface
+    "bl_song", "distance", "version",
+    # batch: resident corpora, contexts, host batches, rate conversion, diagnostics
+    "DeviceCorpus", "Context", "analyze_batch_host", "analyze_batch_host_s32", "analyze_batch_host_rate", "analyze_files",
+    "analyze_corpus_multi", "analyze_corpus_multi_device", "levels_batch_host", "timbre_batch_host", "resample_host",
+    "resample_batch_device", "last_freq_stats", "tail_from_envelope",
+    # records
+    "results_to_numpy", "levels_to_numpy", "timbre_to_numpy", "levels_db", "timbre_hz", "gapless_links",
+    # queries
+    "distance_matrix", "cosine_matrix", "playlist", "playlist_vec", "knn", "knn_device", "knn_cross", "knn_cross_device",
+    "chain", "chain_device", "mix", "mix_device", "radius", "radius_device", "radius_cross", "radius_cross_device",
+    "duplicate_groups", "duplicate_groups_device"]
 
 
 def __getattr__(name):

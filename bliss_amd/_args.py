@@ -1,0 +1,48 @@
+"""The argument checks and conversions the wrappers share.  Every refusal is a ValueError that names the argument and
+shows the offending value."""
+import ctypes as C
+
+import numpy as np
+
+
+def per_song(x, n):
+    """x for each of n songs as a list: a scalar stands for all of them, a sequence is taken as it is"""
+    return [x] * n if np.isscalar(x) else list(x)
+
+
+def int_in(name, x, lo, hi=None):
+    """int(x), once x is a Python or numpy integer (no bool, no float however integral) in [lo, hi]; hi None: no upper
+    bound"""
+    if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or x < lo or (hi is not None and x > hi):
+        raise ValueError(f"{name} must be an integer in [{lo}, {'inf' if hi is None else hi}], got {x!r}")
+    return int(x)
+
+
+def songs_check(lengths, channels, shortest):
+    """per-song channel list, once there is a song and every song has 1 or 2 channels and at least shortest[channels - 1]
+    interleaved samples"""
+    n = len(lengths)
+    if n < 1:
+        raise ValueError("at least one song is needed")
+    channels = per_song(channels, n)
+    if len(channels) != n:
+        raise ValueError(f"{n} songs but {len(channels)} channel counts")
+    for i, (ln, ch) in enumerate(zip(lengths, channels)):
+        channels[i] = int_in("channels", ch, 1, 2)
+        if int(ln) < shortest[channels[i] - 1]:
+            raise ValueError(f"a song of {channels[i]} channels needs at least {shortest[channels[i] - 1]} samples, "
+                             f"got {int(ln)}")
+    return channels
+
+
+def vecs_shape_check(name, shape):
+    if len(shape) != 2 or shape[1] != 4 or shape[0] < 1:
+        raise ValueError(f"{name} must have shape (n, 4) with n >= 1, got {tuple(shape)}")
+
+
+def host_pcm(pcm_list, dtype):
+    """(arrays, pointers, sizes) of a list of host PCM arrays: contiguous arrays of `dtype`, which keep alive what the
+    c_void_p array points to, and the c_int32 array of their sample counts"""
+    arrs = [np.ascontiguousarray(p, dtype=dtype) for p in pcm_list]
+    n = len(arrs)
+    return arrs, (C.c_void_p * n)(*[a.ctypes.data for a in arrs]), (C.c_int32 * n)(*[a.size for a in arrs])

@@ -242,3 +242,14 @@ def load():
         fn.argtypes = args
     _lib = lib
     return lib
+
+
+def check(rc, what):
+    """Raise for the return code rc of the entry point `what` unless it is BL_OK."""
+    if rc != BL_OK:
+        raise RuntimeError(f"{what} failed with BL_UNEXPECTED ({rc}); see stderr")
+
+
+def libc_free(ptr):
+    """free() a block the library handed to the caller."""
+    C.CDLL(None).free(C.cast(ptr, C.c_void_p))

@@ -121,6 +121,51 @@ def test_entry_points_interleaved_on_two_streams_without_host_sync(gpu_lib, orac
     check_song(got_res["X"][0], oracle.analyze(*xs[0]), "X, song 0")
 
 
+def test_corpus_owned_outputs(gpu_lib):
+    """The output buffers a DeviceCorpus owns, on three short songs: not there before the first call, allocated by it,
+    the frame records dropped by timbre(frames=False) and allocated again, and the same bytes from the default context
+    and from an explicit one, for levels, timbre and the analysis."""
+    corpus = bliss_amd.DeviceCorpus([5120, 5633, 6144], [1, 2, 1], 1)
+    corpus.synth(seed_base=8100, sample_rate=22050)
+    assert corpus.levels_raw is None and corpus.timbre_raw is None and corpus.timbre_frames_raw is None
+    with pytest.raises(RuntimeError):
+        corpus.fetch_levels()
+    with pytest.raises(RuntimeError):
+        corpus.fetch_timbre()
+    with bliss_amd.Context(0) as ctx:
+        assert corpus.levels() is corpus.levels_raw
+        levels = corpus.fetch_levels()
+        assert levels["frames"].tolist() == [5120, 2816, 6144] and int(levels["status"].max()) == 0
+        corpus.levels_raw.fill_(0xAB)
+        corpus.levels(ctx=ctx)
+        assert corpus.fetch_levels().tobytes() == levels.tobytes()
+
+        raw_songs, raw_frames = corpus.timbre(frames=True)
+        assert raw_songs is corpus.timbre_raw and raw_frames is corpus.timbre_frames_raw
+        songs, frames = corpus.fetch_timbre()
+        assert songs["frames"].tolist() == [10, 5, 12] and frames.shape == (27,)
+        raw_songs, raw_frames = corpus.timbre(frames=False)
+        assert raw_songs is corpus.timbre_raw and raw_frames is None and corpus.timbre_frames_raw is None
+        only_songs, none = corpus.fetch_timbre()
+        assert none is None and only_songs.tobytes() == songs.tobytes()
+        for kw in ({}, {"ctx": ctx}):   # the frame records are allocated again, then written over through the context
+            corpus.timbre_raw.fill_(0xAB)
+            if corpus.timbre_frames_raw is not None:
+                corpus.timbre_frames_raw.fill_(0xAB)
+            corpus.timbre(frames=True, **kw)
+            again_songs, again_frames = corpus.fetch_timbre()
+            assert again_songs.tobytes() == songs.tobytes() and again_frames.tobytes() == frames.tobytes(), kw
+
+        corpus.analyze()
+        plain = corpus.fetch()
+        corpus.results.fill_(0xAB)
+        corpus.analyze(ctx=ctx)
+        again = corpus.fetch()
+        for k in plain.dtype.names:   # field by field: bytes 68..71 of an analysis record are padding, whose value is not defined
+            assert again[k].tobytes() == plain[k].tobytes(), k
+        assert not (again["status"].view(np.uint32) == 0xABABABAB).any()   # the second call wrote every record
+
+
 def test_launch_groups_and_async_enqueue(oracle, tmp_path):
     """More songs than one launch group holds (group size lowered through the environment for a
     fresh process) give the same records as a single group; and the device entry point returns
