@@ -114,11 +114,13 @@ def mean_variance(total, sumsq, n):
 
 def hist_integral(hist, start, end, n):
     """np.float32: the integral of the 301 times smoothed histogram around the zero bin (oracle :42-79) from the 4096
-    central counts of ALL samples.  The zeros outside [start, end] come off bin 2048 first; 301 passes of a +-3 stencil
-    reach 903 bins, so neither the bins outside the central 4096 nor the array's ends can reach the window of +-1000."""
+    central counts of ALL samples.  The zeros outside [start, end] come off bin 2048 first, in integers; then every
+    count stops at 2^24, where the reference's `float += 1` stops growing.  301 passes of a +-3 stencil reach 903 bins,
+    so neither the bins outside the central 4096 nor the array's ends can reach the window of +-1000."""
+    counts = np.array(hist, dtype=np.int64)
+    counts[2048] -= start + (n - 1 - end)
     h = np.zeros(4096 + 6, dtype=np.float32)
-    h[3:-3] = hist
-    h[3 + 2048] -= np.float32(start + (n - 1 - end))
+    h[3:-3] = np.minimum(counts, 2 ** 24)
     third = np.float32(3)
     for _ in range(301):
         acc = h[0:-6] + third * h[1:-5]
@@ -130,9 +132,10 @@ def hist_integral(hist, start, end, n):
         s = ((1. / 27.) * acc.astype(np.float64)).astype(np.float32)
         h[3:-3] = s
     lo = 3 + 2048 - 1 - 1000   # reference bins 32767 - 1000 .. 32767 + 1000; local bin of value v is v + 2048
-    v = h[lo:lo + 2001] / np.float32(start - end)
-    v = np.abs((v.astype(np.float64) * 100.).astype(np.float32))
-    return np.float32(np.cumsum(v, dtype=np.float32)[-1])
+    with np.errstate(divide="ignore", invalid="ignore"):   # start == end: the reference divides by 0
+        v = h[lo:lo + 2001] / np.float32(start - end)
+        v = np.abs((v.astype(np.float64) * 100.).astype(np.float32))
+        return np.float32(np.cumsum(v, dtype=np.float32)[-1])
 
 
 # ---- the song set -------------------------------------------------------------------------------------------------

@@ -29,7 +29,7 @@ import functools
 
 import numpy as np
 
-from tests import freq_reference
+from tests import freq_reference, stats_reference
 
 RATE = 44100
 W = 512
@@ -45,11 +45,13 @@ BOUND = 257 * 2.0 ** -24 + 2.0 ** -40   # see within_bound
 
 def mean_variance(oracle, pcm):
     """(mean, variance) by the reference's int32-wrapping definitions: tests/freq_reference.py's exact integers where
-    they hold (|mean| <= 13 571: no (sample - mean)^2 leaves an int32), the oracle's loops beyond"""
+    they hold (|mean| <= 13 571: no (sample - mean)^2 leaves an int32), tests/stats_reference.py's wrapping squares
+    beyond; the mean is the oracle's and tests/stats_reference.py's, which must agree"""
     pcm = np.asarray(pcm, dtype=np.int16)
     mean = int(oracle.mean(pcm))
+    assert mean == stats_reference.mean_wrapped(pcm)
     if abs(mean) > 13571:
-        return mean, int(oracle.variance(pcm, mean))
+        return mean, stats_reference.variance_wrapped(pcm, mean)
     total, sumsq, _ = freq_reference.statistics(pcm)
     m, v = freq_reference.mean_variance(total, sumsq, pcm.size)
     assert m == mean
