@@ -75,6 +75,12 @@ class SongTimbre(C.Structure):  # include/bliss_amd.h bl_amd_song_timbre
                 ("reserved", C.c_int32)]
 
 
+class SongRhythm(C.Structure):  # include/bliss_amd.h bl_amd_song_rhythm
+    _fields_ = [("r0", C.c_uint64), ("r_prev", C.c_uint64), ("r_lag", C.c_uint64), ("r_next", C.c_uint64),
+                ("r_peak", C.c_uint64), ("onset_sum", C.c_uint64), ("onset_max", C.c_uint32), ("hops", C.c_int32),
+                ("terms", C.c_int32), ("lag", C.c_int32), ("lag_peak", C.c_int32), ("status", C.c_int32)]
+
+
 class Shard(C.Structure):  # include/bliss_amd.h bl_amd_shard
     _fields_ = [("device", C.c_int32), ("n_songs", C.c_int32), ("d_pcm", C.c_void_p),
                 ("h_desc", C.POINTER(SongDesc)), ("d_results", C.c_void_p), ("d_rows", C.c_void_p)]
@@ -206,6 +212,18 @@ SYMBOLS = {
     "bl_amd_timbre_centroid_hz": (C.c_double, [_P(SongTimbre), C.c_int, _P(C.c_double)]),
     "bl_amd_timbre_rolloff_hz": (C.c_double, [_P(SongTimbre), C.c_int, _P(C.c_double)]),
     "bl_amd_timbre_peak_hz": (C.c_double, [_P(SongTimbre), C.c_int, _P(C.c_double)]),
+    "bl_amd_rhythm_hops": (C.c_int, [C.c_int, C.c_int]),
+    "bl_amd_rhythm_batch_device": (C.c_int, [C.c_void_p, _P(SongDesc), C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                             C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]),
+    "bl_amd_ctx_rhythm_batch_device": (C.c_int, [C.c_void_p, C.c_void_p, _P(SongDesc), C.c_int, C.c_int, C.c_int,
+                                                 C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]),
+    "bl_amd_rhythm_batch_host": (C.c_int, [_P(C.c_void_p), _P(C.c_int32), _P(C.c_int32), C.c_int, C.c_int, C.c_int,
+                                           _P(SongRhythm), _P(C.c_uint32), _P(C.c_uint64)]),
+    "bl_amd_rhythm_from_onsets": (C.c_int, [_P(C.c_uint32), _P(C.c_int32), C.c_int, C.c_int, C.c_int, _P(SongRhythm),
+                                            _P(C.c_uint64)]),
+    "bl_amd_rhythm_bpm": (C.c_double, [_P(SongRhythm), C.c_int]),
+    "bl_amd_rhythm_strength": (C.c_double, [_P(SongRhythm)]),
+    "bl_amd_selftest_isqrt": (C.c_int, [_P(C.c_uint64)]),
     "bl_amd_synth_pcm_device": (C.c_int, [C.c_void_p, _P(SongDesc), C.c_int, C.c_uint32, C.c_uint32, C.c_void_p]),
     "bl_amd_set_fir_mode": (C.c_int, [C.c_int]),
     "bl_amd_fir_mode": (C.c_int, []),

@@ -277,3 +277,30 @@ double bl_amd_timbre_peak_hz(const bl_amd_song_timbre *st, int rate, double *std
   if (!st) { if (std_hz) *std_hz = NAN; return NAN; }
   return timbre_mean_std(st->peak_sum, st->peak_sumsq, st->used, (double)rate / 512.0, std_hz);
 }
+
+/* ---- tempo: the host arithmetic over bl_amd_song_rhythm (include/bliss_amd.h) ---- */
+
+/* H = (n_samples / channels) / 128 */
+int bl_amd_rhythm_hops(int n_samples, int channels) {
+  if (n_samples < 0 || (channels != 1 && channels != 2)) return -1;
+  return (n_samples / channels) / BL_AMD_RHYTHM_HOP;
+}
+
+/* The period in hops is the lag moved by the vertex of the parabola through (lag - 1, r_prev), (lag, r_lag),
+ * (lag + 1, r_next), where there is one: the three values are below 2^60 and become doubles one by one, to 2^-53
+ * each. */
+double bl_amd_rhythm_bpm(const bl_amd_song_rhythm *r, int rate) {
+  if (!r || rate < 1 || r->lag <= 0) return NAN;
+  const double p = (double)r->r_prev, c = (double)r->r_lag, n = (double)r->r_next;
+  const double den = p - 2.0 * c + n;
+  double delta = 0.0;
+  if (den < 0.0 && c >= p && c >= n) delta = 0.5 * (p - n) / den;
+  if (delta > 0.5) delta = 0.5;
+  if (delta < -0.5) delta = -0.5;
+  return 60.0 * (double)rate / ((double)BL_AMD_RHYTHM_HOP * ((double)r->lag + delta));
+}
+
+double bl_amd_rhythm_strength(const bl_amd_song_rhythm *r) {
+  if (!r) return NAN;
+  return r->r0 ? (double)r->r_lag / (double)r->r0 : 0.0;
+}

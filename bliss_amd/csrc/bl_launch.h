@@ -2,7 +2,8 @@
  * bl_launch.h — internal seam between the kernel translation units (device code + launch
  * geometry: bl_kernels.hip the launch order of the per-song analysis, whose stages are
  * bl_stats_kernels.hip, bl_freq_kernels.hip and bl_env_kernels.hip; bl_level_kernels.hip the signal
- * levels, bl_timbre_kernels.hip the per-frame spectral timbre, bl_matrix_kernels.hip the pairwise matrix,
+ * levels, bl_timbre_kernels.hip the per-frame spectral timbre, bl_rhythm_kernels.hip the tempo,
+ * bl_matrix_kernels.hip the pairwise matrix,
  * bl_query_kernels.hip the vector queries, bl_rs_kernels.hip the rate converter)
  * and the runtime (bl_runtime.hip: contexts, workspaces, streams, the analysis C-ABI of
  * include/bliss_amd.h; bl_query_api.hip: its matrix, playlist and vector-query C-ABI; bl_multi.hip: the multi-device
@@ -78,7 +79,8 @@ struct bl_tables {
 
 /* ---- per-kernel timing (bench.py's roofline leg) ---------------------------- */
 
-enum { PK_SCAN, PK_AMP, PK_FREQ, PK_FREQ_FIN, PK_ENV, PK_TAIL, PK_DIST, PK_FREQ_SCAN, PK_COUNT };
+enum { PK_SCAN, PK_AMP, PK_FREQ, PK_FREQ_FIN, PK_ENV, PK_TAIL, PK_DIST, PK_FREQ_SCAN, PK_RHYTHM_HOPS, PK_RHYTHM_ACF,
+       PK_RHYTHM_PICK, PK_COUNT };
 
 /* called by the launchers around a kernel when profiling is on: begin = 1 before the
  * launch, 0 after it, on the stream the kernel is launched on */
@@ -192,6 +194,35 @@ int blk_timbre_configure_device(void);                 /* dynamic-LDS attribute,
  * unless d_frames is nullptr, of every frame record */
 int blk_timbre(hipStream_t s, const int16_t *d_pcm, const bl_timbre_song *d_songs, int n_songs, const bl_tables &tb,
                int pct, unsigned long long min_energy, bl_amd_song_timbre *d_songs_out, bl_amd_frame_timbre *d_frames);
+
+/* ---- per-song tempo (bl_rhythm_kernels.hip) -------------------------------------- */
+
+struct bl_rhythm_song { /* one song of a launch group; the records are sorted longest first */
+  unsigned long long pcm_off; /* int16 elements from the arena base, a multiple of 8 (unused from a curve) */
+  long long onset_off;        /* the song's first hop in d_onsets_out / the caller's curve: the sum of H over the songs
+                                 before it in the caller's order */
+  long long hop_off;          /* the song's first hop in the novelty scratch: the sum of H over the songs before it in
+                                 its launch group */
+  int hops, channels;         /* H >= 1, 1 | 2 */
+  int out_idx;                /* position in the caller's order: its record in d_songs_out, its row in d_acf_out */
+  int reserved;
+};
+#define BL_RHYTHM_GROUP_SONGS 32768          /* songs per launch group: gridDim.y of the (blocks, songs) grids */
+#define BL_RHYTHM_GROUP_HOPS (1ll << 25)     /* hops per launch group, unless its first song alone has more */
+/* bytes of the per-group block d_rows: the songs' onset sums, then (own_rows) their 512 lag products */
+size_t blk_rhythm_rows_bytes(int n_songs, bool own_rows);
+/* One launch group of bl_amd_rhythm_batch_device (d_curve == nullptr: from d_pcm through the novelty scratch d_n, one
+ * uint32 per hop of the group) or of bl_amd_rhythm_from_onsets (d_curve: the caller's onset curve on the device, d_n
+ * unused).  d_songs: the group's n_songs records, the first of them the longest (max_hops).  d_rows: at least
+ * blk_rhythm_rows_bytes(n_songs, !d_acf_out) bytes, zeroed here.  d_acf_out: nullptr, or the rows of ALL songs of the
+ * call in the caller's order, zeroed by the caller of this function.  Writes every field of the group's records in
+ * d_songs_out and, unless d_onsets_out is nullptr, the onset curve of every hop of the group. */
+int blk_rhythm_group(hipStream_t s, const int16_t *d_pcm, const uint32_t *d_curve, const bl_rhythm_song *d_songs,
+                     int n_songs, int max_hops, int lag_min, int lag_max, int n_cu, uint32_t *d_n, void *d_rows,
+                     bl_amd_song_rhythm *d_songs_out, uint32_t *d_onsets_out, uint64_t *d_acf_out, blk_mark_fn mark,
+                     void *mark_user);
+/* bl_amd_selftest_isqrt: d_counts[0..1] += values checked, values whose bl_isqrt64 is not the floor of the root */
+int blk_isqrt_sweep(hipStream_t s, unsigned long long *d_counts, int n_cu);
 
 /* ---- benchmark corpus and sample narrowing (bl_kernels.hip) -------------------- */
 

@@ -91,6 +91,9 @@ struct bl_amd_ctx {
   bl_buf level_songs;
   /* bl_amd_timbre_batch_device: the songs' records (bl_timbre_song), longest first */
   bl_buf timbre_songs;
+  /* bl_amd_rhythm_batch_device, bl_amd_rhythm_from_onsets: the songs' records (bl_rhythm_song), longest first; one
+   * launch group's novelty values (4 bytes per hop) and its onset sums and lag products (blk_rhythm_rows_bytes) */
+  bl_buf rhythm_songs, rhythm_n, rhythm_rows;
 };
 
 /* bl_runtime.hip */
@@ -128,6 +131,13 @@ inline bool levels_song_ok(unsigned long long pcm_offset, int n_samples, int cha
 }
 inline bool timbre_song_ok(unsigned long long pcm_offset, int n_samples, int channels) {
   return bl_amd_timbre_frames(n_samples, channels) >= 1 && !(pcm_offset & 7);
+}
+/* the same for the tempo (bl_amd_rhythm_hops: bl_api.c), and its lag range */
+inline bool rhythm_song_ok(unsigned long long pcm_offset, int n_samples, int channels) {
+  return bl_amd_rhythm_hops(n_samples, channels) >= 1 && !(pcm_offset & 7);
+}
+inline bool rhythm_lags_ok(int lag_min, int lag_max) {
+  return lag_min >= 1 && lag_min <= lag_max && lag_max <= BL_AMD_RHYTHM_LAGS - 2;
 }
 
 /* makes the context's device current for the duration of a call and puts the caller's back:

@@ -1,8 +1,8 @@
 /*
  * bl_runtime.hip — contexts, workspaces, streams and the single-device C-ABI of
  * include/bliss_amd.h, but for the matrix, playlists and vector queries (bl_query_api.hip) and for everything that feeds
- * songs from host memory (bl_host_batch.hip: the host batch, bl_amd_analyze_files, the *_host forms of levels and
- * timbre).  Host code only (compiled by hipcc for the HIP runtime API); every
+ * songs from host memory (bl_host_batch.hip: the host batch, bl_amd_analyze_files, the *_host forms of levels,
+ * timbre and tempo).  Host code only (compiled by hipcc for the HIP runtime API); every
  * kernel lives in a bl_*kernels.hip file and is reached through the launchers of bl_launch.h.
  *
  * Contexts.  A bl_amd_ctx owns one device's scratch workspace, internal streams and pinned
@@ -16,12 +16,12 @@
  * pinned slots (hipMemcpyAsync from pinned memory does not block), launch groups of more than
  * 32 768 songs follow each other on the stream, and the shared workspace is handed from one
  * batch to the next by an event, not by a host synchronisation.  Every entry point that uploads
- * per-song records (analysis, rate conversion, levels, timbre, synthesis, bld_mean_variance_host)
+ * per-song records (analysis, rate conversion, levels, timbre, tempo, synthesis, bld_mean_variance_host)
  * does so through record_call, the one place that knows this protocol; the vector queries have
  * query_call (bl_runtime.h), which shares the hand-over (ws_wait, ws_pass) with it.
  *
  * Guards.  An entry point that uses the workspace takes a CtxGuard (context lock + device guard);
- * the *_host forms of levels and timbre, the selftests and bl_amd_narrow_s32_device use no workspace themselves and
+ * the *_host forms of levels, timbre and tempo, the selftests and bl_amd_narrow_s32_device use no workspace themselves and
  * take a DevGuard alone.  Either way a device that cannot be made current ends the call.
  */
 #include <stdio.h>
@@ -114,7 +114,8 @@ void ctx_release(bl_amd_ctx *c) {
   prof_collect(c);
   bl_buf *bufs[] = {&c->songs,   &c->stats,   &c->hist, &c->spectrum, &c->energies, &c->lc,
                     &c->results, &c->arena[0], &c->arena[1], &c->arena22[0], &c->arena22[1],
-                    &c->rs_songs, &c->rs_bank, &c->mx_my, &c->mx_gath, &c->mx_all, &c->mx_order, &c->mx_rows, &c->knn, &c->chain, &c->radius, &c->level_songs, &c->timbre_songs};
+                    &c->rs_songs, &c->rs_bank, &c->mx_my, &c->mx_gath, &c->mx_all, &c->mx_order, &c->mx_rows, &c->knn, &c->chain, &c->radius, &c->level_songs, &c->timbre_songs,
+                    &c->rhythm_songs, &c->rhythm_n, &c->rhythm_rows};
   for (bl_buf *b : bufs) release_buf(*b);
   for (int k = 0; k < 2; ++k) {
     blr_unregister_wave(c, k);
@@ -478,6 +479,66 @@ static int selftest(uint64_t *counts, int n, Sweep sweep) {
   return BL_OK;
 }
 
+/* ---- tempo: the call path of bl_amd_rhythm_batch_device and bl_amd_rhythm_from_onsets ---- */
+
+/* One call on n_songs songs, from PCM (d_curve == nullptr) or from onset curves on the device; the caller holds the
+ * context.  `song(i, rec)` writes pcm_off, hops and channels of song i in the caller's order.  The records are sorted
+ * longest first, as the analysis lays its songs out, and cut into launch groups of at most c->group_songs songs and
+ * BL_RHYTHM_GROUP_HOPS = 2^25 hops (a longer song is a group of its own; H < 2^24, so there is none).  The groups
+ * follow each other on the stream and share the scratch, which is therefore bounded whatever the call: 4 bytes per hop
+ * = 128 MiB of novelty values, and per song 16 bytes of sums and, without d_acf_out, 4 KiB of lag products = 128.5 MiB
+ * at 32 768 songs. */
+template <class Song>
+static int rhythm_call(bl_amd_ctx *c, hipStream_t s, int n_songs, Song song, const int16_t *d_pcm,
+                       const uint32_t *d_curve, int lag_min, int lag_max, bl_amd_song_rhythm *d_songs_out,
+                       uint32_t *d_onsets_out, uint64_t *d_acf_out) {
+  return record_call<bl_rhythm_song>(c, s, c->rhythm_songs, n_songs, [&](bl_rhythm_song *hs) {
+    long long onset_off = 0;
+    for (int i = 0; i < n_songs; ++i) {
+      song(i, hs[i]);
+      hs[i].onset_off = onset_off;
+      hs[i].out_idx = i;
+      hs[i].reserved = 0;
+      onset_off += hs[i].hops;
+    }
+    std::stable_sort(hs, hs + n_songs, [](const bl_rhythm_song &a, const bl_rhythm_song &b) { return a.hops > b.hops; });
+    const int group_songs = std::min(c->group_songs, BL_RHYTHM_GROUP_SONGS);
+    long long in_group = 0; /* hop_off == 0 marks the first song of a group: every song has H >= 1 */
+    for (int i = 0, count = 0; i < n_songs; ++i, ++count) {
+      if (count == group_songs || (count && in_group + hs[i].hops > BL_RHYTHM_GROUP_HOPS)) in_group = count = 0;
+      hs[i].hop_off = in_group;
+      in_group += hs[i].hops;
+    }
+    return BL_OK;
+  }, [&](const bl_rhythm_song *hs, bl_rhythm_song *d_songs) {
+    auto group_end = [&](int b, long long &hops) {
+      int e = b + 1;
+      for (hops = hs[b].hops; e < n_songs && hs[e].hop_off; ++e) hops += hs[e].hops;
+      return e;
+    };
+    long long hops, max_hops = 0;
+    int max_songs = 0;
+    for (int b = 0, e; b < n_songs; b = e) {
+      e = group_end(b, hops);
+      max_hops = std::max(max_hops, hops);
+      max_songs = std::max(max_songs, e - b);
+    }
+    if ((!d_curve && blr_ensure(c->rhythm_n, sizeof(uint32_t) * (size_t)max_hops) != BL_OK) ||
+        blr_ensure(c->rhythm_rows, blk_rhythm_rows_bytes(max_songs, !d_acf_out)) != BL_OK)
+      return BL_UNEXPECTED;
+    if (d_acf_out)
+      BL_HIP_CHECK(hipMemsetAsync(d_acf_out, 0, sizeof(uint64_t) * BL_AMD_RHYTHM_LAGS * (size_t)n_songs, s));
+    for (int b = 0, e; b < n_songs; b = e) {
+      e = group_end(b, hops);
+      if (blk_rhythm_group(s, d_pcm, d_curve, d_songs + b, e - b, hs[b].hops, lag_min, lag_max, c->n_cu,
+                           static_cast<uint32_t *>(c->rhythm_n.p), c->rhythm_rows.p, d_songs_out, d_onsets_out,
+                           d_acf_out, c->prof ? mark_cb : nullptr, c) != BL_OK)
+        return BL_UNEXPECTED;
+    }
+    return BL_OK;
+  });
+}
+
 /* ========================================================================= */
 /* C-ABI                                                                      */
 
@@ -546,7 +607,8 @@ void bl_amd_profile_reset(void) {
 
 double bl_amd_profile_ms(const char *name, int *launches) {
   static const char *const kProfNames[PK_COUNT] = {"pcm_scan",    "amp_finish", "freq_frames", "freq_finish",
-                                                   "env_windows", "env_tail",   "distance",    "freq_scan"};
+                                                   "env_windows", "env_tail",   "distance",    "freq_scan",
+                                                   "rhythm_hops", "rhythm_acf", "rhythm_pick"};
   if (launches) *launches = 0;
   bl_amd_ctx *c = blr_default_ctx();
   if (!c || !name) return -1.0;
@@ -660,6 +722,76 @@ int bl_amd_timbre_batch_device(const int16_t *d_pcm, const bl_amd_song_desc *h_d
                                bl_amd_frame_timbre *d_frames_out, long long n_frame_records, void *stream) {
   return timbre_device(nullptr, true, d_pcm, h_desc, n_songs, pct, min_energy, d_songs_out, d_frames_out,
                        n_frame_records, stream);
+}
+
+/* ---- tempo (bl_rhythm_kernels.hip) --------------------------------------------- */
+
+static int rhythm_device(bl_amd_ctx *c, bool dflt, const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs,
+                         int lag_min, int lag_max, bl_amd_song_rhythm *d_songs_out, uint32_t *d_onsets_out,
+                         long long n_onsets, uint64_t *d_acf_out, void *stream) {
+  if (!d_pcm || ((uintptr_t)d_pcm & 15) || !h_desc || !d_songs_out || ((uintptr_t)d_songs_out & 7) ||
+      ((uintptr_t)d_onsets_out & 3) || ((uintptr_t)d_acf_out & 7) || n_songs < 1 || !rhythm_lags_ok(lag_min, lag_max))
+    return BL_UNEXPECTED;
+  long long total = 0; /* the sum of H over the songs */
+  for (int i = 0; i < n_songs; ++i) {
+    if (!rhythm_song_ok(h_desc[i].pcm_offset, h_desc[i].n_samples, h_desc[i].channels)) return BL_UNEXPECTED;
+    total += bl_amd_rhythm_hops(h_desc[i].n_samples, h_desc[i].channels);
+  }
+  if ((d_onsets_out && n_onsets != total) || !(c = call_ctx(c, dflt))) return BL_UNEXPECTED;
+  CtxGuard g(c);
+  if (!g.ok()) return BL_UNEXPECTED;
+  return rhythm_call(c, static_cast<hipStream_t>(stream), n_songs, [&](int i, bl_rhythm_song &r) {
+    r.pcm_off = h_desc[i].pcm_offset;
+    r.hops = bl_amd_rhythm_hops(h_desc[i].n_samples, h_desc[i].channels);
+    r.channels = h_desc[i].channels;
+  }, d_pcm, nullptr, lag_min, lag_max, d_songs_out, d_onsets_out, d_acf_out);
+}
+
+int bl_amd_ctx_rhythm_batch_device(bl_amd_ctx *c, const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs,
+                                   int lag_min, int lag_max, bl_amd_song_rhythm *d_songs_out, uint32_t *d_onsets_out,
+                                   long long n_onsets, uint64_t *d_acf_out, void *stream) {
+  return rhythm_device(c, false, d_pcm, h_desc, n_songs, lag_min, lag_max, d_songs_out, d_onsets_out, n_onsets,
+                       d_acf_out, stream);
+}
+
+int bl_amd_rhythm_batch_device(const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs, int lag_min,
+                               int lag_max, bl_amd_song_rhythm *d_songs_out, uint32_t *d_onsets_out,
+                               long long n_onsets, uint64_t *d_acf_out, void *stream) {
+  return rhythm_device(nullptr, true, d_pcm, h_desc, n_songs, lag_min, lag_max, d_songs_out, d_onsets_out, n_onsets,
+                       d_acf_out, stream);
+}
+
+/* stages 7 and 8 on the caller's curves: uploaded, through the same launch as the device form, fetched */
+int bl_amd_rhythm_from_onsets(const uint32_t *h_onsets, const int32_t *h_hops, int n_songs, int lag_min, int lag_max,
+                              bl_amd_song_rhythm *h_songs_out, uint64_t *h_acf_out) {
+  if (!h_onsets || !h_hops || !h_songs_out || n_songs < 1 || !rhythm_lags_ok(lag_min, lag_max)) return BL_UNEXPECTED;
+  long long total = 0;
+  for (int i = 0; i < n_songs; ++i) {
+    if (h_hops[i] < 1 || h_hops[i] >= (1 << 24)) return BL_UNEXPECTED;
+    total += h_hops[i];
+  }
+  for (long long k = 0; k < total; ++k)
+    if (h_onsets[k] >= (1u << 18)) return BL_UNEXPECTED;
+  bl_amd_ctx *c = blr_default_ctx();
+  if (!c) return BL_UNEXPECTED;
+  CtxGuard g(c);
+  if (!g.ok()) return BL_UNEXPECTED;
+  DevMem curve(sizeof(uint32_t) * (size_t)total), out(sizeof(bl_amd_song_rhythm) * (size_t)n_songs),
+      acf(h_acf_out ? sizeof(uint64_t) * BL_AMD_RHYTHM_LAGS * (size_t)n_songs : 0);
+  if (!curve.ok() || !out.ok() || !acf.ok() || !curve.up(h_onsets)) return BL_UNEXPECTED;
+  if (rhythm_call(c, nullptr, n_songs, [&](int i, bl_rhythm_song &r) {
+        r.pcm_off = 0;
+        r.hops = h_hops[i];
+        r.channels = 1;
+      }, nullptr, curve.as<uint32_t>(), lag_min, lag_max, out.as<bl_amd_song_rhythm>(), nullptr,
+      acf.as<uint64_t>()) != BL_OK)
+    return BL_UNEXPECTED;
+  BL_HIP_CHECK(hipStreamSynchronize(nullptr));
+  return out.down(h_songs_out) && (!h_acf_out || acf.down(h_acf_out)) ? BL_OK : BL_UNEXPECTED;
+}
+
+int bl_amd_selftest_isqrt(uint64_t counts[2]) {
+  return selftest(counts, 2, [](unsigned long long *d, int n_cu) { return blk_isqrt_sweep(nullptr, d, n_cu); });
 }
 
 int bl_amd_synth_pcm_device(int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs,

@@ -551,6 +551,83 @@ double bl_amd_timbre_centroid_hz(const bl_amd_song_timbre *st, int rate, double 
 double bl_amd_timbre_rolloff_hz(const bl_amd_song_timbre *st, int rate, double *std_hz);
 double bl_amd_timbre_peak_hz(const bl_amd_song_timbre *st, int rate, double *std_hz);
 
+/* Tempo: a song's beat period, which — unlike the reference's `tempo` rating — converts to beats per minute, and how
+ * much of the onset energy repeats at it.  The reference's author lists "BPM" and "Beat loudness" in ROADMAP.md
+ * ("Temporal features"); none of it is in the reference's API.  Every field is an exact integer: all arithmetic below
+ * is integer arithmetic and fits 64 bits.
+ * F = n_samples / channels frames, H = F / 128 hops (BL_AMD_RHYTHM_HOP frames each), T = H - 511 terms.
+ *   1 mix         m[i] = l[i] + r[i] (stereo) or 2 s[i] (mono: a mono song and its dual-mono copy give the same
+ *                 bytes); d[0] = 0, d[i] = m[i] - m[i-1]: across hop boundaries, never across the song's start.  No
+ *                 sample outside the song's 128 H whole frames is read.
+ *   2 energies    over the hop's 128 frames: A_h = sum m[i]^2, B_h = sum d[i]^2
+ *   3 amplitudes  a_h = isqrt((A_h + A_{h-1} + A_{h-2} + A_{h-3}) >> 9), b_h the same from B; indices below 0
+ *                 contribute 0; isqrt is the exact floor of the square root
+ *   4 novelty     n_0 = 0, n_h = max(0, a_h - a_{h-1}) + max(0, b_h - b_{h-1})
+ *   5 local mean  q_h = max(0, 16 n_h - sum_{k=-8..7} n_{h+k}) >> 4, n outside [0, H) taken as 0
+ *   6 smoothing   o_h = (q_{h-1} + 2 q_h + q_{h+1}) >> 2, q outside [0, H) taken as 0: the onset curve
+ *   7 lags        R[tau] = sum_{h=0}^{T-1} o_h o_{h+tau}, tau = 0 .. 511: the same number of terms for every lag
+ *   8 pick        over the caller's range 1 <= lag_min <= lag_max <= 510: r_peak = max R[tau], lag_peak the smallest
+ *                 tau that attains it.  r_peak == 0: lag = lag_peak = 0.  Otherwise lag is the smallest tau in the range
+ *                 with R[tau] >= R[tau-1], R[tau] >= R[tau+1] and 16 R[tau] >= 15 r_peak (the shortest period that is
+ *                 a local maximum within 1/16 of the best: a periodic curve scores equally at every multiple of its
+ *                 period), or lag_peak if there is none.
+ * Bounds: |m| <= 2^16, so m^2 reaches 2^32 (the all -32768 stereo song) and does not fit 32 bits; d^2 < 2^34;
+ * A_h <= 2^39, B_h < 2^41, the window sums < 2^43, so a_h <= 2^16, b_h < 2^17 and n, q, o < 2^18; a product is
+ * < 2^36 and H < 2^24 (n_samples is an int), so R < 2^60 and 16 R < 2^64. */
+#define BL_AMD_RHYTHM_HOP 128
+#define BL_AMD_RHYTHM_LAGS 512
+typedef struct bl_amd_song_rhythm { /* 72 bytes */
+  uint64_t r0, r_prev, r_lag, r_next; /* R[0], R[lag-1], R[lag], R[lag+1]; the last three are 0 when lag == 0 */
+  uint64_t r_peak, onset_sum;         /* max over the range; sum of o_h over all H hops */
+  uint32_t onset_max;                 /* max of o_h over all H hops */
+  int32_t hops, terms;                /* H, T */
+  int32_t lag, lag_peak;
+  int32_t status;                     /* BL_OK; BL_UNEXPECTED for a song with H < 512 */
+} bl_amd_song_rhythm;
+/* bl_amd_rhythm_hops: H of a song, plain host arithmetic; -1 for n_samples < 0 or channels outside {1, 2}.
+ * bl_amd_rhythm_batch_device: the tempo of n_songs songs whose PCM sits in device memory.  The descriptors are those
+ * of bl_amd_analyze_batch_device with other limits: pcm_offset a multiple of 8, channels 1 or 2, H >= 1, duration
+ * ignored; d_pcm 16-byte aligned.  1 <= lag_min <= lag_max <= 510, n_songs >= 1.  d_songs_out: n_songs records in the
+ * caller's order.  d_onsets_out may be NULL (n_onsets is then ignored); otherwise it receives o_h of every hop, songs
+ * concatenated in the caller's order, song i at the sum of H_j over j < i, and n_onsets must equal the sum of all H_j.
+ * d_acf_out may be NULL; otherwise it receives R[0 .. 511] of every song, 512 values per song in the caller's order.
+ * No output needs zeroing and every byte of every record is written.  A rejected call returns BL_UNEXPECTED and
+ * writes nothing.  A song with H < 512 is no error of the call: its record has status = BL_UNEXPECTED, hops = H,
+ * terms = 0 and everything else 0, its row of d_acf_out is 0 and its onsets are written.  Asynchronous on `stream`;
+ * h_desc is copied before the call returns.  Calls of one context are ordered on the device like its batches.  A
+ * song's outputs are a pure function of its samples, `channels`, lag_min and lag_max: they depend neither on the other
+ * songs, n_songs, the order, the launch shape nor on which optional outputs are asked for.  Read-only towards
+ * bl_amd_last_energies and bl_amd_last_freq_stats.
+ *   bl_amd_rhythm_batch_host: the same from host memory, blocking: the songs are uploaded and analysed in waves;
+ *     h_onsets_out and h_acf_out may be NULL.
+ *   bl_amd_rhythm_from_onsets: stages 7 and 8 alone on onset curves the caller supplies, from host memory, blocking:
+ *     h_onsets holds the curves one behind the other, h_hops[i] >= 1 values of song i, each value < 2^18 and
+ *     h_hops[i] < 2^24 (else the call is rejected); onset_sum and onset_max are those of the given curve; h_acf_out
+ *     may be NULL.
+ *   bl_amd_rhythm_bpm: plain host arithmetic in double from the exact integers, no device.  NaN for lag == 0 (or a
+ *     NULL record, or rate < 1).  With den = r_prev - 2 r_lag + r_next: delta = 0.5 (r_prev - r_next) / den if
+ *     den < 0 and r_lag is at least as large as both neighbours, else 0; clamped to +-0.5;
+ *     bpm = 60 rate / (128 (lag + delta)).
+ *   bl_amd_rhythm_strength: r_lag / r0, 0 when r0 == 0 (NaN for a NULL record): how much of the curve's energy repeats
+ *     at the beat.  It can slightly exceed 1 because the two factors cover different stretches of the curve.
+ *   bl_amd_selftest_isqrt: sweeps, on the device, 0 and k^2 - 1, k^2, k^2 + 1 for every k in [1, 2^17] against
+ *     r^2 <= x < (r + 1)^2; counts = {checked, wrong}. */
+int bl_amd_rhythm_hops(int n_samples, int channels);
+int bl_amd_rhythm_batch_device(const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs, int lag_min,
+                               int lag_max, bl_amd_song_rhythm *d_songs_out, uint32_t *d_onsets_out,
+                               long long n_onsets, uint64_t *d_acf_out, void *stream);
+int bl_amd_ctx_rhythm_batch_device(bl_amd_ctx *ctx, const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs,
+                                   int lag_min, int lag_max, bl_amd_song_rhythm *d_songs_out, uint32_t *d_onsets_out,
+                                   long long n_onsets, uint64_t *d_acf_out, void *stream);
+int bl_amd_rhythm_batch_host(const int16_t *const *h_pcm, const int32_t *n_samples, const int32_t *channels,
+                             int n_songs, int lag_min, int lag_max, bl_amd_song_rhythm *h_songs_out,
+                             uint32_t *h_onsets_out, uint64_t *h_acf_out);
+int bl_amd_rhythm_from_onsets(const uint32_t *h_onsets, const int32_t *h_hops, int n_songs, int lag_min, int lag_max,
+                              bl_amd_song_rhythm *h_songs_out, uint64_t *h_acf_out);
+double bl_amd_rhythm_bpm(const bl_amd_song_rhythm *r, int rate);
+double bl_amd_rhythm_strength(const bl_amd_song_rhythm *r);
+int bl_amd_selftest_isqrt(uint64_t counts[2]);
+
 /* Integer-only synthetic PCM (the benchmark corpus of BASELINE.json),
  * generated in place on the device: song i = seed_base + i, written at
  * h_desc[i].pcm_offset.  Byte-identical to oracle/orc_synth.c. */
@@ -574,7 +651,7 @@ int bl_amd_fir_mode(void);
 /* Per-kernel device time, measured with hipEvents on the launch stream while
  * profiling is on (bench.py's roofline leg).  name is one of "pcm_scan", "freq_scan",
  * "amp_finish", "freq_frames", "freq_finish", "env_windows", "env_tail",
- * "distance"; returns accumulated milliseconds and the launch count since the
+ * "distance", "rhythm_hops", "rhythm_acf", "rhythm_pick"; returns accumulated milliseconds and the launch count since the
  * last reset, or -1 for an unknown name. */
 void bl_amd_profile(int enable);
 void bl_amd_profile_reset(void);
