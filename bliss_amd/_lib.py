@@ -81,6 +81,15 @@ class SongRhythm(C.Structure):  # include/bliss_amd.h bl_amd_song_rhythm
                 ("terms", C.c_int32), ("lag", C.c_int32), ("lag_peak", C.c_int32), ("status", C.c_int32)]
 
 
+class FrameChroma(C.Structure):  # include/bliss_amd.h bl_amd_frame_chroma
+    _fields_ = [("x", C.c_uint64 * 12)]
+
+
+class SongChroma(C.Structure):  # include/bliss_amd.h bl_amd_song_chroma
+    _fields_ = [("chroma", C.c_uint64 * 12), ("score", C.c_int64), ("score_next", C.c_int64), ("frames", C.c_int32),
+                ("key", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
 class Shard(C.Structure):  # include/bliss_amd.h bl_amd_shard
     _fields_ = [("device", C.c_int32), ("n_songs", C.c_int32), ("d_pcm", C.c_void_p),
                 ("h_desc", C.POINTER(SongDesc)), ("d_results", C.c_void_p), ("d_rows", C.c_void_p)]
@@ -224,6 +233,15 @@ SYMBOLS = {
     "bl_amd_rhythm_bpm": (C.c_double, [_P(SongRhythm), C.c_int]),
     "bl_amd_rhythm_strength": (C.c_double, [_P(SongRhythm)]),
     "bl_amd_selftest_isqrt": (C.c_int, [_P(C.c_uint64)]),
+    "bl_amd_chroma_frames": (C.c_int, [C.c_int, C.c_int]),
+    "bl_amd_chroma_batch_device": (C.c_int, [C.c_void_p, _P(SongDesc), C.c_int, C.c_void_p, C.c_void_p, C.c_longlong,
+                                             C.c_void_p]),
+    "bl_amd_ctx_chroma_batch_device": (C.c_int, [C.c_void_p, C.c_void_p, _P(SongDesc), C.c_int, C.c_void_p, C.c_void_p,
+                                                 C.c_longlong, C.c_void_p]),
+    "bl_amd_chroma_batch_host": (C.c_int, [_P(C.c_void_p), _P(C.c_int32), _P(C.c_int32), C.c_int, _P(SongChroma),
+                                           _P(FrameChroma)]),
+    "bl_amd_chroma_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bl_amd_chroma_key_name": (C.c_int, [C.c_int, C.c_char_p]),
     "bl_amd_synth_pcm_device": (C.c_int, [C.c_void_p, _P(SongDesc), C.c_int, C.c_uint32, C.c_uint32, C.c_void_p]),
     "bl_amd_set_fir_mode": (C.c_int, [C.c_int]),
     "bl_amd_fir_mode": (C.c_int, []),

@@ -23,6 +23,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "bl_chroma_table.h"
 #include "bl_device.h"
 #include "bliss.h"
 
@@ -303,4 +304,28 @@ double bl_amd_rhythm_bpm(const bl_amd_song_rhythm *r, int rate) {
 double bl_amd_rhythm_strength(const bl_amd_song_rhythm *r) {
   if (!r) return NAN;
   return r->r0 ? (double)r->r_lag / (double)r->r0 : 0.0;
+}
+
+/* ---- chroma and key: the host side of bl_amd_song_chroma (include/bliss_amd.h) ---- */
+
+/* T = 0 below one frame, else (Fr - 4096) / 2048 + 1 */
+int bl_amd_chroma_frames(int n_samples, int channels) {
+  if (n_samples < 0 || (channels != 1 && channels != 2)) return -1;
+  const int fr = n_samples / channels;
+  return fr < BL_AMD_CHROMA_FRAME ? 0 : (fr - BL_AMD_CHROMA_FRAME) / BL_AMD_CHROMA_HOP + 1;
+}
+
+int bl_amd_chroma_table(int8_t *re, int8_t *im, uint32_t *gain, int32_t *len) {
+  bl_chroma_build(re, im, gain, len);
+  return BL_OK;
+}
+
+int bl_amd_chroma_key_name(int key, char out[8]) {
+  static const char *const kTonic[12] = {"C", "C#", "D", "D#", "E", "F", "F#", "G", "G#", "A", "A#", "B"};
+  if (!out) return BL_UNEXPECTED;
+  out[0] = 0;
+  if (key < 0 || key > 23) return BL_UNEXPECTED;
+  strcpy(out, kTonic[key % 12]);
+  if (key >= 12) strcat(out, "m");
+  return BL_OK;
 }

@@ -3,6 +3,7 @@
  * geometry: bl_kernels.hip the launch order of the per-song analysis, whose stages are
  * bl_stats_kernels.hip, bl_freq_kernels.hip and bl_env_kernels.hip; bl_level_kernels.hip the signal
  * levels, bl_timbre_kernels.hip the per-frame spectral timbre, bl_rhythm_kernels.hip the tempo,
+ * bl_chroma_kernels.hip chroma and key,
  * bl_matrix_kernels.hip the pairwise matrix,
  * bl_query_kernels.hip the vector queries, bl_rs_kernels.hip the rate converter)
  * and the runtime (bl_runtime.hip: contexts, workspaces, streams, the analysis C-ABI of
@@ -80,7 +81,7 @@ struct bl_tables {
 /* ---- per-kernel timing (bench.py's roofline leg) ---------------------------- */
 
 enum { PK_SCAN, PK_AMP, PK_FREQ, PK_FREQ_FIN, PK_ENV, PK_TAIL, PK_DIST, PK_FREQ_SCAN, PK_RHYTHM_HOPS, PK_RHYTHM_ACF,
-       PK_RHYTHM_PICK, PK_COUNT };
+       PK_RHYTHM_PICK, PK_CHROMA_PITCH, PK_CHROMA_KEY, PK_COUNT };
 
 /* called by the launchers around a kernel when profiling is on: begin = 1 before the
  * launch, 0 after it, on the stream the kernel is launched on */
@@ -223,6 +224,25 @@ int blk_rhythm_group(hipStream_t s, const int16_t *d_pcm, const uint32_t *d_curv
                      void *mark_user);
 /* bl_amd_selftest_isqrt: d_counts[0..1] += values checked, values whose bl_isqrt64 is not the floor of the root */
 int blk_isqrt_sweep(hipStream_t s, unsigned long long *d_counts, int n_cu);
+
+/* ---- chroma and key (bl_chroma_kernels.hip) ---------------------------------------- */
+
+struct bl_chroma_song { /* record i belongs to d_songs_out[i]: the caller's order */
+  unsigned long long pcm_off; /* int16 elements from the arena base, a multiple of 8 */
+  long long frame_off;        /* the song's first record in d_frames: the sum of T over the songs before it */
+  int frames, channels;       /* T >= 0, 1 | 2 */
+};
+#define BL_CHROMA_GROUP_SONGS 32768 /* songs per launch: gridDim.y of the (blocks, songs) grid */
+/* the image of the bank the pitch kernel reads (coefficients in the order its lanes take them, the rows' constants, the
+ * gains, the live blocks): its size, and its bytes as built on the host from bl_chroma_table.h, once per process */
+size_t blk_chroma_image_bytes(void);
+const unsigned char *blk_chroma_image_host(void);
+/* bl_amd_chroma_batch_device on one launch group: d_songs its n_songs records, the longest of them max_frames frames;
+ * d_image: the device copy of the image; d_acc: 12 uint64 per song, zeroed here.  Writes every byte of the group's
+ * records in d_songs_out and, unless d_frames is nullptr, of every frame record of the group. */
+int blk_chroma(hipStream_t s, const int16_t *d_pcm, const bl_chroma_song *d_songs, int n_songs, int max_frames,
+               int n_cu, const void *d_image, unsigned long long *d_acc, bl_amd_song_chroma *d_songs_out,
+               bl_amd_frame_chroma *d_frames, blk_mark_fn mark, void *mark_user);
 
 /* ---- benchmark corpus and sample narrowing (bl_kernels.hip) -------------------- */
 

@@ -94,6 +94,10 @@ struct bl_amd_ctx {
   /* bl_amd_rhythm_batch_device, bl_amd_rhythm_from_onsets: the songs' records (bl_rhythm_song), longest first; one
    * launch group's novelty values (4 bytes per hop) and its onset sums and lag products (blk_rhythm_rows_bytes) */
   bl_buf rhythm_songs, rhythm_n, rhythm_rows;
+  /* bl_amd_chroma_batch_device: the songs' records (bl_chroma_song), their twelve sums, and the bank's image
+   * (blk_chroma_image_host), uploaded by the context's first call */
+  bl_buf chroma_songs, chroma_acc, chroma_image;
+  bool chroma_image_ready = false;
 };
 
 /* bl_runtime.hip */
@@ -135,6 +139,10 @@ inline bool timbre_song_ok(unsigned long long pcm_offset, int n_samples, int cha
 /* the same for the tempo (bl_amd_rhythm_hops: bl_api.c), and its lag range */
 inline bool rhythm_song_ok(unsigned long long pcm_offset, int n_samples, int channels) {
   return bl_amd_rhythm_hops(n_samples, channels) >= 1 && !(pcm_offset & 7);
+}
+/* the same for chroma and key: one whole frame of 1 | 2 channels at least (bl_amd_chroma_frames: bl_api.c) */
+inline bool chroma_song_ok(unsigned long long pcm_offset, int n_samples, int channels) {
+  return bl_amd_chroma_frames(n_samples, channels) >= 0 && n_samples / channels >= 1 && !(pcm_offset & 7);
 }
 inline bool rhythm_lags_ok(int lag_min, int lag_max) {
   return lag_min >= 1 && lag_min <= lag_max && lag_max <= BL_AMD_RHYTHM_LAGS - 2;

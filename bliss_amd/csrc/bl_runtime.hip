@@ -16,7 +16,7 @@
  * pinned slots (hipMemcpyAsync from pinned memory does not block), launch groups of more than
  * 32 768 songs follow each other on the stream, and the shared workspace is handed from one
  * batch to the next by an event, not by a host synchronisation.  Every entry point that uploads
- * per-song records (analysis, rate conversion, levels, timbre, tempo, synthesis, bld_mean_variance_host)
+ * per-song records (analysis, rate conversion, levels, timbre, tempo, chroma, synthesis, bld_mean_variance_host)
  * does so through record_call, the one place that knows this protocol; the vector queries have
  * query_call (bl_runtime.h), which shares the hand-over (ws_wait, ws_pass) with it.
  *
@@ -115,7 +115,7 @@ void ctx_release(bl_amd_ctx *c) {
   bl_buf *bufs[] = {&c->songs,   &c->stats,   &c->hist, &c->spectrum, &c->energies, &c->lc,
                     &c->results, &c->arena[0], &c->arena[1], &c->arena22[0], &c->arena22[1],
                     &c->rs_songs, &c->rs_bank, &c->mx_my, &c->mx_gath, &c->mx_all, &c->mx_order, &c->mx_rows, &c->knn, &c->chain, &c->radius, &c->level_songs, &c->timbre_songs,
-                    &c->rhythm_songs, &c->rhythm_n, &c->rhythm_rows};
+                    &c->rhythm_songs, &c->rhythm_n, &c->rhythm_rows, &c->chroma_songs, &c->chroma_acc, &c->chroma_image};
   for (bl_buf *b : bufs) release_buf(*b);
   for (int k = 0; k < 2; ++k) {
     blr_unregister_wave(c, k);
@@ -141,6 +141,7 @@ void ctx_release(bl_amd_ctx *c) {
     c->*m = nullptr;
   }
   c->ws_used = false;
+  c->chroma_image_ready = false;
   c->rs_rate = 0;
   c->rs_kind = -1;
 }
@@ -608,7 +609,8 @@ void bl_amd_profile_reset(void) {
 double bl_amd_profile_ms(const char *name, int *launches) {
   static const char *const kProfNames[PK_COUNT] = {"pcm_scan",    "amp_finish", "freq_frames", "freq_finish",
                                                    "env_windows", "env_tail",   "distance",    "freq_scan",
-                                                   "rhythm_hops", "rhythm_acf", "rhythm_pick"};
+                                                   "rhythm_hops", "rhythm_acf", "rhythm_pick",
+                                                   "chroma_pitch", "chroma_key"};
   if (launches) *launches = 0;
   bl_amd_ctx *c = blr_default_ctx();
   if (!c || !name) return -1.0;
@@ -759,6 +761,70 @@ int bl_amd_rhythm_batch_device(const int16_t *d_pcm, const bl_amd_song_desc *h_d
                                long long n_onsets, uint64_t *d_acf_out, void *stream) {
   return rhythm_device(nullptr, true, d_pcm, h_desc, n_songs, lag_min, lag_max, d_songs_out, d_onsets_out, n_onsets,
                        d_acf_out, stream);
+}
+
+/* ---- chroma and key (bl_chroma_kernels.hip) -------------------------------------- */
+
+static int chroma_device(bl_amd_ctx *c, bool dflt, const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs,
+                         bl_amd_song_chroma *d_songs_out, bl_amd_frame_chroma *d_frames_out, long long n_frame_records,
+                         void *stream) {
+  if (!d_pcm || ((uintptr_t)d_pcm & 15) || !h_desc || !d_songs_out || ((uintptr_t)d_songs_out & 7) ||
+      ((uintptr_t)d_frames_out & 7) || n_songs < 1)
+    return BL_UNEXPECTED;
+  long long total = 0; /* the sum of T over the songs */
+  for (int i = 0; i < n_songs; ++i) {
+    if (!chroma_song_ok(h_desc[i].pcm_offset, h_desc[i].n_samples, h_desc[i].channels)) return BL_UNEXPECTED;
+    total += bl_amd_chroma_frames(h_desc[i].n_samples, h_desc[i].channels);
+  }
+  if ((d_frames_out && n_frame_records != total) || !blk_chroma_image_host() || !(c = call_ctx(c, dflt)))
+    return BL_UNEXPECTED;
+  CtxGuard g(c);
+  if (!g.ok()) return BL_UNEXPECTED;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return record_call<bl_chroma_song>(c, s, c->chroma_songs, n_songs, [&](bl_chroma_song *hs) {
+    long long frame_off = 0;
+    for (int i = 0; i < n_songs; ++i) {
+      hs[i].pcm_off = h_desc[i].pcm_offset;
+      hs[i].frame_off = frame_off;
+      hs[i].frames = bl_amd_chroma_frames(h_desc[i].n_samples, h_desc[i].channels);
+      hs[i].channels = h_desc[i].channels;
+      frame_off += hs[i].frames;
+    }
+    return BL_OK;
+  }, [&](const bl_chroma_song *hs, bl_chroma_song *d_songs) {
+    if (blr_ensure(c->chroma_acc, sizeof(uint64_t) * 12 * (size_t)n_songs) != BL_OK ||
+        blr_ensure(c->chroma_image, blk_chroma_image_bytes()) != BL_OK)
+      return BL_UNEXPECTED;
+    if (!c->chroma_image_ready) { /* blocking, once per context: nothing on the device reads the block before it */
+      BL_HIP_CHECK(hipMemcpy(c->chroma_image.p, blk_chroma_image_host(), blk_chroma_image_bytes(),
+                             hipMemcpyHostToDevice));
+      c->chroma_image_ready = true;
+    }
+    /* the caller's order, cut into launch groups of at most c->group_songs songs that follow each other on the stream */
+    const int group_songs = std::min(c->group_songs, BL_CHROMA_GROUP_SONGS);
+    for (int b = 0; b < n_songs; b += group_songs) {
+      const int count = std::min(group_songs, n_songs - b);
+      int max_frames = 0;
+      for (int i = b; i < b + count; ++i) max_frames = std::max(max_frames, hs[i].frames);
+      if (blk_chroma(s, d_pcm, d_songs + b, count, max_frames, c->n_cu, c->chroma_image.p,
+                     static_cast<unsigned long long *>(c->chroma_acc.p) + 12 * (size_t)b, d_songs_out + b, d_frames_out,
+                     c->prof ? mark_cb : nullptr, c) != BL_OK)
+        return BL_UNEXPECTED;
+    }
+    return BL_OK;
+  });
+}
+
+int bl_amd_ctx_chroma_batch_device(bl_amd_ctx *c, const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs,
+                                   bl_amd_song_chroma *d_songs_out, bl_amd_frame_chroma *d_frames_out,
+                                   long long n_frame_records, void *stream) {
+  return chroma_device(c, false, d_pcm, h_desc, n_songs, d_songs_out, d_frames_out, n_frame_records, stream);
+}
+
+int bl_amd_chroma_batch_device(const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs,
+                               bl_amd_song_chroma *d_songs_out, bl_amd_frame_chroma *d_frames_out,
+                               long long n_frame_records, void *stream) {
+  return chroma_device(nullptr, true, d_pcm, h_desc, n_songs, d_songs_out, d_frames_out, n_frame_records, stream);
 }
 
 /* stages 7 and 8 on the caller's curves: uploaded, through the same launch as the device form, fetched */

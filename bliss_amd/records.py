@@ -24,6 +24,8 @@ LEVELS_DTYPE = np.dtype(_lib.SongLevels)
 TIMBRE_SONG_DTYPE = np.dtype(_lib.SongTimbre)
 TIMBRE_FRAME_DTYPE = np.dtype(_lib.FrameTimbre)
 RHYTHM_DTYPE = np.dtype(_lib.SongRhythm)
+CHROMA_DTYPE = np.dtype(_lib.SongChroma)
+FRAME_CHROMA_DTYPE = np.dtype(_lib.FrameChroma)
 
 LEVELS_DB_DTYPE = np.dtype([("peak_db", "<f8", (2,)), ("rms_db", "<f8", (2,)), ("dc", "<f8", (2,)),
                             ("zcr", "<f8", (2,))])

@@ -628,6 +628,82 @@ double bl_amd_rhythm_bpm(const bl_amd_song_rhythm *r, int rate);
 double bl_amd_rhythm_strength(const bl_amd_song_rhythm *r);
 int bl_amd_selftest_isqrt(uint64_t counts[2]);
 
+/* Chroma and key: how a song's energy spreads over the twelve pitch classes, and the major or minor key whose profile
+ * fits that spread best ("same or compatible key next", the companion of the tempo).  The reference's author lists
+ * "Chromagram / HPCP" in ROADMAP.md ("Tonal features"); none of it is in the reference's API.  The 512-point frames of
+ * the frequency pass cannot give it (one bin is 43 Hz, a semitone at A3 13 Hz): this is a constant-Q bank of 48
+ * pitches, A3 .. G#7, over frames of 4 096 samples at a hop of 2 048.  Every field is an exact integer: all arithmetic
+ * below is integer arithmetic and fits 64 bits.  Nominal rate 22 050 Hz.
+ *   0 table     data, built on the host once per process (bl_amd_chroma_table shows it).  Pitch p = 0 .. 47,
+ *               f_p = B[p % 12] * 2^(p / 12) with B = {220.0, 233.081881, 246.941651, 261.625565, 277.182631,
+ *               293.664768, 311.126984, 329.627557, 349.228231, 369.994423, 391.995436, 415.304698};
+ *               L_p = 2 floor(374850.0 / f_p) (3 406 for p = 0, 224 for p = 47), n0 = (4096 - L_p) / 2; for n in
+ *               [0, L_p): w = 0.5 - 0.5 cos(2 pi (n + 0.5) / L_p), t = f_p (n - L_p/2 + 0.5) / 22050, t -= floor(t),
+ *               cr[p][n0 + n] = floor(127 w cos(2 pi t) + 0.5), ci[p][n0 + n] = floor(127 w sin(2 pi t) + 0.5), both
+ *               int8, every other entry 0.  Sine and cosine are fixed polynomials in IEEE double + - * / (not libm's:
+ *               within 1e-9 of them), so the table is the same bits wherever it is built.  Gain G[p] =
+ *               (65536 L_47^2) / L_p^2 in integers (283 for p = 0, 65 536 for p = 47): a tone of a given amplitude
+ *               scores alike at every pitch.  Pitch class k(p) = (p + 9) % 12, C = 0.
+ *   1 mix       m[i] = l[i] + r[i] (stereo) or 2 s[i] (mono: a mono song and its dual-mono copy give the same bytes).
+ *               Fr = n_samples / channels, T = 0 if Fr < 4096, else (Fr - 4096) / 2048 + 1; frame t covers
+ *               m[2048 t .. 2048 t + 4095].  No sample outside those frames is read.
+ *   2 sums      Re_t[p] = sum_n cr[p][n] m[2048 t + n], Im_t[p] the same with ci: exact
+ *   3 energy    a = Re >> 15, b = Im >> 15 (arithmetic shifts: floor), e = a^2 + b^2, E_t[p] = (e G[p]) >> 16
+ *   4 fold      X_t[k] = sum of E_t[p] over the four p with k(p) = k: the chromagram
+ *   5 song      chroma[k] = sum_t X_t[k]
+ *   6 key       mx = max_k chroma[k].  mx == 0 (or T == 0): key = -1, score = score_next = 0.  Otherwise
+ *               s = max(0, bitlength(mx) - 12), c[k] = chroma[k] >> s (< 4096); with the Krumhansl-Kessler profiles,
+ *               mean-removed, unit-normalised and scaled by 2^14,
+ *                 QM = {10737, -4690, -9, -4315, 3361, 2275, -3604, 6394, -4091, 665, -4465, -2256}   (major)
+ *                 Qm = {10733, -4215, -775, 6842, -4542, -734, -4788, 4262, 1109, -4174, -1512, -2208} (minor)
+ *               score[k] = sum_j QM[j] c[(j + k) % 12], score[12 + k] the same with Qm, k = 0 .. 11; key is the
+ *               smallest index with the largest score (0 .. 11 major with tonic C .. B, 12 .. 23 minor), score that
+ *               maximum, score_next the largest of the other 23.
+ * Bounds: sum_n |cr[p][n]| <= 140 000 for every p, likewise ci (137 652 and 137 690 at most in the table as built), and
+ * |m| <= 2^16, so |Re| < 2^33.1, |a| < 2^18.1, e < 2^37.2, E <= e, X < 2^39.2; T < 2^20 (n_samples is an int), so
+ * chroma[k] < 2^59.2; |score| < 12 * 10737 * 4096 < 2^29. */
+#define BL_AMD_CHROMA_FRAME 4096
+#define BL_AMD_CHROMA_HOP 2048
+#define BL_AMD_CHROMA_PITCHES 48
+typedef struct bl_amd_frame_chroma { uint64_t x[12]; } bl_amd_frame_chroma; /* 96 bytes: X_t[0 .. 11] */
+typedef struct bl_amd_song_chroma {                                         /* 128 bytes */
+  uint64_t chroma[12];
+  int64_t score, score_next;
+  int32_t frames;   /* T */
+  int32_t key;      /* -1, 0 .. 23 */
+  int32_t status;   /* BL_OK; BL_UNEXPECTED for a song with T == 0: frames 0, key -1, everything else 0 */
+  int32_t reserved; /* 0 */
+} bl_amd_song_chroma;
+/* bl_amd_chroma_frames: T of a song, plain host arithmetic; -1 for n_samples < 0 or channels outside {1, 2}.
+ * bl_amd_chroma_batch_device: chroma and key of n_songs songs whose PCM sits in device memory.  The descriptors are
+ * those of bl_amd_analyze_batch_device with other limits: pcm_offset a multiple of 8, channels 1 or 2, Fr >= 1,
+ * duration ignored; d_pcm 16-byte aligned; n_songs >= 1.  d_songs_out: n_songs records in the caller's order.
+ * d_frames_out may be NULL (n_frame_records is then ignored); otherwise it receives every frame's record, songs
+ * concatenated in the caller's order, song i at the sum of T_j over j < i, and n_frame_records must equal the sum of all
+ * T_j.  No output needs zeroing and every byte of every record is written.  A rejected call returns BL_UNEXPECTED and
+ * writes nothing.  A song with T == 0 is no error of the call (see status).  Asynchronous on `stream` (the first call
+ * of a context uploads the table before it returns); h_desc is copied before the call returns.  Calls of one context
+ * are ordered on the device like its batches.  A song's outputs are a pure function of its samples and `channels`:
+ * they depend neither on the other songs, n_songs, the order, the launch shape nor on whether the frames are asked for.
+ * Read-only towards bl_amd_last_energies and bl_amd_last_freq_stats.
+ *   bl_amd_chroma_batch_host: the same from host memory, blocking: the songs are uploaded and analysed in waves;
+ *     h_frames_out may be NULL.
+ *   bl_amd_chroma_table: copies the bank to host buffers, no device work: re, im [48][4096] (cr, ci), gain [48] (G),
+ *     len [48] (L); any pointer may be NULL.
+ *   bl_amd_chroma_key_name: "C", "F#" (major), "A#m" (minor) for key 0 .. 23, BL_OK; "" and BL_UNEXPECTED for any
+ *     other key (BL_UNEXPECTED alone for a NULL out). */
+int bl_amd_chroma_frames(int n_samples, int channels);
+int bl_amd_chroma_batch_device(const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs,
+                               bl_amd_song_chroma *d_songs_out, bl_amd_frame_chroma *d_frames_out,
+                               long long n_frame_records, void *stream);
+int bl_amd_ctx_chroma_batch_device(bl_amd_ctx *ctx, const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs,
+                                   bl_amd_song_chroma *d_songs_out, bl_amd_frame_chroma *d_frames_out,
+                                   long long n_frame_records, void *stream);
+int bl_amd_chroma_batch_host(const int16_t *const *h_pcm, const int32_t *n_samples, const int32_t *channels,
+                             int n_songs, bl_amd_song_chroma *h_songs_out, bl_amd_frame_chroma *h_frames_out);
+int bl_amd_chroma_table(int8_t *re, int8_t *im, uint32_t *gain, int32_t *len);
+int bl_amd_chroma_key_name(int key, char out[8]);
+
 /* Integer-only synthetic PCM (the benchmark corpus of BASELINE.json),
  * generated in place on the device: song i = seed_base + i, written at
  * h_desc[i].pcm_offset.  Byte-identical to oracle/orc_synth.c. */
@@ -651,7 +727,7 @@ int bl_amd_fir_mode(void);
 /* Per-kernel device time, measured with hipEvents on the launch stream while
  * profiling is on (bench.py's roofline leg).  name is one of "pcm_scan", "freq_scan",
  * "amp_finish", "freq_frames", "freq_finish", "env_windows", "env_tail",
- * "distance", "rhythm_hops", "rhythm_acf", "rhythm_pick"; returns accumulated milliseconds and the launch count since the
+ * "distance", "rhythm_hops", "rhythm_acf", "rhythm_pick", "chroma_pitch", "chroma_key"; returns accumulated milliseconds and the launch count since the
  * last reset, or -1 for an unknown name. */
 void bl_amd_profile(int enable);
 void bl_amd_profile_reset(void);
