@@ -46,3 +46,22 @@ def host_pcm(pcm_list, dtype):
     arrs = [np.ascontiguousarray(p, dtype=dtype) for p in pcm_list]
     n = len(arrs)
     return arrs, (C.c_void_p * n)(*[a.ctypes.data for a in arrs]), (C.c_int32 * n)(*[a.size for a in arrs])
+
+
+def desc_scale(scale, d, scale_max):
+    """the ctypes uint16 array of a descriptor's d scales (None: NULL, all at the maximum), once every one is an
+    integer in [0, scale_max]; a scalar stands for all columns"""
+    if scale is None:
+        return None
+    vals = per_song(scale, d)
+    if len(vals) != d:
+        raise ValueError(f"{d} columns but {len(vals)} scales")
+    return (C.c_uint16 * d)(*[int_in("scale", v, 0, scale_max) for v in vals])
+
+
+def feature_matrix(name, x, dims_max):
+    """x as a contiguous float32 (n, d) array with n >= 1 and 1 <= d <= dims_max"""
+    a = np.ascontiguousarray(x, dtype=np.float32)
+    if a.ndim != 2 or a.shape[0] < 1 or not 1 <= a.shape[1] <= dims_max:
+        raise ValueError(f"{name} must have shape (n, d) with n >= 1 and 1 <= d <= {dims_max}, got {a.shape}")
+    return a

@@ -18,6 +18,7 @@ BL_AMD_KNN_DISTANCE, BL_AMD_KNN_COSINE, BL_AMD_KNN_MAX_K = 0, 1, 128  # include/
 BL_AMD_CHAIN_AUTO, BL_AMD_CHAIN_PER_CHAIN, BL_AMD_CHAIN_SPLIT = 0, 1, 2  # include/bliss_amd.h
 BL_AMD_MIX_MAX_GAP = 16  # include/bliss_amd.h
 BL_AMD_PART_SPECTRUM, BL_AMD_PART_SUMS, BL_AMD_PART_HIST = 1, 2, 4  # include/bliss_amd.h
+BL_AMD_DESC_DIMS, BL_AMD_DESC_SCALE_MAX = 32, 32512  # include/bliss_amd.h
 
 
 class ForceVector(C.Structure):  # ref include/bliss.h:26-31
@@ -88,6 +89,14 @@ class FrameChroma(C.Structure):  # include/bliss_amd.h bl_amd_frame_chroma
 class SongChroma(C.Structure):  # include/bliss_amd.h bl_amd_song_chroma
     _fields_ = [("chroma", C.c_uint64 * 12), ("score", C.c_int64), ("score_next", C.c_int64), ("frames", C.c_int32),
                 ("key", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
+class Desc(C.Structure):  # include/bliss_amd.h bl_amd_desc
+    _fields_ = [("q", C.c_int16 * 32)]
+
+
+class DescRange(C.Structure):  # include/bliss_amd.h bl_amd_desc_range
+    _fields_ = [("lo", C.c_float * 32), ("hi", C.c_float * 32), ("n_finite", C.c_uint32 * 32)]
 
 
 class Shard(C.Structure):  # include/bliss_amd.h bl_amd_shard
@@ -242,6 +251,21 @@ SYMBOLS = {
                                            _P(FrameChroma)]),
     "bl_amd_chroma_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bl_amd_chroma_key_name": (C.c_int, [C.c_int, C.c_char_p]),
+    "bl_amd_desc_range_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "bl_amd_desc_quantize_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, _P(C.c_uint16), C.c_void_p,
+                                              C.c_void_p]),
+    "bl_amd_desc_knn_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
+    "bl_amd_desc_cross_knn_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                               C.c_void_p, C.c_void_p]),
+    "bl_amd_ctx_desc_knn_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                             C.c_void_p, C.c_void_p]),
+    "bl_amd_ctx_desc_cross_knn_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bl_amd_desc_build_host": (C.c_int, [_P(C.c_float), C.c_int, C.c_int, _P(C.c_uint16), C.c_int, _P(DescRange),
+                                         _P(Desc)]),
+    "bl_amd_desc_knn_host": (C.c_int, [_P(Desc), C.c_int, _P(Desc), C.c_int, C.c_int, _P(C.c_int32), _P(C.c_uint64)]),
+    "bl_amd_desc_knn_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "bl_amd_synth_pcm_device": (C.c_int, [C.c_void_p, _P(SongDesc), C.c_int, C.c_uint32, C.c_uint32, C.c_void_p]),
     "bl_amd_set_fir_mode": (C.c_int, [C.c_int]),
     "bl_amd_fir_mode": (C.c_int, []),

@@ -5,9 +5,10 @@
  * levels, bl_timbre_kernels.hip the per-frame spectral timbre, bl_rhythm_kernels.hip the tempo,
  * bl_chroma_kernels.hip chroma and key,
  * bl_matrix_kernels.hip the pairwise matrix,
- * bl_query_kernels.hip the vector queries, bl_rs_kernels.hip the rate converter)
+ * bl_query_kernels.hip the vector queries, bl_desc_kernels.hip the descriptors and their kNN,
+ * bl_rs_kernels.hip the rate converter)
  * and the runtime (bl_runtime.hip: contexts, workspaces, streams, the analysis C-ABI of
- * include/bliss_amd.h; bl_query_api.hip: its matrix, playlist and vector-query C-ABI; bl_multi.hip: the multi-device
+ * include/bliss_amd.h; bl_query_api.hip: its matrix, playlist and vector-query C-ABI; bl_desc_api.hip: its descriptor C-ABI; bl_multi.hip: the multi-device
  * corpus path).  Also BL_HIP_CHECK, which
  * every .hip file uses.  C++ only, not installed.
  */
@@ -81,7 +82,8 @@ struct bl_tables {
 /* ---- per-kernel timing (bench.py's roofline leg) ---------------------------- */
 
 enum { PK_SCAN, PK_AMP, PK_FREQ, PK_FREQ_FIN, PK_ENV, PK_TAIL, PK_DIST, PK_FREQ_SCAN, PK_RHYTHM_HOPS, PK_RHYTHM_ACF,
-       PK_RHYTHM_PICK, PK_CHROMA_PITCH, PK_CHROMA_KEY, PK_COUNT };
+       PK_RHYTHM_PICK, PK_CHROMA_PITCH, PK_CHROMA_KEY, PK_DESC_RANGE, PK_DESC_QUANTIZE, PK_DESC_KNN, PK_DESC_MERGE,
+       PK_COUNT };
 
 /* called by the launchers around a kernel when profiling is on: begin = 1 before the
  * launch, 0 after it, on the stream the kernel is launched on */
@@ -278,6 +280,7 @@ int blk_query_configure_device(void);                  /* dynamic-LDS attributes
 /* Column split shared by the queries: waves of `qpw` query rows, splits of at least `min_cols` columns; *cols is a
  * multiple of 64 and *n_split the number of blockIdx.y slices.  Not static so that it can be checked on the host. */
 void blk_split_plan(int n, int n_rows, int n_cu, int qpw, int min_cols, int *n_split, int *cols);
+#define KNN_SPLIT_MIN_COLS 4096 /* min_cols of both kNN forms (force vectors here, descriptors in bl_desc_kernels.hip) */
 /* kNN and radius take the query array beside the library.  d_queries == nullptr: the queries are rows
  * [row_begin, row_begin + n_rows) of d_vecs, and a row is no candidate of its own (bl_amd_knn_device,
  * bl_amd_radius_*_device).  Otherwise they are d_queries[0 .. n_rows), vectors of their own that may alias the library,
@@ -318,6 +321,24 @@ int blk_radius_fill(hipStream_t s, const struct force_vector_s *d_queries, const
 size_t blk_groups_scratch_bytes(int n, bool cosine);
 int blk_groups(hipStream_t s, const struct force_vector_s *d_vecs, int n, bool cosine, float bound, int n_cu,
                void *d_scratch, int32_t *d_group);
+
+/* ---- library-normalised descriptors (bl_desc_kernels.hip) --------------------- */
+
+struct blk_desc_scale { uint16_t s[BL_AMD_DESC_DIMS]; }; /* the per-column scale, passed to the kernel by value */
+/* column-wise range of the finite entries of x[n][d]; d_scratch: at least blk_desc_range_scratch_bytes(n, n_cu) */
+size_t blk_desc_range_scratch_bytes(int n, int n_cu);
+int blk_desc_range(hipStream_t s, const float *d_x, int n, int d, int n_cu, void *d_scratch, bl_amd_desc_range *d_range,
+                   blk_mark_fn mark, void *mark_user);
+int blk_desc_quantize(hipStream_t s, const float *d_x, int n, int d, const bl_amd_desc_range *d_range,
+                      const blk_desc_scale &scale, bl_amd_desc *d_out, blk_mark_fn mark, void *mark_user);
+/* the k nearest descriptors of each query by (d^2, index).  d_queries == nullptr: the queries are rows [row_begin,
+ * row_begin + n_rows) of d_lib and a row is no candidate of its own; otherwise d_queries[0 .. n_rows), row_begin 0 and
+ * nothing excluded.  The column split is blk_split_plan(n, n_rows, n_cu, 16, KNN_SPLIT_MIN_COLS); d_scratch: at least
+ * blk_desc_knn_scratch_bytes(n, n_rows, k, n_cu) bytes, which is 0 exactly when the call is not split. */
+size_t blk_desc_knn_scratch_bytes(int n, int n_rows, int k, int n_cu);
+int blk_desc_knn(hipStream_t s, const bl_amd_desc *d_queries, const bl_amd_desc *d_lib, int n, int row_begin, int n_rows,
+                 int k, int n_cu, void *d_scratch, int32_t *d_index, uint64_t *d_dist2, blk_mark_fn mark,
+                 void *mark_user);
 
 /* ---- device rate converter (bl_rs_kernels.hip) ------------------------------ */
 

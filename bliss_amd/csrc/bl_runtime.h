@@ -98,6 +98,8 @@ struct bl_amd_ctx {
    * (blk_chroma_image_host), uploaded by the context's first call */
   bl_buf chroma_songs, chroma_acc, chroma_image;
   bool chroma_image_ready = false;
+  /* bl_amd_desc_*: the range's per-workgroup shares, the partial lists of a kNN's column split */
+  bl_buf desc;
 };
 
 /* bl_runtime.hip */

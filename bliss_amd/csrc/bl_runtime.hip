@@ -115,7 +115,8 @@ void ctx_release(bl_amd_ctx *c) {
   bl_buf *bufs[] = {&c->songs,   &c->stats,   &c->hist, &c->spectrum, &c->energies, &c->lc,
                     &c->results, &c->arena[0], &c->arena[1], &c->arena22[0], &c->arena22[1],
                     &c->rs_songs, &c->rs_bank, &c->mx_my, &c->mx_gath, &c->mx_all, &c->mx_order, &c->mx_rows, &c->knn, &c->chain, &c->radius, &c->level_songs, &c->timbre_songs,
-                    &c->rhythm_songs, &c->rhythm_n, &c->rhythm_rows, &c->chroma_songs, &c->chroma_acc, &c->chroma_image};
+                    &c->rhythm_songs, &c->rhythm_n, &c->rhythm_rows, &c->chroma_songs, &c->chroma_acc, &c->chroma_image,
+                    &c->desc};
   for (bl_buf *b : bufs) release_buf(*b);
   for (int k = 0; k < 2; ++k) {
     blr_unregister_wave(c, k);
@@ -610,7 +611,8 @@ double bl_amd_profile_ms(const char *name, int *launches) {
   static const char *const kProfNames[PK_COUNT] = {"pcm_scan",    "amp_finish", "freq_frames", "freq_finish",
                                                    "env_windows", "env_tail",   "distance",    "freq_scan",
                                                    "rhythm_hops", "rhythm_acf", "rhythm_pick",
-                                                   "chroma_pitch", "chroma_key"};
+                                                   "chroma_pitch", "chroma_key",
+                                                   "desc_range",  "desc_quantize", "desc_knn", "desc_merge"};
   if (launches) *launches = 0;
   bl_amd_ctx *c = blr_default_ctx();
   if (!c || !name) return -1.0;

@@ -1,0 +1,223 @@
+"""Library-normalised descriptors and exact nearest neighbours over them (include/bliss_amd.h: bl_amd_desc,
+bl_amd_desc_range, bl_amd_desc_*): up to 32 features per song, every column mapped onto the same int16 range by the
+library's own minimum and maximum, and the squared Euclidean distance of two descriptors as an exact integer.
+
+    x, names = features(results, levels=lv, timbre=tb, rhythm=rh, chroma=ch)
+    desc, rng = fit(x)                      # the library
+    index, dist2 = knn(desc, 10)            # its ten nearest songs per song
+    q = quantize(x_new, rng)                # songs from outside, with the library's range
+    index, dist2 = knn(desc, 10, queries=q)
+
+This module is imported explicitly (`import bliss_amd.descriptor`): the package's own namespace is unchanged."""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._args import desc_scale, feature_matrix, int_in
+from ._lib import check
+from .records import (CHROMA_DTYPE, LEVELS_DTYPE, RESULT_DTYPE, RHYTHM_DTYPE, TIMBRE_SONG_DTYPE, levels_db, timbre_hz)
+
+DIMS, SCALE_MAX = _lib.BL_AMD_DESC_DIMS, _lib.BL_AMD_DESC_SCALE_MAX
+MAX_N = 1 << 27          # a kNN library stays below it: the index bits of a key
+EMPTY_DIST2 = 2 ** 64 - 1  # d2 of an empty slot (index -1)
+DESC_DTYPE = np.dtype(_lib.Desc)            # one field q: int16 (32,)
+RANGE_DTYPE = np.dtype(_lib.DescRange)      # lo, hi float32 (32,), n_finite uint32 (32,)
+
+_I32, _U64 = C.POINTER(C.c_int32), C.POINTER(C.c_uint64)
+_F32, _DESC, _RANGE = C.POINTER(C.c_float), C.POINTER(_lib.Desc), C.POINTER(_lib.DescRange)
+
+
+def _desc_array(name, desc):
+    """desc as a contiguous int16 (n, 32) array, n >= 1"""
+    a = np.ascontiguousarray(desc)
+    if a.dtype == DESC_DTYPE and a.ndim == 1:
+        a = a["q"]
+    if a.dtype != np.int16 or a.ndim != 2 or a.shape[1] != DIMS or a.shape[0] < 1:
+        raise ValueError(f"{name} must be int16 of shape (n, {DIMS}) with n >= 1, got {a.dtype} {a.shape}")
+    return np.ascontiguousarray(a)
+
+
+def _range_record(rng):
+    r = np.ascontiguousarray(rng)
+    if r.dtype != RANGE_DTYPE or r.size != 1:
+        raise ValueError("range must be one bl_amd_desc_range record, as fit() returns it")
+    return r.reshape(1).copy()
+
+
+def _build(x, scale, fit_range, rng):
+    a = feature_matrix("x", x, DIMS)
+    n, d = a.shape
+    sc = desc_scale(scale, d, SCALE_MAX)
+    out = np.empty((n, DIMS), dtype=np.int16)
+    check(_lib.load().bl_amd_desc_build_host(a.ctypes.data_as(_F32), n, d, sc, 1 if fit_range else 0,
+                                             rng.ctypes.data_as(_RANGE), out.ctypes.data_as(_DESC)),
+          "bl_amd_desc_build_host")
+    return out
+
+
+def fit(x, scale=None):
+    """Fit the per-column range on the (n, d) float32 feature matrix x, 1 <= d <= 32, and quantise x with it
+    (bl_amd_desc_build_host): (desc int16 (n, 32), range record).  Non-finite entries are ignored by the range and
+    quantise to 0, as does a constant column.  scale: None (every column at 32512), one integer for all columns or d of
+    them in [0, 32512]: a column's weight in the distance."""
+    rng = np.zeros(1, dtype=RANGE_DTYPE)
+    return _build(x, scale, True, rng), rng[0]
+
+
+def quantize(x, range, scale=None):
+    """Quantise x with a range fitted elsewhere (fit()[1]): values outside it are clamped to -scale / +scale."""
+    return _build(x, scale, False, _range_record(range))
+
+
+def knn(desc, k, queries=None):
+    """The k nearest descriptors of every row of desc (queries None: a row is no candidate of its own) or of every row
+    of queries (nothing excluded): (index (rows, k) int32, dist2 (rows, k) uint64), ascending by (dist2, index).  Slots
+    beyond the number of candidates hold -1 and 2^64 - 1.  k in [1, 128], fewer than 2^27 library rows."""
+    lib = _desc_array("desc", desc)
+    k = int_in("k", k, 1, _lib.BL_AMD_KNN_MAX_K)
+    n = lib.shape[0]
+    if n >= MAX_N:
+        raise ValueError(f"desc must have fewer than {MAX_N} rows, got {n}")
+    q = None if queries is None else _desc_array("queries", queries)
+    rows = n if q is None else q.shape[0]
+    index, dist2 = np.empty((rows, k), dtype=np.int32), np.empty((rows, k), dtype=np.uint64)
+    check(_lib.load().bl_amd_desc_knn_host(None if q is None else q.ctypes.data_as(_DESC), rows, lib.ctypes.data_as(_DESC),
+                                           n, k, index.ctypes.data_as(_I32), dist2.ctypes.data_as(_U64)),
+          "bl_amd_desc_knn_host")
+    return index, dist2
+
+
+def _device_desc_check(name, t):
+    import torch
+    if t.dtype != torch.int16 or not t.is_cuda or not t.is_contiguous() or t.dim() != 2 or t.shape[1] != DIMS or \
+            t.shape[0] < 1:
+        raise ValueError(f"{name} must be a contiguous int16 CUDA tensor of shape (n, {DIMS}) with n >= 1")
+
+
+def _on_device(lib, tensor, stream):
+    from .queries import _on_device_of
+    return _on_device_of(lib, tensor, stream)
+
+
+def fit_device(d_x, scale=None, stream=None):
+    """fit() on a contiguous float32 (n, d) CUDA tensor (bl_amd_desc_range_device, bl_amd_desc_quantize_device),
+    asynchronously on `stream`: (desc int16 (n, 32) CUDA tensor, range as a uint8 CUDA tensor of 384 bytes)."""
+    import torch
+    rng = torch.empty(RANGE_DTYPE.itemsize, dtype=torch.uint8, device=d_x.device)
+    return quantize_device(d_x, rng, scale, stream, _fit=True), rng
+
+
+def quantize_device(d_x, d_range, scale=None, stream=None, _fit=False):
+    """quantize() on the device: d_range the uint8 CUDA tensor fit_device() returned."""
+    import torch
+    if d_x.dtype != torch.float32 or not d_x.is_cuda or not d_x.is_contiguous() or d_x.dim() != 2 or \
+            d_x.shape[0] < 1 or not 1 <= d_x.shape[1] <= DIMS:
+        raise ValueError(f"d_x must be a contiguous float32 CUDA tensor of shape (n, d) with 1 <= d <= {DIMS}")
+    if d_range.dtype != torch.uint8 or d_range.numel() != RANGE_DTYPE.itemsize or d_range.device != d_x.device or \
+            not d_range.is_contiguous():
+        raise ValueError("d_range must be the uint8 CUDA tensor of one bl_amd_desc_range on d_x's device")
+    n, d = d_x.shape
+    sc = desc_scale(scale, d, SCALE_MAX)
+    lib = _lib.load()
+    out = torch.empty((n, DIMS), dtype=torch.int16, device=d_x.device)
+    with _on_device(lib, d_x, stream) as cur:
+        s = C.c_void_p(cur.cuda_stream)
+        if _fit:
+            check(lib.bl_amd_desc_range_device(d_x.data_ptr(), n, d, d_range.data_ptr(), s), "bl_amd_desc_range_device")
+        check(lib.bl_amd_desc_quantize_device(d_x.data_ptr(), n, d, d_range.data_ptr(), sc, out.data_ptr(), s),
+              "bl_amd_desc_quantize_device")
+    return out
+
+
+def knn_device(d_desc, k, queries=None, row_begin=0, n_rows=None, stream=None, ctx=None):
+    """knn() on torch tensors: d_desc a contiguous int16 (n, 32) CUDA tensor.  queries None: the rows
+    [row_begin, row_begin + n_rows) of d_desc (default: all) are the queries; otherwise `queries` is a tensor like
+    d_desc on the same device (row_begin and n_rows must be left alone).  Returns (index int32, dist2 as int64 bits of
+    the uint64: an empty slot reads -1) CUDA tensors of shape (rows, k), asynchronously on `stream` (default: the
+    current stream of that device).  ctx: an explicit Context."""
+    import torch
+    _device_desc_check("d_desc", d_desc)
+    k = int_in("k", k, 1, _lib.BL_AMD_KNN_MAX_K)
+    n = d_desc.shape[0]
+    if n >= MAX_N:
+        raise ValueError(f"d_desc must have fewer than {MAX_N} rows, got {n}")
+    if queries is None:
+        from .queries import _rows_check
+        rows = _rows_check(n, int_in("row_begin", row_begin, 0), n_rows)
+        name, args = "desc_knn_device", (d_desc.data_ptr(), n, int(row_begin), int(rows), k)
+    else:
+        _device_desc_check("queries", queries)
+        if queries.device != d_desc.device or row_begin != 0 or n_rows is not None:
+            raise ValueError("queries must be on d_desc's device, and a cross query takes no row range")
+        rows = queries.shape[0]
+        name, args = "desc_cross_knn_device", (queries.data_ptr(), int(rows), d_desc.data_ptr(), n, k)
+    lib = _lib.load()
+    index = torch.empty((rows, k), dtype=torch.int32, device=d_desc.device)
+    dist2 = torch.empty((rows, k), dtype=torch.int64, device=d_desc.device)
+    with _on_device(lib, d_desc, stream) as cur:
+        tail = (index.data_ptr(), dist2.data_ptr(), C.c_void_p(cur.cuda_stream))
+        if ctx is None:
+            check(getattr(lib, "bl_amd_" + name)(*args, *tail), "bl_amd_" + name)
+        else:
+            check(getattr(lib, "bl_amd_ctx_" + name)(ctx.handle, *args, *tail), "bl_amd_ctx_" + name)
+    return index, dist2
+
+
+def distance(dist2):
+    """sqrt(dist2) / 32512 as float64: 2.0 is one column at full scale going from its minimum to its maximum.  Plain
+    host arithmetic; an empty slot (2^64 - 1) gives inf."""
+    d2 = np.asarray(dist2)
+    out = np.sqrt(d2.astype(np.float64)) / float(SCALE_MAX)
+    return np.where(d2.astype(np.uint64) == np.uint64(EMPTY_DIST2), np.inf, out)
+
+
+_RATINGS = ("tempo", "amplitude", "frequency", "attack")
+
+
+def _records(name, rec, dtype, n):
+    a = np.ascontiguousarray(rec)
+    if a.dtype != dtype or a.ndim != 1 or a.size != n:
+        raise ValueError(f"{name} must be a 1-D array of {n} records of dtype {dtype.names}, got {a.dtype} {a.shape}")
+    return a
+
+
+def features(results, levels=None, timbre=None, rhythm=None, chroma=None):
+    """The float32 feature matrix of n songs from the records the other modules return, and its column names: (x, names).
+    Host numpy only.  Groups that are not passed are left out; with all of them there are 25 columns:
+
+      ratings  tempo, amplitude, frequency, attack      the four ratings of `results` (results_to_numpy) as they are
+      levels   rms_db, peak_db                          levels_db(): the louder channel's RMS and peak in dB (-inf for
+                                                        silence, which the range ignores and the quantiser maps to 0)
+               zcr                                      the larger of the channels' zero crossings per frame
+      timbre   centroid_hz, centroid_std_hz,            timbre_hz(): mean and standard deviation over the used frames,
+               rolloff_hz, rolloff_std_hz               in Hz; NaN for a song without a used frame
+      rhythm   bpm, strength                            rhythm_bpm(): beats per minute (NaN without a tempo), r_lag / r0
+      chroma   chroma_0 .. chroma_11                    chroma[k] / sum_k chroma[k] in float64, 0 when the sum is 0"""
+    res = np.ascontiguousarray(results)
+    if res.dtype != RESULT_DTYPE or res.ndim != 1 or res.size < 1:
+        raise ValueError("results must be a non-empty 1-D array of bl_amd_song_result records (results_to_numpy)")
+    n = res.size
+    cols, names = [res[k].astype(np.float64) for k in _RATINGS], list(_RATINGS)
+    if levels is not None:
+        db = levels_db(_records("levels", levels, LEVELS_DTYPE, n))
+        cols += [db["rms_db"].max(axis=1), db["peak_db"].max(axis=1), db["zcr"].max(axis=1)]
+        names += ["rms_db", "peak_db", "zcr"]
+    if timbre is not None:
+        hz = timbre_hz(_records("timbre", timbre, TIMBRE_SONG_DTYPE, n))
+        keys = ["centroid_hz", "centroid_std_hz", "rolloff_hz", "rolloff_std_hz"]
+        cols += [hz[k] for k in keys]
+        names += keys
+    if rhythm is not None:
+        from .rhythm import rhythm_bpm
+        bpm, strength = rhythm_bpm(_records("rhythm", rhythm, RHYTHM_DTYPE, n))
+        cols += [bpm, strength]
+        names += ["bpm", "strength"]
+    if chroma is not None:
+        ch = _records("chroma", chroma, CHROMA_DTYPE, n)["chroma"].astype(np.float64)
+        total = ch.sum(axis=1, keepdims=True)
+        share = np.divide(ch, total, out=np.zeros_like(ch), where=total > 0)
+        cols += [share[:, k] for k in range(12)]
+        names += [f"chroma_{k}" for k in range(12)]
+    with np.errstate(over="ignore"):
+        return np.stack(cols, axis=1).astype(np.float32), names

@@ -704,6 +704,69 @@ int bl_amd_chroma_batch_host(const int16_t *const *h_pcm, const int32_t *n_sampl
 int bl_amd_chroma_table(int8_t *re, int8_t *im, uint32_t *gain, int32_t *len);
 int bl_amd_chroma_key_name(int key, char out[8]);
 
+/* Library-normalised descriptors and exact nearest neighbours over them.  The queries above compare force vectors;
+ * this layer compares anything: the caller puts up to 32 features per song into a row-major f32 matrix x[n][d]
+ * (bliss_amd.descriptor.features builds one from the records of the sections above), every column is mapped onto the
+ * same integer range by the library's own minimum and maximum, and the squared Euclidean distance of two descriptors is
+ * an exact integer, so a result depends neither on the reduction order, the column split nor the row range.
+ *   range     per column c < d: lo[c] / hi[c] the minimum / maximum over the FINITE entries of the column, compared as
+ *             numbers, a zero stored as +0; n_finite[c] their count.  A column without a finite entry, and every
+ *             column c >= d, has lo = hi = +0 and n_finite = 0.
+ *   quantise  given a range (not necessarily the one fitted on these rows) and scale[c] in 0 .. BL_AMD_DESC_SCALE_MAX
+ *             (NULL: all at the maximum): for c < d with x, lo and hi finite and hi > lo, in IEEE double, unfused, in
+ *             this order
+ *               t = ((double)x - (double)lo) / ((double)hi - (double)lo),  u = 2.0 * t - 1.0,  u clamped to [-1, 1],
+ *               q = (int16) rint(u * (double)scale[c])        (ties to even)
+ *             and q = 0 in every other case (x not finite, a bound not finite, hi <= lo, c >= d).  The scale is the
+ *             feature's weight: half the scale, half the pull.  The clamp is what lets a song from outside the library
+ *             be quantised with the library's range.  The cap 32512 = 127 * 256 makes the digits h = (q + 128) >> 8,
+ *             l = q - 256 h both signed bytes, which the int8 matrix products of the distance rely on.
+ *   distance  d2(a, b) = sum_c (a_c - b_c)^2, an integer below 32 * 65024^2 < 2^37.
+ *   kNN       per query the k candidates with the smallest (d2, index), ascending, 1 <= k <= BL_AMD_KNN_MAX_K.  The self
+ *             form (queries are rows of the library) excludes the query's own row, the cross form excludes nothing.
+ *             Slots beyond the number of candidates hold index -1 and d2 = 2^64 - 1.  n < 2^27.
+ * Every argument is checked before any device work: a rejected call returns BL_UNEXPECTED and leaves the outputs
+ * untouched (n < 1, n >= 2^27 for the kNN, d outside 1 .. 32, k outside 1 .. BL_AMD_KNN_MAX_K, a row range outside the
+ * library, a scale above the maximum, a NULL pointer other than h_scale and h_dist2).  The device forms are
+ * asynchronous on `stream`; calls of one context are ordered on the device like its batches.
+ *   bl_amd_desc_range_device      writes every byte of *d_range (device memory) from d_x[n][d]
+ *   bl_amd_desc_quantize_device   d_out[n] from d_x[n][d] and *d_range (device); h_scale: d values on the host or NULL
+ *   bl_amd_desc_knn_device        the self form for rows [row_begin, row_begin + n_rows) of d_lib[n]; d_index and
+ *                                 d_dist2 are [n_rows][k]
+ *   bl_amd_desc_cross_knn_device  the cross form for d_queries[n_queries]; outputs [n_queries][k]
+ *   bl_amd_ctx_desc_*             the same on an explicit context
+ *   bl_amd_desc_build_host        blocking, host memory: fit != 0 fits *h_range on h_x and writes it, fit == 0 reads it;
+ *                                 then quantises h_x into h_out[n]
+ *   bl_amd_desc_knn_host          blocking, host memory: h_queries NULL is the self form over all n rows (n_queries is
+ *                                 ignored), otherwise the cross form; h_dist2 may be NULL
+ *   bl_amd_desc_knn_scratch_bytes the workspace bytes a kNN call of this shape takes on the default context: 0 exactly
+ *                                 when the candidates are not split over workgroup columns (diagnostic; 0 as well for
+ *                                 arguments the call would reject) */
+#define BL_AMD_DESC_DIMS 32
+#define BL_AMD_DESC_SCALE_MAX 32512 /* 127 * 256 */
+typedef struct bl_amd_desc { int16_t q[BL_AMD_DESC_DIMS]; } bl_amd_desc; /* 64 bytes */
+typedef struct bl_amd_desc_range {                                       /* 384 bytes */
+  float lo[BL_AMD_DESC_DIMS], hi[BL_AMD_DESC_DIMS];
+  uint32_t n_finite[BL_AMD_DESC_DIMS];
+} bl_amd_desc_range;
+int bl_amd_desc_range_device(const float *d_x, int n, int d, bl_amd_desc_range *d_range, void *stream);
+int bl_amd_desc_quantize_device(const float *d_x, int n, int d, const bl_amd_desc_range *d_range,
+                                const uint16_t *h_scale, bl_amd_desc *d_out, void *stream);
+int bl_amd_desc_knn_device(const bl_amd_desc *d_lib, int n, int row_begin, int n_rows, int k, int32_t *d_index,
+                           uint64_t *d_dist2, void *stream);
+int bl_amd_desc_cross_knn_device(const bl_amd_desc *d_queries, int n_queries, const bl_amd_desc *d_lib, int n, int k,
+                                 int32_t *d_index, uint64_t *d_dist2, void *stream);
+int bl_amd_ctx_desc_knn_device(bl_amd_ctx *ctx, const bl_amd_desc *d_lib, int n, int row_begin, int n_rows, int k,
+                               int32_t *d_index, uint64_t *d_dist2, void *stream);
+int bl_amd_ctx_desc_cross_knn_device(bl_amd_ctx *ctx, const bl_amd_desc *d_queries, int n_queries,
+                                     const bl_amd_desc *d_lib, int n, int k, int32_t *d_index, uint64_t *d_dist2,
+                                     void *stream);
+int bl_amd_desc_build_host(const float *h_x, int n, int d, const uint16_t *h_scale, int fit, bl_amd_desc_range *h_range,
+                           bl_amd_desc *h_out);
+int bl_amd_desc_knn_host(const bl_amd_desc *h_queries, int n_queries, const bl_amd_desc *h_lib, int n, int k,
+                         int32_t *h_index, uint64_t *h_dist2);
+size_t bl_amd_desc_knn_scratch_bytes(int n, int n_rows, int k);
+
 /* Integer-only synthetic PCM (the benchmark corpus of BASELINE.json),
  * generated in place on the device: song i = seed_base + i, written at
  * h_desc[i].pcm_offset.  Byte-identical to oracle/orc_synth.c. */
@@ -727,7 +790,8 @@ int bl_amd_fir_mode(void);
 /* Per-kernel device time, measured with hipEvents on the launch stream while
  * profiling is on (bench.py's roofline leg).  name is one of "pcm_scan", "freq_scan",
  * "amp_finish", "freq_frames", "freq_finish", "env_windows", "env_tail",
- * "distance", "rhythm_hops", "rhythm_acf", "rhythm_pick", "chroma_pitch", "chroma_key"; returns accumulated milliseconds and the launch count since the
+ * "distance", "rhythm_hops", "rhythm_acf", "rhythm_pick", "chroma_pitch", "chroma_key",
+ * "desc_range", "desc_quantize", "desc_knn", "desc_merge"; returns accumulated milliseconds and the launch count since the
  * last reset, or -1 for an unknown name. */
 void bl_amd_profile(int enable);
 void bl_amd_profile_reset(void);
