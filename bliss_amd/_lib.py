@@ -19,6 +19,7 @@ BL_AMD_CHAIN_AUTO, BL_AMD_CHAIN_PER_CHAIN, BL_AMD_CHAIN_SPLIT = 0, 1, 2  # inclu
 BL_AMD_MIX_MAX_GAP = 16  # include/bliss_amd.h
 BL_AMD_PART_SPECTRUM, BL_AMD_PART_SUMS, BL_AMD_PART_HIST = 1, 2, 4  # include/bliss_amd.h
 BL_AMD_DESC_DIMS, BL_AMD_DESC_SCALE_MAX = 32, 32512  # include/bliss_amd.h
+BL_AMD_MEL_BANDS, BL_AMD_MEL_COEFFS = 32, 13  # include/bliss_amd.h
 
 
 class ForceVector(C.Structure):  # ref include/bliss.h:26-31
@@ -89,6 +90,16 @@ class FrameChroma(C.Structure):  # include/bliss_amd.h bl_amd_frame_chroma
 class SongChroma(C.Structure):  # include/bliss_amd.h bl_amd_song_chroma
     _fields_ = [("chroma", C.c_uint64 * 12), ("score", C.c_int64), ("score_next", C.c_int64), ("frames", C.c_int32),
                 ("key", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
+class FrameMel(C.Structure):  # include/bliss_amd.h bl_amd_frame_mel
+    _fields_ = [("mfcc", C.c_int32 * 13), ("flat", C.c_int32)]
+
+
+class SongMel(C.Structure):  # include/bliss_amd.h bl_amd_song_mel
+    _fields_ = [("mfcc_sum", C.c_int64 * 13), ("mfcc_sumsq", C.c_uint64 * 13), ("flat_sum", C.c_int64),
+                ("flat_sumsq", C.c_uint64), ("band_sum", C.c_uint64 * 32), ("frames", C.c_int32), ("used", C.c_int32),
+                ("status", C.c_int32), ("reserved", C.c_int32)]
 
 
 class Desc(C.Structure):  # include/bliss_amd.h bl_amd_desc
@@ -251,6 +262,17 @@ SYMBOLS = {
                                            _P(FrameChroma)]),
     "bl_amd_chroma_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bl_amd_chroma_key_name": (C.c_int, [C.c_int, C.c_char_p]),
+    "bl_amd_mel_frames": (C.c_int, [C.c_int, C.c_int]),
+    "bl_amd_mel_batch_device": (C.c_int, [C.c_void_p, _P(SongDesc), C.c_int, C.c_uint64, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_longlong, C.c_void_p]),
+    "bl_amd_ctx_mel_batch_device": (C.c_int, [C.c_void_p, C.c_void_p, _P(SongDesc), C.c_int, C.c_uint64, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "bl_amd_mel_batch_host": (C.c_int, [_P(C.c_void_p), _P(C.c_int32), _P(C.c_int32), C.c_int, C.c_uint64, _P(SongMel),
+                                        _P(FrameMel), _P(C.c_uint32)]),
+    "bl_amd_mel_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bl_amd_mel_mfcc": (C.c_double, [_P(SongMel), C.c_int, _P(C.c_double)]),
+    "bl_amd_mel_flatness_db": (C.c_double, [_P(SongMel), _P(C.c_double)]),
+    "bl_amd_selftest_ilog2": (C.c_int, [_P(C.c_uint64)]),
     "bl_amd_desc_range_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "bl_amd_desc_quantize_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, _P(C.c_uint16), C.c_void_p,
                                               C.c_void_p]),

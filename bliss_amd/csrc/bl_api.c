@@ -24,6 +24,7 @@
 #include <string.h>
 
 #include "bl_chroma_table.h"
+#include "bl_mel_table.h"
 #include "bl_device.h"
 #include "bliss.h"
 
@@ -328,4 +329,39 @@ int bl_amd_chroma_key_name(int key, char out[8]) {
   strcpy(out, kTonic[key % 12]);
   if (key >= 12) strcat(out, "m");
   return BL_OK;
+}
+
+/* ---- mel bands, cepstrum and flatness: the host side of bl_amd_song_mel (include/bliss_amd.h) ---- */
+
+int bl_amd_mel_frames(int n_samples, int channels) { return bl_amd_timbre_frames(n_samples, channels); }
+
+int bl_amd_mel_table(int32_t *edges, uint8_t *weights, int32_t *dct) {
+  return bl_mel_build(edges, weights, dct) == 0 ? BL_OK : BL_UNEXPECTED;
+}
+
+/* mean and population standard deviation of a signed quantity from its sum and sum of squares over `used` frames, in
+ * units of `unit` (timbre_mean_std with a sign): used * sumsq - sum^2 is taken exactly before it becomes a double */
+static double mel_mean_std(int64_t sum, uint64_t sumsq, int used, double unit, double *std_out) {
+  if (used < 1) {
+    if (std_out) *std_out = NAN;
+    return NAN;
+  }
+  if (std_out) {
+    const unsigned __int128 a = (unsigned __int128)(sum < 0 ? -(unsigned __int128)sum : (unsigned __int128)sum);
+    const unsigned __int128 n = (unsigned __int128)(unsigned)used * sumsq, s2 = a * a;
+    const double var = n > s2 ? (double)(n - s2) / ((double)used * (double)used) : 0.0;
+    *std_out = sqrt(var) * fabs(unit);
+  }
+  return (double)sum / (double)used * unit;
+}
+
+double bl_amd_mel_mfcc(const bl_amd_song_mel *song, int k, double *std) {
+  if (!song || k < 0 || k >= BL_AMD_MEL_COEFFS) { if (std) *std = NAN; return NAN; }
+  return mel_mean_std(song->mfcc_sum[k], song->mfcc_sumsq[k], song->used, 1.0 / 4096.0, std);
+}
+
+double bl_amd_mel_flatness_db(const bl_amd_song_mel *song, double *std) {
+  if (!song) { if (std) *std = NAN; return NAN; }
+  /* 10 log10 2 per unit of log2, and flat is 32 * 4096 times the log2 ratio */
+  return mel_mean_std(song->flat_sum, song->flat_sumsq, song->used, -3.010299956639812 / (32.0 * 4096.0), std);
 }

@@ -2,7 +2,7 @@
  * bl_host_batch.hip — everything that feeds songs from host memory: the host batch (blr_analyze_host: waves of songs
  * through two pinned buffers or the caller's registered ones, copy/compute overlap on 2 streams, optional device rate
  * conversion), its C-ABI (bl_amd_*analyze_batch_host*, bl_amd_set_host_transfer), the corpus loop over files
- * (bl_amd_analyze_files) and the host forms of the signal levels, the spectral timbre, the tempo and the chroma.  Host code only; contexts,
+ * (bl_amd_analyze_files) and the host forms of the signal levels, the spectral timbre, the tempo, the chroma and the mel call.  Host code only; contexts,
  * the record uploads and every device entry point are bl_runtime.hip's, the wave rule is bl_waves.h's.
  */
 #include <stdio.h>
@@ -264,8 +264,8 @@ int blr_analyze_host(bl_amd_ctx *c, const void *const *h_pcm, int pcm_is_s32, co
 
 /* ---- host forms of the signal levels, the spectral timbre and the tempo: what they share ---- */
 
-/* samples per wave of bl_amd_levels_batch_host, bl_amd_timbre_batch_host, bl_amd_rhythm_batch_host and
- * bl_amd_chroma_batch_host: the songs are uploaded, analysed and
+/* samples per wave of bl_amd_levels_batch_host, bl_amd_timbre_batch_host, bl_amd_rhythm_batch_host,
+ * bl_amd_chroma_batch_host and bl_amd_mel_batch_host: the songs are uploaded, analysed and
  * fetched 256 MiB of PCM at a time, or the context's host_wave_bytes if that is less (a song longer than that is a
  * wave of its own) */
 #define BL_HOST_WAVE_SAMPLES ((size_t)128 << 20)
@@ -403,6 +403,36 @@ int bl_amd_chroma_batch_host(const int16_t *const *h_pcm, const int32_t *n_sampl
                           !out.down(h_songs_out + b) || (h_frames_out && !fout.down(h_frames_out)))
                         return BL_UNEXPECTED;
                       if (h_frames_out) h_frames_out += frames;
+                      return BL_OK;
+                    });
+}
+
+int bl_amd_mel_batch_host(const int16_t *const *h_pcm, const int32_t *n_samples, const int32_t *channels, int n_songs,
+                          uint64_t min_energy, bl_amd_song_mel *h_songs_out, bl_amd_frame_mel *h_frames_out,
+                          uint32_t *h_bands_out) {
+  if (!h_pcm || !n_samples || !channels || !h_songs_out || n_songs < 1) return BL_UNEXPECTED;
+  for (int i = 0; i < n_songs; ++i)
+    if (!h_pcm[i] || !timbre_song_ok(0, n_samples[i], channels[i])) return BL_UNEXPECTED;
+  bl_amd_ctx *c = blr_default_ctx();
+  if (!c) return BL_UNEXPECTED;
+  DevGuard dg(c->device);
+  if (!dg.ok) return BL_UNEXPECTED;
+  return host_waves(c, h_pcm, n_samples, channels, n_songs,
+                    [&](const int16_t *d_pcm, const bl_amd_song_desc *desc, int b, int e) {
+                      long long frames = 0;
+                      for (int i = b; i < e; ++i) frames += bl_amd_mel_frames(n_samples[i], channels[i]);
+                      DevMem out(sizeof(bl_amd_song_mel) * (size_t)(e - b)),
+                          fout(h_frames_out ? sizeof(bl_amd_frame_mel) * (size_t)frames : 0),
+                          bout(h_bands_out ? sizeof(uint32_t) * BL_AMD_MEL_BANDS * (size_t)frames : 0);
+                      if (!out.ok() || !fout.ok() || !bout.ok() ||
+                          bl_amd_mel_batch_device(d_pcm, desc, e - b, min_energy, out.as<bl_amd_song_mel>(),
+                                                  fout.as<bl_amd_frame_mel>(), bout.as<uint32_t>(), frames,
+                                                  nullptr) != BL_OK ||
+                          !out.down(h_songs_out + b) || (h_frames_out && !fout.down(h_frames_out)) ||
+                          (h_bands_out && !bout.down(h_bands_out)))
+                        return BL_UNEXPECTED;
+                      if (h_frames_out) h_frames_out += frames;
+                      if (h_bands_out) h_bands_out += (size_t)BL_AMD_MEL_BANDS * (size_t)frames;
                       return BL_OK;
                     });
 }

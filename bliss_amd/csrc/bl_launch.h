@@ -3,7 +3,7 @@
  * geometry: bl_kernels.hip the launch order of the per-song analysis, whose stages are
  * bl_stats_kernels.hip, bl_freq_kernels.hip and bl_env_kernels.hip; bl_level_kernels.hip the signal
  * levels, bl_timbre_kernels.hip the per-frame spectral timbre, bl_rhythm_kernels.hip the tempo,
- * bl_chroma_kernels.hip chroma and key,
+ * bl_chroma_kernels.hip chroma and key, bl_mel_kernels.hip mel bands, cepstrum and flatness,
  * bl_matrix_kernels.hip the pairwise matrix,
  * bl_query_kernels.hip the vector queries, bl_desc_kernels.hip the descriptors and their kNN,
  * bl_rs_kernels.hip the rate converter)
@@ -197,6 +197,23 @@ int blk_timbre_configure_device(void);                 /* dynamic-LDS attribute,
  * unless d_frames is nullptr, of every frame record */
 int blk_timbre(hipStream_t s, const int16_t *d_pcm, const bl_timbre_song *d_songs, int n_songs, const bl_tables &tb,
                int pct, unsigned long long min_energy, bl_amd_song_timbre *d_songs_out, bl_amd_frame_timbre *d_frames);
+
+/* ---- mel bands, cepstrum and flatness (bl_mel_kernels.hip) ------------------------- */
+
+/* the image of bl_mel_table.h the kernel copies into its LDS (the bands' first bin, length and weights, the cosine
+ * table in the order the lanes take it): its size, and its bytes as built on the host, once per process (nullptr if
+ * the table does not have the properties the kernel's bounds rest on) */
+size_t blk_mel_image_bytes(void);
+const unsigned char *blk_mel_image_host(void);
+int blk_mel_configure_device(void);                    /* dynamic-LDS attribute, once per device */
+/* bl_amd_mel_batch_device: one workgroup per record of d_songs (the timbre's records: the frames are the same); writes
+ * every field of the n_songs song records and, unless they are nullptr, of every frame record and every frame's 32
+ * band levels.  d_image: the device copy of the image. */
+int blk_mel(hipStream_t s, const int16_t *d_pcm, const bl_timbre_song *d_songs, int n_songs, const bl_tables &tb,
+            const void *d_image, unsigned long long min_energy, bl_amd_song_mel *d_songs_out,
+            bl_amd_frame_mel *d_frames, uint32_t *d_bands);
+/* bl_amd_selftest_ilog2: d_out[i] = bl_ilog2_q12(bl_ilog2_sweep_value(i)) for i < BL_ILOG2_SWEEP (bl_ilog2.h) */
+int blk_ilog2_sweep(hipStream_t s, uint32_t *d_out, int n_cu);
 
 /* ---- per-song tempo (bl_rhythm_kernels.hip) -------------------------------------- */
 

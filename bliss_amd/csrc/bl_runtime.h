@@ -98,6 +98,10 @@ struct bl_amd_ctx {
    * (blk_chroma_image_host), uploaded by the context's first call */
   bl_buf chroma_songs, chroma_acc, chroma_image;
   bool chroma_image_ready = false;
+  /* bl_amd_mel_batch_device: the songs' records (bl_timbre_song), longest first, and the tables' image
+   * (blk_mel_image_host), uploaded by the context's first call */
+  bl_buf mel_songs, mel_image;
+  bool mel_image_ready = false;
   /* bl_amd_desc_*: the range's per-workgroup shares, the partial lists of a kNN's column split */
   bl_buf desc;
 };
@@ -131,7 +135,8 @@ inline void blr_unregister_wave(bl_amd_ctx *c, int k) {
   c->registered[k].clear();
 }
 
-/* what the levels and the timbre accept of a song, device and host forms alike (bl_amd_timbre_frames: bl_api.c) */
+/* what the levels, the timbre and the mel call accept of a song, device and host forms alike (bl_amd_timbre_frames:
+ * bl_api.c) */
 inline bool levels_song_ok(unsigned long long pcm_offset, int n_samples, int channels) {
   return n_samples >= 2 && (channels == 1 || channels == 2) && !(pcm_offset & 7);
 }

@@ -16,7 +16,7 @@
  * pinned slots (hipMemcpyAsync from pinned memory does not block), launch groups of more than
  * 32 768 songs follow each other on the stream, and the shared workspace is handed from one
  * batch to the next by an event, not by a host synchronisation.  Every entry point that uploads
- * per-song records (analysis, rate conversion, levels, timbre, tempo, chroma, synthesis, bld_mean_variance_host)
+ * per-song records (analysis, rate conversion, levels, timbre, tempo, chroma, mel, synthesis, bld_mean_variance_host)
  * does so through record_call, the one place that knows this protocol; the vector queries have
  * query_call (bl_runtime.h), which shares the hand-over (ws_wait, ws_pass) with it.
  *
@@ -30,8 +30,10 @@
 
 #include <algorithm>
 #include <atomic>
+#include <vector>
 
 #include "bl_runtime.h"
+#include "bl_ilog2.h"
 #include "bl_resample.h"
 
 namespace {
@@ -75,7 +77,8 @@ int ctx_init(bl_amd_ctx *c, int device) {
   BL_HIP_CHECK(hipMalloc(&c->tables_mem, h.size()));
   BL_HIP_CHECK(hipMemcpy(c->tables_mem, h.data(), h.size(), hipMemcpyHostToDevice));
   c->tb = blk_tables_bind(c->tables_mem);
-  if (blk_configure_device() != BL_OK || blk_query_configure_device() != BL_OK || blk_timbre_configure_device() != BL_OK)
+  if (blk_configure_device() != BL_OK || blk_query_configure_device() != BL_OK || blk_timbre_configure_device() != BL_OK ||
+      blk_mel_configure_device() != BL_OK)
     return BL_UNEXPECTED;
   {
     /* songs per launch group; lowered by the tests to exercise the multi-group path */
@@ -116,7 +119,7 @@ void ctx_release(bl_amd_ctx *c) {
                     &c->results, &c->arena[0], &c->arena[1], &c->arena22[0], &c->arena22[1],
                     &c->rs_songs, &c->rs_bank, &c->mx_my, &c->mx_gath, &c->mx_all, &c->mx_order, &c->mx_rows, &c->knn, &c->chain, &c->radius, &c->level_songs, &c->timbre_songs,
                     &c->rhythm_songs, &c->rhythm_n, &c->rhythm_rows, &c->chroma_songs, &c->chroma_acc, &c->chroma_image,
-                    &c->desc};
+                    &c->mel_songs, &c->mel_image, &c->desc};
   for (bl_buf *b : bufs) release_buf(*b);
   for (int k = 0; k < 2; ++k) {
     blr_unregister_wave(c, k);
@@ -143,6 +146,7 @@ void ctx_release(bl_amd_ctx *c) {
   }
   c->ws_used = false;
   c->chroma_image_ready = false;
+  c->mel_image_ready = false;
   c->rs_rate = 0;
   c->rs_kind = -1;
 }
@@ -678,6 +682,25 @@ int bl_amd_levels_batch_device(const int16_t *d_pcm, const bl_amd_song_desc *h_d
 
 /* ---- per-frame spectral timbre (bl_timbre_kernels.hip) ------------------------ */
 
+/* the records of the kernels that take one workgroup per song over the frames of the frequency pass (k_timbre, k_mel) */
+static int frame_songs_fill(const bl_amd_song_desc *h_desc, int n_songs, bl_timbre_song *hs) {
+  long long frame_off = 0;
+  for (int i = 0; i < n_songs; ++i) {
+    hs[i].pcm_off = h_desc[i].pcm_offset;
+    hs[i].frame_off = frame_off;
+    hs[i].n_frames = bl_amd_timbre_frames(h_desc[i].n_samples, h_desc[i].channels);
+    hs[i].channels = h_desc[i].channels;
+    hs[i].out_idx = i;
+    hs[i].reserved = 0;
+    frame_off += hs[i].n_frames;
+  }
+  /* one workgroup per song, the longest first, as the analysis lays its songs out: the long songs start while there
+   * are short ones left to fill the chip behind them */
+  std::stable_sort(hs, hs + n_songs,
+                   [](const bl_timbre_song &a, const bl_timbre_song &b) { return a.n_frames > b.n_frames; });
+  return BL_OK;
+}
+
 static int timbre_device(bl_amd_ctx *c, bool dflt, const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs,
                          int pct, uint64_t min_energy, bl_amd_song_timbre *d_songs_out,
                          bl_amd_frame_timbre *d_frames_out, long long n_frame_records, void *stream) {
@@ -694,21 +717,7 @@ static int timbre_device(bl_amd_ctx *c, bool dflt, const int16_t *d_pcm, const b
   if (!g.ok()) return BL_UNEXPECTED;
   hipStream_t s = static_cast<hipStream_t>(stream);
   return record_call<bl_timbre_song>(c, s, c->timbre_songs, n_songs, [&](bl_timbre_song *hs) {
-    long long frame_off = 0;
-    for (int i = 0; i < n_songs; ++i) {
-      hs[i].pcm_off = h_desc[i].pcm_offset;
-      hs[i].frame_off = frame_off;
-      hs[i].n_frames = bl_amd_timbre_frames(h_desc[i].n_samples, h_desc[i].channels);
-      hs[i].channels = h_desc[i].channels;
-      hs[i].out_idx = i;
-      hs[i].reserved = 0;
-      frame_off += hs[i].n_frames;
-    }
-    /* one workgroup per song, the longest first, as the analysis lays its songs out: the long songs start while there
-     * are short ones left to fill the chip behind them */
-    std::stable_sort(hs, hs + n_songs,
-                     [](const bl_timbre_song &a, const bl_timbre_song &b) { return a.n_frames > b.n_frames; });
-    return BL_OK;
+    return frame_songs_fill(h_desc, n_songs, hs);
   }, [&](const bl_timbre_song *, bl_timbre_song *d_songs) {
     return blk_timbre(s, d_pcm, d_songs, n_songs, c->tb, pct, min_energy, d_songs_out, d_frames_out);
   });
@@ -827,6 +836,73 @@ int bl_amd_chroma_batch_device(const int16_t *d_pcm, const bl_amd_song_desc *h_d
                                bl_amd_song_chroma *d_songs_out, bl_amd_frame_chroma *d_frames_out,
                                long long n_frame_records, void *stream) {
   return chroma_device(nullptr, true, d_pcm, h_desc, n_songs, d_songs_out, d_frames_out, n_frame_records, stream);
+}
+
+/* ---- mel bands, cepstrum and flatness (bl_mel_kernels.hip) ------------------------ */
+
+static int mel_device(bl_amd_ctx *c, bool dflt, const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs,
+                      uint64_t min_energy, bl_amd_song_mel *d_songs_out, bl_amd_frame_mel *d_frames_out,
+                      uint32_t *d_bands_out, long long n_frame_records, void *stream) {
+  if (!d_pcm || ((uintptr_t)d_pcm & 15) || !h_desc || !d_songs_out || ((uintptr_t)d_songs_out & 7) ||
+      ((uintptr_t)d_frames_out & 3) || ((uintptr_t)d_bands_out & 3) || n_songs < 1)
+    return BL_UNEXPECTED;
+  long long total = 0; /* the sum of F over the songs */
+  for (int i = 0; i < n_songs; ++i) {
+    if (!timbre_song_ok(h_desc[i].pcm_offset, h_desc[i].n_samples, h_desc[i].channels)) return BL_UNEXPECTED;
+    total += bl_amd_timbre_frames(h_desc[i].n_samples, h_desc[i].channels);
+  }
+  if (((d_frames_out || d_bands_out) && n_frame_records != total) || !blk_mel_image_host() || !(c = call_ctx(c, dflt)))
+    return BL_UNEXPECTED;
+  CtxGuard g(c);
+  if (!g.ok()) return BL_UNEXPECTED;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return record_call<bl_timbre_song>(c, s, c->mel_songs, n_songs, [&](bl_timbre_song *hs) {
+    return frame_songs_fill(h_desc, n_songs, hs);
+  }, [&](const bl_timbre_song *, bl_timbre_song *d_songs) {
+    if (blr_ensure(c->mel_image, blk_mel_image_bytes()) != BL_OK) return BL_UNEXPECTED;
+    if (!c->mel_image_ready) { /* blocking, once per context: nothing on the device reads the block before it */
+      BL_HIP_CHECK(hipMemcpy(c->mel_image.p, blk_mel_image_host(), blk_mel_image_bytes(), hipMemcpyHostToDevice));
+      c->mel_image_ready = true;
+    }
+    return blk_mel(s, d_pcm, d_songs, n_songs, c->tb, c->mel_image.p, min_energy, d_songs_out, d_frames_out,
+                   d_bands_out);
+  });
+}
+
+int bl_amd_ctx_mel_batch_device(bl_amd_ctx *c, const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs,
+                                uint64_t min_energy, bl_amd_song_mel *d_songs_out, bl_amd_frame_mel *d_frames_out,
+                                uint32_t *d_bands_out, long long n_frame_records, void *stream) {
+  return mel_device(c, false, d_pcm, h_desc, n_songs, min_energy, d_songs_out, d_frames_out, d_bands_out,
+                    n_frame_records, stream);
+}
+
+int bl_amd_mel_batch_device(const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs, uint64_t min_energy,
+                            bl_amd_song_mel *d_songs_out, bl_amd_frame_mel *d_frames_out, uint32_t *d_bands_out,
+                            long long n_frame_records, void *stream) {
+  return mel_device(nullptr, true, d_pcm, h_desc, n_songs, min_energy, d_songs_out, d_frames_out, d_bands_out,
+                    n_frame_records, stream);
+}
+
+/* L on the device against the same source on the host (bl_ilog2.h), over bl_ilog2_sweep_value */
+int bl_amd_selftest_ilog2(uint64_t counts[2]) {
+  bl_amd_ctx *c = blr_default_ctx();
+  if (!c) return BL_UNEXPECTED;
+  DevGuard dg(c->device);
+  if (!dg.ok) return BL_UNEXPECTED;
+  DevMem d(sizeof(uint32_t) * (size_t)BL_ILOG2_SWEEP);
+  std::vector<uint32_t> h(BL_ILOG2_SWEEP);
+  if (!d.ok() || hipMemset(d.p, 0xFF, d.bytes) != hipSuccess || blk_ilog2_sweep(nullptr, d.as<uint32_t>(), c->n_cu) != BL_OK ||
+      !d.down(h.data()))
+    return BL_UNEXPECTED;
+  uint64_t checked = 0, wrong = 0;
+  for (uint32_t i = 0; i < BL_ILOG2_SWEEP; ++i) {
+    const uint64_t x = bl_ilog2_sweep_value(i);
+    if (!x) continue;
+    checked += 1;
+    wrong += h[i] != bl_ilog2_q12(x);
+  }
+  if (counts) { counts[0] = checked; counts[1] = wrong; }
+  return wrong ? BL_UNEXPECTED : BL_OK;
 }
 
 /* stages 7 and 8 on the caller's curves: uploaded, through the same launch as the device form, fetched */

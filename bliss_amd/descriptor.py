@@ -2,7 +2,7 @@
 bl_amd_desc_range, bl_amd_desc_*): up to 32 features per song, every column mapped onto the same int16 range by the
 library's own minimum and maximum, and the squared Euclidean distance of two descriptors as an exact integer.
 
-    x, names = features(results, levels=lv, timbre=tb, rhythm=rh, chroma=ch)
+    x, names = features(results, levels=lv, timbre=tb, rhythm=rh, chroma=ch, mel=ml)
     desc, rng = fit(x)                      # the library
     index, dist2 = knn(desc, 10)            # its ten nearest songs per song
     q = quantize(x_new, rng)                # songs from outside, with the library's range
@@ -16,7 +16,8 @@ import numpy as np
 from . import _lib
 from ._args import desc_scale, feature_matrix, int_in
 from ._lib import check
-from .records import (CHROMA_DTYPE, LEVELS_DTYPE, RESULT_DTYPE, RHYTHM_DTYPE, TIMBRE_SONG_DTYPE, levels_db, timbre_hz)
+from .records import (CHROMA_DTYPE, LEVELS_DTYPE, MEL_DTYPE, RESULT_DTYPE, RHYTHM_DTYPE, TIMBRE_SONG_DTYPE, levels_db,
+                      timbre_hz)
 
 DIMS, SCALE_MAX = _lib.BL_AMD_DESC_DIMS, _lib.BL_AMD_DESC_SCALE_MAX
 MAX_N = 1 << 27          # a kNN library stays below it: the index bits of a key
@@ -182,9 +183,9 @@ def _records(name, rec, dtype, n):
     return a
 
 
-def features(results, levels=None, timbre=None, rhythm=None, chroma=None):
+def features(results, levels=None, timbre=None, rhythm=None, chroma=None, mel=None):
     """The float32 feature matrix of n songs from the records the other modules return, and its column names: (x, names).
-    Host numpy only.  Groups that are not passed are left out; with all of them there are 25 columns:
+    Host numpy only.  Groups that are not passed are left out; with all of them there are 32 columns, a full descriptor:
 
       ratings  tempo, amplitude, frequency, attack      the four ratings of `results` (results_to_numpy) as they are
       levels   rms_db, peak_db                          levels_db(): the louder channel's RMS and peak in dB (-inf for
@@ -193,7 +194,9 @@ def features(results, levels=None, timbre=None, rhythm=None, chroma=None):
       timbre   centroid_hz, centroid_std_hz,            timbre_hz(): mean and standard deviation over the used frames,
                rolloff_hz, rolloff_std_hz               in Hz; NaN for a song without a used frame
       rhythm   bpm, strength                            rhythm_bpm(): beats per minute (NaN without a tempo), r_lag / r0
-      chroma   chroma_0 .. chroma_11                    chroma[k] / sum_k chroma[k] in float64, 0 when the sum is 0"""
+      chroma   chroma_0 .. chroma_11                    chroma[k] / sum_k chroma[k] in float64, 0 when the sum is 0
+      mel      flatness_db, mfcc_1 .. mfcc_6            mel_summary(): means over the used frames, NaN without one;
+                                                        coefficient 0 is the overall level, which rms_db carries"""
     res = np.ascontiguousarray(results)
     if res.dtype != RESULT_DTYPE or res.ndim != 1 or res.size < 1:
         raise ValueError("results must be a non-empty 1-D array of bl_amd_song_result records (results_to_numpy)")
@@ -219,5 +222,10 @@ def features(results, levels=None, timbre=None, rhythm=None, chroma=None):
         share = np.divide(ch, total, out=np.zeros_like(ch), where=total > 0)
         cols += [share[:, k] for k in range(12)]
         names += [f"chroma_{k}" for k in range(12)]
+    if mel is not None:
+        from .mel import mel_summary
+        ms = mel_summary(_records("mel", mel, MEL_DTYPE, n))
+        cols += [ms["flatness_db"]] + [ms["mfcc"][:, k] for k in range(1, 7)]
+        names += ["flatness_db"] + [f"mfcc_{k}" for k in range(1, 7)]
     with np.errstate(over="ignore"):
         return np.stack(cols, axis=1).astype(np.float32), names

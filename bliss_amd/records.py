@@ -26,6 +26,8 @@ TIMBRE_FRAME_DTYPE = np.dtype(_lib.FrameTimbre)
 RHYTHM_DTYPE = np.dtype(_lib.SongRhythm)
 CHROMA_DTYPE = np.dtype(_lib.SongChroma)
 FRAME_CHROMA_DTYPE = np.dtype(_lib.FrameChroma)
+MEL_DTYPE = np.dtype(_lib.SongMel)
+FRAME_MEL_DTYPE = np.dtype(_lib.FrameMel)
 
 LEVELS_DB_DTYPE = np.dtype([("peak_db", "<f8", (2,)), ("rms_db", "<f8", (2,)), ("dc", "<f8", (2,)),
                             ("zcr", "<f8", (2,))])

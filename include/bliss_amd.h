@@ -704,6 +704,96 @@ int bl_amd_chroma_batch_host(const int16_t *const *h_pcm, const int32_t *n_sampl
 int bl_amd_chroma_table(int8_t *re, int8_t *im, uint32_t *gain, int32_t *len);
 int bl_amd_chroma_key_name(int key, char out[8]);
 
+/* Mel bands, cepstrum and flatness: the shape of every frame's spectrum.  The centroid and the rolloff of the timbre
+ * block say where a frame's power sits and where it stops; the 32 log-mel band levels say how it is spread, the 13
+ * cepstral coefficients (MFCC) are the usual compact description of that spread, and the flatness tells noise from
+ * tone.  The reference's author lists "MFCC" and "spectral flatness" in ROADMAP.md ("Timbral features"); none of it is
+ * in the reference's API.  The band levels of all frames are the log-mel spectrogram a learned model takes as input.
+ * Every field is an exact integer, defined by the algorithms below and not by libm.
+ * Frames, P_t[d], Q_t[d] = floor(16 P_t[d]) (uint64, d = 1 .. 255, their sum below 2^50) and energy = sum_d Q_t[d] are
+ * exactly those of the timbre block above.
+ *   edges    34 integers in sixteenths of a bin, equally spaced on the mel scale 2595 log10(1 + f / 700) from bin 1 to
+ *            bin 256 of the 512-point transform at 22 050 Hz, rounded to nearest:
+ *              16 40 66 95 126 159 196 236 279 326 377 432 493 558 630 707 792 883 983 1091 1209 1337 1477 1628 1793
+ *              1972 2166 2378 2608 2858 3130 3425 3747 4096
+ *   weights  32 triangular bands.  With x = 16 d and (a, c, z) = (e[b], e[b+1], e[b+2]), in integer floor divisions:
+ *              W[b][d] = (64 (x - a)) / (c - a)  for a < x <= c
+ *              W[b][d] = (64 (z - x)) / (z - c)  for c < x < z,   0 otherwise.
+ *            Every band has 3 to 41 non-zero weights, no bin feeds more than two bands, a column sums to at most 64 and
+ *            that of bin 1 (where a DC offset leaks to under the Hann window) to 0; the row sums run from 90 to 1320.
+ *   sums     S_t[b] = sum_d W[b][d] Q_t[d], a uint64, at most 64 * 2^50 = 2^56
+ *   log      L(x), 1 <= x < 2^64: log2 x in 1/4096, DEFINED by: e = floor(log2 x); m = x << (30 - e) if e <= 30, else
+ *            x >> (e - 30), so 2^30 <= m < 2^31; acc = e; twelve times: t = (m m) >> 30, bit = t >> 31, m = t >> bit,
+ *            acc = 2 acc + bit; L = acc.  L(1) = 0, L(2) = 4096, L(3) = 6492, L(2^63) = 258048;
+ *            0 <= 4096 log2 x - L(x) < 1 + 2^-10, and L is non-decreasing.
+ *   levels   E_t[b] = L(S_t[b] + 1): the log-mel frame, 0 <= E < 2^18
+ *   cepstrum D[k][b] = floor(16384 cos(pi k (2 b + 1) / 64) + 0.5), k = 0 .. 12, the cosine the portable polynomial of
+ *            the chroma bank at (k (2 b + 1) mod 128) / 128 of a turn (bl_amd_mel_table shows the result);
+ *            mfcc_t[k] = floor((sum_b D[k][b] E_t[b]) / 2^14), an arithmetic shift of an int64; |mfcc| < 2^23
+ *   flatness T = sum_b (S_t[b] + 1) < 2^57, G = sum_b E_t[b], flat_t = 32 L(T) - 160 * 4096 - G: 32 * 4096 times the
+ *            log2 of the ratio of the arithmetic to the geometric mean of the 32 values S + 1.  0 for digital silence
+ *            and for a flat band spectrum, growing with tonality; slightly negative values occur because L truncates.
+ * Per song: a frame is USED iff energy > 0 and energy >= min_energy (the timbre's rule); the sums run over the used
+ * frames.  The sums of squares are exact below 2^64, which |value| < 2^23 guarantees for 2^18 used frames (1.7 hours
+ * at 22 050 Hz) whatever the signal; beyond that they are taken modulo 2^64. */
+#define BL_AMD_MEL_BANDS 32
+#define BL_AMD_MEL_COEFFS 13
+typedef struct bl_amd_frame_mel { /* 56 bytes */
+  int32_t mfcc[13];
+  int32_t flat;
+} bl_amd_frame_mel;
+typedef struct bl_amd_song_mel { /* 496 bytes */
+  int64_t mfcc_sum[13];
+  uint64_t mfcc_sumsq[13];
+  int64_t flat_sum;
+  uint64_t flat_sumsq;
+  uint64_t band_sum[32]; /* the sums of E_t[b] */
+  int32_t frames;        /* F */
+  int32_t used;
+  int32_t status;        /* BL_OK */
+  int32_t reserved;      /* 0 */
+} bl_amd_song_mel;
+/* bl_amd_mel_frames: F of a song (that of bl_amd_timbre_frames); -1 for n_samples < 0 or channels outside {1, 2}.
+ * bl_amd_mel_batch_device: the mel records of n_songs songs whose PCM sits in device memory.  The descriptors are those
+ * of bl_amd_analyze_batch_device with the timbre's limits: pcm_offset a multiple of 8, channels 1 or 2, F >= 1,
+ * duration ignored; d_pcm 16-byte aligned; n_songs >= 1.  d_songs_out: n_songs records in the caller's order.
+ * d_frames_out (one bl_amd_frame_mel per frame) and d_bands_out (32 uint32 per frame: E_t[0 .. 31], the log-mel
+ * spectrogram) may each be NULL; either receives every frame, songs concatenated in the caller's order, song i at the
+ * sum of F_j over j < i, and if one of them is given n_frame_records must equal the sum of all F_j (it is ignored
+ * when both are NULL).  No output needs zeroing.  A rejected call returns BL_UNEXPECTED and writes nothing.
+ * Asynchronous on `stream`; h_desc is copied before the call returns.  Calls of one context are ordered on the device
+ * like its batches.  A song's records are a pure function of its samples, `channels` and min_energy: they depend
+ * neither on the other songs, n_songs, the order, the launch shape nor on which of the frame outputs are asked for,
+ * and no sample outside the song's whole frames is read.  Read-only towards bl_amd_last_energies and
+ * bl_amd_last_freq_stats.
+ *   bl_amd_mel_batch_host: the same from host memory, blocking: the songs are uploaded and analysed in waves;
+ *     h_frames_out and h_bands_out may be NULL.
+ *   bl_amd_mel_table: copies the tables to host buffers, no device work: edges [34], weights [32][256] (bin 0 is 0),
+ *     dct [13][32]; any pointer may be NULL.  BL_UNEXPECTED if the weights lack the properties listed above.
+ *   bl_amd_mel_mfcc: plain host arithmetic in double from the exact integers, no device: the mean of coefficient k
+ *     over the used frames in log2 units (sum / used / 4096), the population standard deviation in *std if that is not
+ *     NULL; NaN for both when used == 0 (or song is NULL, or k outside 0 .. 12).
+ *   bl_amd_mel_flatness_db: -mean(flat) / (32 * 4096) * 10 log10 2: the geometric over the arithmetic mean of the band
+ *     powers in dB, 0 for a flat spectrum and more negative the more tonal; *std its standard deviation in dB; NaN as
+ *     above.
+ *   bl_amd_selftest_ilog2: runs L on the device for 2^e - 1, 2^e, 2^e + 1 of every e <= 63 and for a fixed
+ *     multiplicative sequence of 2^17 values, and compares with the host's results from the same source; BL_OK iff
+ *     all agree.  counts, if not NULL, receives {checked, wrong}. */
+int bl_amd_mel_frames(int n_samples, int channels);
+int bl_amd_mel_batch_device(const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs, uint64_t min_energy,
+                            bl_amd_song_mel *d_songs_out, bl_amd_frame_mel *d_frames_out, uint32_t *d_bands_out,
+                            long long n_frame_records, void *stream);
+int bl_amd_ctx_mel_batch_device(bl_amd_ctx *ctx, const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs,
+                                uint64_t min_energy, bl_amd_song_mel *d_songs_out, bl_amd_frame_mel *d_frames_out,
+                                uint32_t *d_bands_out, long long n_frame_records, void *stream);
+int bl_amd_mel_batch_host(const int16_t *const *h_pcm, const int32_t *n_samples, const int32_t *channels, int n_songs,
+                          uint64_t min_energy, bl_amd_song_mel *h_songs_out, bl_amd_frame_mel *h_frames_out,
+                          uint32_t *h_bands_out);
+int bl_amd_mel_table(int32_t *edges, uint8_t *weights, int32_t *dct);
+double bl_amd_mel_mfcc(const bl_amd_song_mel *song, int k, double *std);
+double bl_amd_mel_flatness_db(const bl_amd_song_mel *song, double *std);
+int bl_amd_selftest_ilog2(uint64_t counts[2]);
+
 /* Library-normalised descriptors and exact nearest neighbours over them.  The queries above compare force vectors;
  * this layer compares anything: the caller puts up to 32 features per song into a row-major f32 matrix x[n][d]
  * (bliss_amd.descriptor.features builds one from the records of the sections above), every column is mapped onto the
