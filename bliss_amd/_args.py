@@ -35,6 +35,22 @@ def songs_check(lengths, channels, shortest):
     return channels
 
 
+def seeds_array(seeds, n_limit):
+    """the seeds of chains (a scalar or a non-empty 1-D sequence of integers) as a contiguous 1-D int32 array; n_limit:
+    reject seeds outside [0, n_limit) (None: leave them to the device, which answers with an empty row)"""
+    s = np.asarray(seeds)
+    if s.dtype == np.bool_ or not np.issubdtype(s.dtype, np.integer):
+        raise ValueError(f"seeds must be integers, got dtype {s.dtype}")
+    if s.ndim > 1 or s.size < 1:
+        raise ValueError(f"seeds must be a scalar or a non-empty 1-D sequence, got shape {s.shape}")
+    s = s.reshape(-1)
+    if n_limit is not None and (s.min() < 0 or s.max() >= n_limit):
+        raise ValueError(f"seeds must lie in [0, {n_limit})")
+    if s.min() < -2 ** 31 or s.max() >= 2 ** 31:
+        raise ValueError("seeds do not fit 32 bits")
+    return np.ascontiguousarray(s, dtype=np.int32)
+
+
 def vecs_shape_check(name, shape):
     if len(shape) != 2 or shape[1] != 4 or shape[0] < 1:
         raise ValueError(f"{name} must have shape (n, 4) with n >= 1, got {tuple(shape)}")

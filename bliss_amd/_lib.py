@@ -288,6 +288,13 @@ SYMBOLS = {
                                          _P(Desc)]),
     "bl_amd_desc_knn_host": (C.c_int, [_P(Desc), C.c_int, _P(Desc), C.c_int, C.c_int, _P(C.c_int32), _P(C.c_uint64)]),
     "bl_amd_desc_knn_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "bl_amd_desc_chain_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                           C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bl_amd_ctx_desc_chain_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                               C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bl_amd_desc_chain_host": (C.c_int, [_P(Desc), C.c_int, _P(C.c_int32), _P(Desc), C.c_int, C.c_int, _P(C.c_int32),
+                                         C.c_int, _P(C.c_uint8), _P(C.c_int32), _P(C.c_uint64)]),
+    "bl_amd_desc_chain_shape": (C.c_int, [C.c_int, C.c_int]),
     "bl_amd_synth_pcm_device": (C.c_int, [C.c_void_p, _P(SongDesc), C.c_int, C.c_uint32, C.c_uint32, C.c_void_p]),
     "bl_amd_set_fir_mode": (C.c_int, [C.c_int]),
     "bl_amd_fir_mode": (C.c_int, []),

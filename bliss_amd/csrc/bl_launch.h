@@ -6,6 +6,7 @@
  * bl_chroma_kernels.hip chroma and key, bl_mel_kernels.hip mel bands, cepstrum and flatness,
  * bl_matrix_kernels.hip the pairwise matrix,
  * bl_query_kernels.hip the vector queries, bl_desc_kernels.hip the descriptors and their kNN,
+ * bl_desc_chain_kernels.hip the playlist chains over descriptors,
  * bl_rs_kernels.hip the rate converter)
  * and the runtime (bl_runtime.hip: contexts, workspaces, streams, the analysis C-ABI of
  * include/bliss_amd.h; bl_query_api.hip: its matrix, playlist and vector-query C-ABI; bl_desc_api.hip: its descriptor C-ABI; bl_multi.hip: the multi-device
@@ -356,6 +357,20 @@ size_t blk_desc_knn_scratch_bytes(int n, int n_rows, int k, int n_cu);
 int blk_desc_knn(hipStream_t s, const bl_amd_desc *d_queries, const bl_amd_desc *d_lib, int n, int row_begin, int n_rows,
                  int k, int n_cu, void *d_scratch, int32_t *d_index, uint64_t *d_dist2, blk_mark_fn mark,
                  void *mark_user);
+
+/* ---- playlist chains over descriptors (bl_desc_chain_kernels.hip) -------------- */
+
+int blk_desc_chain_configure_device(void);             /* dynamic-LDS attributes, once per device */
+/* bl_amd_desc_chain_device: exactly one of d_seeds / d_seed_desc, d_tags used when gap > 0, d_exclude nullptr or n
+ * bytes.  blk_desc_chain_shape: 1 = one workgroup per group of 16 chains, 2 = column split with one launch per step;
+ * force: 0 = the launch layer's rule, 1 / 2 = that shape.  d_scratch: at least blk_desc_chain_scratch_bytes(...) bytes
+ * for the same (n, n_chains, n_cu, force), 256-byte aligned; it is re-initialised by every call. */
+int blk_desc_chain_shape(int n, int n_chains, int n_cu, int force);
+size_t blk_desc_chain_scratch_bytes(int n, int n_chains, int n_cu, int force);
+int blk_desc_chain(hipStream_t s, const bl_amd_desc *d_lib, int n, const int32_t *d_seeds,
+                   const bl_amd_desc *d_seed_desc, int n_chains, int length, const int32_t *d_tags, int gap,
+                   const uint8_t *d_exclude, int n_cu, int force, void *d_scratch, int32_t *d_order,
+                   uint64_t *d_dist2);
 
 /* ---- device rate converter (bl_rs_kernels.hip) ------------------------------ */
 

@@ -119,6 +119,7 @@ static int knn_host(const struct force_vector_s *h_queries, int n_queries, const
 }
 
 static std::atomic<int> g_chain_force{BL_AMD_CHAIN_AUTO};
+int blr_chain_force(void) { return g_chain_force.load(); }
 
 static bool chain_args_ok(const void *vecs, int n, const void *seeds, int n_chains, int length, int metric,
                           const void *order, const void *value) {

@@ -102,7 +102,8 @@ struct bl_amd_ctx {
    * (blk_mel_image_host), uploaded by the context's first call */
   bl_buf mel_songs, mel_image;
   bool mel_image_ready = false;
-  /* bl_amd_desc_*: the range's per-workgroup shares, the partial lists of a kNN's column split */
+  /* bl_amd_desc_*: the range's per-workgroup shares, the partial lists of a kNN's column split, a chain call's
+   * per-group state and played words */
   bl_buf desc;
 };
 
@@ -234,6 +235,9 @@ int query_call(bl_amd_ctx *c, void *stream, bl_buf &buf, size_t bytes, Launch la
   if (ws_wait(c, s) != BL_OK || blr_ensure(buf, bytes) != BL_OK || launch(s, buf.p) != BL_OK) return BL_UNEXPECTED;
   return ws_pass(c, s);
 }
+
+/* bl_amd_chain_force_shape's setting (bl_query_api.hip), which pins the shape of the descriptor chains too */
+int blr_chain_force(void);
 
 /* the profiling callback of the launchers (blk_mark_fn); user: the context */
 void mark_cb(void *user, int k, hipStream_t s, int begin);

@@ -78,7 +78,7 @@ int ctx_init(bl_amd_ctx *c, int device) {
   BL_HIP_CHECK(hipMemcpy(c->tables_mem, h.data(), h.size(), hipMemcpyHostToDevice));
   c->tb = blk_tables_bind(c->tables_mem);
   if (blk_configure_device() != BL_OK || blk_query_configure_device() != BL_OK || blk_timbre_configure_device() != BL_OK ||
-      blk_mel_configure_device() != BL_OK)
+      blk_mel_configure_device() != BL_OK || blk_desc_chain_configure_device() != BL_OK)
     return BL_UNEXPECTED;
   {
     /* songs per launch group; lowered by the tests to exercise the multi-group path */

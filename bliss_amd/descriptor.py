@@ -7,6 +7,7 @@ library's own minimum and maximum, and the squared Euclidean distance of two des
     index, dist2 = knn(desc, 10)            # its ten nearest songs per song
     q = quantize(x_new, rng)                # songs from outside, with the library's range
     index, dist2 = knn(desc, 10, queries=q)
+    order, dist2 = chain(desc, seeds, 50, tags=artists, gap=3)   # playlists: no artist twice within 3 slots
 
 This module is imported explicitly (`import bliss_amd.descriptor`): the package's own namespace is unchanged."""
 import ctypes as C
@@ -14,7 +15,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._args import desc_scale, feature_matrix, int_in
+from ._args import desc_scale, feature_matrix, int_in, seeds_array
 from ._lib import check
 from .records import (CHROMA_DTYPE, LEVELS_DTYPE, MEL_DTYPE, RESULT_DTYPE, RHYTHM_DTYPE, TIMBRE_SONG_DTYPE, levels_db,
                       timbre_hz)
@@ -163,6 +164,119 @@ def knn_device(d_desc, k, queries=None, row_begin=0, n_rows=None, stream=None, c
         else:
             check(getattr(lib, "bl_amd_ctx_" + name)(ctx.handle, *args, *tail), "bl_amd_ctx_" + name)
     return index, dist2
+
+
+def _chain_seeds_check(seeds, seed_desc):
+    if (seeds is None) == (seed_desc is None):
+        raise ValueError("exactly one of seeds and seed_desc must be given")
+
+
+def _chain_ints(length, gap, tags):
+    length = int_in("length", length, 1)
+    gap = int_in("gap", gap, 0, _lib.BL_AMD_MIX_MAX_GAP)
+    if gap > 0 and tags is None:
+        raise ValueError("gap > 0 needs tags")
+    return length, gap
+
+
+def chain(desc, seeds, length, tags=None, gap=0, exclude=None, seed_desc=None):
+    """Playlist chains over descriptors (bl_amd_desc_chain_host), one per seed: slot 0 is the seed and every next slot
+    the allowed song nearest to the previous one by (dist2, index).  A song is allowed if the chain has not played it,
+    exclude (n bools or bytes) does not mask it, and its tag (tags: n integers such as artist ids, negative = untagged)
+    is not the tag of one of the last `gap` slots (0 <= gap <= 16; 0 ignores the tags).  seed_desc: (m, 32) int16
+    descriptors instead of seeds (pass seeds=None): slot 0 is the nearest song not excluded.  An index seed takes slot 0
+    even if it is excluded.  Returns (order (n_chains, length) int32, dist2 (n_chains, length) uint64): dist2[c, t] is the
+    exact squared distance between the songs of slots t - 1 and t (slot 0: 0, or the seed descriptor's to its pick).  A
+    chain with no allowed song left ends: the rest of its row, like the slots past n, holds -1 and 2^64 - 1.  To continue
+    a chain, call again with seed = its last song and exclude = everything played so far."""
+    lib = _desc_array("desc", desc)
+    _chain_seeds_check(seeds, seed_desc)
+    length, gap = _chain_ints(length, gap, tags)
+    n = lib.shape[0]
+    if n >= MAX_N:
+        raise ValueError(f"desc must have fewer than {MAX_N} rows, got {n}")
+    s = q = None
+    if seed_desc is not None:
+        q = _desc_array("seed_desc", seed_desc)
+    else:
+        s = seeds_array(seeds, n)
+    tg = None
+    if tags is not None:
+        tg = np.asarray(tags)
+        if tg.dtype == np.bool_ or not np.issubdtype(tg.dtype, np.integer) or tg.shape != (n,):
+            raise ValueError(f"tags must be {n} integers, got dtype {tg.dtype} and shape {tg.shape}")
+        if tg.size and (tg.min() < -2 ** 31 or tg.max() >= 2 ** 31):
+            raise ValueError("tags do not fit 32 bits")
+        tg = np.ascontiguousarray(tg, dtype=np.int32)
+    ex = None
+    if exclude is not None:
+        ex = np.asarray(exclude)
+        if ex.dtype not in (np.bool_, np.uint8) or ex.shape != (n,):
+            raise ValueError(f"exclude must be {n} bools or uint8, got dtype {ex.dtype} and shape {ex.shape}")
+        ex = np.ascontiguousarray(ex).view(np.uint8)
+    n_chains = q.shape[0] if q is not None else s.size
+    order, dist2 = np.empty((n_chains, length), dtype=np.int32), np.empty((n_chains, length), dtype=np.uint64)
+    check(_lib.load().bl_amd_desc_chain_host(
+        lib.ctypes.data_as(_DESC), n, s.ctypes.data_as(_I32) if s is not None else None,
+        q.ctypes.data_as(_DESC) if q is not None else None, n_chains, length,
+        tg.ctypes.data_as(_I32) if tg is not None else None, gap,
+        ex.ctypes.data_as(C.POINTER(C.c_uint8)) if ex is not None else None, order.ctypes.data_as(_I32),
+        dist2.ctypes.data_as(_U64)), "bl_amd_desc_chain_host")
+    return order, dist2
+
+
+def chain_device(d_desc, d_seeds, length, tags=None, gap=0, exclude=None, seed_desc=None, stream=None, ctx=None):
+    """chain() on torch tensors: d_desc a contiguous int16 (n, 32) CUDA tensor; d_seeds an int32 CUDA tensor on the same
+    device (0-D or 1-D) or host integers, which are uploaded, or None with seed_desc, a tensor like d_desc that may be a
+    view into it.  tags: an int32 CUDA tensor of n entries; exclude: a bool or uint8 CUDA tensor of n entries; both
+    contiguous and on d_desc's device.  A seed outside [0, n) gives a row of -1.  Returns (order int32, dist2 as int64
+    bits of the uint64: an empty slot reads -1) CUDA tensors of shape (n_chains, length), asynchronously on `stream`
+    (default: the current stream of that device).  ctx: an explicit Context."""
+    import torch
+    _chain_seeds_check(d_seeds, seed_desc)
+    length, gap = _chain_ints(length, gap, tags)
+    _device_desc_check("d_desc", d_desc)
+    n = d_desc.shape[0]
+    if n >= MAX_N:
+        raise ValueError(f"d_desc must have fewer than {MAX_N} rows, got {n}")
+    s = None
+    if seed_desc is not None:
+        _device_desc_check("seed_desc", seed_desc)
+    elif isinstance(d_seeds, torch.Tensor):
+        if d_seeds.dtype != torch.int32 or d_seeds.dim() > 1 or d_seeds.numel() < 1:
+            raise ValueError("d_seeds must be an int32 tensor with 0 or 1 dimensions and at least one element")
+        if not d_seeds.is_cuda:
+            raise ValueError("d_seeds must be on the device of d_desc")
+    else:
+        s = seeds_array(d_seeds, None)
+    for name, t, kinds in (("tags", tags, (torch.int32,)), ("exclude", exclude, (torch.bool, torch.uint8))):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype not in kinds or tuple(t.shape) != (n,)):
+            raise ValueError(f"{name} must be a tensor of {n} entries of {' or '.join(str(k) for k in kinds)}")
+    for name, t in (("d_seeds", d_seeds if s is None and seed_desc is None else None), ("seed_desc", seed_desc),
+                    ("tags", tags), ("exclude", exclude)):
+        if t is not None and (not t.is_cuda or t.device != d_desc.device or not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous tensor on the device of d_desc")
+    lib = _lib.load()
+    with _on_device(lib, d_desc, stream) as cur, torch.cuda.stream(cur):
+        sd = None
+        if s is not None:
+            sd = torch.from_numpy(s).to(d_desc.device)
+        elif seed_desc is None:
+            sd = d_seeds.reshape(-1)
+        n_chains = sd.numel() if sd is not None else seed_desc.shape[0]
+        order = torch.empty((n_chains, length), dtype=torch.int32, device=d_desc.device)
+        dist2 = torch.empty((n_chains, length), dtype=torch.int64, device=d_desc.device)
+        args = (d_desc.data_ptr(), n, sd.data_ptr() if sd is not None else None,
+                seed_desc.data_ptr() if seed_desc is not None else None, n_chains, length,
+                tags.data_ptr() if tags is not None else None, gap, exclude.data_ptr() if exclude is not None else None,
+                order.data_ptr(), dist2.data_ptr(), C.c_void_p(cur.cuda_stream))
+        if ctx is None:
+            check(lib.bl_amd_desc_chain_device(*args), "bl_amd_desc_chain_device")
+        else:
+            check(lib.bl_amd_ctx_desc_chain_device(ctx.handle, *args), "bl_amd_ctx_desc_chain_device")
+        if s is not None:
+            sd.record_stream(cur)   # the uploaded seeds are freed when this returns
+    return order, dist2
 
 
 def distance(dist2):

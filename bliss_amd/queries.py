@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._args import int_in, vecs_shape_check
+from ._args import int_in, seeds_array, vecs_shape_check
 from ._lib import check, libc_free
 
 _FV, _I32, _F32 = C.POINTER(_lib.ForceVector), C.POINTER(C.c_int32), C.POINTER(C.c_float)
@@ -158,17 +158,7 @@ def _chain_check(seeds, length, metric, shape, n_limit):
     m = _metric_check(metric, shape)
     if hasattr(seeds, "is_cuda"):   # a torch tensor: _device_seeds_check checks it
         return m, None
-    s = np.asarray(seeds)
-    if s.dtype == np.bool_ or not np.issubdtype(s.dtype, np.integer):
-        raise ValueError(f"seeds must be integers, got dtype {s.dtype}")
-    if s.ndim > 1 or s.size < 1:
-        raise ValueError(f"seeds must be a scalar or a non-empty 1-D sequence, got shape {s.shape}")
-    s = s.reshape(-1)
-    if n_limit is not None and (s.min() < 0 or s.max() >= n_limit):
-        raise ValueError(f"seeds must lie in [0, {n_limit})")
-    if s.min() < -2 ** 31 or s.max() >= 2 ** 31:
-        raise ValueError("seeds do not fit 32 bits")
-    return m, np.ascontiguousarray(s, dtype=np.int32)
+    return m, seeds_array(seeds, n_limit)
 
 
 def _device_seeds_check(d_seeds, d_vecs):

@@ -857,6 +857,50 @@ int bl_amd_desc_knn_host(const bl_amd_desc *h_queries, int n_queries, const bl_a
                          int32_t *h_index, uint64_t *h_dist2);
 size_t bl_amd_desc_knn_scratch_bytes(int n, int n_rows, int k);
 
+/* Playlist chains over descriptors (continuous play in which every feature counts): bl_amd_mix_device's contract with
+ * descriptors in place of force vectors and the exact integer d2 of the section above in place of the f32 metric.
+ * With no rules (index seeds, d_tags and d_exclude NULL, gap 0) it is the plain chain: slot t + 1 is the song nearest to
+ * the song of slot t among those the chain has not played.
+ *   Outputs   d_order and d_dist2 are [n_chains][length], row-major.
+ *   Nearest   the smallest (d2, index): the descriptor kNN's order.
+ *   Needs     1 <= n < 2^27, n_chains >= 1, length >= 1; the entries of every descriptor as the kNN needs them
+ *             (|q| <= BL_AMD_DESC_SCALE_MAX, which the quantiser guarantees).
+ *   Seeds     exactly one of d_seeds and d_seed_desc is non-NULL.  d_seeds: slot 0 is the seed with d2 = 0, even if the
+ *             seed is excluded; a seed outside [0, n) gives a row of -1 / 2^64 - 1 from the device forms, and the host
+ *             form checks the seeds first and refuses the call.  d_seed_desc: n_chains descriptors, which may alias
+ *             d_lib; slot 0 is the nearest song among those not excluded (tags play no part), its value
+ *             d2(seed, lib[pick]), so a seed equal to library song 7 picks song 7 at 0 (or an equal song of a smaller
+ *             index); if every song is excluded the row is -1 / 2^64 - 1.
+ *   Exclude   d_exclude is NULL or n bytes, one mask for all chains: a song with a non-zero byte is never picked.
+ *   Tags      d_tags is NULL or n int32 (artist, album ...); a negative tag means untagged: never blocked, blocks
+ *             nothing.  0 <= gap <= BL_AMD_MIX_MAX_GAP; gap == 0 ignores the tags, gap > 0 needs them.
+ *   A step    at slot t >= 1 song j is allowed iff it is in none of the slots 0 .. t-1, d_exclude[j] == 0, and
+ *             tags[j] < 0 or tags[j] differs from the tag of every song in slots max(0, t-gap) .. t-1.  Slot t is the
+ *             allowed song nearest to the song of slot t-1, its value that d2.  If no song is allowed the chain ends:
+ *             slots t .. length-1 hold -1 / 2^64 - 1, as do the slots past n when length > n.
+ *   Chains    are independent: a chain's row depends neither on n_chains, on the other seeds, nor on the launch shape.
+ *   Shape     bl_amd_desc_chain_shape(n, n_chains) is the shape a call takes on the calling thread's device:
+ *             BL_AMD_CHAIN_PER_CHAIN (one workgroup per 16 chains) or BL_AMD_CHAIN_SPLIT (columns split over
+ *             workgroups, one launch per step); BL_UNEXPECTED without a device or for n, n_chains the call would
+ *             reject.  bl_amd_chain_force_shape pins the shape for these calls too; what it does for
+ *             bl_amd_chain_* and bl_amd_mix_* is unchanged.
+ * A rejected call (a NULL d_lib, d_order or d_dist2, both seeds or neither, n, n_chains, length or gap outside their
+ * ranges, gap > 0 without tags) returns BL_UNEXPECTED before any device work and writes nothing.  Asynchronous on
+ * `stream`; no allocation, copy or synchronisation inside once the context's workspace is large enough; calls of one
+ * context are ordered on the device like its batches.  To continue a chain call again with seed = its last song and
+ * d_exclude = everything played so far.
+ *   bl_amd_desc_chain_host: host pointers, blocking; h_dist2 may be NULL. */
+int bl_amd_desc_chain_device(const bl_amd_desc *d_lib, int n, const int32_t *d_seeds, const bl_amd_desc *d_seed_desc,
+                             int n_chains, int length, const int32_t *d_tags, int gap, const uint8_t *d_exclude,
+                             int32_t *d_order, uint64_t *d_dist2, void *stream);
+int bl_amd_ctx_desc_chain_device(bl_amd_ctx *ctx, const bl_amd_desc *d_lib, int n, const int32_t *d_seeds,
+                                 const bl_amd_desc *d_seed_desc, int n_chains, int length, const int32_t *d_tags,
+                                 int gap, const uint8_t *d_exclude, int32_t *d_order, uint64_t *d_dist2, void *stream);
+int bl_amd_desc_chain_host(const bl_amd_desc *h_lib, int n, const int32_t *h_seeds, const bl_amd_desc *h_seed_desc,
+                           int n_chains, int length, const int32_t *h_tags, int gap, const uint8_t *h_exclude,
+                           int32_t *h_order, uint64_t *h_dist2);
+int bl_amd_desc_chain_shape(int n, int n_chains);
+
 /* Integer-only synthetic PCM (the benchmark corpus of BASELINE.json),
  * generated in place on the device: song i = seed_base + i, written at
  * h_desc[i].pcm_offset.  Byte-identical to oracle/orc_synth.c. */
