@@ -20,6 +20,7 @@ BL_AMD_MIX_MAX_GAP = 16  # include/bliss_amd.h
 BL_AMD_PART_SPECTRUM, BL_AMD_PART_SUMS, BL_AMD_PART_HIST = 1, 2, 4  # include/bliss_amd.h
 BL_AMD_DESC_DIMS, BL_AMD_DESC_SCALE_MAX = 32, 32512  # include/bliss_amd.h
 BL_AMD_MEL_BANDS, BL_AMD_MEL_COEFFS = 32, 13  # include/bliss_amd.h
+BL_AMD_HMIX_KEY, BL_AMD_HMIX_TEMPO, BL_AMD_HMIX_HALF_DOUBLE = 1, 2, 4  # include/bliss_amd.h
 
 
 class ForceVector(C.Structure):  # ref include/bliss.h:26-31
@@ -108,6 +109,14 @@ class Desc(C.Structure):  # include/bliss_amd.h bl_amd_desc
 
 class DescRange(C.Structure):  # include/bliss_amd.h bl_amd_desc_range
     _fields_ = [("lo", C.c_float * 32), ("hi", C.c_float * 32), ("n_finite", C.c_uint32 * 32)]
+
+
+class HmixAttr(C.Structure):  # include/bliss_amd.h bl_amd_hmix_attr
+    _fields_ = [("tempo", C.c_uint16), ("key", C.c_uint8), ("reserved", C.c_uint8)]
+
+
+class HmixRule(C.Structure):  # include/bliss_amd.h bl_amd_hmix_rule
+    _fields_ = [("key_ok", C.c_uint32 * 24), ("tempo_tol", C.c_uint32), ("flags", C.c_uint32)]
 
 
 class Shard(C.Structure):  # include/bliss_amd.h bl_amd_shard
@@ -295,6 +304,15 @@ SYMBOLS = {
     "bl_amd_desc_chain_host": (C.c_int, [_P(Desc), C.c_int, _P(C.c_int32), _P(Desc), C.c_int, C.c_int, _P(C.c_int32),
                                          C.c_int, _P(C.c_uint8), _P(C.c_int32), _P(C.c_uint64)]),
     "bl_amd_desc_chain_shape": (C.c_int, [C.c_int, C.c_int]),
+    "bl_amd_desc_hmix_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _P(HmixRule), C.c_void_p, C.c_void_p, C.c_int,
+                                          C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bl_amd_ctx_desc_hmix_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, _P(HmixRule), C.c_void_p,
+                                              C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p]),
+    "bl_amd_desc_hmix_host": (C.c_int, [_P(Desc), _P(HmixAttr), C.c_int, _P(HmixRule), _P(C.c_int32), _P(Desc), C.c_int,
+                                        C.c_int, _P(C.c_int32), C.c_int, _P(C.c_uint8), _P(C.c_int32), _P(C.c_uint64)]),
+    "bl_amd_hmix_rule_camelot": (C.c_int, [_P(HmixRule), C.c_int, C.c_int]),
+    "bl_amd_hmix_attrs": (C.c_int, [_P(SongRhythm), _P(SongChroma), C.c_int, C.c_int, _P(HmixAttr)]),
     "bl_amd_synth_pcm_device": (C.c_int, [C.c_void_p, _P(SongDesc), C.c_int, C.c_uint32, C.c_uint32, C.c_void_p]),
     "bl_amd_set_fir_mode": (C.c_int, [C.c_int]),
     "bl_amd_fir_mode": (C.c_int, []),

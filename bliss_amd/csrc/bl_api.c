@@ -307,6 +307,46 @@ double bl_amd_rhythm_strength(const bl_amd_song_rhythm *r) {
   return r->r0 ? (double)r->r_lag / (double)r->r0 : 0.0;
 }
 
+/* ---- harmonic mixes: the host arithmetic of bl_amd_hmix_* (include/bliss_amd.h) ---- */
+
+static int hmix_rule_args_ok(int tempo_tol, int flags) {
+  const int all = BL_AMD_HMIX_KEY | BL_AMD_HMIX_TEMPO | BL_AMD_HMIX_HALF_DOUBLE;
+  return tempo_tol >= 0 && tempo_tol <= 1000 && !(flags & ~all) &&
+         (!(flags & BL_AMD_HMIX_HALF_DOUBLE) || (flags & BL_AMD_HMIX_TEMPO));
+}
+
+/* the wheel: the same key, a fifth up, a fifth down, and the relative key of the other mode */
+int bl_amd_hmix_rule_camelot(bl_amd_hmix_rule *out, int tempo_tol, int flags) {
+  if (!out || !hmix_rule_args_ok(tempo_tol, flags)) return BL_UNEXPECTED;
+  for (int k = 0; k < 12; ++k) {
+    const int up = (k + 7) % 12, down = (k + 5) % 12;
+    out->key_ok[k] = (1u << k) | (1u << up) | (1u << down) | (1u << (12 + (k + 9) % 12));
+    out->key_ok[12 + k] = (1u << (12 + k)) | (1u << (12 + up)) | (1u << (12 + down)) | (1u << ((k + 3) % 12));
+  }
+  out->tempo_tol = (uint32_t)tempo_tol;
+  out->flags = (uint32_t)flags;
+  return BL_OK;
+}
+
+int bl_amd_hmix_attrs(const bl_amd_song_rhythm *rhythm, const bl_amd_song_chroma *chroma, int n, int rate,
+                      bl_amd_hmix_attr *out) {
+  if (!out || n < 1) return BL_UNEXPECTED;
+  for (int i = 0; i < n; ++i) {
+    const double bpm = rhythm ? bl_amd_rhythm_bpm(&rhythm[i], rate) : NAN;
+    long long t = 0;
+    if (!isnan(bpm)) {
+      const double x = 100.0 * bpm;
+      t = x >= 65535.0 ? 65535 : llrint(x);
+      if (t < 1) t = 1;
+    }
+    const int key = chroma ? chroma[i].key : -1;
+    out[i].tempo = (uint16_t)t;
+    out[i].key = key >= 0 && key <= 23 ? (uint8_t)key : 255;
+    out[i].reserved = 0;
+  }
+  return BL_OK;
+}
+
 /* ---- chroma and key: the host side of bl_amd_song_chroma (include/bliss_amd.h) ---- */
 
 /* T = 0 below one frame, else (Fr - 4096) / 2048 + 1 */

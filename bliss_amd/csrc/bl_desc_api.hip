@@ -1,6 +1,6 @@
 /*
  * bl_desc_api.hip — the C-ABI of include/bliss_amd.h over descriptors (bl_amd_desc_*): range, quantiser, the exact
- * nearest neighbours and the playlist chains.  Host code only, built like bl_query_api.hip: one static body per call holds the argument check,
+ * nearest neighbours, the playlist chains and the harmonic mixes.  Host code only, built like bl_query_api.hip: one static body per call holds the argument check,
  * the workspace choice and the blk_ call; contexts, query_call, call_ctx, DevGuard and DevMem come from bl_runtime.h, the
  * kernels from bl_launch.h.  Every argument is checked before any device work and before the default context is
  * fetched, so a rejected call leaves the outputs untouched.  The workspace is the context's `desc` block, handed from
@@ -79,6 +79,29 @@ static int chain_device(bl_amd_ctx *c, bool dflt, const bl_amd_desc *d_lib, int 
                     [&](hipStream_t s, void *scratch) {
                       return blk_desc_chain(s, d_lib, n, d_seeds, d_seed_desc, n_chains, length, d_tags, gap, d_exclude,
                                             c->n_cu, force, scratch, d_order, d_dist2);
+                    });
+}
+
+/* Harmonic mixes: the chain's checks and the rule's.  The rule is copied here, into the launch's arguments. */
+static bool hmix_rule_ok(const bl_amd_hmix_rule *rule, const void *attr) {
+  const uint32_t all = BL_AMD_HMIX_KEY | BL_AMD_HMIX_TEMPO | BL_AMD_HMIX_HALF_DOUBLE;
+  return rule && !(rule->flags & ~all) && (!(rule->flags & BL_AMD_HMIX_HALF_DOUBLE) || (rule->flags & BL_AMD_HMIX_TEMPO)) &&
+         rule->tempo_tol <= 1000u && (!(rule->flags & (BL_AMD_HMIX_KEY | BL_AMD_HMIX_TEMPO)) || attr);
+}
+
+static int hmix_device(bl_amd_ctx *c, bool dflt, const bl_amd_desc *d_lib, const bl_amd_hmix_attr *d_attr, int n,
+                       const bl_amd_hmix_rule *rule, const int32_t *d_seeds, const bl_amd_desc *d_seed_desc,
+                       int n_chains, int length, const int32_t *d_tags, int gap, const uint8_t *d_exclude,
+                       int32_t *d_order, uint64_t *d_dist2, void *stream) {
+  if (!chain_args_ok(d_lib, n, d_seeds, d_seed_desc, n_chains, length, d_tags, gap, d_order, d_dist2) ||
+      !hmix_rule_ok(rule, d_attr) || !(c = call_ctx(c, dflt)))
+    return BL_UNEXPECTED;
+  const int force = blr_chain_force();
+  const bl_amd_hmix_rule r = *rule;
+  return query_call(c, stream, c->desc, blk_desc_hmix_scratch_bytes(n, n_chains, r, c->n_cu, force),
+                    [&](hipStream_t s, void *scratch) {
+                      return blk_desc_hmix(s, d_lib, d_attr, n, r, d_seeds, d_seed_desc, n_chains, length, d_tags, gap,
+                                           d_exclude, c->n_cu, force, scratch, d_order, d_dist2);
                     });
 }
 
@@ -195,6 +218,54 @@ int bl_amd_desc_chain_host(const bl_amd_desc *h_lib, int n, const int32_t *h_see
                  chain_device(nullptr, true, dl.as<bl_amd_desc>(), n, ds.as<int32_t>(), dq.as<bl_amd_desc>(), n_chains,
                               length, dt.as<int32_t>(), gap, dx.as<uint8_t>(), di.as<int32_t>(), dd.as<uint64_t>(),
                               nullptr) == BL_OK &&
+                 di.down(h_order) && (!h_dist2 || dd.down(h_dist2))
+             ? BL_OK
+             : BL_UNEXPECTED;
+}
+
+int bl_amd_desc_hmix_device(const bl_amd_desc *d_lib, const bl_amd_hmix_attr *d_attr, int n,
+                            const bl_amd_hmix_rule *rule, const int32_t *d_seeds, const bl_amd_desc *d_seed_desc,
+                            int n_chains, int length, const int32_t *d_tags, int gap, const uint8_t *d_exclude,
+                            int32_t *d_order, uint64_t *d_dist2, void *stream) {
+  return hmix_device(nullptr, true, d_lib, d_attr, n, rule, d_seeds, d_seed_desc, n_chains, length, d_tags, gap,
+                     d_exclude, d_order, d_dist2, stream);
+}
+
+int bl_amd_ctx_desc_hmix_device(bl_amd_ctx *ctx, const bl_amd_desc *d_lib, const bl_amd_hmix_attr *d_attr, int n,
+                                const bl_amd_hmix_rule *rule, const int32_t *d_seeds, const bl_amd_desc *d_seed_desc,
+                                int n_chains, int length, const int32_t *d_tags, int gap, const uint8_t *d_exclude,
+                                int32_t *d_order, uint64_t *d_dist2, void *stream) {
+  return hmix_device(ctx, false, d_lib, d_attr, n, rule, d_seeds, d_seed_desc, n_chains, length, d_tags, gap, d_exclude,
+                     d_order, d_dist2, stream);
+}
+
+int bl_amd_desc_hmix_host(const bl_amd_desc *h_lib, const bl_amd_hmix_attr *h_attr, int n, const bl_amd_hmix_rule *rule,
+                          const int32_t *h_seeds, const bl_amd_desc *h_seed_desc, int n_chains, int length,
+                          const int32_t *h_tags, int gap, const uint8_t *h_exclude, int32_t *h_order,
+                          uint64_t *h_dist2) {
+  if (!chain_args_ok(h_lib, n, h_seeds, h_seed_desc, n_chains, length, h_tags, gap, h_order,
+                     h_order /* h_dist2 may be NULL */) ||
+      !hmix_rule_ok(rule, h_attr))
+    return BL_UNEXPECTED;
+  for (int c = 0; h_seeds && c < n_chains; ++c)
+    if (h_seeds[c] < 0 || h_seeds[c] >= n) return BL_UNEXPECTED;
+  bl_amd_ctx *c = blr_default_ctx();
+  if (!c) return BL_UNEXPECTED;
+  DevGuard dg(c->device);
+  if (!dg.ok) return BL_UNEXPECTED;
+  const bool use_tags = gap > 0, use_attr = rule->flags & (BL_AMD_HMIX_KEY | BL_AMD_HMIX_TEMPO);
+  const size_t out = (size_t)n_chains * length;
+  DevMem dl(sizeof(bl_amd_desc) * (size_t)n), ds(h_seeds ? sizeof(int32_t) * (size_t)n_chains : 0);
+  DevMem dq(h_seed_desc ? sizeof(bl_amd_desc) * (size_t)n_chains : 0);
+  DevMem da(use_attr ? sizeof(bl_amd_hmix_attr) * (size_t)n : 0);
+  DevMem dt(use_tags ? sizeof(int32_t) * (size_t)n : 0), dx(h_exclude ? (size_t)n : 0);
+  DevMem di(sizeof(int32_t) * out), dd(sizeof(uint64_t) * out);
+  return dl.up(h_lib) && (!h_seeds || ds.up(h_seeds)) && (!h_seed_desc || dq.up(h_seed_desc)) &&
+                 (!use_attr || da.up(h_attr)) && (!use_tags || dt.up(h_tags)) && (!h_exclude || dx.up(h_exclude)) &&
+                 di.ok() && dd.ok() &&
+                 hmix_device(nullptr, true, dl.as<bl_amd_desc>(), da.as<bl_amd_hmix_attr>(), n, rule, ds.as<int32_t>(),
+                             dq.as<bl_amd_desc>(), n_chains, length, dt.as<int32_t>(), gap, dx.as<uint8_t>(),
+                             di.as<int32_t>(), dd.as<uint64_t>(), nullptr) == BL_OK &&
                  di.down(h_order) && (!h_dist2 || dd.down(h_dist2))
              ? BL_OK
              : BL_UNEXPECTED;

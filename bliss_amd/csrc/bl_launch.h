@@ -371,6 +371,16 @@ int blk_desc_chain(hipStream_t s, const bl_amd_desc *d_lib, int n, const int32_t
                    const bl_amd_desc *d_seed_desc, int n_chains, int length, const int32_t *d_tags, int gap,
                    const uint8_t *d_exclude, int n_cu, int force, void *d_scratch, int32_t *d_order,
                    uint64_t *d_dist2);
+/* bl_amd_desc_hmix_device: blk_desc_chain under a rule on consecutive songs, the PAIR variant of the same kernels.
+ * rule: checked by the caller (flags, tempo_tol) and passed to the kernels by value; d_attr: n attributes, nullptr
+ * allowed when the rule has neither BL_AMD_HMIX_KEY nor BL_AMD_HMIX_TEMPO, and then the call is blk_desc_chain.  The
+ * shape is blk_desc_chain_shape's; the workspace is its own figure, since the rule's state takes LDS from the played
+ * words of the per-chain shape. */
+size_t blk_desc_hmix_scratch_bytes(int n, int n_chains, const bl_amd_hmix_rule &rule, int n_cu, int force);
+int blk_desc_hmix(hipStream_t s, const bl_amd_desc *d_lib, const bl_amd_hmix_attr *d_attr, int n,
+                  const bl_amd_hmix_rule &rule, const int32_t *d_seeds, const bl_amd_desc *d_seed_desc, int n_chains,
+                  int length, const int32_t *d_tags, int gap, const uint8_t *d_exclude, int n_cu, int force,
+                  void *d_scratch, int32_t *d_order, uint64_t *d_dist2);
 
 /* ---- device rate converter (bl_rs_kernels.hip) ------------------------------ */
 

@@ -8,6 +8,8 @@ library's own minimum and maximum, and the squared Euclidean distance of two des
     q = quantize(x_new, rng)                # songs from outside, with the library's range
     index, dist2 = knn(desc, 10, queries=q)
     order, dist2 = chain(desc, seeds, 50, tags=artists, gap=3)   # playlists: no artist twice within 3 slots
+    attrs, rule = hmix_attrs(rhythm=rh, chroma=ch), camelot_rule(60, half_double=True)
+    order, dist2 = hmix(desc, attrs, rule, seeds, 50)            # harmonic mixes: compatible key, tempo within 6 %
 
 This module is imported explicitly (`import bliss_amd.descriptor`): the package's own namespace is unchanged."""
 import ctypes as C
@@ -25,9 +27,12 @@ MAX_N = 1 << 27          # a kNN library stays below it: the index bits of a key
 EMPTY_DIST2 = 2 ** 64 - 1  # d2 of an empty slot (index -1)
 DESC_DTYPE = np.dtype(_lib.Desc)            # one field q: int16 (32,)
 RANGE_DTYPE = np.dtype(_lib.DescRange)      # lo, hi float32 (32,), n_finite uint32 (32,)
+HMIX_ATTR_DTYPE = np.dtype(_lib.HmixAttr)   # tempo uint16 (1/100 BPM, 0 unknown), key uint8 (>= 24 unknown), reserved
+HMIX_RULE_DTYPE = np.dtype(_lib.HmixRule)   # key_ok uint32 (24,), tempo_tol uint32, flags uint32
 
 _I32, _U64 = C.POINTER(C.c_int32), C.POINTER(C.c_uint64)
 _F32, _DESC, _RANGE = C.POINTER(C.c_float), C.POINTER(_lib.Desc), C.POINTER(_lib.DescRange)
+_ATTR, _RULE = C.POINTER(_lib.HmixAttr), C.POINTER(_lib.HmixRule)
 
 
 def _desc_array(name, desc):
@@ -179,6 +184,32 @@ def _chain_ints(length, gap, tags):
     return length, gap
 
 
+def _hmix_args(attrs, rule, n, device=None):
+    """(attrs or None, the rule as a one-record array) of a hmix call after its checks: a rule that applies a test needs
+    n attributes, as an array of HMIX_ATTR_DTYPE (device None) or a uint8 (n, 4) / int32 (n,) tensor on `device`"""
+    r = np.ascontiguousarray(rule)
+    if r.dtype != HMIX_RULE_DTYPE or r.size != 1:
+        raise ValueError("rule must be one bl_amd_hmix_rule record, as camelot_rule() returns it")
+    r = r.reshape(1).copy()
+    flags, tol = int(r["flags"][0]), int(r["tempo_tol"][0])
+    if flags & ~7 or (flags & _lib.BL_AMD_HMIX_HALF_DOUBLE and not flags & _lib.BL_AMD_HMIX_TEMPO) or tol > 1000:
+        raise ValueError(f"rule has flags {flags} and tempo_tol {tol}: flags are KEY | TEMPO | HALF_DOUBLE (the last only "
+                         "with TEMPO) and tempo_tol is 0 .. 1000 per mille")
+    if attrs is None:
+        if flags & (_lib.BL_AMD_HMIX_KEY | _lib.BL_AMD_HMIX_TEMPO):
+            raise ValueError("a rule that applies a test needs attrs")
+    elif device is None:
+        attrs = np.ascontiguousarray(attrs)
+        if attrs.dtype != HMIX_ATTR_DTYPE or attrs.shape != (n,):
+            raise ValueError(f"attrs must be {n} bl_amd_hmix_attr records (hmix_attrs), got {attrs.dtype} {attrs.shape}")
+    else:
+        import torch
+        if not isinstance(attrs, torch.Tensor) or not attrs.is_contiguous() or attrs.device != device or \
+                (attrs.dtype, tuple(attrs.shape)) not in ((torch.uint8, (n, 4)), (torch.int32, (n,))):
+            raise ValueError(f"attrs must be a contiguous uint8 ({n}, 4) or int32 ({n},) tensor on the device of d_desc")
+    return attrs, r
+
+
 def chain(desc, seeds, length, tags=None, gap=0, exclude=None, seed_desc=None):
     """Playlist chains over descriptors (bl_amd_desc_chain_host), one per seed: slot 0 is the seed and every next slot
     the allowed song nearest to the previous one by (dist2, index).  A song is allowed if the chain has not played it,
@@ -189,6 +220,23 @@ def chain(desc, seeds, length, tags=None, gap=0, exclude=None, seed_desc=None):
     exact squared distance between the songs of slots t - 1 and t (slot 0: 0, or the seed descriptor's to its pick).  A
     chain with no allowed song left ends: the rest of its row, like the slots past n, holds -1 and 2^64 - 1.  To continue
     a chain, call again with seed = its last song and exclude = everything played so far."""
+    return _chain_host(desc, seeds, length, tags, gap, exclude, seed_desc, None)
+
+
+def hmix(desc, attrs, rule, seeds, length, tags=None, gap=0, exclude=None, seed_desc=None):
+    """Harmonic mixes (bl_amd_desc_hmix_host): chain() with one more, hard, rule on consecutive songs.  attrs: n records
+    of HMIX_ATTR_DTYPE (hmix_attrs()); rule: one record of HMIX_RULE_DTYPE (camelot_rule(), or a table of your own: bit b
+    of key_ok[a] lets key b follow key a).  From slot 1 on a song is allowed only if chain() allows it and it passes
+    against the song of the slot before: its key may follow that song's key (unknown keys pass), and its tempo is
+    within tempo_tol per mille of that song's tempo, or of half or double of it with HALF_DOUBLE (unknown tempos
+    pass).  Slot 0 is chain()'s; an index seed's attribute binds slot 1.  A chain with no allowed song ends; to go on
+    without the rule, continue with chain() from its last song.  A rule with neither KEY nor TEMPO takes attrs=None and
+    gives chain()'s arrays."""
+    return _chain_host(desc, seeds, length, tags, gap, exclude, seed_desc, (attrs, rule))
+
+
+def _chain_host(desc, seeds, length, tags, gap, exclude, seed_desc, pair):
+    """chain() (pair None) and hmix() (pair = (attrs, rule))"""
     lib = _desc_array("desc", desc)
     _chain_seeds_check(seeds, seed_desc)
     length, gap = _chain_ints(length, gap, tags)
@@ -216,12 +264,16 @@ def chain(desc, seeds, length, tags=None, gap=0, exclude=None, seed_desc=None):
         ex = np.ascontiguousarray(ex).view(np.uint8)
     n_chains = q.shape[0] if q is not None else s.size
     order, dist2 = np.empty((n_chains, length), dtype=np.int32), np.empty((n_chains, length), dtype=np.uint64)
-    check(_lib.load().bl_amd_desc_chain_host(
-        lib.ctypes.data_as(_DESC), n, s.ctypes.data_as(_I32) if s is not None else None,
-        q.ctypes.data_as(_DESC) if q is not None else None, n_chains, length,
-        tg.ctypes.data_as(_I32) if tg is not None else None, gap,
-        ex.ctypes.data_as(C.POINTER(C.c_uint8)) if ex is not None else None, order.ctypes.data_as(_I32),
-        dist2.ctypes.data_as(_U64)), "bl_amd_desc_chain_host")
+    args = (s.ctypes.data_as(_I32) if s is not None else None, q.ctypes.data_as(_DESC) if q is not None else None,
+            n_chains, length, tg.ctypes.data_as(_I32) if tg is not None else None, gap,
+            ex.ctypes.data_as(C.POINTER(C.c_uint8)) if ex is not None else None, order.ctypes.data_as(_I32),
+            dist2.ctypes.data_as(_U64))
+    if pair is None:
+        check(_lib.load().bl_amd_desc_chain_host(lib.ctypes.data_as(_DESC), n, *args), "bl_amd_desc_chain_host")
+    else:
+        at, r = _hmix_args(*pair, n)
+        check(_lib.load().bl_amd_desc_hmix_host(lib.ctypes.data_as(_DESC), at.ctypes.data_as(_ATTR) if at is not None else None,
+                                                n, r.ctypes.data_as(_RULE), *args), "bl_amd_desc_hmix_host")
     return order, dist2
 
 
@@ -232,6 +284,20 @@ def chain_device(d_desc, d_seeds, length, tags=None, gap=0, exclude=None, seed_d
     contiguous and on d_desc's device.  A seed outside [0, n) gives a row of -1.  Returns (order int32, dist2 as int64
     bits of the uint64: an empty slot reads -1) CUDA tensors of shape (n_chains, length), asynchronously on `stream`
     (default: the current stream of that device).  ctx: an explicit Context."""
+    return _chain_device(d_desc, d_seeds, length, tags, gap, exclude, seed_desc, stream, ctx, None)
+
+
+def hmix_device(d_desc, d_attrs, rule, d_seeds, length, tags=None, gap=0, exclude=None, seed_desc=None, stream=None,
+                ctx=None):
+    """hmix() on torch tensors (bl_amd_desc_hmix_device), the other arguments as chain_device() takes them.  d_attrs: the
+    n attributes as a contiguous uint8 (n, 4) or int32 (n,) CUDA tensor on d_desc's device, the bytes of hmix_attrs()
+    (torch.from_numpy(attrs.view(np.uint8).reshape(n, 4)).cuda()), or None with a rule that applies no test; rule: one
+    record of HMIX_RULE_DTYPE in host memory, copied before the call returns."""
+    return _chain_device(d_desc, d_seeds, length, tags, gap, exclude, seed_desc, stream, ctx, (d_attrs, rule))
+
+
+def _chain_device(d_desc, d_seeds, length, tags, gap, exclude, seed_desc, stream, ctx, pair):
+    """chain_device() (pair None) and hmix_device() (pair = (d_attrs, rule))"""
     import torch
     _chain_seeds_check(d_seeds, seed_desc)
     length, gap = _chain_ints(length, gap, tags)
@@ -256,6 +322,11 @@ def chain_device(d_desc, d_seeds, length, tags=None, gap=0, exclude=None, seed_d
                     ("tags", tags), ("exclude", exclude)):
         if t is not None and (not t.is_cuda or t.device != d_desc.device or not t.is_contiguous()):
             raise ValueError(f"{name} must be a contiguous tensor on the device of d_desc")
+    name, head = "desc_chain_device", (d_desc.data_ptr(), n)
+    if pair is not None:
+        d_attrs, r = _hmix_args(*pair, n, d_desc.device)
+        name = "desc_hmix_device"
+        head = (d_desc.data_ptr(), d_attrs.data_ptr() if d_attrs is not None else None, n, r.ctypes.data_as(_RULE))
     lib = _lib.load()
     with _on_device(lib, d_desc, stream) as cur, torch.cuda.stream(cur):
         sd = None
@@ -266,17 +337,53 @@ def chain_device(d_desc, d_seeds, length, tags=None, gap=0, exclude=None, seed_d
         n_chains = sd.numel() if sd is not None else seed_desc.shape[0]
         order = torch.empty((n_chains, length), dtype=torch.int32, device=d_desc.device)
         dist2 = torch.empty((n_chains, length), dtype=torch.int64, device=d_desc.device)
-        args = (d_desc.data_ptr(), n, sd.data_ptr() if sd is not None else None,
+        args = (*head, sd.data_ptr() if sd is not None else None,
                 seed_desc.data_ptr() if seed_desc is not None else None, n_chains, length,
                 tags.data_ptr() if tags is not None else None, gap, exclude.data_ptr() if exclude is not None else None,
                 order.data_ptr(), dist2.data_ptr(), C.c_void_p(cur.cuda_stream))
         if ctx is None:
-            check(lib.bl_amd_desc_chain_device(*args), "bl_amd_desc_chain_device")
+            check(getattr(lib, "bl_amd_" + name)(*args), "bl_amd_" + name)
         else:
-            check(lib.bl_amd_ctx_desc_chain_device(ctx.handle, *args), "bl_amd_ctx_desc_chain_device")
+            check(getattr(lib, "bl_amd_ctx_" + name)(ctx.handle, *args), "bl_amd_ctx_" + name)
         if s is not None:
             sd.record_stream(cur)   # the uploaded seeds are freed when this returns
     return order, dist2
+
+
+def hmix_attrs(rhythm=None, chroma=None, rate=22050):
+    """The attributes of n songs for hmix() from their analysis records (bl_amd_hmix_attrs): a structured array of
+    HMIX_ATTR_DTYPE.  rhythm: records of rhythm_to_numpy, tempo = round(100 * BPM) clamped to 1 .. 65535, 0 without a
+    tempo; chroma: records of chroma_to_numpy, key as they hold it, 255 for key -1.  A group that is not passed is
+    unknown for every song; at least one must be passed, and both must have the same length."""
+    if rhythm is None and chroma is None:
+        raise ValueError("at least one of rhythm and chroma must be given")
+    first = np.asarray(rhythm if rhythm is not None else chroma)
+    if first.ndim != 1 or first.size < 1:
+        raise ValueError("the records must be a non-empty 1-D array")
+    n = first.size
+    rh = None if rhythm is None else _records("rhythm", rhythm, RHYTHM_DTYPE, n)
+    ch = None if chroma is None else _records("chroma", chroma, CHROMA_DTYPE, n)
+    out = np.zeros(n, dtype=HMIX_ATTR_DTYPE)
+    check(_lib.load().bl_amd_hmix_attrs(
+        rh.ctypes.data_as(C.POINTER(_lib.SongRhythm)) if rh is not None else None,
+        ch.ctypes.data_as(C.POINTER(_lib.SongChroma)) if ch is not None else None, n, int_in("rate", rate, 1),
+        out.ctypes.data_as(_ATTR)), "bl_amd_hmix_attrs")
+    return out
+
+
+def camelot_rule(tempo_tol, half_double=False, key=True, tempo=True):
+    """The usual wheel as one record of HMIX_RULE_DTYPE (bl_amd_hmix_rule_camelot): after a key may follow the same key,
+    the keys a fifth above and below in the same mode, and the relative key of the other mode.  tempo_tol: per mille of
+    the previous song's tempo, 0 .. 1000; half_double: half and double time match too; key / tempo: whether that test
+    is applied at all."""
+    tempo_tol = int_in("tempo_tol", tempo_tol, 0, 1000)
+    if half_double and not tempo:
+        raise ValueError("half_double needs tempo")
+    flags = (_lib.BL_AMD_HMIX_KEY if key else 0) | (_lib.BL_AMD_HMIX_TEMPO if tempo else 0) | \
+        (_lib.BL_AMD_HMIX_HALF_DOUBLE if half_double else 0)
+    out = np.zeros(1, dtype=HMIX_RULE_DTYPE)
+    check(_lib.load().bl_amd_hmix_rule_camelot(out.ctypes.data_as(_RULE), tempo_tol, flags), "bl_amd_hmix_rule_camelot")
+    return out[0]
 
 
 def distance(dist2):

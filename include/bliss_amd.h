@@ -901,6 +901,77 @@ int bl_amd_desc_chain_host(const bl_amd_desc *h_lib, int n, const int32_t *h_see
                            int32_t *h_order, uint64_t *h_dist2);
 int bl_amd_desc_chain_shape(int n, int n_chains);
 
+/* Harmonic mixes (beat-matched crossfades, same or compatible key next): bl_amd_desc_chain_*'s contract, seeds, mask,
+ * tags and gap, nearest by (d2, index), outputs, sentinels, shapes and ordering on a context, plus one hard rule on
+ * consecutive songs, evaluated on a 4-byte attribute per song in exact integer arithmetic.
+ *   Attribute d_attr is n of bl_amd_hmix_attr: tempo in 1/100 BPM, 0 = unknown; key 0 .. 23 as bl_amd_song_chroma.key,
+ *             any value >= 24 = unknown; reserved is ignored.  bl_amd_hmix_attrs fills them from analysis records.
+ *   Rule      flags chooses the tests: BL_AMD_HMIX_KEY applies key_ok, BL_AMD_HMIX_TEMPO applies tempo_tol, and with
+ *             BL_AMD_HMIX_TEMPO, BL_AMD_HMIX_HALF_DOUBLE lets half and double time match as well.  Bit b of key_ok[a]:
+ *             a song of key b may follow a song of key a; bits 24 .. 31 are ignored.  The table is used as given and
+ *             need not be symmetric; no entry is ever indexed by a value >= 24.  tempo_tol is per mille of the
+ *             previous song's tempo, 0 .. 1000.  `rule` is host memory, copied before the call returns.
+ *   A step    at slot t >= 1 song j is allowed iff bl_amd_desc_chain_device allows it and the pair (p, j) passes, p
+ *             the song of slot t-1.  With (a, ka) the tempo and key of p and (b, kb) those of j:
+ *               key    (BL_AMD_HMIX_KEY) passes if ka >= 24, or kb >= 24, or bit kb of key_ok[ka] is set;
+ *               tempo  (BL_AMD_HMIX_TEMPO) passes if a == 0, or b == 0, or 1000 |b - a| <= tol a; with
+ *                      BL_AMD_HMIX_HALF_DOUBLE also if 1000 |2b - a| <= tol a or 1000 |b - 2a| <= 2 tol a.  All of
+ *                      these are integers below 2^28, and the tolerance is relative to the previous song, not to the
+ *                      candidate.
+ *             Slot t is the allowed song nearest to p, its value that d2.  If no song is allowed the chain ends as
+ *             bl_amd_desc_chain_device's does; there is no fall-back to a relaxed rule: the caller continues with a
+ *             plain chain from the last song (seed = that song, d_exclude = everything played so far).
+ *   Slot 0    is exactly bl_amd_desc_chain_device's and under no pair rule.  An index seed takes slot 0 whatever its
+ *             attribute, and its attribute then binds slot 1, even when the seed is excluded.  For a descriptor seed
+ *             neither tags nor the pair rule play a part in slot 0; the attribute of its pick binds slot 1.
+ *   Off       with neither BL_AMD_HMIX_KEY nor BL_AMD_HMIX_TEMPO in flags d_attr may be NULL and the outputs are byte
+ *             for byte those of bl_amd_desc_chain_device with the same remaining arguments; the same holds when every
+ *             attribute is unknown.
+ *   Shape     bl_amd_desc_chain_shape and bl_amd_chain_force_shape govern these calls as they govern
+ *             bl_amd_desc_chain_*; the result never depends on the shape.
+ * A rejected call (everything bl_amd_desc_chain_device rejects, a NULL rule, flag bits other than the three,
+ * BL_AMD_HMIX_HALF_DOUBLE without BL_AMD_HMIX_TEMPO, tempo_tol > 1000, BL_AMD_HMIX_KEY or BL_AMD_HMIX_TEMPO with a NULL
+ * d_attr) returns BL_UNEXPECTED before any device work and writes nothing.
+ *   bl_amd_desc_hmix_host: host pointers, blocking; h_dist2 may be NULL; the seeds are checked first as
+ *   bl_amd_desc_chain_host checks them.
+ *   bl_amd_hmix_rule_camelot: host arithmetic, the usual wheel with tempo_tol and flags as given.  After a major key of
+ *   tonic k (index k) may follow: major k, major (k+7)%12, major (k+5)%12 and the relative minor 12 + (k+9)%12; after
+ *   a minor key 12 + k: minor 12 + k, 12 + (k+7)%12, 12 + (k+5)%12 and the relative major (k+3)%12.  After C: C, G, F,
+ *   Am; after Am: Am, Em, Dm, C.  BL_UNEXPECTED, and nothing written, for a NULL out or for a tempo_tol or flags the
+ *   calls above would reject.
+ *   bl_amd_hmix_attrs: host arithmetic over n >= 1 records.  Either record array may be NULL, and that field is then
+ *   unknown for every song.  tempo = llrint(100 * bl_amd_rhythm_bpm(&rhythm[i], rate)) clamped to 1 .. 65535, and 0
+ *   where the BPM is NaN; key = the chroma key, 255 for key -1 (or any key outside 0 .. 23); reserved = 0. */
+typedef struct bl_amd_hmix_attr { /* 4 bytes per song */
+  uint16_t tempo;                 /* 1/100 BPM; 0 = unknown */
+  uint8_t key;                    /* 0 .. 23 as bl_amd_song_chroma.key; any value >= 24 = unknown */
+  uint8_t reserved;               /* ignored */
+} bl_amd_hmix_attr;
+
+#define BL_AMD_HMIX_KEY 1         /* apply key_ok */
+#define BL_AMD_HMIX_TEMPO 2       /* apply tempo_tol */
+#define BL_AMD_HMIX_HALF_DOUBLE 4 /* with TEMPO: half and double time also match */
+typedef struct bl_amd_hmix_rule { /* 104 bytes */
+  uint32_t key_ok[24];            /* bit b of key_ok[a]: a song of key b may follow a song of key a */
+  uint32_t tempo_tol;             /* per mille of the previous song's tempo, 0 .. 1000 */
+  uint32_t flags;
+} bl_amd_hmix_rule;
+int bl_amd_desc_hmix_device(const bl_amd_desc *d_lib, const bl_amd_hmix_attr *d_attr, int n,
+                            const bl_amd_hmix_rule *rule, const int32_t *d_seeds, const bl_amd_desc *d_seed_desc,
+                            int n_chains, int length, const int32_t *d_tags, int gap, const uint8_t *d_exclude,
+                            int32_t *d_order, uint64_t *d_dist2, void *stream);
+int bl_amd_ctx_desc_hmix_device(bl_amd_ctx *ctx, const bl_amd_desc *d_lib, const bl_amd_hmix_attr *d_attr, int n,
+                                const bl_amd_hmix_rule *rule, const int32_t *d_seeds, const bl_amd_desc *d_seed_desc,
+                                int n_chains, int length, const int32_t *d_tags, int gap, const uint8_t *d_exclude,
+                                int32_t *d_order, uint64_t *d_dist2, void *stream);
+int bl_amd_desc_hmix_host(const bl_amd_desc *h_lib, const bl_amd_hmix_attr *h_attr, int n, const bl_amd_hmix_rule *rule,
+                          const int32_t *h_seeds, const bl_amd_desc *h_seed_desc, int n_chains, int length,
+                          const int32_t *h_tags, int gap, const uint8_t *h_exclude, int32_t *h_order,
+                          uint64_t *h_dist2);
+int bl_amd_hmix_rule_camelot(bl_amd_hmix_rule *out, int tempo_tol, int flags);
+int bl_amd_hmix_attrs(const bl_amd_song_rhythm *rhythm, const bl_amd_song_chroma *chroma, int n, int rate,
+                      bl_amd_hmix_attr *out);
+
 /* Integer-only synthetic PCM (the benchmark corpus of BASELINE.json),
  * generated in place on the device: song i = seed_base + i, written at
  * h_desc[i].pcm_offset.  Byte-identical to oracle/orc_synth.c. */
