@@ -84,6 +84,11 @@ class SongRhythm(C.Structure):  # include/bliss_amd.h bl_amd_song_rhythm
                 ("terms", C.c_int32), ("lag", C.c_int32), ("lag_peak", C.c_int32), ("status", C.c_int32)]
 
 
+class SongBeats(C.Structure):  # include/bliss_amd.h bl_amd_song_beats
+    _fields_ = [("score", C.c_int64), ("pen_scale", C.c_uint64), ("hops", C.c_int32), ("period", C.c_int32),
+                ("n_beats", C.c_int32), ("first", C.c_int32), ("last", C.c_int32), ("status", C.c_int32)]
+
+
 class FrameChroma(C.Structure):  # include/bliss_amd.h bl_amd_frame_chroma
     _fields_ = [("x", C.c_uint64 * 12)]
 
@@ -262,6 +267,14 @@ SYMBOLS = {
     "bl_amd_rhythm_bpm": (C.c_double, [_P(SongRhythm), C.c_int]),
     "bl_amd_rhythm_strength": (C.c_double, [_P(SongRhythm)]),
     "bl_amd_selftest_isqrt": (C.c_int, [_P(C.c_uint64)]),
+    "bl_amd_beats_device": (C.c_int, [C.c_void_p, _P(C.c_int32), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bl_amd_ctx_beats_device": (C.c_int, [C.c_void_p, C.c_void_p, _P(C.c_int32), C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bl_amd_beats_host": (C.c_int, [_P(C.c_uint32), _P(C.c_int32), C.c_int, _P(C.c_int32), C.c_int, _P(SongBeats),
+                                    _P(C.c_uint8), _P(C.c_uint16), _P(C.c_int64)]),
+    "bl_amd_beats_list": (C.c_int, [_P(C.c_uint8), C.c_int, C.c_int, _P(C.c_int32), _P(C.c_double), C.c_int]),
+    "bl_amd_beats_bpm": (C.c_double, [_P(SongBeats), C.c_int]),
     "bl_amd_chroma_frames": (C.c_int, [C.c_int, C.c_int]),
     "bl_amd_chroma_batch_device": (C.c_int, [C.c_void_p, _P(SongDesc), C.c_int, C.c_void_p, C.c_void_p, C.c_longlong,
                                              C.c_void_p]),

@@ -307,6 +307,28 @@ double bl_amd_rhythm_strength(const bl_amd_song_rhythm *r) {
   return r->r0 ? (double)r->r_lag / (double)r->r0 : 0.0;
 }
 
+/* ---- beats: the host arithmetic over the flags and bl_amd_song_beats (include/bliss_amd.h) ---- */
+
+int bl_amd_beats_list(const uint8_t *h_flags, int hops, int rate, int32_t *h_hop_out, double *h_sec_out, int cap) {
+  if (!h_flags || hops < 0 || rate < 1 || cap < 0) return -1;
+  int count = 0;
+  for (int h = 0; h < hops; ++h) {
+    if (!h_flags[h]) continue;
+    if (count < cap) {
+      if (h_hop_out) h_hop_out[count] = h;
+      if (h_sec_out) h_sec_out[count] = (double)BL_AMD_RHYTHM_HOP * (double)h / (double)rate;
+    }
+    count += 1;
+  }
+  return count;
+}
+
+double bl_amd_beats_bpm(const bl_amd_song_beats *b, int rate) {
+  if (!b || rate < 1 || b->n_beats < 2 || b->last <= b->first) return NAN;
+  return 60.0 * (double)rate * (double)(b->n_beats - 1) /
+         ((double)BL_AMD_RHYTHM_HOP * (double)(b->last - b->first));
+}
+
 /* ---- harmonic mixes: the host arithmetic of bl_amd_hmix_* (include/bliss_amd.h) ---- */
 
 static int hmix_rule_args_ok(int tempo_tol, int flags) {

@@ -3,6 +3,7 @@
  * geometry: bl_kernels.hip the launch order of the per-song analysis, whose stages are
  * bl_stats_kernels.hip, bl_freq_kernels.hip and bl_env_kernels.hip; bl_level_kernels.hip the signal
  * levels, bl_timbre_kernels.hip the per-frame spectral timbre, bl_rhythm_kernels.hip the tempo,
+ * bl_beat_kernels.hip the beat grid,
  * bl_chroma_kernels.hip chroma and key, bl_mel_kernels.hip mel bands, cepstrum and flatness,
  * bl_matrix_kernels.hip the pairwise matrix,
  * bl_query_kernels.hip the vector queries, bl_desc_kernels.hip the descriptors and their kNN,
@@ -84,7 +85,7 @@ struct bl_tables {
 
 enum { PK_SCAN, PK_AMP, PK_FREQ, PK_FREQ_FIN, PK_ENV, PK_TAIL, PK_DIST, PK_FREQ_SCAN, PK_RHYTHM_HOPS, PK_RHYTHM_ACF,
        PK_RHYTHM_PICK, PK_CHROMA_PITCH, PK_CHROMA_KEY, PK_DESC_RANGE, PK_DESC_QUANTIZE, PK_DESC_KNN, PK_DESC_MERGE,
-       PK_COUNT };
+       PK_BEATS, PK_COUNT };
 
 /* called by the launchers around a kernel when profiling is on: begin = 1 before the
  * launch, 0 after it, on the stream the kernel is launched on */
@@ -244,6 +245,27 @@ int blk_rhythm_group(hipStream_t s, const int16_t *d_pcm, const uint32_t *d_curv
                      void *mark_user);
 /* bl_amd_selftest_isqrt: d_counts[0..1] += values checked, values whose bl_isqrt64 is not the floor of the root */
 int blk_isqrt_sweep(hipStream_t s, unsigned long long *d_counts, int n_cu);
+
+/* ---- per-song beat grid (bl_beat_kernels.hip) -------------------------------------- */
+
+struct bl_beat_song { /* one song of a launch group; the records are sorted longest first */
+  long long onset_off; /* the song's first hop in the caller's curve and arrays: the sum of H over the songs before it in
+                          the caller's order */
+  long long hop_off;   /* the song's first hop in the link scratch: the sum of H over the songs before it in its launch
+                          group */
+  int hops;            /* 1 <= H < 2^24 */
+  int out_idx;         /* position in the caller's order: its record in d_songs_out, its period in d_period */
+};
+#define BL_BEAT_GROUP_SONGS 32768        /* songs per launch group */
+#define BL_BEAT_GROUP_HOPS (1ll << 25)   /* hops per launch group, unless its first song alone has more */
+/* One launch group of bl_amd_beats_device: one workgroup per record of d_songs.  The period of a song is the int32 at
+ * d_period + out_idx * period_stride.  d_links_out, d_scores_out: nullptr or the arrays of ALL songs of the call;
+ * d_link_scratch: used without d_links_out, one uint16 per hop of the group.  Writes every byte of the group's records
+ * in d_songs_out and every element of its songs in the arrays. */
+int blk_beats_group(hipStream_t s, const uint32_t *d_onsets, const bl_beat_song *d_songs, int n_songs,
+                    const void *d_period, int period_stride, int tight, bl_amd_song_beats *d_songs_out,
+                    uint8_t *d_flags_out, uint16_t *d_links_out, uint16_t *d_link_scratch, int64_t *d_scores_out,
+                    blk_mark_fn mark, void *mark_user);
 
 /* ---- chroma and key (bl_chroma_kernels.hip) ---------------------------------------- */
 

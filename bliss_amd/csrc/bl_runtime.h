@@ -94,6 +94,9 @@ struct bl_amd_ctx {
   /* bl_amd_rhythm_batch_device, bl_amd_rhythm_from_onsets: the songs' records (bl_rhythm_song), longest first; one
    * launch group's novelty values (4 bytes per hop) and its onset sums and lag products (blk_rhythm_rows_bytes) */
   bl_buf rhythm_songs, rhythm_n, rhythm_rows;
+  /* bl_amd_beats_device, bl_amd_beats_host: the songs' records (bl_beat_song), longest first, and, for a call without
+   * a links output, one launch group's links (2 bytes per hop) */
+  bl_buf beat_songs, beat_links;
   /* bl_amd_chroma_batch_device: the songs' records (bl_chroma_song), their twelve sums, and the bank's image
    * (blk_chroma_image_host), uploaded by the context's first call */
   bl_buf chroma_songs, chroma_acc, chroma_image;

@@ -16,7 +16,7 @@
  * pinned slots (hipMemcpyAsync from pinned memory does not block), launch groups of more than
  * 32 768 songs follow each other on the stream, and the shared workspace is handed from one
  * batch to the next by an event, not by a host synchronisation.  Every entry point that uploads
- * per-song records (analysis, rate conversion, levels, timbre, tempo, chroma, mel, synthesis, bld_mean_variance_host)
+ * per-song records (analysis, rate conversion, levels, timbre, tempo, beats, chroma, mel, synthesis, bld_mean_variance_host)
  * does so through record_call, the one place that knows this protocol; the vector queries have
  * query_call (bl_runtime.h), which shares the hand-over (ws_wait, ws_pass) with it.
  *
@@ -118,7 +118,7 @@ void ctx_release(bl_amd_ctx *c) {
   bl_buf *bufs[] = {&c->songs,   &c->stats,   &c->hist, &c->spectrum, &c->energies, &c->lc,
                     &c->results, &c->arena[0], &c->arena[1], &c->arena22[0], &c->arena22[1],
                     &c->rs_songs, &c->rs_bank, &c->mx_my, &c->mx_gath, &c->mx_all, &c->mx_order, &c->mx_rows, &c->knn, &c->chain, &c->radius, &c->level_songs, &c->timbre_songs,
-                    &c->rhythm_songs, &c->rhythm_n, &c->rhythm_rows, &c->chroma_songs, &c->chroma_acc, &c->chroma_image,
+                    &c->rhythm_songs, &c->rhythm_n, &c->rhythm_rows, &c->beat_songs, &c->beat_links, &c->chroma_songs, &c->chroma_acc, &c->chroma_image,
                     &c->mel_songs, &c->mel_image, &c->desc};
   for (bl_buf *b : bufs) release_buf(*b);
   for (int k = 0; k < 2; ++k) {
@@ -545,6 +545,66 @@ static int rhythm_call(bl_amd_ctx *c, hipStream_t s, int n_songs, Song song, con
   });
 }
 
+/* ---- beats: the call path of bl_amd_beats_device and bl_amd_beats_host ---- */
+
+/* what both forms reject before anything is enqueued; *total: the sum of H over the songs */
+static bool beats_args_ok(const int32_t *h_hops, int n_songs, int tight, long long *total) {
+  if (!h_hops || n_songs < 1 || tight < 0 || tight > BL_AMD_BEATS_TIGHT_MAX) return false;
+  *total = 0;
+  for (int i = 0; i < n_songs; ++i) {
+    if (h_hops[i] < 1 || h_hops[i] >= (1 << 24)) return false;
+    *total += h_hops[i];
+  }
+  return true;
+}
+
+/* One call on n_songs onset curves on the device; the caller holds the context and has checked the arguments.  As the
+ * tempo call does, the records are sorted longest first, so that the long songs do not straggle at the end of the
+ * grid, and cut into launch groups of at most c->group_songs songs and BL_BEAT_GROUP_HOPS = 2^25 hops, which follow
+ * each other on the stream and share the link scratch: 2 bytes per hop = 64 MiB, whatever the call. */
+static int beats_call(bl_amd_ctx *c, hipStream_t s, const uint32_t *d_onsets, const int32_t *h_hops, int n_songs,
+                      const void *d_period, int period_stride, int tight, bl_amd_song_beats *d_songs_out,
+                      uint8_t *d_flags_out, uint16_t *d_links_out, int64_t *d_scores_out) {
+  return record_call<bl_beat_song>(c, s, c->beat_songs, n_songs, [&](bl_beat_song *hs) {
+    long long onset_off = 0;
+    for (int i = 0; i < n_songs; ++i) {
+      hs[i].onset_off = onset_off;
+      hs[i].hops = h_hops[i];
+      hs[i].out_idx = i;
+      onset_off += h_hops[i];
+    }
+    std::stable_sort(hs, hs + n_songs, [](const bl_beat_song &a, const bl_beat_song &b) { return a.hops > b.hops; });
+    const int group_songs = std::min(c->group_songs, BL_BEAT_GROUP_SONGS);
+    long long in_group = 0; /* hop_off == 0 marks the first song of a group: every song has H >= 1 */
+    for (int i = 0, count = 0; i < n_songs; ++i, ++count) {
+      if (count == group_songs || (count && in_group + hs[i].hops > BL_BEAT_GROUP_HOPS)) in_group = count = 0;
+      hs[i].hop_off = in_group;
+      in_group += hs[i].hops;
+    }
+    return BL_OK;
+  }, [&](const bl_beat_song *hs, bl_beat_song *d_songs) {
+    auto group_end = [&](int b, long long &hops) {
+      int e = b + 1;
+      for (hops = hs[b].hops; e < n_songs && hs[e].hop_off; ++e) hops += hs[e].hops;
+      return e;
+    };
+    long long hops, max_hops = 0;
+    for (int b = 0, e; b < n_songs; b = e) {
+      e = group_end(b, hops);
+      max_hops = std::max(max_hops, hops);
+    }
+    if (!d_links_out && blr_ensure(c->beat_links, sizeof(uint16_t) * (size_t)max_hops) != BL_OK) return BL_UNEXPECTED;
+    for (int b = 0, e; b < n_songs; b = e) {
+      e = group_end(b, hops);
+      if (blk_beats_group(s, d_onsets, d_songs + b, e - b, d_period, period_stride, tight, d_songs_out, d_flags_out,
+                          d_links_out, static_cast<uint16_t *>(c->beat_links.p), d_scores_out,
+                          c->prof ? mark_cb : nullptr, c) != BL_OK)
+        return BL_UNEXPECTED;
+    }
+    return BL_OK;
+  });
+}
+
 /* ========================================================================= */
 /* C-ABI                                                                      */
 
@@ -616,7 +676,8 @@ double bl_amd_profile_ms(const char *name, int *launches) {
                                                    "env_windows", "env_tail",   "distance",    "freq_scan",
                                                    "rhythm_hops", "rhythm_acf", "rhythm_pick",
                                                    "chroma_pitch", "chroma_key",
-                                                   "desc_range",  "desc_quantize", "desc_knn", "desc_merge"};
+                                                   "desc_range",  "desc_quantize", "desc_knn", "desc_merge",
+                                                   "beats"};
   if (launches) *launches = 0;
   bl_amd_ctx *c = blr_default_ctx();
   if (!c || !name) return -1.0;
@@ -772,6 +833,66 @@ int bl_amd_rhythm_batch_device(const int16_t *d_pcm, const bl_amd_song_desc *h_d
                                long long n_onsets, uint64_t *d_acf_out, void *stream) {
   return rhythm_device(nullptr, true, d_pcm, h_desc, n_songs, lag_min, lag_max, d_songs_out, d_onsets_out, n_onsets,
                        d_acf_out, stream);
+}
+
+/* ---- beats (bl_beat_kernels.hip) ------------------------------------------------- */
+
+static int beats_device(bl_amd_ctx *c, bool dflt, const uint32_t *d_onsets, const int32_t *h_hops, int n_songs,
+                        const void *d_period, int period_stride, int tight, bl_amd_song_beats *d_songs_out,
+                        uint8_t *d_flags_out, uint16_t *d_links_out, int64_t *d_scores_out, void *stream) {
+  long long total = 0;
+  if (!d_onsets || ((uintptr_t)d_onsets & 3) || !d_period || ((uintptr_t)d_period & 3) || period_stride < 4 ||
+      (period_stride & 3) || !d_songs_out || ((uintptr_t)d_songs_out & 7) || !d_flags_out ||
+      ((uintptr_t)d_links_out & 1) || ((uintptr_t)d_scores_out & 7) || !beats_args_ok(h_hops, n_songs, tight, &total) ||
+      !(c = call_ctx(c, dflt)))
+    return BL_UNEXPECTED;
+  CtxGuard g(c);
+  if (!g.ok()) return BL_UNEXPECTED;
+  return beats_call(c, static_cast<hipStream_t>(stream), d_onsets, h_hops, n_songs, d_period, period_stride, tight,
+                    d_songs_out, d_flags_out, d_links_out, d_scores_out);
+}
+
+int bl_amd_ctx_beats_device(bl_amd_ctx *c, const uint32_t *d_onsets, const int32_t *h_hops, int n_songs,
+                            const void *d_period, int period_stride, int tight, bl_amd_song_beats *d_songs_out,
+                            uint8_t *d_flags_out, uint16_t *d_links_out, int64_t *d_scores_out, void *stream) {
+  return beats_device(c, false, d_onsets, h_hops, n_songs, d_period, period_stride, tight, d_songs_out, d_flags_out,
+                      d_links_out, d_scores_out, stream);
+}
+
+int bl_amd_beats_device(const uint32_t *d_onsets, const int32_t *h_hops, int n_songs, const void *d_period,
+                        int period_stride, int tight, bl_amd_song_beats *d_songs_out, uint8_t *d_flags_out,
+                        uint16_t *d_links_out, int64_t *d_scores_out, void *stream) {
+  return beats_device(nullptr, true, d_onsets, h_hops, n_songs, d_period, period_stride, tight, d_songs_out,
+                      d_flags_out, d_links_out, d_scores_out, stream);
+}
+
+/* the caller's curves and periods: uploaded, through the same launch as the device form, fetched */
+int bl_amd_beats_host(const uint32_t *h_onsets, const int32_t *h_hops, int n_songs, const int32_t *h_period, int tight,
+                      bl_amd_song_beats *h_songs_out, uint8_t *h_flags_out, uint16_t *h_links_out,
+                      int64_t *h_scores_out) {
+  long long total = 0;
+  if (!h_onsets || !h_period || !h_songs_out || !h_flags_out || !beats_args_ok(h_hops, n_songs, tight, &total))
+    return BL_UNEXPECTED;
+  for (long long k = 0; k < total; ++k)
+    if (h_onsets[k] >= (1u << 18)) return BL_UNEXPECTED;
+  bl_amd_ctx *c = blr_default_ctx();
+  if (!c) return BL_UNEXPECTED;
+  CtxGuard g(c);
+  if (!g.ok()) return BL_UNEXPECTED;
+  DevMem curve(sizeof(uint32_t) * (size_t)total), per(sizeof(int32_t) * (size_t)n_songs),
+      out(sizeof(bl_amd_song_beats) * (size_t)n_songs), flags((size_t)total),
+      links(h_links_out ? sizeof(uint16_t) * (size_t)total : 0), scores(h_scores_out ? sizeof(int64_t) * (size_t)total : 0);
+  if (!curve.ok() || !per.ok() || !out.ok() || !flags.ok() || !links.ok() || !scores.ok() || !curve.up(h_onsets) ||
+      !per.up(h_period))
+    return BL_UNEXPECTED;
+  if (beats_call(c, nullptr, curve.as<uint32_t>(), h_hops, n_songs, per.p, 4, tight, out.as<bl_amd_song_beats>(),
+                 flags.as<uint8_t>(), links.as<uint16_t>(), scores.as<int64_t>()) != BL_OK)
+    return BL_UNEXPECTED;
+  BL_HIP_CHECK(hipStreamSynchronize(nullptr));
+  return out.down(h_songs_out) && flags.down(h_flags_out) && (!h_links_out || links.down(h_links_out)) &&
+                 (!h_scores_out || scores.down(h_scores_out))
+             ? BL_OK
+             : BL_UNEXPECTED;
 }
 
 /* ---- chroma and key (bl_chroma_kernels.hip) -------------------------------------- */

@@ -1,5 +1,6 @@
 """Per-song tempo (include/bliss_amd.h: bl_amd_song_rhythm, bl_amd_rhythm_*): the beat period of a song as a lag of its
-onset curve, in exact integers, and the beats per minute and beat strength read off them.
+onset curve, in exact integers, and the beats per minute and beat strength read off them; and the beat grid
+(bl_amd_song_beats, bl_amd_beats_*): where the beats are, by dynamic programming over that curve at that period.
 
 This module is imported explicitly (`import bliss_amd.rhythm`): the package's own namespace is unchanged."""
 import ctypes as C
@@ -10,9 +11,10 @@ import numpy as np
 from . import _lib
 from ._args import host_pcm, int_in, songs_check
 from ._lib import check
-from .records import RHYTHM_DTYPE
+from .records import BEATS_DTYPE, RHYTHM_DTYPE
 
 HOP, LAGS = 128, 512   # BL_AMD_RHYTHM_HOP, BL_AMD_RHYTHM_LAGS
+PERIOD_MAX, TIGHT_MAX = 510, 4096   # BL_AMD_BEATS_PERIOD_MAX, BL_AMD_BEATS_TIGHT_MAX
 _SHORTEST = (HOP, 2 * HOP)   # the least interleaved samples of a mono and of a stereo song: one hop
 
 
@@ -93,10 +95,8 @@ def rhythm_batch_host(pcm_list, channels, lag_min, lag_max, onsets=True, acf=Fal
     return rhythm_to_numpy(bytes(out)), ons, rows
 
 
-def rhythm_from_onsets(onsets_list, lag_min, lag_max, acf=False):
-    """Stages 7 and 8 alone (bl_amd_rhythm_from_onsets) on onset curves of the caller's: a list of 1-D arrays of
-    integers in [0, 2^18), one per song, of 1 to 2^24 - 1 hops each.  Returns the records, or (records, acf)."""
-    lag_min, lag_max = _lags_check(lag_min, lag_max)
+def _curves_check(onsets_list):
+    """the curves as arrays, once there is one and each is 1-D, of integers in [0, 2^18) and of 1 to 2^24 - 1 hops"""
     curves = [np.asarray(o) for o in onsets_list]
     if not curves:
         raise ValueError("at least one onset curve is needed")
@@ -106,6 +106,14 @@ def rhythm_from_onsets(onsets_list, lag_min, lag_max, acf=False):
                              f"of {o.dtype}")
         if int(o.min()) < 0 or int(o.max()) >= 1 << 18:
             raise ValueError(f"onset values must lie in [0, 2^18), got [{int(o.min())}, {int(o.max())}]")
+    return curves
+
+
+def rhythm_from_onsets(onsets_list, lag_min, lag_max, acf=False):
+    """Stages 7 and 8 alone (bl_amd_rhythm_from_onsets) on onset curves of the caller's: a list of 1-D arrays of
+    integers in [0, 2^18), one per song, of 1 to 2^24 - 1 hops each.  Returns the records, or (records, acf)."""
+    lag_min, lag_max = _lags_check(lag_min, lag_max)
+    curves = _curves_check(onsets_list)
     n = len(curves)
     flat = np.ascontiguousarray(np.concatenate(curves), dtype=np.uint32)
     hops = (C.c_int32 * n)(*[o.size for o in curves])
@@ -130,3 +138,115 @@ def rhythm_bpm(records, rate=22050):
     bpm = np.array([lib.bl_amd_rhythm_bpm(C.byref(p[i]), rate) for i in range(rec.size)], dtype=np.float64)
     strength = np.array([lib.bl_amd_rhythm_strength(C.byref(p[i])) for i in range(rec.size)], dtype=np.float64)
     return bpm, strength
+
+
+# ---- beats -----------------------------------------------------------------------------------------------------------
+
+def beats_to_numpy(raw):
+    """bytes / uint8 array of bl_amd_song_beats records -> structured numpy array with the header's field names."""
+    return np.frombuffer(bytes(raw), dtype=BEATS_DTYPE).copy()
+
+
+def _hops_check(hops):
+    hops = [int_in("hops", h, 1, (1 << 24) - 1) for h in hops]
+    if not hops:
+        raise ValueError("at least one song is needed")
+    return hops
+
+
+def beats_device(onsets, hops, period, tight=128, links=False, scores=False, ctx=None):
+    """Enqueue the beat grids of n songs (bl_amd_beats_device) on torch's current stream.  onsets: a contiguous int32
+    CUDA tensor holding the uint32 onset curves one behind the other (what rhythm_device() returns); hops: the n hop
+    counts; period: an int32 CUDA tensor of n periods in hops, or the uint8 record tensor of rhythm_device(), whose
+    `lag` fields are then read in place (stride 72, no copy).  A song whose period lies outside 2 .. 510 (a lag of 0:
+    no tempo) gets a record with status BL_UNEXPECTED and no beats.  Returns the CUDA tensors (records as uint8, flags
+    as uint8, links as int16 holding the uint16 values or None, scores as int64 or None); beats_to_numpy() reads the
+    records once the stream has been waited for.  ctx: an explicit Context.
+
+    tight weighs staying on the period against landing on onsets: 16 prices one octave off the period at one maximal
+    onset.  The default of 128 has not been tuned against annotated music: on synthetic click curves with jitter every
+    value from 16 to 256 followed every click."""
+    import torch
+    from .queries import _on_device_of
+    hops = _hops_check(hops)
+    n, total = len(hops), sum(hops)
+    tight = int_in("tight", tight, 0, TIGHT_MAX)
+    if onsets.dtype != torch.int32 or not onsets.is_cuda or not onsets.is_contiguous() or onsets.dim() != 1 or \
+            onsets.numel() != total:
+        raise ValueError(f"onsets must be a contiguous 1-D int32 CUDA tensor of sum(hops) = {total} values")
+    if not period.is_cuda or period.device != onsets.device or not period.is_contiguous() or period.dim() != 1:
+        raise ValueError("period must be a contiguous 1-D CUDA tensor on the device of onsets")
+    if period.dtype == torch.int32 and period.numel() == n:
+        at, stride = period.data_ptr(), 4
+    elif period.dtype == torch.uint8 and period.numel() == n * RHYTHM_DTYPE.itemsize:
+        at, stride = period.data_ptr() + RHYTHM_DTYPE.fields["lag"][1], RHYTHM_DTYPE.itemsize
+    else:
+        raise ValueError(f"period must hold {n} int32 periods or, as uint8, {n} bl_amd_song_rhythm records")
+    lib = _lib.load()
+    dev = onsets.device
+    rec = torch.empty(n * BEATS_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    flags = torch.empty(total, dtype=torch.uint8, device=dev)
+    lk = torch.empty(total, dtype=torch.int16, device=dev) if links else None
+    sc = torch.empty(total, dtype=torch.int64, device=dev) if scores else None
+    with _on_device_of(lib, onsets, None) as cur:
+        args = (C.c_void_p(onsets.data_ptr()), (C.c_int32 * n)(*hops), n, C.c_void_p(at), stride, tight,
+                C.c_void_p(rec.data_ptr()), C.c_void_p(flags.data_ptr()), C.c_void_p(lk.data_ptr()) if links else None,
+                C.c_void_p(sc.data_ptr()) if scores else None, C.c_void_p(cur.cuda_stream))
+        if ctx is None:
+            check(lib.bl_amd_beats_device(*args), "bl_amd_beats_device")
+        else:
+            check(lib.bl_amd_ctx_beats_device(ctx.handle, *args), "bl_amd_ctx_beats_device")
+    return rec, flags, lk, sc
+
+
+def beats_host(onsets_list, periods, tight=128, links=False, scores=False):
+    """Beat grids of onset curves in host memory (bl_amd_beats_host), blocking: onsets_list as rhythm_from_onsets()
+    takes it, periods one int per song.  Returns (records, flags, links or None, scores or None): the records as
+    beats_to_numpy() gives them, the arrays over all hops, songs one behind the other.  tight: see beats_device()."""
+    curves = _curves_check(onsets_list)
+    n = len(curves)
+    periods = [int_in("period", p, -2 ** 31, 2 ** 31 - 1) for p in periods]
+    if len(periods) != n:
+        raise ValueError(f"{n} curves but {len(periods)} periods")
+    tight = int_in("tight", tight, 0, TIGHT_MAX)
+    flat = np.ascontiguousarray(np.concatenate(curves), dtype=np.uint32)
+    out = (_lib.SongBeats * n)()
+    flags = np.empty(flat.size, dtype=np.uint8)
+    lk = np.empty(flat.size, dtype=np.uint16) if links else None
+    sc = np.empty(flat.size, dtype=np.int64) if scores else None
+    check(_lib.load().bl_amd_beats_host(
+        flat.ctypes.data_as(C.POINTER(C.c_uint32)), (C.c_int32 * n)(*[o.size for o in curves]), n,
+        (C.c_int32 * n)(*periods), tight, out, flags.ctypes.data_as(C.POINTER(C.c_uint8)),
+        lk.ctypes.data_as(C.POINTER(C.c_uint16)) if links else None,
+        sc.ctypes.data_as(C.POINTER(C.c_int64)) if scores else None), "bl_amd_beats_host")
+    return beats_to_numpy(bytes(out)), flags, lk, sc
+
+
+def beat_list(flags, rate=22050):
+    """(hops int32, seconds float64) of the beats of one song from its flags (bl_amd_beats_list): the indices of the set
+    flags and 128 hop / rate."""
+    f = np.ascontiguousarray(flags, dtype=np.uint8)
+    if f.ndim != 1:
+        raise ValueError("flags must be 1-D: the flags of one song")
+    rate = int_in("rate", rate, 1, 2 ** 31 - 1)
+    lib = _lib.load()
+    p = f.ctypes.data_as(C.POINTER(C.c_uint8))
+    count = lib.bl_amd_beats_list(p, f.size, rate, None, None, 0)
+    if count < 0:
+        raise RuntimeError("bl_amd_beats_list rejected its arguments")
+    hop, sec = np.empty(count, dtype=np.int32), np.empty(count, dtype=np.float64)
+    lib.bl_amd_beats_list(p, f.size, rate, hop.ctypes.data_as(C.POINTER(C.c_int32)),
+                          sec.ctypes.data_as(C.POINTER(C.c_double)), count)
+    return hop, sec
+
+
+def beats_bpm(records, rate=22050):
+    """float64 array of the tempo of each grid of bl_amd_song_beats records (bl_amd_beats_bpm):
+    60 rate (n_beats - 1) / (128 (last - first)), NaN for fewer than two beats."""
+    rec = np.ascontiguousarray(records)
+    if rec.dtype != BEATS_DTYPE or rec.ndim != 1 or rec.size < 1:
+        raise ValueError("records must be a non-empty 1-D array of bl_amd_song_beats records (beats_to_numpy)")
+    rate = int_in("rate", rate, 1, 2 ** 31 - 1)
+    lib = _lib.load()
+    p = rec.ctypes.data_as(C.POINTER(_lib.SongBeats))
+    return np.array([lib.bl_amd_beats_bpm(C.byref(p[i]), rate) for i in range(rec.size)], dtype=np.float64)

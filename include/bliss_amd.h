@@ -628,6 +628,70 @@ double bl_amd_rhythm_bpm(const bl_amd_song_rhythm *r, int rate);
 double bl_amd_rhythm_strength(const bl_amd_song_rhythm *r);
 int bl_amd_selftest_isqrt(uint64_t counts[2]);
 
+/* Beats: where the beats of a song are, the half of the tempo that the lags of stage 7 discard by construction.  A
+ * beat-matched crossfade aligns two songs on a beat; the tempo call gives the period, this gives the grid.  It is
+ * Ellis's dynamic-programming beat tracker ("Beat Tracking by Dynamic Programming", 2007) over the onset curve o_h of
+ * the tempo call, stated in exact integers: all arithmetic below is integer arithmetic and fits a signed 64-bit value.
+ * Per song: a curve o[0 .. H-1] with values < 2^18 and 1 <= H < 2^24, a period L in hops, and one `tight` per call,
+ * 0 <= tight <= 4096.  Log2q12 is the base-2 logarithm in 1/4096 of the mel block (bl_ilog2_q12).
+ *   1 scale       omax = max o_h, W = tight omax (the record's pen_scale); lo = (L + 1) >> 1, hi = 2 L
+ *   2 penalty     for d in [lo, hi]: e(d) = |Log2q12(d) - Log2q12(L)|, pen(d) = (W e(d)^2) >> 28.  tight = 16 prices
+ *                 one octave off the period at one omax.
+ *   3 scores      for t = 0 .. H-1: best(t) = max over d in [lo, min(hi, t)] of C[t-d] - pen(d), ties to the smallest
+ *                 d.  If the range is empty or best(t) <= 0: C[t] = o[t], P[t] = 0.  Otherwise C[t] = o[t] + best(t)
+ *                 and P[t] = that d.
+ *   4 end         t_end = the arg-max of C[t] over t in [max(0, H - L), H - 1], ties to the largest t;
+ *                 score = C[t_end].  score == 0: the song has no beats (n_beats = 0, first = last = -1).
+ *   5 back-trace  the beats are t_end, t_end - P[t_end], ... down to and including the first hop with P == 0;
+ *                 flag[h] = 1 on a beat and 0 elsewhere; first and last are the smallest and largest beat, n_beats
+ *                 their number.
+ * Bounds: W < 2^30; e <= 4096 for every L in 2 .. 510 and d in [lo, hi], so W e^2 < 2^54 and pen < 2^26;
+ * 0 <= C < 2^42 and P <= 1020.
+ * A song whose L lies outside [2, 510] is no error of the call (a lag of 0 means "no tempo"): its record has
+ * status = BL_UNEXPECTED, hops = H, period = L as given and every other field 0, and its flags, links and scores are 0. */
+#define BL_AMD_BEATS_PERIOD_MAX 510
+#define BL_AMD_BEATS_TIGHT_MAX 4096
+typedef struct bl_amd_song_beats { /* 40 bytes */
+  int64_t score;                   /* C[t_end] */
+  uint64_t pen_scale;              /* W */
+  int32_t hops, period;            /* H, L */
+  int32_t n_beats, first, last;
+  int32_t status;                  /* BL_OK; BL_UNEXPECTED for a song with L outside [2, 510] */
+} bl_amd_song_beats;
+/* bl_amd_beats_device: the beat grids of n_songs songs whose onset curves sit in device memory.  The layout of
+ * d_onsets, d_flags_out, d_links_out (P) and d_scores_out (C) is that of d_onsets_out of bl_amd_rhythm_batch_device:
+ * songs concatenated in the caller's order, song i at the sum of h_hops[j] over j < i.  The int32 period of song i is
+ * read on the device at (char *)d_period + i * period_stride: a stride of 4 takes a packed array, a stride of
+ * sizeof(bl_amd_song_rhythm) = 72 together with &d_records->lag takes the tempo straight from the records of the
+ * tempo call, with no copy and no kernel in between; the stride is a multiple of 4 and >= 4.  d_links_out and
+ * d_scores_out may be NULL: P then stays in the context's workspace and C never leaves the chip.  No output needs
+ * zeroing and every element of every output is written.  A rejected call returns BL_UNEXPECTED and writes nothing:
+ * a NULL required pointer, a pointer misaligned for its element type, n_songs < 1, an h_hops[i] outside [1, 2^24), a
+ * bad stride, tight outside [0, 4096].  An onset value >= 2^18 is the caller's error and is not checked on the device.
+ * Asynchronous on `stream`; h_hops is copied before the call returns.  A song's outputs are a pure function of its
+ * curve, L and tight: they depend neither on the other songs, n_songs, the order nor on which optional outputs are
+ * asked for.  One workgroup works on one song, whatever its length: the recurrence is serial in time.
+ *   bl_amd_beats_host: the same from host memory, blocking; h_period is a packed int32 array; an onset value >= 2^18
+ *     rejects the call; h_links_out and h_scores_out may be NULL.
+ *   bl_amd_beats_list: plain host arithmetic, no device.  Returns the number of set flags among h_flags[0 .. hops) and
+ *     writes the first min(count, cap) beats as hop indices to h_hop_out and as seconds, 128.0 hop / rate, to
+ *     h_sec_out; either may be NULL.  -1 for a NULL h_flags, hops < 0, rate < 1 or cap < 0.
+ *   bl_amd_beats_bpm: plain host arithmetic: 60 rate (n_beats - 1) / (128 (last - first)), the tempo of the grid
+ *     itself, finer than one hop.  NaN for n_beats < 2, a NULL record or rate < 1.
+ * tight has not been tuned against annotated music; on synthetic click curves with jitter every value from 16 to 256
+ * followed every click, and the Python binding's default is 128. */
+int bl_amd_beats_device(const uint32_t *d_onsets, const int32_t *h_hops, int n_songs, const void *d_period,
+                        int period_stride, int tight, bl_amd_song_beats *d_songs_out, uint8_t *d_flags_out,
+                        uint16_t *d_links_out, int64_t *d_scores_out, void *stream);
+int bl_amd_ctx_beats_device(bl_amd_ctx *ctx, const uint32_t *d_onsets, const int32_t *h_hops, int n_songs,
+                            const void *d_period, int period_stride, int tight, bl_amd_song_beats *d_songs_out,
+                            uint8_t *d_flags_out, uint16_t *d_links_out, int64_t *d_scores_out, void *stream);
+int bl_amd_beats_host(const uint32_t *h_onsets, const int32_t *h_hops, int n_songs, const int32_t *h_period, int tight,
+                      bl_amd_song_beats *h_songs_out, uint8_t *h_flags_out, uint16_t *h_links_out,
+                      int64_t *h_scores_out);
+int bl_amd_beats_list(const uint8_t *h_flags, int hops, int rate, int32_t *h_hop_out, double *h_sec_out, int cap);
+double bl_amd_beats_bpm(const bl_amd_song_beats *b, int rate);
+
 /* Chroma and key: how a song's energy spreads over the twelve pitch classes, and the major or minor key whose profile
  * fits that spread best ("same or compatible key next", the companion of the tempo).  The reference's author lists
  * "Chromagram / HPCP" in ROADMAP.md ("Tonal features"); none of it is in the reference's API.  The 512-point frames of
@@ -996,7 +1060,7 @@ int bl_amd_fir_mode(void);
  * profiling is on (bench.py's roofline leg).  name is one of "pcm_scan", "freq_scan",
  * "amp_finish", "freq_frames", "freq_finish", "env_windows", "env_tail",
  * "distance", "rhythm_hops", "rhythm_acf", "rhythm_pick", "chroma_pitch", "chroma_key",
- * "desc_range", "desc_quantize", "desc_knn", "desc_merge"; returns accumulated milliseconds and the launch count since the
+ * "desc_range", "desc_quantize", "desc_knn", "desc_merge", "beats"; returns accumulated milliseconds and the launch count since the
  * last reset, or -1 for an unknown name. */
 void bl_amd_profile(int enable);
 void bl_amd_profile_reset(void);
