@@ -89,6 +89,18 @@ class SongBeats(C.Structure):  # include/bliss_amd.h bl_amd_song_beats
                 ("n_beats", C.c_int32), ("first", C.c_int32), ("last", C.c_int32), ("status", C.c_int32)]
 
 
+class LoudParams(C.Structure):  # include/bliss_amd.h bl_amd_loud_params
+    _fields_ = [("s1_b", C.c_double * 3), ("s1_a", C.c_double * 2), ("s2_a", C.c_double * 2), ("hop", C.c_int32),
+                ("warm", C.c_int32), ("abs_gate", C.c_uint64)]
+
+
+class SongLoud(C.Structure):  # include/bliss_amd.h bl_amd_song_loud
+    _fields_ = [("gated_sum", C.c_uint64 * 2), ("abs_sum", C.c_uint64 * 2), ("momentary_max", C.c_uint64),
+                ("st_max", C.c_uint64), ("lra_lo", C.c_uint64), ("lra_hi", C.c_uint64), ("gated_count", C.c_int32),
+                ("abs_count", C.c_int32), ("st_gated", C.c_int32), ("hops", C.c_int32), ("blocks", C.c_int32),
+                ("status", C.c_int32)]
+
+
 class FrameChroma(C.Structure):  # include/bliss_amd.h bl_amd_frame_chroma
     _fields_ = [("x", C.c_uint64 * 12)]
 
@@ -275,6 +287,20 @@ SYMBOLS = {
                                     _P(C.c_uint8), _P(C.c_uint16), _P(C.c_int64)]),
     "bl_amd_beats_list": (C.c_int, [_P(C.c_uint8), C.c_int, C.c_int, _P(C.c_int32), _P(C.c_double), C.c_int]),
     "bl_amd_beats_bpm": (C.c_double, [_P(SongBeats), C.c_int]),
+    "bl_amd_loud_batch_device": (C.c_int, [C.c_void_p, _P(SongDesc), C.c_int, _P(LoudParams), C.c_void_p, C.c_void_p,
+                                           C.c_longlong, C.c_void_p]),
+    "bl_amd_ctx_loud_batch_device": (C.c_int, [C.c_void_p, C.c_void_p, _P(SongDesc), C.c_int, _P(LoudParams), C.c_void_p,
+                                               C.c_void_p, C.c_longlong, C.c_void_p]),
+    "bl_amd_loud_batch_host": (C.c_int, [_P(C.c_void_p), _P(C.c_int32), _P(C.c_int32), C.c_int, _P(LoudParams),
+                                         _P(SongLoud), _P(C.c_uint64)]),
+    "bl_amd_loud_from_hops": (C.c_int, [_P(C.c_uint64), _P(C.c_int32), C.c_int, _P(LoudParams), _P(SongLoud)]),
+    "bl_amd_loud_kweight": (C.c_int, [C.c_int, _P(LoudParams)]),
+    "bl_amd_loud_lufs": (C.c_double, [_P(SongLoud), C.c_int]),
+    "bl_amd_loud_momentary_max_lufs": (C.c_double, [_P(SongLoud), C.c_int]),
+    "bl_amd_loud_short_max_lufs": (C.c_double, [_P(SongLoud), C.c_int]),
+    "bl_amd_loud_range_lu": (C.c_double, [_P(SongLoud)]),
+    "bl_amd_loud_gain_db": (C.c_double, [_P(SongLoud), C.c_int, C.c_double]),
+    "bl_amd_loud_profile_ms": (C.c_double, [C.c_char_p, _P(C.c_int)]),
     "bl_amd_chroma_frames": (C.c_int, [C.c_int, C.c_int]),
     "bl_amd_chroma_batch_device": (C.c_int, [C.c_void_p, _P(SongDesc), C.c_int, C.c_void_p, C.c_void_p, C.c_longlong,
                                              C.c_void_p]),

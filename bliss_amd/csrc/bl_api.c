@@ -329,6 +329,67 @@ double bl_amd_beats_bpm(const bl_amd_song_beats *b, int rate) {
          ((double)BL_AMD_RHYTHM_HOP * (double)(b->last - b->first));
 }
 
+/* ---- loudness: the host arithmetic over bl_amd_loud_params and bl_amd_song_loud (include/bliss_amd.h) ---- */
+
+/* The bilinear design of the two K-weighting sections.  The constants are the analogue prototype that gives
+ * BS.1770-4's printed coefficients at 48 000 Hz. */
+int bl_amd_loud_kweight(int rate, bl_amd_loud_params *p) {
+  if (!p || rate < 8000 || rate > 48000 || rate % 10) return BL_UNEXPECTED;
+  const double pi = 3.14159265358979323846;
+  double f0 = 1681.974450955533, G = 3.999843853973347, Q = 0.7071752369554196;
+  double K = tan(pi * f0 / (double)rate);
+  const double Vh = pow(10.0, G / 20.0), Vb = pow(Vh, 0.4996667741545416);
+  double a0 = 1.0 + K / Q + K * K;
+  p->s1_b[0] = (Vh + Vb * K / Q + K * K) / a0;
+  p->s1_b[1] = 2.0 * (K * K - Vh) / a0;
+  p->s1_b[2] = (Vh - Vb * K / Q + K * K) / a0;
+  p->s1_a[0] = 2.0 * (K * K - 1.0) / a0;
+  p->s1_a[1] = (1.0 - K / Q + K * K) / a0;
+  f0 = 38.13547087602444;
+  Q = 0.5003270373238773;
+  K = tan(pi * f0 / (double)rate);
+  a0 = 1.0 + K / Q + K * K;
+  p->s2_a[0] = 2.0 * (K * K - 1.0) / a0;
+  p->s2_a[1] = (1.0 - K / Q + K * K) / a0;
+  p->hop = rate / 10;
+  p->warm = 4096;
+  p->abs_gate = (uint64_t)floor(4.0 * (double)p->hop * 1073741824.0 * pow(10.0, -6.9309));
+  return BL_OK;
+}
+
+static double loud_limbs(const uint64_t s[2]) { return (double)s[1] * 18446744073709551616.0 + (double)s[0]; }
+/* -0.691 + 10 log10(sum / (count hops_per_block hop 2^30)); -inf for nothing */
+static double loud_lufs_of(double sum, double count, int hops_per_block, int hop) {
+  if (sum <= 0.0 || count <= 0.0) return -INFINITY;
+  return -0.691 + 10.0 * log10(sum / (count * (double)hops_per_block * (double)hop * 1073741824.0));
+}
+
+double bl_amd_loud_lufs(const bl_amd_song_loud *r, int hop) {
+  if (!r || hop < 1) return NAN;
+  return loud_lufs_of(loud_limbs(r->gated_sum), (double)r->gated_count, 4, hop);
+}
+
+double bl_amd_loud_momentary_max_lufs(const bl_amd_song_loud *r, int hop) {
+  if (!r || hop < 1) return NAN;
+  return loud_lufs_of((double)r->momentary_max, 1.0, 4, hop);
+}
+
+double bl_amd_loud_short_max_lufs(const bl_amd_song_loud *r, int hop) {
+  if (!r || hop < 1) return NAN;
+  return loud_lufs_of((double)r->st_max, 1.0, 30, hop);
+}
+
+double bl_amd_loud_range_lu(const bl_amd_song_loud *r) {
+  if (!r) return NAN;
+  if (r->st_gated < 1 || !r->lra_lo) return 0.0;
+  return 10.0 * log10((double)r->lra_hi / (double)r->lra_lo);
+}
+
+double bl_amd_loud_gain_db(const bl_amd_song_loud *r, int hop, double target_lufs) {
+  if (!r || hop < 1) return NAN;
+  return r->gated_count > 0 ? target_lufs - bl_amd_loud_lufs(r, hop) : 0.0;
+}
+
 /* ---- harmonic mixes: the host arithmetic of bl_amd_hmix_* (include/bliss_amd.h) ---- */
 
 static int hmix_rule_args_ok(int tempo_tol, int flags) {

@@ -124,6 +124,10 @@ int blr_analyze_device(bl_amd_ctx *c, const int16_t *d_pcm, const bl_amd_song_de
 int blr_resample_device(bl_amd_ctx *c, const void *d_in, int in_is_s32, const bl_amd_resample_desc *h_desc,
                         int n_songs, int in_rate, int16_t *d_out, hipStream_t s);
 
+/* bl_loud_api.hip: frees the loudness workspace of a context that is being released (ctx_release: the context held,
+ * its device current and idle) */
+void blr_loud_release(bl_amd_ctx *c);
+
 /* bl_host_batch.hip */
 /* host-memory batch on one context; pcm_is_s32: h_pcm[i] points at int32 samples that are
  * narrowed with >> 16 while they are staged.  in_rate: 0 / 22 050 = as is; another rate = the songs

@@ -25,6 +25,7 @@ TIMBRE_SONG_DTYPE = np.dtype(_lib.SongTimbre)
 TIMBRE_FRAME_DTYPE = np.dtype(_lib.FrameTimbre)
 RHYTHM_DTYPE = np.dtype(_lib.SongRhythm)
 BEATS_DTYPE = np.dtype(_lib.SongBeats)
+LOUD_DTYPE = np.dtype(_lib.SongLoud)
 CHROMA_DTYPE = np.dtype(_lib.SongChroma)
 FRAME_CHROMA_DTYPE = np.dtype(_lib.FrameChroma)
 MEL_DTYPE = np.dtype(_lib.SongMel)

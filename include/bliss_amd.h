@@ -692,6 +692,101 @@ int bl_amd_beats_host(const uint32_t *h_onsets, const int32_t *h_hops, int n_son
 int bl_amd_beats_list(const uint8_t *h_flags, int hops, int rate, int32_t *h_hop_out, double *h_sec_out, int cap);
 double bl_amd_beats_bpm(const bl_amd_song_beats *b, int rate);
 
+/* Loudness: the K-weighted, gated programme loudness of ITU-R BS.1770-4 / EBU R128 and the loudness range of EBU Tech
+ * 3342, the figure a player needs to level "B after A" (the reference's author lists "Loudness features" in ROADMAP.md;
+ * bl_amd_levels_* gives peak and plain RMS, which is not loudness).  The filter is f64 in a fixed operation order;
+ * everything behind it is exact integers.  One parameter record per call (bl_amd_loud_kweight fills it for a rate);
+ * per song F = n_samples / channels frames and H = F / hop whole hops; frames behind hop H-1 are never read.
+ *   1 chunks      chunk k covers hops [16 k, min(16 k + 16, H)).  Its filter starts from zero state at frame
+ *                 max(0, 16 k hop - warm) and runs serially to the chunk's end.  A chunk's output is a pure function of
+ *                 those frames: this cut is what makes the recurrence parallel, and it is part of the definition, not
+ *                 a launch detail.
+ *   2 filter      per channel, x = (double)sample; every product and sum rounded to f64, unfused, in this order, with
+ *                 the y[n-1] term last:
+ *                   v = ((((b0*x + b1*x1) + b2*x2) - a2*v2) - a1*v1)          (s1_b, s1_a; v1, v2: v of frames n-1, n-2)
+ *                   y = ((((v - (v1 + v1)) + v2) - A2*y2) - A1*y1)            (A = s2_a)
+ *                 f64 denormals are honoured (the state decays through them under digital silence).
+ *   3 hop energy  e = 0, then e = e + y*y in frame order over the hop's frames (warm-up frames contribute nothing);
+ *                 Z[c][h] = floor(e) as uint64.  With bl_amd_loud_kweight's coefficients the impulse response's l1
+ *                 norm is 3.23 / 3.33 / 3.34 at 22.05 / 44.1 / 48 kHz, so |y| < 2^16.8 and Z < 2^45.7 for hop <= 4800.
+ *                 For other coefficients the caller must keep |y| < 2^17 (Z < 2^46.3); nothing checks it.
+ *   4 blocks      P_j = sum over c and k < 4 of Z[c][j+k], j = 0 .. H-4: 400 ms blocks at a stride of one hop.  A mono
+ *                 song has one channel: as in BS.1770 and ebur128 it is not counted as dual mono.  P < 2^49.3.
+ *   5 gates       A = { j : P_j > abs_gate }, N1 = |A| (abs_count), S1 = sum over A of P_j (abs_sum);
+ *                 G = { j in A : P_j 10 N1 > S1 } (gated_count, gated_sum).  Strict product comparisons in 128 bits: no
+ *                 division on the device.  The sums are carried as two 64-bit limbs {lo, hi}: no sum wraps for any H.
+ *   6 short-term  ST_j = sum over c and k < 30 of Z[c][j+k], j = 0 .. H-30; st_max over every j.  For the range the
+ *                 starts are j = 0, 10, 20, ...: those with 2 ST > 15 abs_gate number N and sum to S; the survivors
+ *                 of ST 100 N > S (-20 LU) number M (st_gated).  Over the survivors in ascending order v[0 .. M-1]:
+ *                 lra_lo = v[(10 (M-1) + 50) / 100], lra_hi = v[(95 (M-1) + 50) / 100], the nearest-rank rule of Tech
+ *                 3342's reference code; M = 0 gives 0 for both.
+ * A song with H < 4 has blocks = 0 and all sums 0; it is no error of the call. */
+typedef struct bl_amd_loud_params {
+  double s1_b[3], s1_a[2]; /* stage 1 (shelf): b0 b1 b2, a1 a2 */
+  double s2_a[2];          /* stage 2 (high-pass): a1 a2; its numerator is 1 -2 1 by construction */
+  int32_t hop;             /* frames per hop (100 ms), 1 .. 4800 */
+  int32_t warm;            /* warm-up frames in front of a chunk, 0 .. 8192 */
+  uint64_t abs_gate;       /* threshold on a 4-hop block sum, < 2^56 */
+} bl_amd_loud_params;
+#define BL_AMD_LOUD_CHUNK 16 /* hops per chunk */
+typedef struct bl_amd_song_loud { /* 88 bytes */
+  uint64_t gated_sum[2];          /* sum over G of P_j: lo, hi */
+  uint64_t abs_sum[2];            /* S1: lo, hi */
+  uint64_t momentary_max, st_max; /* max P_j, max ST_j */
+  uint64_t lra_lo, lra_hi;
+  int32_t gated_count, abs_count, st_gated;
+  int32_t hops, blocks;           /* H, max(0, H - 3) */
+  int32_t status;                 /* BL_OK */
+} bl_amd_song_loud;
+/* bl_amd_loud_batch_device: the loudness of n_songs songs in the PCM arena d_pcm, laid out as for
+ * bl_amd_rhythm_batch_device: pcm_offset a multiple of 8, channels 1 | 2, n_samples >= 1, duration ignored.
+ * d_hops_out may be NULL (Z then stays in the context's workspace); otherwise it receives Z as uint64[n_hops][2], songs
+ * concatenated in the caller's order, channel 1 of a mono song 0, and n_hops must be the sum of H over the songs.
+ * Every byte of every record and of d_hops_out is written; nothing needs zeroing.  A rejected call returns
+ * BL_UNEXPECTED and writes nothing: a NULL required pointer, a misaligned pointer (d_pcm 16, the outputs 8 bytes),
+ * n_songs < 1, a bad song, hop, warm or abs_gate outside the ranges above, a coefficient that is not finite, a wrong
+ * n_hops, more than 2^30 chunks in all.  Asynchronous on `stream`; h_desc and params are copied before the call
+ * returns.  A song's outputs depend on nothing but its samples, channels and the params.
+ *   bl_amd_loud_batch_host: the same from host memory, blocking; h_hops_out may be NULL.
+ *   bl_amd_loud_from_hops: stages 4 to 6 alone on hop energies of the caller's in host memory, uint64[sum of
+ *     h_hops][2] laid out as d_hops_out, blocking; only params->abs_gate is read.  0 <= h_hops[i] <= 2^27; a value
+ *     >= 2^46 rejects the call.
+ * Host arithmetic, no device:
+ *   bl_amd_loud_kweight: the K-weighting by the usual bilinear design, K = tan(pi f0 / rate): the shelf with
+ *     f0 = 1681.974450955533 Hz, G = 3.999843853973347 dB, Q = 0.7071752369554196, Vb = Vh^0.4996667741545416, the
+ *     high-pass with f0 = 38.13547087602444 Hz, Q = 0.5003270373238773 (BS.1770-4's printed table at 48 000 Hz);
+ *     hop = rate / 10, warm = 4096, abs_gate = floor(4 hop 2^30 10^-6.9309) (-70 LUFS).  BL_UNEXPECTED for a rate
+ *     outside 8000 .. 48000 or no multiple of 10: above 48 kHz a warm-up of 4096 frames is no longer enough.
+ *   bl_amd_loud_lufs: -0.691 + 10 log10(gated_sum / (gated_count 4 hop 2^30)); -inf when gated_count is 0.
+ *   bl_amd_loud_momentary_max_lufs, bl_amd_loud_short_max_lufs: the same of momentary_max / (4 hop 2^30) and
+ *     st_max / (30 hop 2^30); -inf for 0.
+ *   bl_amd_loud_range_lu: 10 log10(lra_hi / lra_lo); 0 when st_gated is 0.
+ *   bl_amd_loud_gain_db: target_lufs - bl_amd_loud_lufs; 0 when gated_count is 0 (silence gets no gain).
+ *   Each returns NaN for a NULL record or hop < 1.
+ *   bl_amd_loud_profile_ms: the device time in milliseconds that k_loud_filter ("loud_filter") or k_loud_gate
+ *     ("loud_gate") took in the calls made while profiling was on (bl_amd_profile) since this function was last
+ *     asked for that name, and the number of launches; -1 for another name.  Waits for those kernels.
+ * The loudness keeps its workspace per context it has been called on (the records, Z of a call without d_hops_out,
+ * 8 bytes per short-term start); bl_amd_ctx_destroy frees it with the context.
+ * True peak (4x oversampling) is not computed. */
+int bl_amd_loud_batch_device(const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs,
+                             const bl_amd_loud_params *params, bl_amd_song_loud *d_songs_out, uint64_t *d_hops_out,
+                             long long n_hops, void *stream);
+int bl_amd_ctx_loud_batch_device(bl_amd_ctx *ctx, const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs,
+                                 const bl_amd_loud_params *params, bl_amd_song_loud *d_songs_out, uint64_t *d_hops_out,
+                                 long long n_hops, void *stream);
+int bl_amd_loud_batch_host(const int16_t *const *h_pcm, const int32_t *n_samples, const int32_t *channels, int n_songs,
+                           const bl_amd_loud_params *params, bl_amd_song_loud *h_songs_out, uint64_t *h_hops_out);
+int bl_amd_loud_from_hops(const uint64_t *h_hop_energy, const int32_t *h_hops, int n_songs,
+                          const bl_amd_loud_params *params, bl_amd_song_loud *h_songs_out);
+int bl_amd_loud_kweight(int rate, bl_amd_loud_params *params);
+double bl_amd_loud_lufs(const bl_amd_song_loud *r, int hop);
+double bl_amd_loud_momentary_max_lufs(const bl_amd_song_loud *r, int hop);
+double bl_amd_loud_short_max_lufs(const bl_amd_song_loud *r, int hop);
+double bl_amd_loud_range_lu(const bl_amd_song_loud *r);
+double bl_amd_loud_gain_db(const bl_amd_song_loud *r, int hop, double target_lufs);
+double bl_amd_loud_profile_ms(const char *name, int *launches);
+
 /* Chroma and key: how a song's energy spreads over the twelve pitch classes, and the major or minor key whose profile
  * fits that spread best ("same or compatible key next", the companion of the tempo).  The reference's author lists
  * "Chromagram / HPCP" in ROADMAP.md ("Tonal features"); none of it is in the reference's API.  The 512-point frames of
