@@ -101,6 +101,11 @@ class SongLoud(C.Structure):  # include/bliss_amd.h bl_amd_song_loud
                 ("status", C.c_int32)]
 
 
+class SongTpeak(C.Structure):  # include/bliss_amd.h bl_amd_song_tpeak
+    _fields_ = [("at", C.c_int64 * 2), ("overs", C.c_int64 * 2), ("tpeak", C.c_uint32 * 2), ("peak", C.c_int32 * 2),
+                ("frames", C.c_int32), ("status", C.c_int32)]
+
+
 class FrameChroma(C.Structure):  # include/bliss_amd.h bl_amd_frame_chroma
     _fields_ = [("x", C.c_uint64 * 12)]
 
@@ -301,6 +306,18 @@ SYMBOLS = {
     "bl_amd_loud_range_lu": (C.c_double, [_P(SongLoud)]),
     "bl_amd_loud_gain_db": (C.c_double, [_P(SongLoud), C.c_int, C.c_double]),
     "bl_amd_loud_profile_ms": (C.c_double, [C.c_char_p, _P(C.c_int)]),
+    "bl_amd_tpeak_batch_device": (C.c_int, [C.c_void_p, _P(SongDesc), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                            C.c_longlong, C.c_void_p]),
+    "bl_amd_ctx_tpeak_batch_device": (C.c_int, [C.c_void_p, C.c_void_p, _P(SongDesc), C.c_int, C.c_int, C.c_int,
+                                                C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "bl_amd_tpeak_batch_host": (C.c_int, [_P(C.c_void_p), _P(C.c_int32), _P(C.c_int32), C.c_int, C.c_int, C.c_int,
+                                          _P(SongTpeak), _P(C.c_uint32)]),
+    "bl_amd_tpeak_table": (None, [_P(C.c_int32)]),
+    "bl_amd_tpeak_shape": (None, [_P(C.c_int), _P(C.c_int)]),
+    "bl_amd_tpeak_dbtp": (C.c_double, [_P(SongTpeak), C.c_int]),
+    "bl_amd_tpeak_song_dbtp": (C.c_double, [_P(SongTpeak)]),
+    "bl_amd_tpeak_gain_db": (C.c_double, [_P(SongLoud), C.c_int, C.c_double, _P(SongTpeak), C.c_double]),
+    "bl_amd_tpeak_profile_ms": (C.c_double, [C.c_char_p, _P(C.c_int)]),
     "bl_amd_chroma_frames": (C.c_int, [C.c_int, C.c_int]),
     "bl_amd_chroma_batch_device": (C.c_int, [C.c_void_p, _P(SongDesc), C.c_int, C.c_void_p, C.c_void_p, C.c_longlong,
                                              C.c_void_p]),

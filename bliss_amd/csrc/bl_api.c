@@ -25,6 +25,7 @@
 
 #include "bl_chroma_table.h"
 #include "bl_mel_table.h"
+#include "bl_tpeak_table.h"
 #include "bl_device.h"
 #include "bliss.h"
 
@@ -388,6 +389,36 @@ double bl_amd_loud_range_lu(const bl_amd_song_loud *r) {
 double bl_amd_loud_gain_db(const bl_amd_song_loud *r, int hop, double target_lufs) {
   if (!r || hop < 1) return NAN;
   return r->gated_count > 0 ? target_lufs - bl_amd_loud_lufs(r, hop) : 0.0;
+}
+
+/* ---- true peak: the table and the host arithmetic over bl_amd_song_tpeak (include/bliss_amd.h) ---- */
+
+void bl_amd_tpeak_table(int32_t out[48]) {
+  if (!out) return;
+  for (int p = 0; p < BL_TPEAK_PHASES; ++p)
+    for (int k = 0; k < BL_TPEAK_TAPS; ++k) out[p * BL_TPEAK_TAPS + k] = BL_TPEAK_G[p][k];
+}
+
+/* 20 log10(tpeak / 2^29): 2^29 is a full-scale sample (2^15) through a unit-gain phase (2^14) */
+double bl_amd_tpeak_dbtp(const bl_amd_song_tpeak *tp, int channel) {
+  if (!tp || channel < 0 || channel > 1) return NAN;
+  if (!tp->tpeak[channel]) return -INFINITY;
+  return 20.0 * log10((double)tp->tpeak[channel] / 536870912.0);
+}
+
+double bl_amd_tpeak_song_dbtp(const bl_amd_song_tpeak *tp) {
+  if (!tp) return NAN;
+  const double a = bl_amd_tpeak_dbtp(tp, 0), b = bl_amd_tpeak_dbtp(tp, 1);
+  return a > b ? a : b;
+}
+
+double bl_amd_tpeak_gain_db(const bl_amd_song_loud *loud, int hop, double target_lufs, const bl_amd_song_tpeak *tp,
+                            double ceiling_dbtp) {
+  const double gain = bl_amd_loud_gain_db(loud, hop, target_lufs);
+  if (!tp || gain != gain) return NAN;
+  if (!tp->tpeak[0] && !tp->tpeak[1]) return gain; /* digital silence has no peak to hold the gain back */
+  const double room = ceiling_dbtp - bl_amd_tpeak_song_dbtp(tp);
+  return gain < room ? gain : room;
 }
 
 /* ---- harmonic mixes: the host arithmetic of bl_amd_hmix_* (include/bliss_amd.h) ---- */

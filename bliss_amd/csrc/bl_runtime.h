@@ -127,6 +127,8 @@ int blr_resample_device(bl_amd_ctx *c, const void *d_in, int in_is_s32, const bl
 /* bl_loud_api.hip: frees the loudness workspace of a context that is being released (ctx_release: the context held,
  * its device current and idle) */
 void blr_loud_release(bl_amd_ctx *c);
+/* bl_tpeak_api.hip: the same for the true-peak workspace */
+void blr_tpeak_release(bl_amd_ctx *c);
 
 /* bl_host_batch.hip */
 /* host-memory batch on one context; pcm_is_s32: h_pcm[i] points at int32 samples that are

@@ -26,6 +26,7 @@ TIMBRE_FRAME_DTYPE = np.dtype(_lib.FrameTimbre)
 RHYTHM_DTYPE = np.dtype(_lib.SongRhythm)
 BEATS_DTYPE = np.dtype(_lib.SongBeats)
 LOUD_DTYPE = np.dtype(_lib.SongLoud)
+TPEAK_DTYPE = np.dtype(_lib.SongTpeak)
 CHROMA_DTYPE = np.dtype(_lib.SongChroma)
 FRAME_CHROMA_DTYPE = np.dtype(_lib.FrameChroma)
 MEL_DTYPE = np.dtype(_lib.SongMel)

@@ -768,7 +768,7 @@ typedef struct bl_amd_song_loud { /* 88 bytes */
  *     asked for that name, and the number of launches; -1 for another name.  Waits for those kernels.
  * The loudness keeps its workspace per context it has been called on (the records, Z of a call without d_hops_out,
  * 8 bytes per short-term start); bl_amd_ctx_destroy frees it with the context.
- * True peak (4x oversampling) is not computed. */
+ * The true peak that goes with a gain is bl_amd_tpeak_* below. */
 int bl_amd_loud_batch_device(const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs,
                              const bl_amd_loud_params *params, bl_amd_song_loud *d_songs_out, uint64_t *d_hops_out,
                              long long n_hops, void *stream);
@@ -786,6 +786,68 @@ double bl_amd_loud_short_max_lufs(const bl_amd_song_loud *r, int hop);
 double bl_amd_loud_range_lu(const bl_amd_song_loud *r);
 double bl_amd_loud_gain_db(const bl_amd_song_loud *r, int hop, double target_lufs);
 double bl_amd_loud_profile_ms(const char *name, int *launches);
+
+/* True peak: how far the RECONSTRUCTED waveform goes above full scale, the figure ReplayGain 2.0 and EBU R128 pair with
+ * the loudness, because a gain to a target is safe only when it is known.  The sample peak of bl_amd_levels_* can be
+ * 3 dB short of it: a full-scale sine at a quarter of the rate, sampled at 45 degrees, has samples at -3.01 dBFS and a
+ * true peak at 0 dBTP.  As in ITU-R BS.1770 the signal is oversampled four times by a fixed interpolator; every
+ * quantity is an exact integer.  Per song F = n_samples / channels frames; per channel c, x_c[t] is the sample for
+ * 0 <= t < F and 0 elsewhere.  For 0 <= t < F and phase p = 0 .. 3
+ *   y_c[4t + p] = sum over j = -5 .. 6 of G[p][j + 5] * x_c[t + j]
+ * with the Q14 table G of bliss_amd/csrc/bl_tpeak_table.h (bl_amd_tpeak_table shows it): G[p][j + 5] =
+ * floor(2^14 w(m) sinc(m / 4) + 1/2), m = 4 j - p, w(m) = (1 + cos(pi m / 24)) / 2 for |m| < 24 and 0 otherwise: a
+ * Hann-windowed sinc of 12 taps per phase.  Phase 0 is the sample times 2^14, so a true peak is never below the sample
+ * peak: tpeak[c] >= peak[c] << 14.  The largest row l1 norm is 30 544, so |y| <= 30 544 * 32 768 < 2^30: full scale is
+ * 2^29, and the scale reaches 5.4 dB above it.  For a mono song every [1] entry is 0 and at[1] = -1. */
+typedef struct bl_amd_song_tpeak { /* 56 bytes */
+  int64_t at[2];     /* the smallest i with |y_c[i]| == tpeak[c]; -1 when F == 0 and for channel 1 of a mono song */
+  int64_t overs[2];  /* the number of i in [0, 4F) with |y_c[i]| > ceiling * 2^14 */
+  uint32_t tpeak[2]; /* max over i in [0, 4F) of |y_c[i]| */
+  int32_t peak[2];   /* max |x_c[t]|, 0 .. 32768 */
+  int32_t frames;    /* F */
+  int32_t status;    /* BL_OK */
+} bl_amd_song_tpeak;
+/* bl_amd_tpeak_batch_device: the true peak of n_songs songs in the PCM arena d_pcm, laid out as for
+ * bl_amd_loud_batch_device: pcm_offset a multiple of 8, channels 1 | 2, n_samples >= 1, duration ignored.
+ * 0 <= ceiling <= 65535 (in sample units: 32767 counts the points above full scale) and 1 <= block <= 65536; both are
+ * always validated.  d_blocks_out may be NULL (n_blocks is then ignored); otherwise it receives the profile as
+ * uint32[n_blocks][2], songs concatenated in the caller's order: block b of a song is max |y_c[i]| over
+ * 4 b block <= i < 4 min(F, (b + 1) block), channel 1 of a mono song 0, and n_blocks must be the sum of
+ * ceil(F / block) over the songs.  It is a meter's or limiter's input.  Every byte of every record and of d_blocks_out
+ * is written; nothing needs zeroing.  A rejected call returns BL_UNEXPECTED and writes nothing: a NULL required
+ * pointer, a misaligned pointer (d_pcm 16, the records 8, the blocks 4 bytes), n_songs < 1, a bad song, ceiling or
+ * block, a wrong n_blocks.  Asynchronous on `stream`; h_desc is copied before the call returns.  A song's outputs are a
+ * pure function of its samples, channels, ceiling and block: they depend neither on the other songs, nor on n_songs,
+ * nor on the launch grid, and no sample outside [pcm_offset, pcm_offset + n_samples) is read.
+ *   bl_amd_tpeak_batch_host: the same from host memory, blocking; h_blocks_out may be NULL.
+ * Host arithmetic, no device:
+ *   bl_amd_tpeak_table: G, row-major, 48 values.
+ *   bl_amd_tpeak_shape: the frames one lane and one workgroup of the kernel own (16 and 4 096): the lengths at which
+ *     its paths change, for tests.
+ *   bl_amd_tpeak_dbtp: 20 log10(tpeak[channel] / 2^29) in dBTP; -inf for 0, NaN for a NULL record or a channel outside
+ *     [0, 1].  bl_amd_tpeak_song_dbtp: the larger of the two channels.
+ *   bl_amd_tpeak_gain_db: min(bl_amd_loud_gain_db(loud, hop, target_lufs), ceiling_dbtp - bl_amd_tpeak_song_dbtp(tp)):
+ *     the gain to the target, held back where it would lift the true peak above ceiling_dbtp.  The loudness gain alone
+ *     when both tpeak are 0; NaN for a NULL record or hop < 1.
+ *   bl_amd_tpeak_profile_ms: as bl_amd_loud_profile_ms, for k_tpeak_scan ("tpeak_scan") and k_tpeak_finish
+ *     ("tpeak_finish").
+ * The true peak keeps its workspace per context it has been called on (the songs' records and 48 bytes per song);
+ * bl_amd_ctx_destroy frees it with the context. */
+int bl_amd_tpeak_batch_device(const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs, int ceiling, int block,
+                              bl_amd_song_tpeak *d_songs_out, uint32_t *d_blocks_out, long long n_blocks,
+                              void *stream);
+int bl_amd_ctx_tpeak_batch_device(bl_amd_ctx *ctx, const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs,
+                                  int ceiling, int block, bl_amd_song_tpeak *d_songs_out, uint32_t *d_blocks_out,
+                                  long long n_blocks, void *stream);
+int bl_amd_tpeak_batch_host(const int16_t *const *h_pcm, const int32_t *n_samples, const int32_t *channels, int n_songs,
+                            int ceiling, int block, bl_amd_song_tpeak *h_songs_out, uint32_t *h_blocks_out);
+void bl_amd_tpeak_table(int32_t out[48]);
+void bl_amd_tpeak_shape(int *frames_per_lane, int *frames_per_group);
+double bl_amd_tpeak_dbtp(const bl_amd_song_tpeak *tp, int channel);
+double bl_amd_tpeak_song_dbtp(const bl_amd_song_tpeak *tp);
+double bl_amd_tpeak_gain_db(const bl_amd_song_loud *loud, int hop, double target_lufs, const bl_amd_song_tpeak *tp,
+                            double ceiling_dbtp);
+double bl_amd_tpeak_profile_ms(const char *name, int *launches);
 
 /* Chroma and key: how a song's energy spreads over the twelve pitch classes, and the major or minor key whose profile
  * fits that spread best ("same or compatible key next", the companion of the tempo).  The reference's author lists
