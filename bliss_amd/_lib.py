@@ -106,6 +106,11 @@ class SongTpeak(C.Structure):  # include/bliss_amd.h bl_amd_song_tpeak
                 ("frames", C.c_int32), ("status", C.c_int32)]
 
 
+class FprintMatch(C.Structure):  # include/bliss_amd.h bl_amd_fprint_match
+    _fields_ = [("errors", C.c_uint32), ("overlap", C.c_uint32), ("offset", C.c_int32), ("score", C.c_uint32),
+                ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
 class FrameChroma(C.Structure):  # include/bliss_amd.h bl_amd_frame_chroma
     _fields_ = [("x", C.c_uint64 * 12)]
 
@@ -318,6 +323,23 @@ SYMBOLS = {
     "bl_amd_tpeak_song_dbtp": (C.c_double, [_P(SongTpeak)]),
     "bl_amd_tpeak_gain_db": (C.c_double, [_P(SongLoud), C.c_int, C.c_double, _P(SongTpeak), C.c_double]),
     "bl_amd_tpeak_profile_ms": (C.c_double, [C.c_char_p, _P(C.c_int)]),
+    "bl_amd_fprint_words": (C.c_int, [C.c_int]),
+    "bl_amd_fprint_words_device": (C.c_int, [C.c_void_p, _P(C.c_int32), C.c_int, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "bl_amd_ctx_fprint_words_device": (C.c_int, [C.c_void_p, C.c_void_p, _P(C.c_int32), C.c_int, C.c_void_p,
+                                                 C.c_longlong, C.c_void_p]),
+    "bl_amd_fprint_words_host": (C.c_int, [C.c_void_p, _P(C.c_int32), C.c_int, C.c_void_p]),
+    "bl_amd_fprint_match_device": (C.c_int, [C.c_void_p, _P(C.c_int32), C.c_int, C.c_void_p, _P(C.c_int32), C.c_int,
+                                             C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                             C.c_void_p]),
+    "bl_amd_ctx_fprint_match_device": (C.c_int, [C.c_void_p, C.c_void_p, _P(C.c_int32), C.c_int, C.c_void_p,
+                                                 _P(C.c_int32), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bl_amd_fprint_match_host": (C.c_int, [C.c_void_p, _P(C.c_int32), C.c_int, C.c_void_p, _P(C.c_int32), C.c_int,
+                                           C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "bl_amd_fprint_shape": (None, [C.c_int, _P(C.c_int), _P(C.c_int), _P(C.c_int), _P(C.c_int)]),
+    "bl_amd_fprint_ber": (C.c_double, [_P(FprintMatch)]),
+    "bl_amd_fprint_offset_seconds": (C.c_double, [_P(FprintMatch), C.c_int]),
+    "bl_amd_fprint_profile_ms": (C.c_double, [C.c_char_p, _P(C.c_int)]),
     "bl_amd_chroma_frames": (C.c_int, [C.c_int, C.c_int]),
     "bl_amd_chroma_batch_device": (C.c_int, [C.c_void_p, _P(SongDesc), C.c_int, C.c_void_p, C.c_void_p, C.c_longlong,
                                              C.c_void_p]),

@@ -421,6 +421,23 @@ double bl_amd_tpeak_gain_db(const bl_amd_song_loud *loud, int hop, double target
   return gain < room ? gain : room;
 }
 
+/* ---- fingerprints: the host arithmetic over bl_amd_fprint_match (include/bliss_amd.h) ---- */
+
+int bl_amd_fprint_words(int frames) {
+  if (frames < 0) return -1;
+  return frames >= BL_AMD_FPRINT_FRAMES ? frames - (BL_AMD_FPRINT_FRAMES - 1) : 0;
+}
+
+double bl_amd_fprint_ber(const bl_amd_fprint_match *m) {
+  if (!m || m->status != BL_OK || !m->overlap) return NAN;
+  return (double)m->errors / (32.0 * (double)m->overlap);
+}
+
+double bl_amd_fprint_offset_seconds(const bl_amd_fprint_match *m, int rate) {
+  if (!m || m->status != BL_OK || rate < 1) return NAN;
+  return (double)m->offset * (double)BL_AMD_CHROMA_HOP / (double)rate;
+}
+
 /* ---- harmonic mixes: the host arithmetic of bl_amd_hmix_* (include/bliss_amd.h) ---- */
 
 static int hmix_rule_args_ok(int tempo_tol, int flags) {

@@ -129,6 +129,8 @@ int blr_resample_device(bl_amd_ctx *c, const void *d_in, int in_is_s32, const bl
 void blr_loud_release(bl_amd_ctx *c);
 /* bl_tpeak_api.hip: the same for the true-peak workspace */
 void blr_tpeak_release(bl_amd_ctx *c);
+/* bl_fprint_api.hip: the same for the fingerprints' workspace */
+void blr_fprint_release(bl_amd_ctx *c);
 
 /* bl_host_batch.hip */
 /* host-memory batch on one context; pcm_is_s32: h_pcm[i] points at int32 samples that are

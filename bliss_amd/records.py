@@ -27,6 +27,7 @@ RHYTHM_DTYPE = np.dtype(_lib.SongRhythm)
 BEATS_DTYPE = np.dtype(_lib.SongBeats)
 LOUD_DTYPE = np.dtype(_lib.SongLoud)
 TPEAK_DTYPE = np.dtype(_lib.SongTpeak)
+FPRINT_MATCH_DTYPE = np.dtype(_lib.FprintMatch)
 CHROMA_DTYPE = np.dtype(_lib.SongChroma)
 FRAME_CHROMA_DTYPE = np.dtype(_lib.FrameChroma)
 MEL_DTYPE = np.dtype(_lib.SongMel)

@@ -925,6 +925,91 @@ int bl_amd_chroma_batch_host(const int16_t *const *h_pcm, const int32_t *n_sampl
 int bl_amd_chroma_table(int8_t *re, int8_t *im, uint32_t *gain, int32_t *len);
 int bl_amd_chroma_key_name(int key, char out[8]);
 
+/* Fingerprints and offset matching: whether two files are the same recording, and how far one starts before the other.
+ * The duplicate groups of bl_amd_groups_* are candidates (two different songs can share a force vector; a re-encode or
+ * two seconds more lead-in move it by an unknown amount); a fingerprint settles them.  It is one 32-bit word per chroma
+ * frame, made of comparisons of sums of the chromagram only, so a gain change cancels except through the chroma
+ * stage's own flooring.  Every quantity is an exact integer.
+ *   words    A song with T chroma frames X_t[0 .. 11] (bl_amd_frame_chroma) has W = max(0, T - 15) words.  Word t is
+ *            built from frames t .. t + 15; per pitch class k: S1[k] = sum of X[k] over frames t .. t + 7, S2[k] the
+ *            same over t + 8 .. t + 15, A[k] = S1[k] + S2[k].  X < 2^39.2, so every sum below is under 2^45.  All
+ *            comparisons are strict: a tie is 0 and a silent window is the word 0.
+ *              bit k,      k = 0 .. 11: S2[k] > S1[k]                                       (is the class rising?)
+ *              bit 12 + k, k = 0 .. 11: A[k] > A[(k + 1) % 12]                              (spectral slope, wrapping)
+ *              bit 24 + k, k = 0 .. 7:  S1[k] + S2[(k + 1) % 12] > S2[k] + S1[(k + 1) % 12] (checkerboard)
+ *   match    Word sequences a (Wa words) and b (Wb words), an offset d in [-D, D], D = max_shift: the overlap is the i
+ *            with 0 <= i < Wa and 0 <= i + d < Wb, n(d) its size, e(d) = sum over it of popcount(a[i] ^ b[i + d]).
+ *            An offset is a candidate when n(d) >= min_overlap (>= 1, so an empty overlap never is).  s(d) =
+ *            floor(e(d) 65536 / n(d)) (<= 2^21), r(d) = 2 |d| - (d < 0) (0, -1, +1, -2, .. in that order); the best
+ *            offset is the candidate with the smallest 64-bit key s(d) 2^32 + r(d): fewest errors per word, then the
+ *            smallest shift, then the negative one.  A positive d means b carries d more words of lead-in than a: a
+ *            copy of a with its first 5 hops cut off matches at d = -5.
+ * Bounds: T < 2^20, so e < 2^25; D <= BL_AMD_FPRINT_SHIFT_MAX (about 95 s). */
+#define BL_AMD_FPRINT_FRAMES 16
+#define BL_AMD_FPRINT_SHIFT_MAX 1024
+typedef struct bl_amd_fprint_match { /* 24 bytes */
+  uint32_t errors;  /* e(d) of the best offset */
+  uint32_t overlap; /* n(d) */
+  int32_t offset;   /* d */
+  uint32_t score;   /* s(d) */
+  int32_t status;   /* BL_OK; BL_UNEXPECTED when no offset is a candidate or a pair index lies outside its set: score
+                       0xFFFFFFFF, errors, overlap, offset 0 */
+  int32_t reserved; /* 0 */
+} bl_amd_fprint_match;
+/* bl_amd_fprint_words: W of a song with `frames` chroma frames, plain host arithmetic; -1 for frames < 0.
+ * bl_amd_fprint_words_device: the words of n_songs songs.  d_frames is what bl_amd_chroma_batch_device wrote: the
+ *   songs' frame records concatenated, song i at the sum of T_j over j < i, h_frames[i] = T_i (0 <= T_i < 2^20).  The
+ *   words are concatenated the same way, song i at the sum of W_j over j < i, and n_words must equal the sum of all
+ *   W_j (it may be 0; d_words_out is needed all the same).  Every word is written; nothing needs zeroing.  A song's
+ *   words depend on its own frames only; no frame of another song is read.
+ * bl_amd_fprint_words_host: the same from host memory, blocking.
+ * bl_amd_fprint_match_device: one record per pair.  Set a is n_a songs' words concatenated (d_words_a, h_count_a[i]
+ *   words each, 0 <= count < 2^20), set b likewise; the self form passes one set twice.  d_pairs is n_pairs x 2 int32
+ *   on the device: an index into set a, then one into set b; the kernel range-checks them (see status) and reads
+ *   nothing through a bad one.  0 <= max_shift <= BL_AMD_FPRINT_SHIFT_MAX, min_overlap >= 1.  d_profile_out may be
+ *   NULL; otherwise it receives (e(d), n(d)) as two uint32 for every pair and every d = -D .. D, non-candidates
+ *   included: n_pairs (2 D + 1) 2 values, all 0 for a pair with a bad index.  Every byte of every record and of the
+ *   profile is written.  A pair's record depends on its two sequences, max_shift and min_overlap only: not on the other
+ *   pairs, their order, n_pairs, the launch shape or whether the profile is asked for; no word outside the two
+ *   sequences is read.
+ * bl_amd_fprint_match_host: the same with everything in host memory, blocking.
+ * A rejected call returns BL_UNEXPECTED and writes nothing: a NULL required pointer, a misaligned pointer (the frame
+ * records 8, everything else 4 bytes), n_songs, n_a, n_b or n_pairs < 1, a count outside [0, 2^20), a wrong n_words,
+ * max_shift or min_overlap out of range.  The device forms are asynchronous on `stream`; the host arrays are copied
+ * before the call returns.  The fingerprints keep their workspace per context they have been called on (32 bytes per
+ * song of a words call, 16 per song of the two sets of a match); bl_amd_ctx_destroy frees it with the context.
+ * Host arithmetic, no device:
+ *   bl_amd_fprint_shape: the lengths at which the kernels change path, for tests: the words one workgroup of the words
+ *     kernel owns (256); for the match at max_shift (clamped to its range) the words of `a` a lane walks per tile (64),
+ *     the words of `a` per tile (64 to 2 048) and the offsets a workgroup takes at a time (a multiple of 4).  Any
+ *     pointer may be NULL.  The match has one launch shape.
+ *   bl_amd_fprint_ber: errors / (32 overlap), the bit-error rate at the best offset; NaN for a NULL record or a failed
+ *     status.
+ *   bl_amd_fprint_offset_seconds: offset 2048 / rate; NaN for a NULL record, a failed status or rate < 1.
+ *   bl_amd_fprint_profile_ms: as bl_amd_tpeak_profile_ms, for k_fprint_words ("fprint_words") and k_fprint_match
+ *     ("fprint_match"). */
+int bl_amd_fprint_words(int frames);
+int bl_amd_fprint_words_device(const bl_amd_frame_chroma *d_frames, const int32_t *h_frames, int n_songs,
+                               uint32_t *d_words_out, long long n_words, void *stream);
+int bl_amd_ctx_fprint_words_device(bl_amd_ctx *ctx, const bl_amd_frame_chroma *d_frames, const int32_t *h_frames,
+                                   int n_songs, uint32_t *d_words_out, long long n_words, void *stream);
+int bl_amd_fprint_words_host(const bl_amd_frame_chroma *h_frame_records, const int32_t *h_frames, int n_songs,
+                             uint32_t *h_words_out);
+int bl_amd_fprint_match_device(const uint32_t *d_words_a, const int32_t *h_count_a, int n_a, const uint32_t *d_words_b,
+                               const int32_t *h_count_b, int n_b, const int32_t *d_pairs, int n_pairs, int max_shift,
+                               int min_overlap, bl_amd_fprint_match *d_out, uint32_t *d_profile_out, void *stream);
+int bl_amd_ctx_fprint_match_device(bl_amd_ctx *ctx, const uint32_t *d_words_a, const int32_t *h_count_a, int n_a,
+                                   const uint32_t *d_words_b, const int32_t *h_count_b, int n_b,
+                                   const int32_t *d_pairs, int n_pairs, int max_shift, int min_overlap,
+                                   bl_amd_fprint_match *d_out, uint32_t *d_profile_out, void *stream);
+int bl_amd_fprint_match_host(const uint32_t *h_words_a, const int32_t *h_count_a, int n_a, const uint32_t *h_words_b,
+                             const int32_t *h_count_b, int n_b, const int32_t *h_pairs, int n_pairs, int max_shift,
+                             int min_overlap, bl_amd_fprint_match *h_out, uint32_t *h_profile_out);
+void bl_amd_fprint_shape(int max_shift, int *words_block, int *strip_words, int *tile_words, int *chunk_offsets);
+double bl_amd_fprint_ber(const bl_amd_fprint_match *m);
+double bl_amd_fprint_offset_seconds(const bl_amd_fprint_match *m, int rate);
+double bl_amd_fprint_profile_ms(const char *name, int *launches);
+
 /* Mel bands, cepstrum and flatness: the shape of every frame's spectrum.  The centroid and the rolloff of the timbre
  * block say where a frame's power sits and where it stops; the 32 log-mel band levels say how it is spread, the 13
  * cepstral coefficients (MFCC) are the usual compact description of that spread, and the flatness tells noise from
