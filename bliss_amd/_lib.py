@@ -111,6 +111,17 @@ class FprintMatch(C.Structure):  # include/bliss_amd.h bl_amd_fprint_match
                 ("status", C.c_int32), ("reserved", C.c_int32)]
 
 
+class FormParams(C.Structure):  # include/bliss_amd.h bl_amd_form_params
+    _fields_ = [("pool", C.c_int32), ("seg", C.c_int32), ("min_lag", C.c_int32), ("nov", C.c_int32),
+                ("peak_num", C.c_int32), ("peak_den", C.c_int32), ("reserved", C.c_int32)]
+
+
+class SongForm(C.Structure):  # include/bliss_amd.h bl_amd_song_form
+    _fields_ = [("units", C.c_int32), ("status", C.c_int32), ("thumb_start", C.c_int32), ("thumb_lag", C.c_int32),
+                ("thumb_score", C.c_uint32), ("thumb_self", C.c_uint32), ("boundaries", C.c_int32),
+                ("nov_max_unit", C.c_int32), ("nov_max", C.c_uint64), ("reserved", C.c_uint64)]
+
+
 class FrameChroma(C.Structure):  # include/bliss_amd.h bl_amd_frame_chroma
     _fields_ = [("x", C.c_uint64 * 12)]
 
@@ -340,6 +351,17 @@ SYMBOLS = {
     "bl_amd_fprint_ber": (C.c_double, [_P(FprintMatch)]),
     "bl_amd_fprint_offset_seconds": (C.c_double, [_P(FprintMatch), C.c_int]),
     "bl_amd_fprint_profile_ms": (C.c_double, [C.c_char_p, _P(C.c_int)]),
+    "bl_amd_form_device": (C.c_int, [C.c_void_p, _P(C.c_int32), C.c_int, _P(FormParams), C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "bl_amd_ctx_form_device": (C.c_int, [C.c_void_p, C.c_void_p, _P(C.c_int32), C.c_int, _P(FormParams), C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "bl_amd_form_host": (C.c_int, [C.c_void_p, _P(C.c_int32), C.c_int, _P(FormParams), C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bl_amd_form_units": (C.c_int, [C.c_int, C.c_int]),
+    "bl_amd_form_seconds": (C.c_double, [C.c_int, C.c_int, C.c_int]),
+    "bl_amd_form_score": (C.c_double, [_P(SongForm)]),
+    "bl_amd_form_shape": (None, [_P(C.c_int), _P(C.c_int)]),
+    "bl_amd_form_profile_ms": (C.c_double, [C.c_char_p, _P(C.c_int)]),
     "bl_amd_chroma_frames": (C.c_int, [C.c_int, C.c_int]),
     "bl_amd_chroma_batch_device": (C.c_int, [C.c_void_p, _P(SongDesc), C.c_int, C.c_void_p, C.c_void_p, C.c_longlong,
                                              C.c_void_p]),

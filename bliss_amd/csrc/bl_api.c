@@ -438,6 +438,23 @@ double bl_amd_fprint_offset_seconds(const bl_amd_fprint_match *m, int rate) {
   return (double)m->offset * (double)BL_AMD_CHROMA_HOP / (double)rate;
 }
 
+/* ---- song structure: the host arithmetic over bl_amd_song_form (include/bliss_amd.h) ---- */
+
+int bl_amd_form_units(int frames, int pool) {
+  if (frames < 0 || pool < 1 || pool > 16) return -1;
+  return frames / pool;
+}
+
+double bl_amd_form_seconds(int unit, int pool, int rate) {
+  if (unit < 0 || pool < 1 || pool > 16 || rate < 1) return NAN;
+  return (double)unit * (double)pool * (double)BL_AMD_CHROMA_HOP / (double)rate;
+}
+
+double bl_amd_form_score(const bl_amd_song_form *f) {
+  if (!f || (f->status & BL_AMD_FORM_NO_THUMB) || !f->thumb_self) return NAN;
+  return (double)f->thumb_score / (double)f->thumb_self;
+}
+
 /* ---- harmonic mixes: the host arithmetic of bl_amd_hmix_* (include/bliss_amd.h) ---- */
 
 static int hmix_rule_args_ok(int tempo_tol, int flags) {

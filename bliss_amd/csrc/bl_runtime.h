@@ -131,6 +131,8 @@ void blr_loud_release(bl_amd_ctx *c);
 void blr_tpeak_release(bl_amd_ctx *c);
 /* bl_fprint_api.hip: the same for the fingerprints' workspace */
 void blr_fprint_release(bl_amd_ctx *c);
+/* bl_form_api.hip: the same for the song structure's workspace */
+void blr_form_release(bl_amd_ctx *c);
 
 /* bl_host_batch.hip */
 /* host-memory batch on one context; pcm_is_s32: h_pcm[i] points at int32 samples that are

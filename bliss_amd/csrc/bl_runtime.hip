@@ -118,6 +118,7 @@ void ctx_release(bl_amd_ctx *c) {
   blr_loud_release(c);
   blr_tpeak_release(c);
   blr_fprint_release(c);
+  blr_form_release(c);
   bl_buf *bufs[] = {&c->songs,   &c->stats,   &c->hist, &c->spectrum, &c->energies, &c->lc,
                     &c->results, &c->arena[0], &c->arena[1], &c->arena22[0], &c->arena22[1],
                     &c->rs_songs, &c->rs_bank, &c->mx_my, &c->mx_gath, &c->mx_all, &c->mx_order, &c->mx_rows, &c->knn, &c->chain, &c->radius, &c->level_songs, &c->timbre_songs,

@@ -1010,6 +1010,99 @@ double bl_amd_fprint_ber(const bl_amd_fprint_match *m);
 double bl_amd_fprint_offset_seconds(const bl_amd_fprint_match *m, int rate);
 double bl_amd_fprint_profile_ms(const char *name, int *launches);
 
+/* Song structure: where the part that comes back is, and where the sections change.  Tempo, key, loudness and
+ * fingerprints describe a whole song or line two songs up; this block looks inside one song.  It reads the chroma frames
+ * (the feature the thumbnailing method of Bartsch and Wakefield, "To catch a chorus", 2001, is defined on) and gives
+ * the start and lag of the most strongly repeated stretch of a chosen length, as sums along the diagonals of the
+ * self-similarity matrix, and a checkerboard novelty curve (Foote) with the section boundaries picked from it.  All
+ * quantities are integers.  No result depends on launch shape, reduction order, batch composition, or which optional
+ * outputs are requested.
+ *   input    As for bl_amd_fprint_words_device: d_frames holds the songs' chroma frame records concatenated, song i at
+ *            the sum of T_j over j < i, h_frames[i] = T_i, 0 <= T_i < 2^20; X_t[k] < 2^39.2 by the chroma block's bound.
+ *   params   bl_amd_form_params, passed by pointer: pool P in 1 .. 16, seg M in 2 .. 1024, min_lag in 1 ..
+ *            BL_AMD_FORM_UNITS_MAX, nov L in 1 .. 64, 0 <= peak_num <= peak_den, 1 <= peak_den <= 256, reserved 0.
+ *   units    U = floor(T / P); trailing frames that do not fill a unit are dropped.  For unit u: Y[k] = sum over j < P
+ *            of X_{uP+j}[k] (below 2^43.2); m = max over k of Y[k].  m = 0: the unit is silent, q_u = 0.  Otherwise
+ *            s = max(0, bitlength(m) - 20), y[k] = Y[k] >> s (below 2^20), r = bl_isqrt64(sum of y[k]^2) (the sum is
+ *            below 2^44, r >= 1), q_u[k] = floor(127 y[k] / r), in 0 .. 127.  A unit is 16 bytes: the twelve q as int8
+ *            and four zero bytes.  The similarity is S(u, v) = sum over k of q_u[k] q_v[k], 0 <= S <= 16129.
+ *   thumb    With minlag = min_lag: lags l run over [minlag, U - M], starts u over [0, U - M - l], and
+ *            F(u, l) = sum over j < M of S(u + j, u + l + j), below 2^24.  The song's thumbnail is the pair with the
+ *            largest 64-bit key F 2^40 + (2^20 - 1 - l) 2^20 + (2^20 - 1 - u): the most similar pair of stretches, then
+ *            the smaller lag, then the earlier start.  If U < M + minlag, or the best F is 0, the song has no
+ *            thumbnail: status has BL_AMD_FORM_NO_THUMB and the four thumbnail fields are 0.  thumb_self = sum over
+ *            j < M of S(u* + j, u* + j), so that thumb_score / thumb_self is a figure near 0 .. 1.  Optional per-unit
+ *            output rep[u] = (R, l), two uint32: R the largest F(u, l) over the valid l, l the smallest lag that
+ *            reaches it; (0, 0) where no l is valid or R = 0.
+ *   novelty  Weights w_a = L + 1 - a for a = 1 .. L.  For u in [L, U - L]: P_u[k] = sum over a of w_a q_{u-a}[k],
+ *            G_u[k] = sum over a of w_a q_{u+a-1}[k], N(u) = sum over k of (P_u[k] - G_u[k])^2: Foote's checkerboard
+ *            kernel with a separable triangular taper, which collapses to the squared distance between the tapered sum
+ *            of the L units before u and of the L units from u on.  Each component is below 2^19, N < 2^40, a uint64.
+ *            N(u) = 0 for u outside that range.  Nmax is the largest value, nov_max_unit the first u that attains it
+ *            (0 when Nmax = 0).  Unit u is a boundary when N(u) > 0, N(u) peak_den >= Nmax peak_num, N(v) < N(u) for v
+ *            in [u - L, u) and N(v) <= N(u) for v in (u, u + L], both ranges clipped to [0, U): the first unit of a
+ *            plateau wins.
+ *   limits   BL_AMD_FORM_UNITS_MAX = 8192: 16 bytes x 8 192 = 128 KB, one song's units in one workgroup's LDS.  A song
+ *            with more units has status BL_AMD_FORM_TOO_LONG | BL_AMD_FORM_NO_THUMB and every other field 0 but
+ *            `units`; its units are written, its rep, novelty and flags are 0.  The call still succeeds for the
+ *            others.  Callers pool such songs with a larger P. */
+#define BL_AMD_FORM_UNITS_MAX 8192
+#define BL_AMD_FORM_NO_THUMB 1
+#define BL_AMD_FORM_TOO_LONG 2
+typedef struct bl_amd_form_params { /* 28 bytes */
+  int32_t pool;     /* P */
+  int32_t seg;      /* M */
+  int32_t min_lag;  /* minlag */
+  int32_t nov;      /* L */
+  int32_t peak_num, peak_den;
+  int32_t reserved; /* must be 0 */
+} bl_amd_form_params;
+typedef struct bl_amd_song_form { /* 48 bytes, every byte written for every song */
+  int32_t units;        /* U, whatever the status: the song's share of the per-unit outputs */
+  int32_t status;       /* 0, or the OR of BL_AMD_FORM_NO_THUMB and BL_AMD_FORM_TOO_LONG */
+  int32_t thumb_start;  /* u* */
+  int32_t thumb_lag;    /* l* */
+  uint32_t thumb_score; /* F(u*, l*) */
+  uint32_t thumb_self;
+  int32_t boundaries;   /* the number of boundary units */
+  int32_t nov_max_unit;
+  uint64_t nov_max;     /* Nmax */
+  uint64_t reserved;    /* 0 */
+} bl_amd_song_form;
+/* bl_amd_form_device: one record per song in d_out.  The optional outputs may each be NULL; each is concatenated at the
+ *   sum of U_j over j < i and every element is written: d_units_out (16 bytes per unit), d_rep_out (2 x uint32 per
+ *   unit), d_nov_out (uint64 per unit), d_flags_out (uint8 per unit, bit 0 = boundary).  n_units is always passed and
+ *   must equal the sum of all U_j (it may be 0).  No unit or frame of another song is read.  Asynchronous on `stream`;
+ *   the host arrays and the parameters are copied before the call returns.
+ * bl_amd_ctx_form_device: the same on an explicit context.  bl_amd_form_host: everything in host memory, blocking.
+ * A rejected call returns BL_UNEXPECTED and writes nothing: a NULL required pointer (frames, counts, parameters,
+ * records), a misaligned pointer (frame records, novelty and records 8 bytes, units 16, rep 4), n_songs < 1, a count
+ * outside [0, 2^20), a wrong n_units, any parameter out of range, a reserved word that is not 0.  The workspace is kept
+ * per context (32 bytes per song, and 16 or 8 bytes per unit where the units or the novelty are not asked for);
+ * bl_amd_ctx_destroy frees it with the context.
+ * Host arithmetic, no device:
+ *   bl_amd_form_units: U = floor(frames / pool); -1 for frames < 0 or pool outside 1 .. 16.
+ *   bl_amd_form_seconds: unit pool 2048 / rate, the time at which a unit starts; NaN for unit < 0, a bad pool, rate < 1.
+ *   bl_amd_form_score: thumb_score / thumb_self; NaN for a NULL record, one without a thumbnail or thumb_self = 0.
+ *   bl_amd_form_shape: the lengths at which the kernels change path, for tests: the lags one workgroup of the thumbnail
+ *     kernel takes at a time, and the units one workgroup of the units kernel owns.  Either pointer may be NULL.
+ *   bl_amd_form_profile_ms: as bl_amd_fprint_profile_ms, for "form_units", "form_thumb" and "form_novelty". */
+int bl_amd_form_device(const bl_amd_frame_chroma *d_frames, const int32_t *h_frames, int n_songs,
+                       const bl_amd_form_params *params, bl_amd_song_form *d_out, void *d_units_out,
+                       uint32_t *d_rep_out, uint64_t *d_nov_out, uint8_t *d_flags_out, long long n_units, void *stream);
+int bl_amd_ctx_form_device(bl_amd_ctx *ctx, const bl_amd_frame_chroma *d_frames, const int32_t *h_frames, int n_songs,
+                           const bl_amd_form_params *params, bl_amd_song_form *d_out, void *d_units_out,
+                           uint32_t *d_rep_out, uint64_t *d_nov_out, uint8_t *d_flags_out, long long n_units,
+                           void *stream);
+int bl_amd_form_host(const bl_amd_frame_chroma *h_frame_records, const int32_t *h_frames, int n_songs,
+                     const bl_amd_form_params *params, bl_amd_song_form *h_out, void *h_units_out, uint32_t *h_rep_out,
+                     uint64_t *h_nov_out, uint8_t *h_flags_out);
+int bl_amd_form_units(int frames, int pool);
+double bl_amd_form_seconds(int unit, int pool, int rate);
+double bl_amd_form_score(const bl_amd_song_form *f);
+void bl_amd_form_shape(int *chunk_lags, int *units_block);
+double bl_amd_form_profile_ms(const char *name, int *launches);
+
 /* Mel bands, cepstrum and flatness: the shape of every frame's spectrum.  The centroid and the rolloff of the timbre
  * block say where a frame's power sits and where it stops; the 32 log-mel band levels say how it is spread, the 13
  * cepstral coefficients (MFCC) are the usual compact description of that spread, and the flatness tells noise from
