@@ -2,92 +2,17 @@
  * bl_form_api.hip — call path and C-ABI of the song structure (include/bliss_amd.h: bl_amd_form_*); the kernels are
  * bl_form_kernels.hip's, the host arithmetic over the records bl_api.c's.  Host code only.
  *
- * The structure pass keeps its workspace beside the context's own, as the fingerprints do, one per context it has been
- * called on: the songs' records, a ring of pinned blocks they are staged in, and the units and the novelty of a call
- * that does not ask for them.  The protocol is the fingerprints' (bl_fprint_api.hip): a call holds the context
- * (CtxGuard), the map from context to workspace has a lock of its own that is held for the look-up only, a pinned block
- * counts as free once the event behind its copy has passed, a call waits on the device for the workspace's previous
- * user before it writes the records, the hand-over point moves behind a call's last launch whatever way the call ends,
- * and ctx_release (bl_runtime.hip) calls blr_form_release, which frees the workspace with the context.
+ * The structure pass keeps a side workspace (bl_side_ws.h, which has the protocol): the songs' records, and as extra
+ * blocks the units and the novelty of a call that does not ask for them.
  */
 #include <string.h>
 
-#include <map>
-#include <memory>
-#include <mutex>
-#include <vector>
-
 #include "bl_form.h"
-#include "bl_runtime.h"
+#include "bl_side_ws.h"
 
 namespace {
 
-struct form_ws {
-  bl_buf recs, units, nov;
-  bl_pin_slot ring[BL_PIN_SLOTS];
-  int ring_next = 0;
-  hipEvent_t ev_done = nullptr; /* behind the last launch of the last call */
-  bool used = false;
-  struct Ev { int k; hipEvent_t a, b; };
-  std::mutex ev_mu;       /* guards events: a call appends, bl_amd_form_profile_ms collects */
-  std::vector<Ev> events; /* kernel timing, while the context's profiling switch is on */
-};
-
-std::mutex g_mu; /* guards g_ws itself; a workspace is its context's, under the context's mutex */
-std::map<bl_amd_ctx *, std::unique_ptr<form_ws>> g_ws;
-
-/* the workspace of a context whose mutex the caller holds, made on first use */
-form_ws *ws_of(bl_amd_ctx *c) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  std::unique_ptr<form_ws> &w = g_ws[c];
-  if (!w) w.reset(new form_ws());
-  return w.get();
-}
-
-void form_mark(void *user, int k, hipStream_t s, int begin) {
-  form_ws *w = static_cast<form_ws *>(user);
-  std::lock_guard<std::mutex> lk(w->ev_mu);
-  if (begin) {
-    form_ws::Ev e{k, nullptr, nullptr};
-    if (hipEventCreate(&e.a) != hipSuccess || hipEventCreate(&e.b) != hipSuccess) return;
-    (void)hipEventRecord(e.a, s);
-    w->events.push_back(e);
-  } else if (!w->events.empty() && w->events.back().k == k) {
-    (void)hipEventRecord(w->events.back().b, s);
-  }
-}
-
-/* pinned block of at least `bytes`; blocks only when BL_PIN_SLOTS calls are still in flight */
-int ws_pin(form_ws &w, size_t bytes, bl_pin_slot **out) {
-  bl_pin_slot &s = w.ring[w.ring_next];
-  w.ring_next = (w.ring_next + 1) % BL_PIN_SLOTS;
-  if (s.busy) {
-    BL_HIP_CHECK(hipEventSynchronize(s.ev));
-    s.busy = false;
-  }
-  if (!s.ev) BL_HIP_CHECK(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
-  if (s.cap < bytes) {
-    if (s.p) (void)hipHostFree(s.p);
-    s.p = nullptr;
-    s.cap = 0;
-    const size_t cap = bytes + bytes / 4 + 4096;
-    BL_HIP_CHECK(hipHostMalloc(&s.p, cap, hipHostMallocDefault));
-    s.cap = cap;
-  }
-  *out = &s;
-  return BL_OK;
-}
-
-/* moves the workspace's hand-over point behind whatever a call has enqueued, however the call ends */
-struct HandOver {
-  form_ws &w;
-  hipStream_t s;
-  bool armed = false;
-  HandOver(form_ws &ws, hipStream_t st) : w(ws), s(st) {}
-  ~HandOver() {
-    if (armed && hipEventRecord(w.ev_done, s) == hipSuccess) w.used = true;
-  }
-};
+enum { X_UNITS, X_NOV }; /* bl_side_ws::extra */
 
 /* what a call's counts add up to; false for a bad count */
 struct form_totals {
@@ -123,72 +48,41 @@ int form_device(bl_amd_ctx *c, bool dflt, const bl_amd_frame_chroma *d_frames, c
   if (!(c = call_ctx(c, dflt))) return BL_UNEXPECTED;
   CtxGuard g(c);
   if (!g.ok()) return BL_UNEXPECTED;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  form_ws &w = *ws_of(c);
-  if (!w.ev_done) BL_HIP_CHECK(hipEventCreateWithFlags(&w.ev_done, hipEventDisableTiming));
-  const size_t bytes = sizeof(bl_form_song) * (size_t)n_songs;
-  bl_pin_slot *slot = nullptr;
-  if (ws_pin(w, bytes, &slot) != BL_OK) return BL_UNEXPECTED;
-  bl_form_song *hs = static_cast<bl_form_song *>(slot->p);
-  long long f = 0, u = 0, gr = 0;
-  for (int i = 0; i < n_songs; ++i) {
-    hs[i].frame_off = f;
-    hs[i].unit_off = u;
-    hs[i].group_off = gr;
-    hs[i].frames = h_frames[i];
-    hs[i].units = h_frames[i] / p.pool;
-    f += hs[i].frames;
-    u += hs[i].units;
-    gr += (hs[i].units + BL_FORM_BLOCK_UNITS - 1) / BL_FORM_BLOCK_UNITS;
-  }
-  if (w.used) BL_HIP_CHECK(hipStreamWaitEvent(s, w.ev_done, 0));
-  const size_t n1 = (size_t)(t.units ? t.units : 1); /* a block even where there is no unit */
-  if (blr_ensure(w.recs, bytes) != BL_OK || (!d_units_out && blr_ensure(w.units, sizeof(uint4) * n1) != BL_OK) ||
-      (!d_nov_out && blr_ensure(w.nov, 8 * n1) != BL_OK))
-    return BL_UNEXPECTED;
-  HandOver done(w, s);
-  BL_HIP_CHECK(hipMemcpyAsync(w.recs.p, slot->p, bytes, hipMemcpyHostToDevice, s));
-  done.armed = true;
-  BL_HIP_CHECK(hipEventRecord(slot->ev, s));
-  slot->busy = true;
-  const bl_form_song *d_songs = static_cast<const bl_form_song *>(w.recs.p);
-  uint4 *d_units = static_cast<uint4 *>(d_units_out ? d_units_out : w.units.p);
-  unsigned long long *d_nov = d_nov_out ? reinterpret_cast<unsigned long long *>(d_nov_out)
-                                        : static_cast<unsigned long long *>(w.nov.p);
-  blk_mark_fn mark = c->prof ? form_mark : nullptr;
-  if (blk_form_units(s, d_frames, d_songs, n_songs, t.groups, p.pool, d_units, mark, &w) != BL_OK ||
-      blk_form_thumb(s, d_units, d_songs, n_songs, t.max_units, p.seg, p.min_lag, d_out, d_rep_out, mark, &w) != BL_OK ||
-      blk_form_novelty(s, d_units, d_songs, n_songs, p.nov, p.peak_num, p.peak_den, d_out, d_nov, d_flags_out, mark,
-                       &w) != BL_OK)
-    return BL_UNEXPECTED;
-  return BL_OK;
+  return side_call(SIDE_FORM, c, static_cast<hipStream_t>(stream), sizeof(bl_form_song) * (size_t)n_songs,
+                   [&](void *pinned) {
+    bl_form_song *hs = static_cast<bl_form_song *>(pinned);
+    long long f = 0, u = 0, gr = 0;
+    for (int i = 0; i < n_songs; ++i) {
+      hs[i].frame_off = f;
+      hs[i].unit_off = u;
+      hs[i].group_off = gr;
+      hs[i].frames = h_frames[i];
+      hs[i].units = h_frames[i] / p.pool;
+      f += hs[i].frames;
+      u += hs[i].units;
+      gr += (hs[i].units + BL_FORM_BLOCK_UNITS - 1) / BL_FORM_BLOCK_UNITS;
+    }
+    return BL_OK;
+  }, [&](hipStream_t s, bl_side_ws &w, blk_mark_fn mark, void *user) {
+    const size_t n1 = (size_t)(t.units ? t.units : 1); /* a block even where there is no unit */
+    if ((!d_units_out && blr_ensure(w.extra[X_UNITS], sizeof(uint4) * n1) != BL_OK) ||
+        (!d_nov_out && blr_ensure(w.extra[X_NOV], 8 * n1) != BL_OK))
+      return BL_UNEXPECTED;
+    const bl_form_song *d_songs = static_cast<const bl_form_song *>(w.recs.p);
+    uint4 *d_units = static_cast<uint4 *>(d_units_out ? d_units_out : w.extra[X_UNITS].p);
+    unsigned long long *d_nov = d_nov_out ? reinterpret_cast<unsigned long long *>(d_nov_out)
+                                          : static_cast<unsigned long long *>(w.extra[X_NOV].p);
+    if (blk_form_units(s, d_frames, d_songs, n_songs, t.groups, p.pool, d_units, mark, user) != BL_OK ||
+        blk_form_thumb(s, d_units, d_songs, n_songs, t.max_units, p.seg, p.min_lag, d_out, d_rep_out, mark, user) !=
+            BL_OK ||
+        blk_form_novelty(s, d_units, d_songs, n_songs, p.nov, p.peak_num, p.peak_den, d_out, d_nov, d_flags_out, mark,
+                         user) != BL_OK)
+      return BL_UNEXPECTED;
+    return BL_OK;
+  });
 }
 
 } // namespace
-
-/* ctx_release's hook (bl_runtime.hip): the caller holds the context, has made its device current and has waited for
- * the device */
-void blr_form_release(bl_amd_ctx *c) {
-  std::unique_ptr<form_ws> w;
-  {
-    std::lock_guard<std::mutex> lk(g_mu);
-    auto it = g_ws.find(c);
-    if (it == g_ws.end()) return;
-    w = std::move(it->second);
-    g_ws.erase(it);
-  }
-  for (bl_buf *b : {&w->recs, &w->units, &w->nov})
-    if (b->p) (void)hipFree(b->p);
-  for (bl_pin_slot &s : w->ring) {
-    if (s.p) (void)hipHostFree(s.p);
-    if (s.ev) (void)hipEventDestroy(s.ev);
-  }
-  if (w->ev_done) (void)hipEventDestroy(w->ev_done);
-  for (auto &e : w->events) {
-    (void)hipEventDestroy(e.a);
-    (void)hipEventDestroy(e.b);
-  }
-}
 
 /* ========================================================================= */
 /* C-ABI                                                                      */
@@ -258,35 +152,7 @@ double bl_amd_form_profile_ms(const char *name, int *launches) {
                 : !strcmp(name, "form_novelty")  ? FMK_NOVELTY
                                                  : -1;
   if (k < 0) return -1.0;
-  std::lock_guard<std::mutex> lk(g_mu); /* a workspace cannot be released while this is held */
-  double ms = 0.0;
-  int n = 0;
-  for (auto &kv : g_ws) {
-    form_ws &w = *kv.second;
-    std::lock_guard<std::mutex> lk_ev(w.ev_mu);
-    if (w.events.empty()) continue;
-    DevGuard dg(kv.first->device);
-    if (!dg.ok) continue;
-    std::vector<form_ws::Ev> keep;
-    for (auto &e : w.events) {
-      if (e.k != k) {
-        keep.push_back(e);
-        continue;
-      }
-      float t = 0.f;
-      if (hipEventSynchronize(e.b) == hipSuccess && hipEventElapsedTime(&t, e.a, e.b) == hipSuccess) {
-        ms += t;
-        n += 1;
-      } else {
-        (void)hipGetLastError();
-      }
-      (void)hipEventDestroy(e.a);
-      (void)hipEventDestroy(e.b);
-    }
-    w.events.swap(keep);
-  }
-  if (launches) *launches = n;
-  return ms;
+  return side_profile_ms(SIDE_FORM, k, launches);
 }
 
 } /* extern "C" */

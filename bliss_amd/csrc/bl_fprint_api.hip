@@ -2,114 +2,27 @@
  * bl_fprint_api.hip — call path and C-ABI of the audio fingerprints (include/bliss_amd.h: bl_amd_fprint_*); the kernels
  * are bl_fprint_kernels.hip's, the host arithmetic over the records bl_api.c's.  Host code only.
  *
- * The fingerprints keep their workspace beside the context's own, as the loudness and the true peak do, one per
- * context they have been called on: the records of a call (the songs of a words call, the two sets of a match) and a
- * ring of pinned blocks they are staged in.  The protocol is the true peak's (bl_tpeak_api.hip): a call holds the
- * context (CtxGuard), the map from context to workspace has a lock of its own that is held for the look-up only, a
- * pinned block counts as free once the event behind its copy has passed, a call waits on the device for the workspace's
- * previous user before it writes the records, the hand-over point moves behind a call's last launch whatever way the
- * call ends, and ctx_release (bl_runtime.hip) calls blr_fprint_release, which frees the workspace with the context.
+ * The fingerprints keep a side workspace (bl_side_ws.h, which has the protocol): the records of a call alone, the songs
+ * of a words call or the two sets of a match.
  */
 #include <string.h>
 
-#include <map>
-#include <memory>
-#include <mutex>
-#include <vector>
-
 #include "bl_fprint.h"
-#include "bl_runtime.h"
+#include "bl_side_ws.h"
 
 namespace {
 
-struct fprint_ws {
-  bl_buf recs;
-  bl_pin_slot ring[BL_PIN_SLOTS];
-  int ring_next = 0;
-  hipEvent_t ev_done = nullptr; /* behind the last launch of the last call */
-  bool used = false;
-  struct Ev { int k; hipEvent_t a, b; };
-  std::mutex ev_mu;       /* guards events: a call appends, bl_amd_fprint_profile_ms collects */
-  std::vector<Ev> events; /* kernel timing, while the context's profiling switch is on */
-};
-
-std::mutex g_mu; /* guards g_ws itself; a workspace is its context's, under the context's mutex */
-std::map<bl_amd_ctx *, std::unique_ptr<fprint_ws>> g_ws;
-
-/* the workspace of a context whose mutex the caller holds, made on first use */
-fprint_ws *ws_of(bl_amd_ctx *c) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  std::unique_ptr<fprint_ws> &w = g_ws[c];
-  if (!w) w.reset(new fprint_ws());
-  return w.get();
-}
-
-void fprint_mark(void *user, int k, hipStream_t s, int begin) {
-  fprint_ws *w = static_cast<fprint_ws *>(user);
-  std::lock_guard<std::mutex> lk(w->ev_mu);
-  if (begin) {
-    fprint_ws::Ev e{k, nullptr, nullptr};
-    if (hipEventCreate(&e.a) != hipSuccess || hipEventCreate(&e.b) != hipSuccess) return;
-    (void)hipEventRecord(e.a, s);
-    w->events.push_back(e);
-  } else if (!w->events.empty() && w->events.back().k == k) {
-    (void)hipEventRecord(w->events.back().b, s);
-  }
-}
-
-/* pinned block of at least `bytes`; blocks only when BL_PIN_SLOTS calls are still in flight */
-int ws_pin(fprint_ws &w, size_t bytes, bl_pin_slot **out) {
-  bl_pin_slot &s = w.ring[w.ring_next];
-  w.ring_next = (w.ring_next + 1) % BL_PIN_SLOTS;
-  if (s.busy) {
-    BL_HIP_CHECK(hipEventSynchronize(s.ev));
-    s.busy = false;
-  }
-  if (!s.ev) BL_HIP_CHECK(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
-  if (s.cap < bytes) {
-    if (s.p) (void)hipHostFree(s.p);
-    s.p = nullptr;
-    s.cap = 0;
-    const size_t cap = bytes + bytes / 4 + 4096;
-    BL_HIP_CHECK(hipHostMalloc(&s.p, cap, hipHostMallocDefault));
-    s.cap = cap;
-  }
-  *out = &s;
-  return BL_OK;
-}
-
-/* moves the workspace's hand-over point behind whatever a call has enqueued, however the call ends */
-struct HandOver {
-  fprint_ws &w;
-  hipStream_t s;
-  bool armed = false;
-  HandOver(fprint_ws &ws, hipStream_t st) : w(ws), s(st) {}
-  ~HandOver() {
-    if (armed && hipEventRecord(w.ev_done, s) == hipSuccess) w.used = true;
-  }
-};
-
-/* One call on context c: `fill` writes `bytes` of records into a pinned block, they are copied to the workspace on `s`
- * behind its previous user, and `launch(device records, mark, mark user)` enqueues the kernels. */
+/* One call on context c, or on the default one: side_call with the context held; `fill` writes `bytes` of records and
+ * `launch(s, device records, mark, mark user)` enqueues the kernels */
 template <class Fill, class Launch>
 int fprint_call(bl_amd_ctx *c, bool dflt, void *stream, size_t bytes, Fill fill, Launch launch) {
   if (!(c = call_ctx(c, dflt))) return BL_UNEXPECTED;
   CtxGuard g(c);
   if (!g.ok()) return BL_UNEXPECTED;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  fprint_ws &w = *ws_of(c);
-  if (!w.ev_done) BL_HIP_CHECK(hipEventCreateWithFlags(&w.ev_done, hipEventDisableTiming));
-  bl_pin_slot *slot = nullptr;
-  if (ws_pin(w, bytes, &slot) != BL_OK) return BL_UNEXPECTED;
-  fill(slot->p);
-  if (w.used) BL_HIP_CHECK(hipStreamWaitEvent(s, w.ev_done, 0));
-  if (blr_ensure(w.recs, bytes) != BL_OK) return BL_UNEXPECTED;
-  HandOver done(w, s);
-  BL_HIP_CHECK(hipMemcpyAsync(w.recs.p, slot->p, bytes, hipMemcpyHostToDevice, s));
-  done.armed = true;
-  BL_HIP_CHECK(hipEventRecord(slot->ev, s));
-  slot->busy = true;
-  return launch(s, w.recs.p, c->prof ? fprint_mark : nullptr, &w);
+  return side_call(SIDE_FPRINT, c, static_cast<hipStream_t>(stream), bytes, [&](void *pinned) {
+    fill(pinned);
+    return BL_OK;
+  }, [&](hipStream_t s, bl_side_ws &w, blk_mark_fn mark, void *user) { return launch(s, w.recs.p, mark, user); });
 }
 
 /* the sum of W over the songs and of ceil(W / 256); false for a bad count */
@@ -195,29 +108,6 @@ long long total_of(const int32_t *h_count, int n) {
 }
 
 } // namespace
-
-/* ctx_release's hook (bl_runtime.hip): the caller holds the context, has made its device current and has waited for
- * the device */
-void blr_fprint_release(bl_amd_ctx *c) {
-  std::unique_ptr<fprint_ws> w;
-  {
-    std::lock_guard<std::mutex> lk(g_mu);
-    auto it = g_ws.find(c);
-    if (it == g_ws.end()) return;
-    w = std::move(it->second);
-    g_ws.erase(it);
-  }
-  if (w->recs.p) (void)hipFree(w->recs.p);
-  for (bl_pin_slot &s : w->ring) {
-    if (s.p) (void)hipHostFree(s.p);
-    if (s.ev) (void)hipEventDestroy(s.ev);
-  }
-  if (w->ev_done) (void)hipEventDestroy(w->ev_done);
-  for (auto &e : w->events) {
-    (void)hipEventDestroy(e.a);
-    (void)hipEventDestroy(e.b);
-  }
-}
 
 /* ========================================================================= */
 /* C-ABI                                                                      */
@@ -317,35 +207,7 @@ double bl_amd_fprint_profile_ms(const char *name, int *launches) {
   if (launches) *launches = 0;
   const int k = !name ? -1 : !strcmp(name, "fprint_words") ? FK_WORDS : !strcmp(name, "fprint_match") ? FK_MATCH : -1;
   if (k < 0) return -1.0;
-  std::lock_guard<std::mutex> lk(g_mu); /* a workspace cannot be released while this is held */
-  double ms = 0.0;
-  int n = 0;
-  for (auto &kv : g_ws) {
-    fprint_ws &w = *kv.second;
-    std::lock_guard<std::mutex> lk_ev(w.ev_mu);
-    if (w.events.empty()) continue;
-    DevGuard dg(kv.first->device);
-    if (!dg.ok) continue;
-    std::vector<fprint_ws::Ev> keep;
-    for (auto &e : w.events) {
-      if (e.k != k) {
-        keep.push_back(e);
-        continue;
-      }
-      float t = 0.f;
-      if (hipEventSynchronize(e.b) == hipSuccess && hipEventElapsedTime(&t, e.a, e.b) == hipSuccess) {
-        ms += t;
-        n += 1;
-      } else {
-        (void)hipGetLastError();
-      }
-      (void)hipEventDestroy(e.a);
-      (void)hipEventDestroy(e.b);
-    }
-    w.events.swap(keep);
-  }
-  if (launches) *launches = n;
-  return ms;
+  return side_profile_ms(SIDE_FPRINT, k, launches);
 }
 
 } /* extern "C" */

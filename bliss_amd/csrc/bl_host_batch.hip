@@ -17,7 +17,6 @@
 
 #include "bl_runtime.h"
 #include "bl_resample.h"
-#include "bl_waves.h"
 
 namespace {
 
@@ -262,43 +261,9 @@ int blr_analyze_host(bl_amd_ctx *c, const void *const *h_pcm, int pcm_is_s32, co
   return BL_OK;
 }
 
-/* ---- host forms of the signal levels, the spectral timbre and the tempo: what they share ---- */
-
-/* samples per wave of bl_amd_levels_batch_host, bl_amd_timbre_batch_host, bl_amd_rhythm_batch_host,
- * bl_amd_chroma_batch_host and bl_amd_mel_batch_host: the songs are uploaded, analysed and
- * fetched 256 MiB of PCM at a time, or the context's host_wave_bytes if that is less (a song longer than that is a
- * wave of its own) */
-#define BL_HOST_WAVE_SAMPLES ((size_t)128 << 20)
-
-/* The host songs in waves (bl_wave_plan): songs [b, e) laid out in a device arena, copied there, and
- * `wave(d_arena, desc, b, e)` called on them with desc[i - b] the place of song i.  The arena is freed when `wave`
- * returns, so `wave` fetches what it computed. */
-template <class Wave>
-static int host_waves(bl_amd_ctx *c, const int16_t *const *h_pcm, const int32_t *n_samples, const int32_t *channels,
-                      int n_songs, Wave wave) {
-  const size_t budget = std::min(BL_HOST_WAVE_SAMPLES, c->host_wave_bytes / 2);
-  std::vector<size_t> off;
-  std::vector<bl_amd_song_desc> desc;
-  for (int b = 0, e; b < n_songs; b = e) {
-    size_t total = 0;
-    e = bl_wave_plan(n_samples, b, n_songs, budget, off, total);
-    desc.resize(off.size());
-    for (int i = b; i < e; ++i) {
-      bl_amd_song_desc &d = desc[i - b];
-      d.pcm_offset = off[i - b];
-      d.n_samples = n_samples[i];
-      d.channels = channels[i];
-      d.duration = 0;
-    }
-    DevMem arena(sizeof(int16_t) * total);
-    if (!arena.ok()) return BL_UNEXPECTED;
-    for (int i = b; i < e; ++i)
-      BL_HIP_CHECK(hipMemcpy(arena.as<int16_t>() + desc[i - b].pcm_offset, h_pcm[i],
-                             sizeof(int16_t) * (size_t)n_samples[i], hipMemcpyHostToDevice));
-    if (wave(arena.as<int16_t>(), desc.data(), b, e) != BL_OK) return BL_UNEXPECTED;
-  }
-  return BL_OK;
-}
+/* The host forms of the signal levels, the spectral timbre, the tempo, the chroma and the mel call below share
+ * host_waves (bl_runtime.h), which cuts the songs into waves; each form's lambda runs its device form on one wave and
+ * fetches what it computed. */
 
 /* ========================================================================= */
 /* C-ABI                                                                      */

@@ -2,97 +2,19 @@
  * bl_loud_api.hip — call path and C-ABI of the K-weighted gated loudness (include/bliss_amd.h: bl_amd_loud_*); the
  * kernels are bl_loud_kernels.hip's, the host arithmetic bl_api.c's.  Host code only.
  *
- * The loudness keeps its workspace beside the context's own, one per context it has been called on (the records, the
- * hop energies of a call without a hops output, the short-term sums, a ring of pinned blocks for the records), and
- * leaves the layout of bl_amd_ctx alone.  A call holds the context like every other entry point (CtxGuard: its mutex
- * and its device), so calls on one context are ordered and contexts are independent of each other; the map from
- * context to workspace has a lock of its own that is held for the look-up only.  ctx_release (bl_runtime.hip) calls
- * blr_loud_release, which frees the context's workspace with the context.  The protocol is the one of the contexts'
- * record uploads: a pinned block counts as free once the event behind its copy has passed (BL_PIN_SLOTS calls may be
- * in flight before a caller waits), a call waits on the device for the workspace's previous user before anything of
- * it writes a block, the hand-over point moves behind a call's last launch whatever way the call ends, and a block
- * grows only behind a device synchronisation (blr_ensure).
+ * The loudness keeps a side workspace (bl_side_ws.h, which has the protocol): the records, and as extra blocks the hop
+ * energies of a call without a hops output and the short-term sums.
  */
 #include <string.h>
 
 #include <algorithm>
-#include <map>
-#include <memory>
-#include <mutex>
-#include <vector>
 
 #include "bl_loud.h"
-#include "bl_runtime.h"
-#include "bl_waves.h"
+#include "bl_side_ws.h"
 
 namespace {
 
-struct loud_ws {
-  bl_buf songs, z, st;
-  bl_pin_slot ring[BL_PIN_SLOTS];
-  int ring_next = 0;
-  hipEvent_t ev_done = nullptr; /* behind the last launch of the last call */
-  bool used = false;
-  struct Ev { int k; hipEvent_t a, b; };
-  std::mutex ev_mu;       /* guards events: a call appends, bl_amd_loud_profile_ms collects */
-  std::vector<Ev> events; /* kernel timing, while the context's profiling switch is on */
-};
-
-std::mutex g_mu; /* guards g_ws itself; a workspace is its context's, under the context's mutex */
-std::map<bl_amd_ctx *, std::unique_ptr<loud_ws>> g_ws;
-
-/* the workspace of a context whose mutex the caller holds, made on first use */
-loud_ws *ws_of(bl_amd_ctx *c) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  std::unique_ptr<loud_ws> &w = g_ws[c];
-  if (!w) w.reset(new loud_ws());
-  return w.get();
-}
-
-void loud_mark(void *user, int k, hipStream_t s, int begin) {
-  loud_ws *w = static_cast<loud_ws *>(user);
-  std::lock_guard<std::mutex> lk(w->ev_mu);
-  if (begin) {
-    loud_ws::Ev e{k, nullptr, nullptr};
-    if (hipEventCreate(&e.a) != hipSuccess || hipEventCreate(&e.b) != hipSuccess) return;
-    (void)hipEventRecord(e.a, s);
-    w->events.push_back(e);
-  } else if (!w->events.empty() && w->events.back().k == k) {
-    (void)hipEventRecord(w->events.back().b, s);
-  }
-}
-
-/* pinned block of at least `bytes`; blocks only when BL_PIN_SLOTS calls are still in flight */
-int ws_pin(loud_ws &w, size_t bytes, bl_pin_slot **out) {
-  bl_pin_slot &s = w.ring[w.ring_next];
-  w.ring_next = (w.ring_next + 1) % BL_PIN_SLOTS;
-  if (s.busy) {
-    BL_HIP_CHECK(hipEventSynchronize(s.ev));
-    s.busy = false;
-  }
-  if (!s.ev) BL_HIP_CHECK(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
-  if (s.cap < bytes) {
-    if (s.p) (void)hipHostFree(s.p);
-    s.p = nullptr;
-    s.cap = 0;
-    const size_t cap = bytes + bytes / 4 + 4096;
-    BL_HIP_CHECK(hipHostMalloc(&s.p, cap, hipHostMallocDefault));
-    s.cap = cap;
-  }
-  *out = &s;
-  return BL_OK;
-}
-
-/* moves the workspace's hand-over point behind whatever a call has enqueued, however the call ends */
-struct HandOver {
-  loud_ws &w;
-  hipStream_t s;
-  bool armed = false;
-  HandOver(loud_ws &ws, hipStream_t st) : w(ws), s(st) {}
-  ~HandOver() {
-    if (armed && hipEventRecord(w.ev_done, s) == hipSuccess) w.used = true;
-  }
-};
+enum { X_Z, X_ST }; /* bl_side_ws::extra */
 
 /* One call on n_songs songs, from PCM (d_z_in == nullptr) or from hop energies on the device; the caller holds the
  * context (CtxGuard).  `song(i, rec)` writes pcm_off, hops and channels of song i in the caller's order.  The records
@@ -102,44 +24,35 @@ struct HandOver {
 template <class Song>
 int loud_call(bl_amd_ctx *c, hipStream_t s, int n_songs, Song song, const int16_t *d_pcm, const uint64_t *d_z_in,
               const bl_amd_loud_params &p, bl_amd_song_loud *d_songs_out, uint64_t *d_hops_out) {
-  loud_ws &w = *ws_of(c);
-  if (!w.ev_done) BL_HIP_CHECK(hipEventCreateWithFlags(&w.ev_done, hipEventDisableTiming));
-  const size_t bytes = sizeof(bl_loud_song) * (size_t)n_songs;
-  bl_pin_slot *slot = nullptr;
-  if (ws_pin(w, bytes, &slot) != BL_OK) return BL_UNEXPECTED;
-  bl_loud_song *hs = static_cast<bl_loud_song *>(slot->p);
   long long hops = 0, starts = 0, chunks = 0;
-  for (int i = 0; i < n_songs; ++i) {
-    song(i, hs[i]);
-    hs[i].hop_off = hops;
-    hs[i].st_off = starts;
-    hs[i].out_idx = i;
-    hs[i].reserved = 0;
-    hops += hs[i].hops;
-    starts += blk_loud_starts(hs[i].hops);
-  }
-  std::stable_sort(hs, hs + n_songs, [](const bl_loud_song &a, const bl_loud_song &b) { return a.channels > b.channels; });
-  for (int i = 0; i < n_songs; ++i) {
-    hs[i].chunk_off = chunks;
-    chunks += (hs[i].hops + BL_AMD_LOUD_CHUNK - 1) / BL_AMD_LOUD_CHUNK;
-  }
-  if (chunks > (1ll << 30)) return BL_UNEXPECTED; /* nothing has been enqueued: the slot stays free */
-  if (w.used) BL_HIP_CHECK(hipStreamWaitEvent(s, w.ev_done, 0));
-  unsigned long long *z = reinterpret_cast<unsigned long long *>(d_z_in ? const_cast<uint64_t *>(d_z_in) : d_hops_out);
-  if (blr_ensure(w.songs, bytes) != BL_OK || blr_ensure(w.st, 8 * (size_t)std::max(starts, 1ll)) != BL_OK ||
-      (!z && blr_ensure(w.z, 16 * (size_t)std::max(hops, 1ll)) != BL_OK))
-    return BL_UNEXPECTED;
-  if (!z) z = static_cast<unsigned long long *>(w.z.p);
-  bl_loud_song *d_songs = static_cast<bl_loud_song *>(w.songs.p);
-  HandOver done(w, s);
-  BL_HIP_CHECK(hipMemcpyAsync(d_songs, hs, bytes, hipMemcpyHostToDevice, s));
-  done.armed = true;
-  BL_HIP_CHECK(hipEventRecord(slot->ev, s));
-  slot->busy = true;
-  blk_mark_fn mark = c->prof ? loud_mark : nullptr;
-  if (!d_z_in && blk_loud_filter(s, d_pcm, d_songs, n_songs, chunks, p, z, mark, &w) != BL_OK) return BL_UNEXPECTED;
-  return blk_loud_gate(s, z, d_songs, n_songs, p.abs_gate, static_cast<unsigned long long *>(w.st.p), d_songs_out, mark,
-                       &w);
+  return side_call(SIDE_LOUD, c, s, sizeof(bl_loud_song) * (size_t)n_songs, [&](void *pinned) {
+    bl_loud_song *hs = static_cast<bl_loud_song *>(pinned);
+    for (int i = 0; i < n_songs; ++i) {
+      song(i, hs[i]);
+      hs[i].hop_off = hops;
+      hs[i].st_off = starts;
+      hs[i].out_idx = i;
+      hs[i].reserved = 0;
+      hops += hs[i].hops;
+      starts += blk_loud_starts(hs[i].hops);
+    }
+    std::stable_sort(hs, hs + n_songs, [](const bl_loud_song &a, const bl_loud_song &b) { return a.channels > b.channels; });
+    for (int i = 0; i < n_songs; ++i) {
+      hs[i].chunk_off = chunks;
+      chunks += (hs[i].hops + BL_AMD_LOUD_CHUNK - 1) / BL_AMD_LOUD_CHUNK;
+    }
+    return chunks > (1ll << 30) ? BL_UNEXPECTED : BL_OK;
+  }, [&](hipStream_t s, bl_side_ws &w, blk_mark_fn mark, void *user) {
+    unsigned long long *z = reinterpret_cast<unsigned long long *>(d_z_in ? const_cast<uint64_t *>(d_z_in) : d_hops_out);
+    if (blr_ensure(w.extra[X_ST], 8 * (size_t)std::max(starts, 1ll)) != BL_OK ||
+        (!z && blr_ensure(w.extra[X_Z], 16 * (size_t)std::max(hops, 1ll)) != BL_OK))
+      return BL_UNEXPECTED;
+    if (!z) z = static_cast<unsigned long long *>(w.extra[X_Z].p);
+    const bl_loud_song *d_songs = static_cast<const bl_loud_song *>(w.recs.p);
+    if (!d_z_in && blk_loud_filter(s, d_pcm, d_songs, n_songs, chunks, p, z, mark, user) != BL_OK) return BL_UNEXPECTED;
+    return blk_loud_gate(s, z, d_songs, n_songs, p.abs_gate, static_cast<unsigned long long *>(w.extra[X_ST].p),
+                         d_songs_out, mark, user);
+  });
 }
 
 int loud_device(bl_amd_ctx *c, bool dflt, const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs,
@@ -165,30 +78,6 @@ int loud_device(bl_amd_ctx *c, bool dflt, const int16_t *d_pcm, const bl_amd_son
 }
 
 } // namespace
-
-/* ctx_release's hook (bl_runtime.hip): the caller holds the context, has made its device current and has waited for
- * the device */
-void blr_loud_release(bl_amd_ctx *c) {
-  std::unique_ptr<loud_ws> w;
-  {
-    std::lock_guard<std::mutex> lk(g_mu);
-    auto it = g_ws.find(c);
-    if (it == g_ws.end()) return;
-    w = std::move(it->second);
-    g_ws.erase(it);
-  }
-  for (bl_buf *b : {&w->songs, &w->z, &w->st})
-    if (b->p) (void)hipFree(b->p);
-  for (bl_pin_slot &s : w->ring) {
-    if (s.p) (void)hipHostFree(s.p);
-    if (s.ev) (void)hipEventDestroy(s.ev);
-  }
-  if (w->ev_done) (void)hipEventDestroy(w->ev_done);
-  for (auto &e : w->events) {
-    (void)hipEventDestroy(e.a);
-    (void)hipEventDestroy(e.b);
-  }
-}
 
 /* ========================================================================= */
 /* C-ABI                                                                      */
@@ -236,8 +125,7 @@ int bl_amd_loud_from_hops(const uint64_t *h_hop_energy, const int32_t *h_hops, i
   return out.down(h_songs_out) ? BL_OK : BL_UNEXPECTED;
 }
 
-/* the songs in waves of at most 256 MiB of PCM (bl_wave_plan; a longer song is a wave of its own): each is laid out in
- * a device arena, copied there, measured by the device form and fetched */
+/* the songs in waves (host_waves, bl_runtime.h): each is measured by the device form and fetched */
 int bl_amd_loud_batch_host(const int16_t *const *h_pcm, const int32_t *n_samples, const int32_t *channels, int n_songs,
                            const bl_amd_loud_params *params, bl_amd_song_loud *h_songs_out, uint64_t *h_hops_out) {
   if (!h_pcm || !n_samples || !channels || !h_songs_out || n_songs < 1 || !loud_params_ok(params, false))
@@ -248,39 +136,21 @@ int bl_amd_loud_batch_host(const int16_t *const *h_pcm, const int32_t *n_samples
   if (!c) return BL_UNEXPECTED;
   DevGuard dg(c->device);
   if (!dg.ok) return BL_UNEXPECTED;
-  size_t budget;
-  {
-    std::lock_guard<std::mutex> lk(c->mu);
-    budget = std::min((size_t)128 << 20, c->host_wave_bytes / 2);
-  }
-  std::vector<size_t> off;
-  std::vector<bl_amd_song_desc> desc;
-  for (int b = 0, e; b < n_songs; b = e) {
-    size_t total = 0;
-    e = bl_wave_plan(n_samples, b, n_songs, budget, off, total);
-    desc.resize(off.size());
-    long long hops = 0;
-    for (int i = b; i < e; ++i) {
-      desc[i - b].pcm_offset = off[i - b];
-      desc[i - b].n_samples = n_samples[i];
-      desc[i - b].channels = channels[i];
-      desc[i - b].duration = 0;
-      hops += loud_hops(n_samples[i], channels[i], params->hop);
-    }
-    DevMem arena(sizeof(int16_t) * total), out(sizeof(bl_amd_song_loud) * (size_t)(e - b)),
-        zout(h_hops_out ? 16 * (size_t)hops : 0);
-    if (!arena.ok() || !out.ok() || !zout.ok()) return BL_UNEXPECTED;
-    for (int i = b; i < e; ++i)
-      BL_HIP_CHECK(hipMemcpy(arena.as<int16_t>() + desc[i - b].pcm_offset, h_pcm[i],
-                             sizeof(int16_t) * (size_t)n_samples[i], hipMemcpyHostToDevice));
-    if (bl_amd_loud_batch_device(arena.as<int16_t>(), desc.data(), e - b, params, out.as<bl_amd_song_loud>(),
-                                 zout.as<uint64_t>(), hops, nullptr) != BL_OK)
-      return BL_UNEXPECTED;
-    BL_HIP_CHECK(hipStreamSynchronize(nullptr));
-    if (!out.down(h_songs_out + b) || (h_hops_out && hops && !zout.down(h_hops_out))) return BL_UNEXPECTED;
-    if (h_hops_out) h_hops_out += 2 * hops;
-  }
-  return BL_OK;
+  return host_waves(c, h_pcm, n_samples, channels, n_songs,
+                    [&](const int16_t *d_pcm, const bl_amd_song_desc *desc, int b, int e) {
+                      long long hops = 0;
+                      for (int i = b; i < e; ++i) hops += loud_hops(n_samples[i], channels[i], params->hop);
+                      DevMem out(sizeof(bl_amd_song_loud) * (size_t)(e - b)), zout(h_hops_out ? 16 * (size_t)hops : 0);
+                      if (!out.ok() || !zout.ok() ||
+                          bl_amd_loud_batch_device(d_pcm, desc, e - b, params, out.as<bl_amd_song_loud>(),
+                                                   zout.as<uint64_t>(), hops, nullptr) != BL_OK)
+                        return BL_UNEXPECTED;
+                      BL_HIP_CHECK(hipStreamSynchronize(nullptr));
+                      if (!out.down(h_songs_out + b) || (h_hops_out && hops && !zout.down(h_hops_out)))
+                        return BL_UNEXPECTED;
+                      if (h_hops_out) h_hops_out += 2 * hops;
+                      return BL_OK;
+                    });
 }
 
 /* device time of a loudness kernel since this was last asked for it: "loud_filter" or "loud_gate" */
@@ -288,35 +158,7 @@ double bl_amd_loud_profile_ms(const char *name, int *launches) {
   if (launches) *launches = 0;
   const int k = !name ? -1 : !strcmp(name, "loud_filter") ? LK_FILTER : !strcmp(name, "loud_gate") ? LK_GATE : -1;
   if (k < 0) return -1.0;
-  std::lock_guard<std::mutex> lk(g_mu); /* a workspace cannot be released while this is held */
-  double ms = 0.0;
-  int n = 0;
-  for (auto &kv : g_ws) {
-    loud_ws &w = *kv.second;
-    std::lock_guard<std::mutex> lk_ev(w.ev_mu);
-    if (w.events.empty()) continue;
-    DevGuard dg(kv.first->device);
-    if (!dg.ok) continue;
-    std::vector<loud_ws::Ev> keep;
-    for (auto &e : w.events) {
-      if (e.k != k) {
-        keep.push_back(e);
-        continue;
-      }
-      float t = 0.f;
-      if (hipEventSynchronize(e.b) == hipSuccess && hipEventElapsedTime(&t, e.a, e.b) == hipSuccess) {
-        ms += t;
-        n += 1;
-      } else {
-        (void)hipGetLastError();
-      }
-      (void)hipEventDestroy(e.a);
-      (void)hipEventDestroy(e.b);
-    }
-    w.events.swap(keep);
-  }
-  if (launches) *launches = n;
-  return ms;
+  return side_profile_ms(SIDE_LOUD, k, launches);
 }
 
 } /* extern "C" */

@@ -1,8 +1,10 @@
 /*
  * bl_runtime.h — internal: the per-device context behind include/bliss_amd.h, shared by
  * bl_runtime.hip (contexts and the single-device analysis C-ABI), bl_host_batch.hip (songs from host memory: the host
- * batch, bl_amd_analyze_files, the *_host forms), bl_query_api.hip (the matrix, playlist and vector-query C-ABI) and
- * bl_multi.hip (multi-device corpus path).
+ * batch, bl_amd_analyze_files, the *_host forms), bl_query_api.hip (the matrix, playlist and vector-query C-ABI),
+ * bl_desc_api.hip (descriptors), bl_multi.hip (multi-device corpus path), bl_side_ws.hip (the workspaces beside the
+ * context's own, bl_side_ws.h) and the four call paths on top of those: bl_loud_api.hip, bl_tpeak_api.hip,
+ * bl_fprint_api.hip, bl_form_api.hip.
  * C++ only, not installed.
  */
 #ifndef BL_RUNTIME_H_
@@ -10,11 +12,13 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <mutex>
 #include <vector>
 
 #include "bl_launch.h"
 #include "bl_resample.h"
+#include "bl_waves.h"
 
 #define BL_MAX_DEVICES 16
 #define BL_GROUP_SONGS_MAX 32768 /* gridDim.y of the (blocks, songs) launch grids */
@@ -124,15 +128,15 @@ int blr_analyze_device(bl_amd_ctx *c, const int16_t *d_pcm, const bl_amd_song_de
 int blr_resample_device(bl_amd_ctx *c, const void *d_in, int in_is_s32, const bl_amd_resample_desc *h_desc,
                         int n_songs, int in_rate, int16_t *d_out, hipStream_t s);
 
-/* bl_loud_api.hip: frees the loudness workspace of a context that is being released (ctx_release: the context held,
- * its device current and idle) */
-void blr_loud_release(bl_amd_ctx *c);
-/* bl_tpeak_api.hip: the same for the true-peak workspace */
-void blr_tpeak_release(bl_amd_ctx *c);
-/* bl_fprint_api.hip: the same for the fingerprints' workspace */
-void blr_fprint_release(bl_amd_ctx *c);
-/* bl_form_api.hip: the same for the song structure's workspace */
-void blr_form_release(bl_amd_ctx *c);
+/* pinned slot of at least `bytes` from a ring of BL_PIN_SLOTS whose next slot is `next`; blocks only when BL_PIN_SLOTS
+ * calls are still in flight.  A slot's event is made on first use (the context's own ring has them from ctx_init). */
+int blr_ring_get(bl_pin_slot *ring, int &next, size_t bytes, bl_pin_slot **out);
+/* frees the blocks and the events of a ring of BL_PIN_SLOTS and leaves it empty */
+void blr_ring_free(bl_pin_slot *ring);
+
+/* bl_side_ws.hip: frees the side workspaces (bl_side_ws.h) of a context that is being released (ctx_release: the
+ * context held, its device current and idle) */
+void blr_side_release(bl_amd_ctx *c);
 
 /* bl_host_batch.hip */
 /* host-memory batch on one context; pcm_is_s32: h_pcm[i] points at int32 samples that are
@@ -231,6 +235,46 @@ struct DevMem {
   bool down(void *h) const { return down(h, bytes); }
   template <class T> T *as() const { return static_cast<T *>(p); }
 };
+
+/* samples per wave of the *_batch_host forms of levels, timbre, tempo, chroma, mel, loudness and true peak: the songs
+ * are uploaded, analysed and fetched 256 MiB of PCM at a time, or the context's host_wave_bytes if that is less (a song
+ * longer than that is a wave of its own) */
+#define BL_HOST_WAVE_SAMPLES ((size_t)128 << 20)
+
+/* The host songs in waves (bl_wave_plan): songs [b, e) laid out in a device arena, copied there, and
+ * `wave(d_arena, desc, b, e)` called on them with desc[i - b] the place of song i.  The arena is freed when `wave`
+ * returns, so `wave` fetches what it computed.  The caller has made c->device current and does not hold c->mu: the
+ * budget is read under it, and `wave` calls device forms that take it themselves. */
+template <class Wave>
+int host_waves(bl_amd_ctx *c, const int16_t *const *h_pcm, const int32_t *n_samples, const int32_t *channels,
+               int n_songs, Wave wave) {
+  size_t budget;
+  {
+    std::lock_guard<std::mutex> lk(c->mu);
+    budget = std::min(BL_HOST_WAVE_SAMPLES, c->host_wave_bytes / 2);
+  }
+  std::vector<size_t> off;
+  std::vector<bl_amd_song_desc> desc;
+  for (int b = 0, e; b < n_songs; b = e) {
+    size_t total = 0;
+    e = bl_wave_plan(n_samples, b, n_songs, budget, off, total);
+    desc.resize(off.size());
+    for (int i = b; i < e; ++i) {
+      bl_amd_song_desc &d = desc[i - b];
+      d.pcm_offset = off[i - b];
+      d.n_samples = n_samples[i];
+      d.channels = channels[i];
+      d.duration = 0;
+    }
+    DevMem arena(sizeof(int16_t) * total);
+    if (!arena.ok()) return BL_UNEXPECTED;
+    for (int i = b; i < e; ++i)
+      BL_HIP_CHECK(hipMemcpy(arena.as<int16_t>() + desc[i - b].pcm_offset, h_pcm[i],
+                             sizeof(int16_t) * (size_t)n_samples[i], hipMemcpyHostToDevice));
+    if (wave(arena.as<int16_t>(), desc.data(), b, e) != BL_OK) return BL_UNEXPECTED;
+  }
+  return BL_OK;
+}
 
 /* the metric and the row range of a vector query (bl_amd_knn_*, bl_amd_chain_*, bl_amd_radius_*, bl_amd_groups_*) */
 inline bool metric_ok(int metric) { return metric == BL_AMD_KNN_DISTANCE || metric == BL_AMD_KNN_COSINE; }

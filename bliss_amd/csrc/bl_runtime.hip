@@ -18,7 +18,9 @@
  * batch to the next by an event, not by a host synchronisation.  Every entry point that uploads
  * per-song records (analysis, rate conversion, levels, timbre, tempo, beats, chroma, mel, synthesis, bld_mean_variance_host)
  * does so through record_call, the one place that knows this protocol; the vector queries have
- * query_call (bl_runtime.h), which shares the hand-over (ws_wait, ws_pass) with it.
+ * query_call (bl_runtime.h), which shares the hand-over (ws_wait, ws_pass) with it.  The loudness, the true peak, the
+ * fingerprints and the song structure keep workspaces of their own beside the context's and have side_call
+ * (bl_side_ws.h), the same protocol over those; the pinned rings of both are served by blr_ring_get.
  *
  * Guards.  An entry point that uses the workspace takes a CtxGuard (context lock + device guard);
  * the *_host forms of levels, timbre and tempo, the selftests and bl_amd_narrow_s32_device use no workspace themselves and
@@ -115,10 +117,7 @@ void ctx_release(bl_amd_ctx *c) {
   if (!dg.ok) return;
   (void)hipDeviceSynchronize();
   prof_collect(c);
-  blr_loud_release(c);
-  blr_tpeak_release(c);
-  blr_fprint_release(c);
-  blr_form_release(c);
+  blr_side_release(c);
   bl_buf *bufs[] = {&c->songs,   &c->stats,   &c->hist, &c->spectrum, &c->energies, &c->lc,
                     &c->results, &c->arena[0], &c->arena[1], &c->arena22[0], &c->arena22[1],
                     &c->rs_songs, &c->rs_bank, &c->mx_my, &c->mx_gath, &c->mx_all, &c->mx_order, &c->mx_rows, &c->knn, &c->chain, &c->radius, &c->level_songs, &c->timbre_songs,
@@ -133,11 +132,7 @@ void ctx_release(bl_amd_ctx *c) {
     if (c->streams[k]) (void)hipStreamDestroy(c->streams[k]);
     c->streams[k] = nullptr;
   }
-  for (int k = 0; k < BL_PIN_SLOTS; ++k) {
-    if (c->ring[k].p) (void)hipHostFree(c->ring[k].p);
-    if (c->ring[k].ev) (void)hipEventDestroy(c->ring[k].ev);
-    c->ring[k] = bl_pin_slot();
-  }
+  blr_ring_free(c->ring);
   if (c->tables_mem) (void)hipFree(c->tables_mem);
   c->tables_mem = nullptr;
   for (auto m : kCtxStreams) {
@@ -161,26 +156,6 @@ int current_device(void) {
   return d >= 0 ? d : 0;
 }
 
-/* pinned slot of at least `bytes`; blocks only when BL_PIN_SLOTS batches are still in flight */
-int ring_get(bl_amd_ctx *c, size_t bytes, bl_pin_slot **out) {
-  bl_pin_slot &s = c->ring[c->ring_next];
-  c->ring_next = (c->ring_next + 1) % BL_PIN_SLOTS;
-  if (s.busy) {
-    BL_HIP_CHECK(hipEventSynchronize(s.ev));
-    s.busy = false;
-  }
-  if (s.cap < bytes) {
-    if (s.p) (void)hipHostFree(s.p);
-    s.p = nullptr;
-    s.cap = 0;
-    const size_t cap = bytes + bytes / 4 + 4096;
-    BL_HIP_CHECK(hipHostMalloc(&s.p, cap, hipHostMallocDefault));
-    s.cap = cap;
-  }
-  *out = &s;
-  return BL_OK;
-}
-
 /* One call that uploads n per-song records of type T into `block` and launches on them; the caller holds c->mu and has
  * made c->device current.  `fill(T *h)` writes the records into a pinned slot (BL_OK, or BL_UNEXPECTED to refuse the
  * call), `launch(const T *h, T *d)` enqueues the kernels on `s` and grows whatever other workspace they need.
@@ -193,7 +168,7 @@ template <class T, class Fill, class Launch>
 int record_call(bl_amd_ctx *c, hipStream_t s, bl_buf &block, int n, Fill fill, Launch launch) {
   const size_t bytes = sizeof(T) * (size_t)n;
   bl_pin_slot *slot = nullptr;
-  if (ring_get(c, bytes, &slot) != BL_OK) return BL_UNEXPECTED;
+  if (blr_ring_get(c->ring, c->ring_next, bytes, &slot) != BL_OK) return BL_UNEXPECTED;
   T *h = static_cast<T *>(slot->p);
   if (fill(h) != BL_OK || ws_wait(c, s) != BL_OK || blr_ensure(block, bytes) != BL_OK) return BL_UNEXPECTED;
   T *d = static_cast<T *>(block.p);
@@ -269,6 +244,34 @@ void mark_cb(void *user, int k, hipStream_t s, int begin) {
         c->open.erase(c->open.begin() + (long)i);
         break;
       }
+  }
+}
+
+int blr_ring_get(bl_pin_slot *ring, int &next, size_t bytes, bl_pin_slot **out) {
+  bl_pin_slot &s = ring[next];
+  next = (next + 1) % BL_PIN_SLOTS;
+  if (s.busy) {
+    BL_HIP_CHECK(hipEventSynchronize(s.ev));
+    s.busy = false;
+  }
+  if (!s.ev) BL_HIP_CHECK(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
+  if (s.cap < bytes) {
+    if (s.p) (void)hipHostFree(s.p);
+    s.p = nullptr;
+    s.cap = 0;
+    const size_t cap = bytes + bytes / 4 + 4096;
+    BL_HIP_CHECK(hipHostMalloc(&s.p, cap, hipHostMallocDefault));
+    s.cap = cap;
+  }
+  *out = &s;
+  return BL_OK;
+}
+
+void blr_ring_free(bl_pin_slot *ring) {
+  for (int k = 0; k < BL_PIN_SLOTS; ++k) {
+    if (ring[k].p) (void)hipHostFree(ring[k].p);
+    if (ring[k].ev) (void)hipEventDestroy(ring[k].ev);
+    ring[k] = bl_pin_slot();
   }
 }
 

@@ -52,9 +52,10 @@ def to_device(a):
 
 
 class Form:
-    """one device call on the chromagrams `songs`; the records and the outputs were filled with 0xA5"""
+    """one device call on the chromagrams `songs`; the records and the outputs were filled with 0xA5.  `stream`: a torch
+    stream instead of the default one; `defer`: the call is made by go() (tests/test_gpu_side_ws.py)"""
 
-    def __init__(self, lib, songs, p, outs=ALL, ctx=None, bad=None):
+    def __init__(self, lib, songs, p, outs=ALL, ctx=None, bad=None, stream=None, defer=False):
         self.songs, self.p, self.outs = songs, dict(p), outs
         self.counts = [int(x.shape[0]) for x in songs]
         self.n = sum(t // p["pool"] for t in self.counts) if 1 <= p["pool"] <= 16 else sum(self.counts)
@@ -70,8 +71,15 @@ class Form:
                    **{name: ptr(self.out[name]) for name in ALL})
         for k, v in (bad or {}).items():
             arg[k] = v(self) if callable(v) else v
-        args = tuple(arg[k] for k in ("frames", "counts", "n", "params", "rec") + ALL + ("n_units",)) + (None,)
-        self.rc = (lib.bl_amd_form_device(*args) if ctx is None else lib.bl_amd_ctx_form_device(ctx.handle, *args))
+        args = tuple(arg[k] for k in ("frames", "counts", "n", "params", "rec") + ALL + ("n_units",))
+        self._call = ((lib.bl_amd_form_device, args) if ctx is None
+                      else (lib.bl_amd_ctx_form_device, (ctx.handle,) + args))
+        self.rc = None if defer else self.go(stream)
+
+    def go(self, stream=None):
+        fn, args = self._call
+        self.rc = fn(*args, None if stream is None else C.c_void_p(stream.cuda_stream))
+        return self.rc
 
     def read(self):
         assert self.rc == 0

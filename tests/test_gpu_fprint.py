@@ -54,9 +54,11 @@ def to_device(a):
 # ---- words -------------------------------------------------------------------------------------------------------
 
 class Words:
-    """one device call on the chromagrams `songs`; the words were filled with 0xA5"""
+    """one device call on the chromagrams `songs`; the words were filled with 0xA5.  `stream`: a torch stream instead of
+    the default one; `defer`: the call is made by go() (tests/test_gpu_side_ws.py)"""
 
-    def __init__(self, lib, songs, ctx=None, n=None, n_words=None, counts=None, frames=True, out=True, shift=(0, 0)):
+    def __init__(self, lib, songs, ctx=None, n=None, n_words=None, counts=None, frames=True, out=True, shift=(0, 0),
+                 stream=None, defer=False):
         self.counts = [int(x.shape[0]) for x in songs] if counts is None else counts
         self.total = sum(max(0, t - 15) for t in self.counts if 0 <= t)
         X = np.concatenate([np.asarray(x, np.uint64).reshape(-1, 12) for x in songs] + [np.zeros((1, 12), np.uint64)])
@@ -65,9 +67,15 @@ class Words:
         arr = (C.c_int32 * len(self.counts))(*self.counts)
         args = (C.c_void_p(self.frames.data_ptr() + shift[0]) if frames else None, arr,
                 len(songs) if n is None else n, C.c_void_p(self.out.data_ptr() + shift[1]) if out else None,
-                self.total if n_words is None else n_words, None)
-        self.rc = (lib.bl_amd_fprint_words_device(*args) if ctx is None
-                   else lib.bl_amd_ctx_fprint_words_device(ctx.handle, *args))
+                self.total if n_words is None else n_words)
+        self._call = ((lib.bl_amd_fprint_words_device, args) if ctx is None
+                      else (lib.bl_amd_ctx_fprint_words_device, (ctx.handle,) + args))
+        self.rc = None if defer else self.go(stream)
+
+    def go(self, stream=None):
+        fn, args = self._call
+        self.rc = fn(*args, None if stream is None else C.c_void_p(stream.cuda_stream))
+        return self.rc
 
     def read(self):
         assert self.rc == 0
@@ -150,9 +158,10 @@ def test_words_rejected_arguments_write_nothing(gpu_lib):
 # ---- match -------------------------------------------------------------------------------------------------------
 
 class Match:
-    """one device call; the records and the profile were filled with 0xA5"""
+    """one device call; the records and the profile were filled with 0xA5.  `stream` and `defer` as for Words"""
 
-    def __init__(self, lib, set_a, set_b, pairs, D, mo=1, profile=True, ctx=None, self_form=False, bad=None):
+    def __init__(self, lib, set_a, set_b, pairs, D, mo=1, profile=True, ctx=None, self_form=False, bad=None,
+                 stream=None, defer=False):
         self.a, self.b = set_a, set_a if self_form else set_b
         self.pairs, self.D, self.mo = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2), D, mo
         self.n = self.pairs.shape[0]
@@ -169,10 +178,15 @@ class Match:
                    prof=C.c_void_p(self.prof.data_ptr()) if profile else None)
         for k, v in (bad or {}).items():
             arg[k] = v(self) if callable(v) else v
-        args = tuple(arg[k] for k in ("wa", "ca", "na", "wb", "cb", "nb", "pairs", "n", "D", "mo", "rec", "prof")) + \
-            (None,)
-        self.rc = (lib.bl_amd_fprint_match_device(*args) if ctx is None
-                   else lib.bl_amd_ctx_fprint_match_device(ctx.handle, *args))
+        args = tuple(arg[k] for k in ("wa", "ca", "na", "wb", "cb", "nb", "pairs", "n", "D", "mo", "rec", "prof"))
+        self._call = ((lib.bl_amd_fprint_match_device, args) if ctx is None
+                      else (lib.bl_amd_ctx_fprint_match_device, (ctx.handle,) + args))
+        self.rc = None if defer else self.go(stream)
+
+    def go(self, stream=None):
+        fn, args = self._call
+        self.rc = fn(*args, None if stream is None else C.c_void_p(stream.cuda_stream))
+        return self.rc
 
     def read(self):
         assert self.rc == 0

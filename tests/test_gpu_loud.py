@@ -43,10 +43,11 @@ def reference(songs, p):
 # ---- running the library -----------------------------------------------------------------------------------------
 
 class Call:
-    """one device call on `songs` = [(pcm, channels)] laid out with gaps of noise; the outputs were filled with 0xA5"""
+    """one device call on `songs` = [(pcm, channels)] laid out with gaps of noise; the outputs were filled with 0xA5.
+    `stream`: a torch stream instead of the default one; `defer`: the call is made by go() (tests/test_gpu_side_ws.py)"""
 
     def __init__(self, lib, songs, p, hops=True, ctx=None, gap=8, n=None, n_hops=None, shift=(0, 0, 0), out=True,
-                 channels=None):
+                 channels=None, stream=None, defer=False):
         import torch
         self.p = params_of(p)
         hop = int(self.p.hop)
@@ -71,9 +72,15 @@ class Call:
         args = (C.c_void_p(self.arena.data_ptr() + shift[0]), desc, self.n, C.byref(self.p),
                 C.c_void_p(self.so.data_ptr() + shift[1]) if out else None,
                 C.c_void_p(self.zo.data_ptr() + shift[2]) if hops else None,
-                self.total if n_hops is None else n_hops, None)
-        self.rc = (lib.bl_amd_loud_batch_device(*args) if ctx is None
-                   else lib.bl_amd_ctx_loud_batch_device(ctx.handle, *args))
+                self.total if n_hops is None else n_hops)
+        self._call = ((lib.bl_amd_loud_batch_device, args) if ctx is None
+                      else (lib.bl_amd_ctx_loud_batch_device, (ctx.handle,) + args))
+        self.rc = None if defer else self.go(stream)
+
+    def go(self, stream=None):
+        fn, args = self._call
+        self.rc = fn(*args, None if stream is None else C.c_void_p(stream.cuda_stream))
+        return self.rc
 
     def _host(self, t, nbytes):
         raw = t.cpu().numpy()
@@ -278,6 +285,7 @@ def test_rejected_calls_write_nothing(lib):
     assert lib.bl_amd_loud_batch_device(C.c_void_p(c.arena.data_ptr()), desc, 1, None,
                                         C.c_void_p(c.so.data_ptr()), None, 0, None) == U
     assert c.untouched()
+    assert_equal(run(lib, songs, p), songs, p, "after the rejections")
 
 
 # ---- the gates, through from_hops ----------------------------------------------------------------------------------------

@@ -43,10 +43,11 @@ def reference(x, ch, ceiling, block):
 # ---- running the library -----------------------------------------------------------------------------------------------------
 
 class Call:
-    """one device call on `songs` = [(pcm, channels)] laid out with gaps of +-32767; the outputs were filled with 0xA5"""
+    """one device call on `songs` = [(pcm, channels)] laid out with gaps of +-32767; the outputs were filled with 0xA5.
+    `stream`: a torch stream instead of the default one; `defer`: the call is made by go() (tests/test_gpu_side_ws.py)"""
 
     def __init__(self, lib, songs, ceiling=32767, block=1, blocks=True, ctx=None, gaps=(8, 24, 40), n=None,
-                 n_blocks=None, shift=(0, 0, 0), out=True, channels=None):
+                 n_blocks=None, shift=(0, 0, 0), out=True, channels=None, stream=None, defer=False):
         import torch
         self.n = len(songs) if n is None else n
         size_of = min(max(block, 1), 65536)   # a rejected block still gets a profile of a plausible size
@@ -69,9 +70,15 @@ class Call:
         args = (C.c_void_p(self.arena.data_ptr() + shift[0]), desc, self.n, ceiling, block,
                 C.c_void_p(self.so.data_ptr() + shift[1]) if out else None,
                 C.c_void_p(self.bo.data_ptr() + shift[2]) if blocks else None,
-                self.total if n_blocks is None else n_blocks, None)
-        self.rc = (lib.bl_amd_tpeak_batch_device(*args) if ctx is None
-                   else lib.bl_amd_ctx_tpeak_batch_device(ctx.handle, *args))
+                self.total if n_blocks is None else n_blocks)
+        self._call = ((lib.bl_amd_tpeak_batch_device, args) if ctx is None
+                      else (lib.bl_amd_ctx_tpeak_batch_device, (ctx.handle,) + args))
+        self.rc = None if defer else self.go(stream)
+
+    def go(self, stream=None):
+        fn, args = self._call
+        self.rc = fn(*args, None if stream is None else C.c_void_p(stream.cuda_stream))
+        return self.rc
 
     def _host(self, t, nbytes):
         raw = t.cpu().numpy()
@@ -311,6 +318,7 @@ def test_rejected_calls_write_nothing(lib):
     for kw in bad:
         c = Call(lib, songs, **kw)
         assert c.rc == U and c.untouched(), kw
+    assert_equal(run(lib, songs), songs, what="after the rejections")
 
 
 def test_host_and_corpus_wrappers_agree_with_the_reference():
