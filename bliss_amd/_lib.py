@@ -122,6 +122,16 @@ class SongForm(C.Structure):  # include/bliss_amd.h bl_amd_song_form
                 ("nov_max_unit", C.c_int32), ("nov_max", C.c_uint64), ("reserved", C.c_uint64)]
 
 
+class CoverParams(C.Structure):  # include/bliss_amd.h bl_amd_cover_params
+    _fields_ = [("thr", C.c_int32), ("gap", C.c_int32), ("transpose", C.c_int32), ("reserved", C.c_int32)]
+
+
+class CoverMatch(C.Structure):  # include/bliss_amd.h bl_amd_cover_match
+    _fields_ = [("score", C.c_uint32), ("a_start", C.c_int32), ("a_end", C.c_int32), ("b_start", C.c_int32),
+                ("b_end", C.c_int32), ("transpose", C.c_int32), ("units_a", C.c_int32), ("units_b", C.c_int32),
+                ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
 class FrameChroma(C.Structure):  # include/bliss_amd.h bl_amd_frame_chroma
     _fields_ = [("x", C.c_uint64 * 12)]
 
@@ -362,6 +372,23 @@ SYMBOLS = {
     "bl_amd_form_score": (C.c_double, [_P(SongForm)]),
     "bl_amd_form_shape": (None, [_P(C.c_int), _P(C.c_int)]),
     "bl_amd_form_profile_ms": (C.c_double, [C.c_char_p, _P(C.c_int)]),
+    "bl_amd_cover_units_device": (C.c_int, [C.c_void_p, _P(C.c_int32), C.c_int, C.c_int, C.c_void_p, C.c_longlong,
+                                            C.c_void_p]),
+    "bl_amd_ctx_cover_units_device": (C.c_int, [C.c_void_p, C.c_void_p, _P(C.c_int32), C.c_int, C.c_int, C.c_void_p,
+                                                C.c_longlong, C.c_void_p]),
+    "bl_amd_cover_units_host": (C.c_int, [C.c_void_p, _P(C.c_int32), C.c_int, C.c_int, C.c_void_p]),
+    "bl_amd_cover_match_device": (C.c_int, [C.c_void_p, _P(C.c_int32), C.c_int, C.c_void_p, _P(C.c_int32), C.c_int,
+                                            C.c_void_p, C.c_int, _P(CoverParams), C.c_void_p, C.c_void_p]),
+    "bl_amd_ctx_cover_match_device": (C.c_int, [C.c_void_p, C.c_void_p, _P(C.c_int32), C.c_int, C.c_void_p,
+                                                _P(C.c_int32), C.c_int, C.c_void_p, C.c_int, _P(CoverParams),
+                                                C.c_void_p, C.c_void_p]),
+    "bl_amd_cover_match_host": (C.c_int, [C.c_void_p, _P(C.c_int32), C.c_int, C.c_void_p, _P(C.c_int32), C.c_int,
+                                          C.c_void_p, C.c_int, _P(CoverParams), C.c_void_p]),
+    "bl_amd_cover_score": (C.c_double, [_P(CoverMatch), C.c_int]),
+    "bl_amd_cover_seconds": (C.c_double, [C.c_int, C.c_int, C.c_int]),
+    "bl_amd_cover_tempo_ratio": (C.c_double, [_P(CoverMatch)]),
+    "bl_amd_cover_shape": (None, [_P(C.c_int), _P(C.c_int)]),
+    "bl_amd_cover_profile_ms": (C.c_double, [C.c_char_p, _P(C.c_int)]),
     "bl_amd_chroma_frames": (C.c_int, [C.c_int, C.c_int]),
     "bl_amd_chroma_batch_device": (C.c_int, [C.c_void_p, _P(SongDesc), C.c_int, C.c_void_p, C.c_void_p, C.c_longlong,
                                              C.c_void_p]),

@@ -455,6 +455,22 @@ double bl_amd_form_score(const bl_amd_song_form *f) {
   return (double)f->thumb_score / (double)f->thumb_self;
 }
 
+/* ---- versions: the host arithmetic over bl_amd_cover_match (include/bliss_amd.h) ---- */
+
+double bl_amd_cover_score(const bl_amd_cover_match *m, int thr) {
+  if (!m || m->status != 0) return NAN;
+  const double den = (16129.0 - (double)thr) * (double)(m->units_a < m->units_b ? m->units_a : m->units_b);
+  if (!(den > 0.0)) return NAN;
+  return (double)m->score / den;
+}
+
+double bl_amd_cover_seconds(int unit, int pool, int rate) { return bl_amd_form_seconds(unit, pool, rate); }
+
+double bl_amd_cover_tempo_ratio(const bl_amd_cover_match *m) {
+  if (!m || m->status != 0 || m->a_end < m->a_start || m->b_end < m->b_start) return NAN;
+  return (double)(m->b_end - m->b_start + 1) / (double)(m->a_end - m->a_start + 1);
+}
+
 /* ---- harmonic mixes: the host arithmetic of bl_amd_hmix_* (include/bliss_amd.h) ---- */
 
 static int hmix_rule_args_ok(int tempo_tol, int flags) {

@@ -3,8 +3,8 @@
  * bl_runtime.hip (contexts and the single-device analysis C-ABI), bl_host_batch.hip (songs from host memory: the host
  * batch, bl_amd_analyze_files, the *_host forms), bl_query_api.hip (the matrix, playlist and vector-query C-ABI),
  * bl_desc_api.hip (descriptors), bl_multi.hip (multi-device corpus path), bl_side_ws.hip (the workspaces beside the
- * context's own, bl_side_ws.h) and the four call paths on top of those: bl_loud_api.hip, bl_tpeak_api.hip,
- * bl_fprint_api.hip, bl_form_api.hip.
+ * context's own, bl_side_ws.h) and the five call paths on top of those: bl_loud_api.hip, bl_tpeak_api.hip,
+ * bl_fprint_api.hip, bl_form_api.hip, bl_cover_api.hip.
  * C++ only, not installed.
  */
 #ifndef BL_RUNTIME_H_

@@ -19,7 +19,7 @@
  * per-song records (analysis, rate conversion, levels, timbre, tempo, beats, chroma, mel, synthesis, bld_mean_variance_host)
  * does so through record_call, the one place that knows this protocol; the vector queries have
  * query_call (bl_runtime.h), which shares the hand-over (ws_wait, ws_pass) with it.  The loudness, the true peak, the
- * fingerprints and the song structure keep workspaces of their own beside the context's and have side_call
+ * fingerprints, the song structure and the version matching keep workspaces of their own beside the context's and have side_call
  * (bl_side_ws.h), the same protocol over those; the pinned rings of both are served by blr_ring_get.
  *
  * Guards.  An entry point that uses the workspace takes a CtxGuard (context lock + device guard);

@@ -1103,6 +1103,104 @@ double bl_amd_form_score(const bl_amd_song_form *f);
 void bl_amd_form_shape(int *chunk_lags, int *units_block);
 double bl_amd_form_profile_ms(const char *name, int *launches);
 
+/* Versions: whether two files are the same piece in another recording, which is what none of the calls above can say.
+ * A live take, a remaster at another speed, a cover in another key and an edit with a different intro are far apart as
+ * fingerprints (on purpose: those compare frame by frame at a fixed offset) and may be far apart as descriptors.  This
+ * block aligns the two songs' chroma sequences: a local alignment (Smith-Waterman) over their cross-similarity matrix,
+ * after one of them has been rotated to the other's key.  It tolerates a key change, a tempo change and extra or
+ * missing material.  Every quantity is an exact integer; no result depends on launch shape, pair order, batch
+ * composition, the context, or whether the self or the cross form is used.  The definition separates synthetic chord
+ * songs; it has not been tuned on recorded music.
+ *   units    Those of the structure call: 16 bytes, the twelve q in 0 .. 127 and four zero bytes, U = floor(T / pool).
+ *            bl_amd_cover_units_device writes them and nothing else; its bytes equal d_units_out of bl_amd_form_device
+ *            at the same pool.
+ *   sets     As for bl_amd_fprint_match_device: set a is n_a songs' units concatenated (d_units_a, h_count_a[i] units
+ *            each, 0 <= count < 2^20), set b likewise; the self form passes one set twice.  d_pairs is n_pairs x 2 int32
+ *            on the device: an index into a, then one into b; the kernel range-checks both and reads nothing through a
+ *            bad one.
+ *   params   bl_amd_cover_params, passed by pointer: thr in 1 .. 16128, gap in 0 .. 2^20, transpose in -1 .. 11,
+ *            reserved 0.
+ *   transp.  g_x[k] = sum over the units of song x of q[k] (below 2^20).  C(r) = sum over k of g_a[k] g_b[(k + r) mod 12]
+ *            (below 2^44).  With transpose = -1, r is the smallest r in 0 .. 11 that attains the largest C; otherwise
+ *            r = transpose.  A positive r means b sounds r semitones above a.
+ *   simil.   S(i, j) = sum over k of q_a,i[k] q_b,j[(k + r) mod 12], in 0 .. 16129; w(i, j) = S(i, j) - thr.
+ *   align    For 0 <= i < Ua, 0 <= j < Ub, with H(-1, .) = H(., -1) = 0:
+ *              d = H(i-1, j-1) + w(i, j),  u = H(i-1, j) - gap,  l = H(i, j-1) - gap,  H(i, j) = max(0, d, u, l).
+ *            H <= 16129 x 8192 < 2^27.
+ *   origin   O(i, j) is defined where H(i, j) > 0; the first rule that applies decides.  If d = H(i, j): (i, j) when
+ *            H(i-1, j-1) = 0 (the path starts here), otherwise O(i-1, j-1).  Else if u = H(i, j): O(i-1, j).  Otherwise
+ *            O(i, j-1).  The diagonal is preferred over up, and up over left.
+ *   best     The cell with the largest 64-bit key H 2^26 + (8191 - i) 2^13 + (8191 - j): the largest score, then the
+ *            smaller i, then the smaller j.  The aligned stretch is from that cell's origin to the cell, inclusive.
+ *   status   0, or an OR of BL_AMD_COVER_NO_MATCH (the best H is 0, which includes an empty song: the units are
+ *            written, the transposition where both songs have units, the rest is 0), BL_AMD_COVER_TOO_LONG (a song has
+ *            more than BL_AMD_FORM_UNITS_MAX units: the units are written, the rest is 0; the other pairs still
+ *            succeed) and BL_AMD_COVER_BAD_INDEX (a pair index outside its set: everything else is 0).
+ * Out of scope: trying all twelve transpositions, a traceback of the path, tuning on recorded music. */
+#define BL_AMD_COVER_NO_MATCH 1
+#define BL_AMD_COVER_TOO_LONG 2
+#define BL_AMD_COVER_BAD_INDEX 4
+typedef struct bl_amd_cover_params { /* 16 bytes */
+  int32_t thr;       /* what a pair of units must reach to count for the alignment */
+  int32_t gap;       /* what a step along one song alone costs */
+  int32_t transpose; /* -1: found from the profiles; 0 .. 11: given */
+  int32_t reserved;  /* must be 0 */
+} bl_amd_cover_params;
+typedef struct bl_amd_cover_match { /* 40 bytes, every byte written for every pair */
+  uint32_t score;    /* H of the best cell */
+  int32_t a_start;   /* the origin's i */
+  int32_t a_end;     /* the best cell's i */
+  int32_t b_start;   /* the origin's j */
+  int32_t b_end;     /* the best cell's j */
+  int32_t transpose; /* r */
+  int32_t units_a;   /* Ua */
+  int32_t units_b;   /* Ub */
+  int32_t status;
+  int32_t reserved;  /* 0 */
+} bl_amd_cover_match;
+/* bl_amd_cover_units_device: the units of n_songs songs; d_frames, h_frames and the counts' rules are those of
+ *   bl_amd_form_device, pool is in 1 .. 16, n_units must equal the sum of all U (it may be 0; d_units_out is needed all
+ *   the same, 16-byte aligned).  bl_amd_ctx_cover_units_device: the same on an explicit context.
+ *   bl_amd_cover_units_host: from host memory, blocking.
+ * bl_amd_cover_match_device: one record per pair.  A pair's record depends on its two sequences and the three
+ *   parameters only; no unit outside the two sequences is read.  Asynchronous on `stream`; the host arrays and the
+ *   parameters are copied before the call returns.  bl_amd_ctx_cover_match_device: on an explicit context.
+ *   bl_amd_cover_match_host: everything in host memory, blocking.
+ * A rejected call returns BL_UNEXPECTED and writes nothing: a NULL required pointer, a misaligned pointer (frame records
+ * and pairs 8 bytes, units 16, records 4), n_songs, n_a, n_b or n_pairs < 1, a count outside [0, 2^20), a wrong n_units,
+ * a parameter out of range, a reserved word that is not 0.  The workspace is kept per context (32 bytes per song of a
+ * units call; 16 + 48 bytes per song of the two sets of a match); bl_amd_ctx_destroy frees it with the context.
+ * Host arithmetic, no device:
+ *   bl_amd_cover_score: score / ((16129 - thr) min(units_a, units_b)), the share of the shorter song that aligns
+ *     perfectly; NaN for a NULL record, a status other than 0 or a denominator that is not positive.
+ *   bl_amd_cover_seconds: unit pool 2048 / rate, as bl_amd_form_seconds.
+ *   bl_amd_cover_tempo_ratio: (b_end - b_start + 1) / (a_end - a_start + 1): how much longer b takes over the aligned
+ *     stretch; NaN for a NULL record or a status other than 0.
+ *   bl_amd_cover_shape: the lengths at which the alignment changes path, for tests: the columns of b one wavefront owns
+ *     at a time and the rows of a it fetches at a time.  Either pointer may be NULL.
+ *   bl_amd_cover_profile_ms: as bl_amd_fprint_profile_ms, for "cover_profile" and "cover_align". */
+int bl_amd_cover_units_device(const bl_amd_frame_chroma *d_frames, const int32_t *h_frames, int n_songs, int pool,
+                              void *d_units_out, long long n_units, void *stream);
+int bl_amd_ctx_cover_units_device(bl_amd_ctx *ctx, const bl_amd_frame_chroma *d_frames, const int32_t *h_frames,
+                                  int n_songs, int pool, void *d_units_out, long long n_units, void *stream);
+int bl_amd_cover_units_host(const bl_amd_frame_chroma *h_frame_records, const int32_t *h_frames, int n_songs, int pool,
+                            void *h_units_out);
+int bl_amd_cover_match_device(const void *d_units_a, const int32_t *h_count_a, int n_a, const void *d_units_b,
+                              const int32_t *h_count_b, int n_b, const int32_t *d_pairs, int n_pairs,
+                              const bl_amd_cover_params *params, bl_amd_cover_match *d_out, void *stream);
+int bl_amd_ctx_cover_match_device(bl_amd_ctx *ctx, const void *d_units_a, const int32_t *h_count_a, int n_a,
+                                  const void *d_units_b, const int32_t *h_count_b, int n_b, const int32_t *d_pairs,
+                                  int n_pairs, const bl_amd_cover_params *params, bl_amd_cover_match *d_out,
+                                  void *stream);
+int bl_amd_cover_match_host(const void *h_units_a, const int32_t *h_count_a, int n_a, const void *h_units_b,
+                            const int32_t *h_count_b, int n_b, const int32_t *h_pairs, int n_pairs,
+                            const bl_amd_cover_params *params, bl_amd_cover_match *h_out);
+double bl_amd_cover_score(const bl_amd_cover_match *m, int thr);
+double bl_amd_cover_seconds(int unit, int pool, int rate);
+double bl_amd_cover_tempo_ratio(const bl_amd_cover_match *m);
+void bl_amd_cover_shape(int *strip_columns, int *row_block);
+double bl_amd_cover_profile_ms(const char *name, int *launches);
+
 /* Mel bands, cepstrum and flatness: the shape of every frame's spectrum.  The centroid and the rolloff of the timbre
  * block say where a frame's power sits and where it stops; the 32 log-mel band levels say how it is spread, the 13
  * cepstral coefficients (MFCC) are the usual compact description of that spread, and the flatness tells noise from
