@@ -1,9 +1,9 @@
 /*
  * bl_host_batch.hip — everything that feeds songs from host memory: the host batch (blr_analyze_host: waves of songs
  * through two pinned buffers or the caller's registered ones, copy/compute overlap on 2 streams, optional device rate
- * conversion), its C-ABI (bl_amd_*analyze_batch_host*, bl_amd_set_host_transfer), the corpus loop over files
- * (bl_amd_analyze_files) and the host forms of the signal levels, the spectral timbre, the tempo, the chroma and the mel call.  Host code only; contexts,
- * the record uploads and every device entry point are bl_runtime.hip's, the wave rule is bl_waves.h's.
+ * conversion), its C-ABI (bl_amd_*analyze_batch_host*, bl_amd_set_host_transfer) and the corpus loop over files
+ * (bl_amd_analyze_files).  Host code only; contexts and the analysis' device form are bl_runtime.hip's, the wave rule
+ * is bl_waves.h's.  The *_batch_host forms of the per-song features are bl_feature_api.hip's and bl_*_api.hip's.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -261,146 +261,10 @@ int blr_analyze_host(bl_amd_ctx *c, const void *const *h_pcm, int pcm_is_s32, co
   return BL_OK;
 }
 
-/* The host forms of the signal levels, the spectral timbre, the tempo, the chroma and the mel call below share
- * host_waves (bl_runtime.h), which cuts the songs into waves; each form's lambda runs its device form on one wave and
- * fetches what it computed. */
-
 /* ========================================================================= */
 /* C-ABI                                                                      */
 
 extern "C" {
-
-int bl_amd_levels_batch_host(const int16_t *const *h_pcm, const int32_t *n_samples, const int32_t *channels,
-                             int n_songs, int silence, bl_amd_song_levels *h_levels) {
-  if (!h_pcm || !n_samples || !channels || !h_levels || n_songs < 1 || silence < 0 || silence > 32767)
-    return BL_UNEXPECTED;
-  for (int i = 0; i < n_songs; ++i)
-    if (!h_pcm[i] || !levels_song_ok(0, n_samples[i], channels[i])) return BL_UNEXPECTED;
-  bl_amd_ctx *c = blr_default_ctx();
-  if (!c) return BL_UNEXPECTED;
-  DevGuard dg(c->device);
-  if (!dg.ok) return BL_UNEXPECTED;
-  return host_waves(c, h_pcm, n_samples, channels, n_songs,
-                    [&](const int16_t *d_pcm, const bl_amd_song_desc *desc, int b, int e) {
-                      DevMem out(sizeof(bl_amd_song_levels) * (size_t)(e - b));
-                      return out.ok() &&
-                                     bl_amd_levels_batch_device(d_pcm, desc, e - b, silence,
-                                                                out.as<bl_amd_song_levels>(), nullptr) == BL_OK &&
-                                     out.down(h_levels + b)
-                                 ? BL_OK
-                                 : BL_UNEXPECTED;
-                    });
-}
-
-int bl_amd_timbre_batch_host(const int16_t *const *h_pcm, const int32_t *n_samples, const int32_t *channels,
-                             int n_songs, int pct, uint64_t min_energy, bl_amd_song_timbre *h_songs_out,
-                             bl_amd_frame_timbre *h_frames_out) {
-  if (!h_pcm || !n_samples || !channels || !h_songs_out || n_songs < 1 || pct < 1 || pct > 100) return BL_UNEXPECTED;
-  for (int i = 0; i < n_songs; ++i)
-    if (!h_pcm[i] || !timbre_song_ok(0, n_samples[i], channels[i])) return BL_UNEXPECTED;
-  bl_amd_ctx *c = blr_default_ctx();
-  if (!c) return BL_UNEXPECTED;
-  DevGuard dg(c->device);
-  if (!dg.ok) return BL_UNEXPECTED;
-  return host_waves(c, h_pcm, n_samples, channels, n_songs,
-                    [&](const int16_t *d_pcm, const bl_amd_song_desc *desc, int b, int e) {
-                      long long frames = 0;
-                      for (int i = b; i < e; ++i) frames += bl_amd_timbre_frames(n_samples[i], channels[i]);
-                      DevMem out(sizeof(bl_amd_song_timbre) * (size_t)(e - b)),
-                          fout(h_frames_out ? sizeof(bl_amd_frame_timbre) * (size_t)frames : 0);
-                      if (!out.ok() || !fout.ok() ||
-                          bl_amd_timbre_batch_device(d_pcm, desc, e - b, pct, min_energy, out.as<bl_amd_song_timbre>(),
-                                                     fout.as<bl_amd_frame_timbre>(), frames, nullptr) != BL_OK ||
-                          !out.down(h_songs_out + b) || (h_frames_out && !fout.down(h_frames_out)))
-                        return BL_UNEXPECTED;
-                      if (h_frames_out) h_frames_out += frames;
-                      return BL_OK;
-                    });
-}
-
-int bl_amd_rhythm_batch_host(const int16_t *const *h_pcm, const int32_t *n_samples, const int32_t *channels,
-                             int n_songs, int lag_min, int lag_max, bl_amd_song_rhythm *h_songs_out,
-                             uint32_t *h_onsets_out, uint64_t *h_acf_out) {
-  if (!h_pcm || !n_samples || !channels || !h_songs_out || n_songs < 1 || !rhythm_lags_ok(lag_min, lag_max))
-    return BL_UNEXPECTED;
-  for (int i = 0; i < n_songs; ++i)
-    if (!h_pcm[i] || !rhythm_song_ok(0, n_samples[i], channels[i])) return BL_UNEXPECTED;
-  bl_amd_ctx *c = blr_default_ctx();
-  if (!c) return BL_UNEXPECTED;
-  DevGuard dg(c->device);
-  if (!dg.ok) return BL_UNEXPECTED;
-  return host_waves(c, h_pcm, n_samples, channels, n_songs,
-                    [&](const int16_t *d_pcm, const bl_amd_song_desc *desc, int b, int e) {
-                      long long hops = 0;
-                      for (int i = b; i < e; ++i) hops += bl_amd_rhythm_hops(n_samples[i], channels[i]);
-                      DevMem out(sizeof(bl_amd_song_rhythm) * (size_t)(e - b)),
-                          oout(h_onsets_out ? sizeof(uint32_t) * (size_t)hops : 0),
-                          aout(h_acf_out ? sizeof(uint64_t) * BL_AMD_RHYTHM_LAGS * (size_t)(e - b) : 0);
-                      if (!out.ok() || !oout.ok() || !aout.ok() ||
-                          bl_amd_rhythm_batch_device(d_pcm, desc, e - b, lag_min, lag_max, out.as<bl_amd_song_rhythm>(),
-                                                     oout.as<uint32_t>(), hops, aout.as<uint64_t>(), nullptr) != BL_OK ||
-                          !out.down(h_songs_out + b) || (h_onsets_out && !oout.down(h_onsets_out)) ||
-                          (h_acf_out && !aout.down(h_acf_out + (size_t)BL_AMD_RHYTHM_LAGS * (size_t)b)))
-                        return BL_UNEXPECTED;
-                      if (h_onsets_out) h_onsets_out += hops;
-                      return BL_OK;
-                    });
-}
-
-int bl_amd_chroma_batch_host(const int16_t *const *h_pcm, const int32_t *n_samples, const int32_t *channels,
-                             int n_songs, bl_amd_song_chroma *h_songs_out, bl_amd_frame_chroma *h_frames_out) {
-  if (!h_pcm || !n_samples || !channels || !h_songs_out || n_songs < 1) return BL_UNEXPECTED;
-  for (int i = 0; i < n_songs; ++i)
-    if (!h_pcm[i] || !chroma_song_ok(0, n_samples[i], channels[i])) return BL_UNEXPECTED;
-  bl_amd_ctx *c = blr_default_ctx();
-  if (!c) return BL_UNEXPECTED;
-  DevGuard dg(c->device);
-  if (!dg.ok) return BL_UNEXPECTED;
-  return host_waves(c, h_pcm, n_samples, channels, n_songs,
-                    [&](const int16_t *d_pcm, const bl_amd_song_desc *desc, int b, int e) {
-                      long long frames = 0;
-                      for (int i = b; i < e; ++i) frames += bl_amd_chroma_frames(n_samples[i], channels[i]);
-                      DevMem out(sizeof(bl_amd_song_chroma) * (size_t)(e - b)),
-                          fout(h_frames_out ? sizeof(bl_amd_frame_chroma) * (size_t)frames : 0);
-                      if (!out.ok() || !fout.ok() ||
-                          bl_amd_chroma_batch_device(d_pcm, desc, e - b, out.as<bl_amd_song_chroma>(),
-                                                     fout.as<bl_amd_frame_chroma>(), frames, nullptr) != BL_OK ||
-                          !out.down(h_songs_out + b) || (h_frames_out && !fout.down(h_frames_out)))
-                        return BL_UNEXPECTED;
-                      if (h_frames_out) h_frames_out += frames;
-                      return BL_OK;
-                    });
-}
-
-int bl_amd_mel_batch_host(const int16_t *const *h_pcm, const int32_t *n_samples, const int32_t *channels, int n_songs,
-                          uint64_t min_energy, bl_amd_song_mel *h_songs_out, bl_amd_frame_mel *h_frames_out,
-                          uint32_t *h_bands_out) {
-  if (!h_pcm || !n_samples || !channels || !h_songs_out || n_songs < 1) return BL_UNEXPECTED;
-  for (int i = 0; i < n_songs; ++i)
-    if (!h_pcm[i] || !timbre_song_ok(0, n_samples[i], channels[i])) return BL_UNEXPECTED;
-  bl_amd_ctx *c = blr_default_ctx();
-  if (!c) return BL_UNEXPECTED;
-  DevGuard dg(c->device);
-  if (!dg.ok) return BL_UNEXPECTED;
-  return host_waves(c, h_pcm, n_samples, channels, n_songs,
-                    [&](const int16_t *d_pcm, const bl_amd_song_desc *desc, int b, int e) {
-                      long long frames = 0;
-                      for (int i = b; i < e; ++i) frames += bl_amd_mel_frames(n_samples[i], channels[i]);
-                      DevMem out(sizeof(bl_amd_song_mel) * (size_t)(e - b)),
-                          fout(h_frames_out ? sizeof(bl_amd_frame_mel) * (size_t)frames : 0),
-                          bout(h_bands_out ? sizeof(uint32_t) * BL_AMD_MEL_BANDS * (size_t)frames : 0);
-                      if (!out.ok() || !fout.ok() || !bout.ok() ||
-                          bl_amd_mel_batch_device(d_pcm, desc, e - b, min_energy, out.as<bl_amd_song_mel>(),
-                                                  fout.as<bl_amd_frame_mel>(), bout.as<uint32_t>(), frames,
-                                                  nullptr) != BL_OK ||
-                          !out.down(h_songs_out + b) || (h_frames_out && !fout.down(h_frames_out)) ||
-                          (h_bands_out && !bout.down(h_bands_out)))
-                        return BL_UNEXPECTED;
-                      if (h_frames_out) h_frames_out += frames;
-                      if (h_bands_out) h_bands_out += (size_t)BL_AMD_MEL_BANDS * (size_t)frames;
-                      return BL_OK;
-                    });
-}
 
 int bl_amd_set_host_transfer(int mode) {
   if (mode != BL_AMD_HOST_STAGED && mode != BL_AMD_HOST_REGISTERED) return BL_UNEXPECTED;

@@ -125,32 +125,21 @@ int bl_amd_loud_from_hops(const uint64_t *h_hop_energy, const int32_t *h_hops, i
   return out.down(h_songs_out) ? BL_OK : BL_UNEXPECTED;
 }
 
-/* the songs in waves (host_waves, bl_runtime.h): each is measured by the device form and fetched */
+/* the songs in waves (host_form, bl_runtime.h): each is measured by the device form and fetched */
 int bl_amd_loud_batch_host(const int16_t *const *h_pcm, const int32_t *n_samples, const int32_t *channels, int n_songs,
                            const bl_amd_loud_params *params, bl_amd_song_loud *h_songs_out, uint64_t *h_hops_out) {
-  if (!h_pcm || !n_samples || !channels || !h_songs_out || n_songs < 1 || !loud_params_ok(params, false))
-    return BL_UNEXPECTED;
-  for (int i = 0; i < n_songs; ++i)
-    if (!h_pcm[i] || !loud_song_ok(0, n_samples[i], channels[i])) return BL_UNEXPECTED;
-  bl_amd_ctx *c = blr_default_ctx();
-  if (!c) return BL_UNEXPECTED;
-  DevGuard dg(c->device);
-  if (!dg.ok) return BL_UNEXPECTED;
-  return host_waves(c, h_pcm, n_samples, channels, n_songs,
-                    [&](const int16_t *d_pcm, const bl_amd_song_desc *desc, int b, int e) {
-                      long long hops = 0;
-                      for (int i = b; i < e; ++i) hops += loud_hops(n_samples[i], channels[i], params->hop);
-                      DevMem out(sizeof(bl_amd_song_loud) * (size_t)(e - b)), zout(h_hops_out ? 16 * (size_t)hops : 0);
-                      if (!out.ok() || !zout.ok() ||
-                          bl_amd_loud_batch_device(d_pcm, desc, e - b, params, out.as<bl_amd_song_loud>(),
-                                                   zout.as<uint64_t>(), hops, nullptr) != BL_OK)
-                        return BL_UNEXPECTED;
-                      BL_HIP_CHECK(hipStreamSynchronize(nullptr));
-                      if (!out.down(h_songs_out + b) || (h_hops_out && hops && !zout.down(h_hops_out)))
-                        return BL_UNEXPECTED;
-                      if (h_hops_out) h_hops_out += 2 * hops;
-                      return BL_OK;
-                    });
+  return host_form(h_pcm, n_samples, channels, n_songs, h_songs_out && loud_params_ok(params, false), loud_song_ok,
+                   [&](const int16_t *d_pcm, const bl_amd_song_desc *desc, int b, int e) {
+                     long long hops = 0;
+                     for (int i = b; i < e; ++i) hops += loud_hops(n_samples[i], channels[i], params->hop);
+                     WaveOut<bl_amd_song_loud> out(h_songs_out, e - b);
+                     WaveOut<uint64_t> zout(h_hops_out, 2 * hops);
+                     if (!out.ok() || !zout.ok() ||
+                         bl_amd_loud_batch_device(d_pcm, desc, e - b, params, out.dev(), zout.dev(), hops, nullptr) != BL_OK)
+                       return BL_UNEXPECTED;
+                     BL_HIP_CHECK(hipStreamSynchronize(nullptr));
+                     return out.fetch() && (!hops || zout.fetch()) ? BL_OK : BL_UNEXPECTED;
+                   });
 }
 
 /* device time of a loudness kernel since this was last asked for it: "loud_filter" or "loud_gate" */

@@ -1,7 +1,8 @@
 /*
  * bl_runtime.h — internal: the per-device context behind include/bliss_amd.h, shared by
  * bl_runtime.hip (contexts and the single-device analysis C-ABI), bl_host_batch.hip (songs from host memory: the host
- * batch, bl_amd_analyze_files, the *_host forms), bl_query_api.hip (the matrix, playlist and vector-query C-ABI),
+ * batch, bl_amd_analyze_files), bl_feature_api.hip (levels, timbre, tempo, beats, chroma and mel: device and host
+ * forms), bl_query_api.hip (the matrix, playlist and vector-query C-ABI),
  * bl_desc_api.hip (descriptors), bl_multi.hip (multi-device corpus path), bl_side_ws.hip (the workspaces beside the
  * context's own, bl_side_ws.h) and the five call paths on top of those: bl_loud_api.hip, bl_tpeak_api.hip,
  * bl_fprint_api.hip, bl_form_api.hip, bl_cover_api.hip.
@@ -276,6 +277,40 @@ int host_waves(bl_amd_ctx *c, const int16_t *const *h_pcm, const int32_t *n_samp
   return BL_OK;
 }
 
+/* A *_batch_host form from its first check to its last wave.  `args_ok`: what the form asks of its other arguments;
+ * `song_ok(0, n_samples, channels)`: what its device form accepts of a song.  The order is behaviour: a call refused
+ * for its arguments creates no context.  Then the default context, its device made current, and host_waves. */
+template <class SongOk, class Wave>
+int host_form(const int16_t *const *h_pcm, const int32_t *n_samples, const int32_t *channels, int n_songs, bool args_ok,
+              SongOk song_ok, Wave wave) {
+  if (!h_pcm || !n_samples || !channels || n_songs < 1 || !args_ok) return BL_UNEXPECTED;
+  for (int i = 0; i < n_songs; ++i)
+    if (!h_pcm[i] || !song_ok(0, n_samples[i], channels[i])) return BL_UNEXPECTED;
+  bl_amd_ctx *c = blr_default_ctx();
+  if (!c) return BL_UNEXPECTED;
+  DevGuard dg(c->device);
+  if (!dg.ok) return BL_UNEXPECTED;
+  return host_waves(c, h_pcm, n_samples, channels, n_songs, wave);
+}
+
+/* One output of one wave of a *_batch_host form: `count` elements on the device for the caller's host cursor `h`, or
+ * no block and dev() == nullptr where the caller passed none.  fetch() copies them to the cursor and moves it behind
+ * them, so the next wave's follow. */
+template <class T>
+struct WaveOut {
+  T *&h;
+  size_t count;
+  DevMem mem;
+  WaveOut(T *&cursor, size_t n) : h(cursor), count(n), mem(cursor ? sizeof(T) * n : 0) {}
+  bool ok() const { return mem.ok(); }
+  T *dev() const { return mem.as<T>(); }
+  bool fetch() {
+    if (h && !mem.down(h)) return false;
+    if (h) h += count;
+    return true;
+  }
+};
+
 /* the metric and the row range of a vector query (bl_amd_knn_*, bl_amd_chain_*, bl_amd_radius_*, bl_amd_groups_*) */
 inline bool metric_ok(int metric) { return metric == BL_AMD_KNN_DISTANCE || metric == BL_AMD_KNN_COSINE; }
 inline bool rows_ok(int n, int row_begin, int n_rows) {
@@ -290,6 +325,29 @@ int query_call(bl_amd_ctx *c, void *stream, bl_buf &buf, size_t bytes, Launch la
   if (!g.ok()) return BL_UNEXPECTED;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (ws_wait(c, s) != BL_OK || blr_ensure(buf, bytes) != BL_OK || launch(s, buf.p) != BL_OK) return BL_UNEXPECTED;
+  return ws_pass(c, s);
+}
+
+/* One call that uploads n per-song records of type T into `block` and launches on them; the caller holds c->mu and has
+ * made c->device current.  `fill(T *h)` writes the records into a pinned slot (BL_OK, or BL_UNEXPECTED to refuse the
+ * call), `launch(const T *h, T *d)` enqueues the kernels on `s` and grows whatever other workspace they need.
+ * The caller's own descriptors are read by `fill` alone, so they are the caller's again when the call returns, and
+ * hipMemcpyAsync from pinned memory does not block, so nothing here waits for the device.  The order is the protocol:
+ * the wait for the workspace's last user is on `s` before the copy (the record block is workspace); the slot counts as
+ * in flight only once its event is recorded behind the copy, so a call that fails before that leaves the slot free
+ * and the hand-over untouched; the hand-over point moves behind the last launch. */
+template <class T, class Fill, class Launch>
+int record_call(bl_amd_ctx *c, hipStream_t s, bl_buf &block, int n, Fill fill, Launch launch) {
+  const size_t bytes = sizeof(T) * (size_t)n;
+  bl_pin_slot *slot = nullptr;
+  if (blr_ring_get(c->ring, c->ring_next, bytes, &slot) != BL_OK) return BL_UNEXPECTED;
+  T *h = static_cast<T *>(slot->p);
+  if (fill(h) != BL_OK || ws_wait(c, s) != BL_OK || blr_ensure(block, bytes) != BL_OK) return BL_UNEXPECTED;
+  T *d = static_cast<T *>(block.p);
+  BL_HIP_CHECK(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s));
+  BL_HIP_CHECK(hipEventRecord(slot->ev, s));
+  slot->busy = true;
+  if (launch(h, d) != BL_OK) return BL_UNEXPECTED;
   return ws_pass(c, s);
 }
 

@@ -1,8 +1,9 @@
 /*
  * bl_runtime.hip — contexts, workspaces, streams and the single-device C-ABI of
- * include/bliss_amd.h, but for the matrix, playlists and vector queries (bl_query_api.hip) and for everything that feeds
- * songs from host memory (bl_host_batch.hip: the host batch, bl_amd_analyze_files, the *_host forms of levels,
- * timbre and tempo).  Host code only (compiled by hipcc for the HIP runtime API); every
+ * include/bliss_amd.h (the analysis, the rate converter, the synthesis, the self-tests, the diagnostics), but for the
+ * matrix, playlists and vector queries (bl_query_api.hip), the per-song features (bl_feature_api.hip: levels, timbre,
+ * tempo, beats, chroma, mel; bl_*_api.hip for the newer ones) and the host batch and bl_amd_analyze_files
+ * (bl_host_batch.hip).  Host code only (compiled by hipcc for the HIP runtime API); every
  * kernel lives in a bl_*kernels.hip file and is reached through the launchers of bl_launch.h.
  *
  * Contexts.  A bl_amd_ctx owns one device's scratch workspace, internal streams and pinned
@@ -17,14 +18,14 @@
  * 32 768 songs follow each other on the stream, and the shared workspace is handed from one
  * batch to the next by an event, not by a host synchronisation.  Every entry point that uploads
  * per-song records (analysis, rate conversion, levels, timbre, tempo, beats, chroma, mel, synthesis, bld_mean_variance_host)
- * does so through record_call, the one place that knows this protocol; the vector queries have
- * query_call (bl_runtime.h), which shares the hand-over (ws_wait, ws_pass) with it.  The loudness, the true peak, the
+ * does so through record_call (bl_runtime.h), the one place that knows this protocol; the vector queries have
+ * query_call beside it, which shares the hand-over (ws_wait, ws_pass) with it.  The loudness, the true peak, the
  * fingerprints, the song structure and the version matching keep workspaces of their own beside the context's and have side_call
  * (bl_side_ws.h), the same protocol over those; the pinned rings of both are served by blr_ring_get.
  *
  * Guards.  An entry point that uses the workspace takes a CtxGuard (context lock + device guard);
- * the *_host forms of levels, timbre and tempo, the selftests and bl_amd_narrow_s32_device use no workspace themselves and
- * take a DevGuard alone.  Either way a device that cannot be made current ends the call.
+ * the *_batch_host forms (host_form, bl_runtime.h), the selftests and bl_amd_narrow_s32_device use no workspace
+ * themselves and take a DevGuard alone.  Either way a device that cannot be made current ends the call.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -154,29 +155,6 @@ int current_device(void) {
   if (tl_device >= 0) return tl_device;
   const int d = g_process_device.load();
   return d >= 0 ? d : 0;
-}
-
-/* One call that uploads n per-song records of type T into `block` and launches on them; the caller holds c->mu and has
- * made c->device current.  `fill(T *h)` writes the records into a pinned slot (BL_OK, or BL_UNEXPECTED to refuse the
- * call), `launch(const T *h, T *d)` enqueues the kernels on `s` and grows whatever other workspace they need.
- * The caller's own descriptors are read by `fill` alone, so they are the caller's again when the call returns, and
- * hipMemcpyAsync from pinned memory does not block, so nothing here waits for the device.  The order is the protocol:
- * the wait for the workspace's last user is on `s` before the copy (the record block is workspace); the slot counts as
- * in flight only once its event is recorded behind the copy, so a call that fails before that leaves the slot free
- * and the hand-over untouched; the hand-over point moves behind the last launch. */
-template <class T, class Fill, class Launch>
-int record_call(bl_amd_ctx *c, hipStream_t s, bl_buf &block, int n, Fill fill, Launch launch) {
-  const size_t bytes = sizeof(T) * (size_t)n;
-  bl_pin_slot *slot = nullptr;
-  if (blr_ring_get(c->ring, c->ring_next, bytes, &slot) != BL_OK) return BL_UNEXPECTED;
-  T *h = static_cast<T *>(slot->p);
-  if (fill(h) != BL_OK || ws_wait(c, s) != BL_OK || blr_ensure(block, bytes) != BL_OK) return BL_UNEXPECTED;
-  T *d = static_cast<T *>(block.p);
-  BL_HIP_CHECK(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s));
-  BL_HIP_CHECK(hipEventRecord(slot->ev, s));
-  slot->busy = true;
-  if (launch(h, d) != BL_OK) return BL_UNEXPECTED;
-  return ws_pass(c, s);
 }
 
 /* host mirror of the per-song geometry (integer work of ref tempo_atk_sort.c:63-67,
@@ -492,126 +470,6 @@ static int selftest(uint64_t *counts, int n, Sweep sweep) {
   return BL_OK;
 }
 
-/* ---- tempo: the call path of bl_amd_rhythm_batch_device and bl_amd_rhythm_from_onsets ---- */
-
-/* One call on n_songs songs, from PCM (d_curve == nullptr) or from onset curves on the device; the caller holds the
- * context.  `song(i, rec)` writes pcm_off, hops and channels of song i in the caller's order.  The records are sorted
- * longest first, as the analysis lays its songs out, and cut into launch groups of at most c->group_songs songs and
- * BL_RHYTHM_GROUP_HOPS = 2^25 hops (a longer song is a group of its own; H < 2^24, so there is none).  The groups
- * follow each other on the stream and share the scratch, which is therefore bounded whatever the call: 4 bytes per hop
- * = 128 MiB of novelty values, and per song 16 bytes of sums and, without d_acf_out, 4 KiB of lag products = 128.5 MiB
- * at 32 768 songs. */
-template <class Song>
-static int rhythm_call(bl_amd_ctx *c, hipStream_t s, int n_songs, Song song, const int16_t *d_pcm,
-                       const uint32_t *d_curve, int lag_min, int lag_max, bl_amd_song_rhythm *d_songs_out,
-                       uint32_t *d_onsets_out, uint64_t *d_acf_out) {
-  return record_call<bl_rhythm_song>(c, s, c->rhythm_songs, n_songs, [&](bl_rhythm_song *hs) {
-    long long onset_off = 0;
-    for (int i = 0; i < n_songs; ++i) {
-      song(i, hs[i]);
-      hs[i].onset_off = onset_off;
-      hs[i].out_idx = i;
-      hs[i].reserved = 0;
-      onset_off += hs[i].hops;
-    }
-    std::stable_sort(hs, hs + n_songs, [](const bl_rhythm_song &a, const bl_rhythm_song &b) { return a.hops > b.hops; });
-    const int group_songs = std::min(c->group_songs, BL_RHYTHM_GROUP_SONGS);
-    long long in_group = 0; /* hop_off == 0 marks the first song of a group: every song has H >= 1 */
-    for (int i = 0, count = 0; i < n_songs; ++i, ++count) {
-      if (count == group_songs || (count && in_group + hs[i].hops > BL_RHYTHM_GROUP_HOPS)) in_group = count = 0;
-      hs[i].hop_off = in_group;
-      in_group += hs[i].hops;
-    }
-    return BL_OK;
-  }, [&](const bl_rhythm_song *hs, bl_rhythm_song *d_songs) {
-    auto group_end = [&](int b, long long &hops) {
-      int e = b + 1;
-      for (hops = hs[b].hops; e < n_songs && hs[e].hop_off; ++e) hops += hs[e].hops;
-      return e;
-    };
-    long long hops, max_hops = 0;
-    int max_songs = 0;
-    for (int b = 0, e; b < n_songs; b = e) {
-      e = group_end(b, hops);
-      max_hops = std::max(max_hops, hops);
-      max_songs = std::max(max_songs, e - b);
-    }
-    if ((!d_curve && blr_ensure(c->rhythm_n, sizeof(uint32_t) * (size_t)max_hops) != BL_OK) ||
-        blr_ensure(c->rhythm_rows, blk_rhythm_rows_bytes(max_songs, !d_acf_out)) != BL_OK)
-      return BL_UNEXPECTED;
-    if (d_acf_out)
-      BL_HIP_CHECK(hipMemsetAsync(d_acf_out, 0, sizeof(uint64_t) * BL_AMD_RHYTHM_LAGS * (size_t)n_songs, s));
-    for (int b = 0, e; b < n_songs; b = e) {
-      e = group_end(b, hops);
-      if (blk_rhythm_group(s, d_pcm, d_curve, d_songs + b, e - b, hs[b].hops, lag_min, lag_max, c->n_cu,
-                           static_cast<uint32_t *>(c->rhythm_n.p), c->rhythm_rows.p, d_songs_out, d_onsets_out,
-                           d_acf_out, c->prof ? mark_cb : nullptr, c) != BL_OK)
-        return BL_UNEXPECTED;
-    }
-    return BL_OK;
-  });
-}
-
-/* ---- beats: the call path of bl_amd_beats_device and bl_amd_beats_host ---- */
-
-/* what both forms reject before anything is enqueued; *total: the sum of H over the songs */
-static bool beats_args_ok(const int32_t *h_hops, int n_songs, int tight, long long *total) {
-  if (!h_hops || n_songs < 1 || tight < 0 || tight > BL_AMD_BEATS_TIGHT_MAX) return false;
-  *total = 0;
-  for (int i = 0; i < n_songs; ++i) {
-    if (h_hops[i] < 1 || h_hops[i] >= (1 << 24)) return false;
-    *total += h_hops[i];
-  }
-  return true;
-}
-
-/* One call on n_songs onset curves on the device; the caller holds the context and has checked the arguments.  As the
- * tempo call does, the records are sorted longest first, so that the long songs do not straggle at the end of the
- * grid, and cut into launch groups of at most c->group_songs songs and BL_BEAT_GROUP_HOPS = 2^25 hops, which follow
- * each other on the stream and share the link scratch: 2 bytes per hop = 64 MiB, whatever the call. */
-static int beats_call(bl_amd_ctx *c, hipStream_t s, const uint32_t *d_onsets, const int32_t *h_hops, int n_songs,
-                      const void *d_period, int period_stride, int tight, bl_amd_song_beats *d_songs_out,
-                      uint8_t *d_flags_out, uint16_t *d_links_out, int64_t *d_scores_out) {
-  return record_call<bl_beat_song>(c, s, c->beat_songs, n_songs, [&](bl_beat_song *hs) {
-    long long onset_off = 0;
-    for (int i = 0; i < n_songs; ++i) {
-      hs[i].onset_off = onset_off;
-      hs[i].hops = h_hops[i];
-      hs[i].out_idx = i;
-      onset_off += h_hops[i];
-    }
-    std::stable_sort(hs, hs + n_songs, [](const bl_beat_song &a, const bl_beat_song &b) { return a.hops > b.hops; });
-    const int group_songs = std::min(c->group_songs, BL_BEAT_GROUP_SONGS);
-    long long in_group = 0; /* hop_off == 0 marks the first song of a group: every song has H >= 1 */
-    for (int i = 0, count = 0; i < n_songs; ++i, ++count) {
-      if (count == group_songs || (count && in_group + hs[i].hops > BL_BEAT_GROUP_HOPS)) in_group = count = 0;
-      hs[i].hop_off = in_group;
-      in_group += hs[i].hops;
-    }
-    return BL_OK;
-  }, [&](const bl_beat_song *hs, bl_beat_song *d_songs) {
-    auto group_end = [&](int b, long long &hops) {
-      int e = b + 1;
-      for (hops = hs[b].hops; e < n_songs && hs[e].hop_off; ++e) hops += hs[e].hops;
-      return e;
-    };
-    long long hops, max_hops = 0;
-    for (int b = 0, e; b < n_songs; b = e) {
-      e = group_end(b, hops);
-      max_hops = std::max(max_hops, hops);
-    }
-    if (!d_links_out && blr_ensure(c->beat_links, sizeof(uint16_t) * (size_t)max_hops) != BL_OK) return BL_UNEXPECTED;
-    for (int b = 0, e; b < n_songs; b = e) {
-      e = group_end(b, hops);
-      if (blk_beats_group(s, d_onsets, d_songs + b, e - b, d_period, period_stride, tight, d_songs_out, d_flags_out,
-                          d_links_out, static_cast<uint16_t *>(c->beat_links.p), d_scores_out,
-                          c->prof ? mark_cb : nullptr, c) != BL_OK)
-        return BL_UNEXPECTED;
-    }
-    return BL_OK;
-  });
-}
-
 /* ========================================================================= */
 /* C-ABI                                                                      */
 
@@ -712,305 +570,6 @@ int bl_amd_analyze_batch_device(const int16_t *d_pcm, const bl_amd_song_desc *h_
   return bl_amd_ctx_analyze_batch_device(blr_default_ctx(), d_pcm, h_desc, n_songs, d_results, stream);
 }
 
-/* ---- signal levels (bl_level_kernels.hip) ---------------------------------- */
-
-static int levels_device(bl_amd_ctx *c, bool dflt, const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs,
-                         int silence, bl_amd_song_levels *d_levels, void *stream) {
-  if (!d_pcm || ((uintptr_t)d_pcm & 15) || !h_desc || !d_levels || n_songs < 1 || silence < 0 || silence > 32767)
-    return BL_UNEXPECTED;
-  for (int i = 0; i < n_songs; ++i)
-    if (!levels_song_ok(h_desc[i].pcm_offset, h_desc[i].n_samples, h_desc[i].channels)) return BL_UNEXPECTED;
-  if (!(c = call_ctx(c, dflt))) return BL_UNEXPECTED;
-  CtxGuard g(c);
-  if (!g.ok()) return BL_UNEXPECTED;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  int max_n = 0;
-  return record_call<bl_level_song>(c, s, c->level_songs, n_songs, [&](bl_level_song *hs) {
-    for (int i = 0; i < n_songs; ++i) {
-      hs[i].pcm_off = h_desc[i].pcm_offset;
-      hs[i].n = h_desc[i].n_samples;
-      hs[i].channels = h_desc[i].channels;
-      max_n = std::max(max_n, h_desc[i].n_samples);
-    }
-    return BL_OK;
-  }, [&](const bl_level_song *, bl_level_song *d_songs) {
-    return blk_levels(s, d_pcm, d_songs, n_songs, max_n, silence, c->n_cu, d_levels);
-  });
-}
-
-int bl_amd_ctx_levels_batch_device(bl_amd_ctx *c, const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs,
-                                   int silence, bl_amd_song_levels *d_levels, void *stream) {
-  return levels_device(c, false, d_pcm, h_desc, n_songs, silence, d_levels, stream);
-}
-
-int bl_amd_levels_batch_device(const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs, int silence,
-                               bl_amd_song_levels *d_levels, void *stream) {
-  return levels_device(nullptr, true, d_pcm, h_desc, n_songs, silence, d_levels, stream);
-}
-
-/* ---- per-frame spectral timbre (bl_timbre_kernels.hip) ------------------------ */
-
-/* the records of the kernels that take one workgroup per song over the frames of the frequency pass (k_timbre, k_mel) */
-static int frame_songs_fill(const bl_amd_song_desc *h_desc, int n_songs, bl_timbre_song *hs) {
-  long long frame_off = 0;
-  for (int i = 0; i < n_songs; ++i) {
-    hs[i].pcm_off = h_desc[i].pcm_offset;
-    hs[i].frame_off = frame_off;
-    hs[i].n_frames = bl_amd_timbre_frames(h_desc[i].n_samples, h_desc[i].channels);
-    hs[i].channels = h_desc[i].channels;
-    hs[i].out_idx = i;
-    hs[i].reserved = 0;
-    frame_off += hs[i].n_frames;
-  }
-  /* one workgroup per song, the longest first, as the analysis lays its songs out: the long songs start while there
-   * are short ones left to fill the chip behind them */
-  std::stable_sort(hs, hs + n_songs,
-                   [](const bl_timbre_song &a, const bl_timbre_song &b) { return a.n_frames > b.n_frames; });
-  return BL_OK;
-}
-
-static int timbre_device(bl_amd_ctx *c, bool dflt, const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs,
-                         int pct, uint64_t min_energy, bl_amd_song_timbre *d_songs_out,
-                         bl_amd_frame_timbre *d_frames_out, long long n_frame_records, void *stream) {
-  if (!d_pcm || ((uintptr_t)d_pcm & 15) || !h_desc || !d_songs_out || ((uintptr_t)d_songs_out & 7) ||
-      ((uintptr_t)d_frames_out & 7) || n_songs < 1 || pct < 1 || pct > 100)
-    return BL_UNEXPECTED;
-  long long total = 0; /* the sum of F over the songs */
-  for (int i = 0; i < n_songs; ++i) {
-    if (!timbre_song_ok(h_desc[i].pcm_offset, h_desc[i].n_samples, h_desc[i].channels)) return BL_UNEXPECTED;
-    total += bl_amd_timbre_frames(h_desc[i].n_samples, h_desc[i].channels);
-  }
-  if ((d_frames_out && n_frame_records != total) || !(c = call_ctx(c, dflt))) return BL_UNEXPECTED;
-  CtxGuard g(c);
-  if (!g.ok()) return BL_UNEXPECTED;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return record_call<bl_timbre_song>(c, s, c->timbre_songs, n_songs, [&](bl_timbre_song *hs) {
-    return frame_songs_fill(h_desc, n_songs, hs);
-  }, [&](const bl_timbre_song *, bl_timbre_song *d_songs) {
-    return blk_timbre(s, d_pcm, d_songs, n_songs, c->tb, pct, min_energy, d_songs_out, d_frames_out);
-  });
-}
-
-int bl_amd_ctx_timbre_batch_device(bl_amd_ctx *c, const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs,
-                                   int pct, uint64_t min_energy, bl_amd_song_timbre *d_songs_out,
-                                   bl_amd_frame_timbre *d_frames_out, long long n_frame_records, void *stream) {
-  return timbre_device(c, false, d_pcm, h_desc, n_songs, pct, min_energy, d_songs_out, d_frames_out, n_frame_records,
-                       stream);
-}
-
-int bl_amd_timbre_batch_device(const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs, int pct,
-                               uint64_t min_energy, bl_amd_song_timbre *d_songs_out,
-                               bl_amd_frame_timbre *d_frames_out, long long n_frame_records, void *stream) {
-  return timbre_device(nullptr, true, d_pcm, h_desc, n_songs, pct, min_energy, d_songs_out, d_frames_out,
-                       n_frame_records, stream);
-}
-
-/* ---- tempo (bl_rhythm_kernels.hip) --------------------------------------------- */
-
-static int rhythm_device(bl_amd_ctx *c, bool dflt, const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs,
-                         int lag_min, int lag_max, bl_amd_song_rhythm *d_songs_out, uint32_t *d_onsets_out,
-                         long long n_onsets, uint64_t *d_acf_out, void *stream) {
-  if (!d_pcm || ((uintptr_t)d_pcm & 15) || !h_desc || !d_songs_out || ((uintptr_t)d_songs_out & 7) ||
-      ((uintptr_t)d_onsets_out & 3) || ((uintptr_t)d_acf_out & 7) || n_songs < 1 || !rhythm_lags_ok(lag_min, lag_max))
-    return BL_UNEXPECTED;
-  long long total = 0; /* the sum of H over the songs */
-  for (int i = 0; i < n_songs; ++i) {
-    if (!rhythm_song_ok(h_desc[i].pcm_offset, h_desc[i].n_samples, h_desc[i].channels)) return BL_UNEXPECTED;
-    total += bl_amd_rhythm_hops(h_desc[i].n_samples, h_desc[i].channels);
-  }
-  if ((d_onsets_out && n_onsets != total) || !(c = call_ctx(c, dflt))) return BL_UNEXPECTED;
-  CtxGuard g(c);
-  if (!g.ok()) return BL_UNEXPECTED;
-  return rhythm_call(c, static_cast<hipStream_t>(stream), n_songs, [&](int i, bl_rhythm_song &r) {
-    r.pcm_off = h_desc[i].pcm_offset;
-    r.hops = bl_amd_rhythm_hops(h_desc[i].n_samples, h_desc[i].channels);
-    r.channels = h_desc[i].channels;
-  }, d_pcm, nullptr, lag_min, lag_max, d_songs_out, d_onsets_out, d_acf_out);
-}
-
-int bl_amd_ctx_rhythm_batch_device(bl_amd_ctx *c, const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs,
-                                   int lag_min, int lag_max, bl_amd_song_rhythm *d_songs_out, uint32_t *d_onsets_out,
-                                   long long n_onsets, uint64_t *d_acf_out, void *stream) {
-  return rhythm_device(c, false, d_pcm, h_desc, n_songs, lag_min, lag_max, d_songs_out, d_onsets_out, n_onsets,
-                       d_acf_out, stream);
-}
-
-int bl_amd_rhythm_batch_device(const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs, int lag_min,
-                               int lag_max, bl_amd_song_rhythm *d_songs_out, uint32_t *d_onsets_out,
-                               long long n_onsets, uint64_t *d_acf_out, void *stream) {
-  return rhythm_device(nullptr, true, d_pcm, h_desc, n_songs, lag_min, lag_max, d_songs_out, d_onsets_out, n_onsets,
-                       d_acf_out, stream);
-}
-
-/* ---- beats (bl_beat_kernels.hip) ------------------------------------------------- */
-
-static int beats_device(bl_amd_ctx *c, bool dflt, const uint32_t *d_onsets, const int32_t *h_hops, int n_songs,
-                        const void *d_period, int period_stride, int tight, bl_amd_song_beats *d_songs_out,
-                        uint8_t *d_flags_out, uint16_t *d_links_out, int64_t *d_scores_out, void *stream) {
-  long long total = 0;
-  if (!d_onsets || ((uintptr_t)d_onsets & 3) || !d_period || ((uintptr_t)d_period & 3) || period_stride < 4 ||
-      (period_stride & 3) || !d_songs_out || ((uintptr_t)d_songs_out & 7) || !d_flags_out ||
-      ((uintptr_t)d_links_out & 1) || ((uintptr_t)d_scores_out & 7) || !beats_args_ok(h_hops, n_songs, tight, &total) ||
-      !(c = call_ctx(c, dflt)))
-    return BL_UNEXPECTED;
-  CtxGuard g(c);
-  if (!g.ok()) return BL_UNEXPECTED;
-  return beats_call(c, static_cast<hipStream_t>(stream), d_onsets, h_hops, n_songs, d_period, period_stride, tight,
-                    d_songs_out, d_flags_out, d_links_out, d_scores_out);
-}
-
-int bl_amd_ctx_beats_device(bl_amd_ctx *c, const uint32_t *d_onsets, const int32_t *h_hops, int n_songs,
-                            const void *d_period, int period_stride, int tight, bl_amd_song_beats *d_songs_out,
-                            uint8_t *d_flags_out, uint16_t *d_links_out, int64_t *d_scores_out, void *stream) {
-  return beats_device(c, false, d_onsets, h_hops, n_songs, d_period, period_stride, tight, d_songs_out, d_flags_out,
-                      d_links_out, d_scores_out, stream);
-}
-
-int bl_amd_beats_device(const uint32_t *d_onsets, const int32_t *h_hops, int n_songs, const void *d_period,
-                        int period_stride, int tight, bl_amd_song_beats *d_songs_out, uint8_t *d_flags_out,
-                        uint16_t *d_links_out, int64_t *d_scores_out, void *stream) {
-  return beats_device(nullptr, true, d_onsets, h_hops, n_songs, d_period, period_stride, tight, d_songs_out,
-                      d_flags_out, d_links_out, d_scores_out, stream);
-}
-
-/* the caller's curves and periods: uploaded, through the same launch as the device form, fetched */
-int bl_amd_beats_host(const uint32_t *h_onsets, const int32_t *h_hops, int n_songs, const int32_t *h_period, int tight,
-                      bl_amd_song_beats *h_songs_out, uint8_t *h_flags_out, uint16_t *h_links_out,
-                      int64_t *h_scores_out) {
-  long long total = 0;
-  if (!h_onsets || !h_period || !h_songs_out || !h_flags_out || !beats_args_ok(h_hops, n_songs, tight, &total))
-    return BL_UNEXPECTED;
-  for (long long k = 0; k < total; ++k)
-    if (h_onsets[k] >= (1u << 18)) return BL_UNEXPECTED;
-  bl_amd_ctx *c = blr_default_ctx();
-  if (!c) return BL_UNEXPECTED;
-  CtxGuard g(c);
-  if (!g.ok()) return BL_UNEXPECTED;
-  DevMem curve(sizeof(uint32_t) * (size_t)total), per(sizeof(int32_t) * (size_t)n_songs),
-      out(sizeof(bl_amd_song_beats) * (size_t)n_songs), flags((size_t)total),
-      links(h_links_out ? sizeof(uint16_t) * (size_t)total : 0), scores(h_scores_out ? sizeof(int64_t) * (size_t)total : 0);
-  if (!curve.ok() || !per.ok() || !out.ok() || !flags.ok() || !links.ok() || !scores.ok() || !curve.up(h_onsets) ||
-      !per.up(h_period))
-    return BL_UNEXPECTED;
-  if (beats_call(c, nullptr, curve.as<uint32_t>(), h_hops, n_songs, per.p, 4, tight, out.as<bl_amd_song_beats>(),
-                 flags.as<uint8_t>(), links.as<uint16_t>(), scores.as<int64_t>()) != BL_OK)
-    return BL_UNEXPECTED;
-  BL_HIP_CHECK(hipStreamSynchronize(nullptr));
-  return out.down(h_songs_out) && flags.down(h_flags_out) && (!h_links_out || links.down(h_links_out)) &&
-                 (!h_scores_out || scores.down(h_scores_out))
-             ? BL_OK
-             : BL_UNEXPECTED;
-}
-
-/* ---- chroma and key (bl_chroma_kernels.hip) -------------------------------------- */
-
-static int chroma_device(bl_amd_ctx *c, bool dflt, const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs,
-                         bl_amd_song_chroma *d_songs_out, bl_amd_frame_chroma *d_frames_out, long long n_frame_records,
-                         void *stream) {
-  if (!d_pcm || ((uintptr_t)d_pcm & 15) || !h_desc || !d_songs_out || ((uintptr_t)d_songs_out & 7) ||
-      ((uintptr_t)d_frames_out & 7) || n_songs < 1)
-    return BL_UNEXPECTED;
-  long long total = 0; /* the sum of T over the songs */
-  for (int i = 0; i < n_songs; ++i) {
-    if (!chroma_song_ok(h_desc[i].pcm_offset, h_desc[i].n_samples, h_desc[i].channels)) return BL_UNEXPECTED;
-    total += bl_amd_chroma_frames(h_desc[i].n_samples, h_desc[i].channels);
-  }
-  if ((d_frames_out && n_frame_records != total) || !blk_chroma_image_host() || !(c = call_ctx(c, dflt)))
-    return BL_UNEXPECTED;
-  CtxGuard g(c);
-  if (!g.ok()) return BL_UNEXPECTED;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return record_call<bl_chroma_song>(c, s, c->chroma_songs, n_songs, [&](bl_chroma_song *hs) {
-    long long frame_off = 0;
-    for (int i = 0; i < n_songs; ++i) {
-      hs[i].pcm_off = h_desc[i].pcm_offset;
-      hs[i].frame_off = frame_off;
-      hs[i].frames = bl_amd_chroma_frames(h_desc[i].n_samples, h_desc[i].channels);
-      hs[i].channels = h_desc[i].channels;
-      frame_off += hs[i].frames;
-    }
-    return BL_OK;
-  }, [&](const bl_chroma_song *hs, bl_chroma_song *d_songs) {
-    if (blr_ensure(c->chroma_acc, sizeof(uint64_t) * 12 * (size_t)n_songs) != BL_OK ||
-        blr_ensure(c->chroma_image, blk_chroma_image_bytes()) != BL_OK)
-      return BL_UNEXPECTED;
-    if (!c->chroma_image_ready) { /* blocking, once per context: nothing on the device reads the block before it */
-      BL_HIP_CHECK(hipMemcpy(c->chroma_image.p, blk_chroma_image_host(), blk_chroma_image_bytes(),
-                             hipMemcpyHostToDevice));
-      c->chroma_image_ready = true;
-    }
-    /* the caller's order, cut into launch groups of at most c->group_songs songs that follow each other on the stream */
-    const int group_songs = std::min(c->group_songs, BL_CHROMA_GROUP_SONGS);
-    for (int b = 0; b < n_songs; b += group_songs) {
-      const int count = std::min(group_songs, n_songs - b);
-      int max_frames = 0;
-      for (int i = b; i < b + count; ++i) max_frames = std::max(max_frames, hs[i].frames);
-      if (blk_chroma(s, d_pcm, d_songs + b, count, max_frames, c->n_cu, c->chroma_image.p,
-                     static_cast<unsigned long long *>(c->chroma_acc.p) + 12 * (size_t)b, d_songs_out + b, d_frames_out,
-                     c->prof ? mark_cb : nullptr, c) != BL_OK)
-        return BL_UNEXPECTED;
-    }
-    return BL_OK;
-  });
-}
-
-int bl_amd_ctx_chroma_batch_device(bl_amd_ctx *c, const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs,
-                                   bl_amd_song_chroma *d_songs_out, bl_amd_frame_chroma *d_frames_out,
-                                   long long n_frame_records, void *stream) {
-  return chroma_device(c, false, d_pcm, h_desc, n_songs, d_songs_out, d_frames_out, n_frame_records, stream);
-}
-
-int bl_amd_chroma_batch_device(const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs,
-                               bl_amd_song_chroma *d_songs_out, bl_amd_frame_chroma *d_frames_out,
-                               long long n_frame_records, void *stream) {
-  return chroma_device(nullptr, true, d_pcm, h_desc, n_songs, d_songs_out, d_frames_out, n_frame_records, stream);
-}
-
-/* ---- mel bands, cepstrum and flatness (bl_mel_kernels.hip) ------------------------ */
-
-static int mel_device(bl_amd_ctx *c, bool dflt, const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs,
-                      uint64_t min_energy, bl_amd_song_mel *d_songs_out, bl_amd_frame_mel *d_frames_out,
-                      uint32_t *d_bands_out, long long n_frame_records, void *stream) {
-  if (!d_pcm || ((uintptr_t)d_pcm & 15) || !h_desc || !d_songs_out || ((uintptr_t)d_songs_out & 7) ||
-      ((uintptr_t)d_frames_out & 3) || ((uintptr_t)d_bands_out & 3) || n_songs < 1)
-    return BL_UNEXPECTED;
-  long long total = 0; /* the sum of F over the songs */
-  for (int i = 0; i < n_songs; ++i) {
-    if (!timbre_song_ok(h_desc[i].pcm_offset, h_desc[i].n_samples, h_desc[i].channels)) return BL_UNEXPECTED;
-    total += bl_amd_timbre_frames(h_desc[i].n_samples, h_desc[i].channels);
-  }
-  if (((d_frames_out || d_bands_out) && n_frame_records != total) || !blk_mel_image_host() || !(c = call_ctx(c, dflt)))
-    return BL_UNEXPECTED;
-  CtxGuard g(c);
-  if (!g.ok()) return BL_UNEXPECTED;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return record_call<bl_timbre_song>(c, s, c->mel_songs, n_songs, [&](bl_timbre_song *hs) {
-    return frame_songs_fill(h_desc, n_songs, hs);
-  }, [&](const bl_timbre_song *, bl_timbre_song *d_songs) {
-    if (blr_ensure(c->mel_image, blk_mel_image_bytes()) != BL_OK) return BL_UNEXPECTED;
-    if (!c->mel_image_ready) { /* blocking, once per context: nothing on the device reads the block before it */
-      BL_HIP_CHECK(hipMemcpy(c->mel_image.p, blk_mel_image_host(), blk_mel_image_bytes(), hipMemcpyHostToDevice));
-      c->mel_image_ready = true;
-    }
-    return blk_mel(s, d_pcm, d_songs, n_songs, c->tb, c->mel_image.p, min_energy, d_songs_out, d_frames_out,
-                   d_bands_out);
-  });
-}
-
-int bl_amd_ctx_mel_batch_device(bl_amd_ctx *c, const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs,
-                                uint64_t min_energy, bl_amd_song_mel *d_songs_out, bl_amd_frame_mel *d_frames_out,
-                                uint32_t *d_bands_out, long long n_frame_records, void *stream) {
-  return mel_device(c, false, d_pcm, h_desc, n_songs, min_energy, d_songs_out, d_frames_out, d_bands_out,
-                    n_frame_records, stream);
-}
-
-int bl_amd_mel_batch_device(const int16_t *d_pcm, const bl_amd_song_desc *h_desc, int n_songs, uint64_t min_energy,
-                            bl_amd_song_mel *d_songs_out, bl_amd_frame_mel *d_frames_out, uint32_t *d_bands_out,
-                            long long n_frame_records, void *stream) {
-  return mel_device(nullptr, true, d_pcm, h_desc, n_songs, min_energy, d_songs_out, d_frames_out, d_bands_out,
-                    n_frame_records, stream);
-}
-
 /* L on the device against the same source on the host (bl_ilog2.h), over bl_ilog2_sweep_value */
 int bl_amd_selftest_ilog2(uint64_t counts[2]) {
   bl_amd_ctx *c = blr_default_ctx();
@@ -1031,35 +590,6 @@ int bl_amd_selftest_ilog2(uint64_t counts[2]) {
   }
   if (counts) { counts[0] = checked; counts[1] = wrong; }
   return wrong ? BL_UNEXPECTED : BL_OK;
-}
-
-/* stages 7 and 8 on the caller's curves: uploaded, through the same launch as the device form, fetched */
-int bl_amd_rhythm_from_onsets(const uint32_t *h_onsets, const int32_t *h_hops, int n_songs, int lag_min, int lag_max,
-                              bl_amd_song_rhythm *h_songs_out, uint64_t *h_acf_out) {
-  if (!h_onsets || !h_hops || !h_songs_out || n_songs < 1 || !rhythm_lags_ok(lag_min, lag_max)) return BL_UNEXPECTED;
-  long long total = 0;
-  for (int i = 0; i < n_songs; ++i) {
-    if (h_hops[i] < 1 || h_hops[i] >= (1 << 24)) return BL_UNEXPECTED;
-    total += h_hops[i];
-  }
-  for (long long k = 0; k < total; ++k)
-    if (h_onsets[k] >= (1u << 18)) return BL_UNEXPECTED;
-  bl_amd_ctx *c = blr_default_ctx();
-  if (!c) return BL_UNEXPECTED;
-  CtxGuard g(c);
-  if (!g.ok()) return BL_UNEXPECTED;
-  DevMem curve(sizeof(uint32_t) * (size_t)total), out(sizeof(bl_amd_song_rhythm) * (size_t)n_songs),
-      acf(h_acf_out ? sizeof(uint64_t) * BL_AMD_RHYTHM_LAGS * (size_t)n_songs : 0);
-  if (!curve.ok() || !out.ok() || !acf.ok() || !curve.up(h_onsets)) return BL_UNEXPECTED;
-  if (rhythm_call(c, nullptr, n_songs, [&](int i, bl_rhythm_song &r) {
-        r.pcm_off = 0;
-        r.hops = h_hops[i];
-        r.channels = 1;
-      }, nullptr, curve.as<uint32_t>(), lag_min, lag_max, out.as<bl_amd_song_rhythm>(), nullptr,
-      acf.as<uint64_t>()) != BL_OK)
-    return BL_UNEXPECTED;
-  BL_HIP_CHECK(hipStreamSynchronize(nullptr));
-  return out.down(h_songs_out) && (!h_acf_out || acf.down(h_acf_out)) ? BL_OK : BL_UNEXPECTED;
 }
 
 int bl_amd_selftest_isqrt(uint64_t counts[2]) {

@@ -6,7 +6,7 @@
  * A feature (its `kind`) has one workspace per context it has been called on, made by the first call: the records of a
  * call, a few further blocks of the feature's own, a ring of pinned blocks the records are staged in.  The layout of
  * bl_amd_ctx stays as it is, and a feature's calls wait for that feature's previous call alone, never for an analysis
- * call on another stream.  The protocol is the one of the contexts' record uploads (record_call, bl_runtime.hip):
+ * call on another stream.  The protocol is the one of the contexts' record uploads (record_call, bl_runtime.h):
  *  - a call holds its context like every other entry point (CtxGuard: its mutex and its device), so calls on one context
  *    are ordered and contexts are independent of each other;
  *  - each kind has a map from context to workspace with a lock of its own, held for the look-up only (and by

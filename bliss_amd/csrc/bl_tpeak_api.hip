@@ -68,32 +68,22 @@ int bl_amd_tpeak_batch_device(const int16_t *d_pcm, const bl_amd_song_desc *h_de
                       stream);
 }
 
-/* the songs in waves (host_waves, bl_runtime.h): each is measured by the device form and fetched */
+/* the songs in waves (host_form, bl_runtime.h): each is measured by the device form and fetched */
 int bl_amd_tpeak_batch_host(const int16_t *const *h_pcm, const int32_t *n_samples, const int32_t *channels, int n_songs,
                             int ceiling, int block, bl_amd_song_tpeak *h_songs_out, uint32_t *h_blocks_out) {
-  if (!h_pcm || !n_samples || !channels || !h_songs_out || n_songs < 1 || !tpeak_args_ok(ceiling, block))
-    return BL_UNEXPECTED;
-  for (int i = 0; i < n_songs; ++i)
-    if (!h_pcm[i] || !tpeak_song_ok(0, n_samples[i], channels[i])) return BL_UNEXPECTED;
-  bl_amd_ctx *c = blr_default_ctx();
-  if (!c) return BL_UNEXPECTED;
-  DevGuard dg(c->device);
-  if (!dg.ok) return BL_UNEXPECTED;
-  return host_waves(c, h_pcm, n_samples, channels, n_songs,
-                    [&](const int16_t *d_pcm, const bl_amd_song_desc *desc, int b, int e) {
-                      long long blocks = 0;
-                      for (int i = b; i < e; ++i) blocks += tpeak_blocks(n_samples[i], channels[i], block);
-                      DevMem out(sizeof(bl_amd_song_tpeak) * (size_t)(e - b)), bout(h_blocks_out ? 8 * (size_t)blocks : 0);
-                      if (!out.ok() || !bout.ok() ||
-                          bl_amd_tpeak_batch_device(d_pcm, desc, e - b, ceiling, block, out.as<bl_amd_song_tpeak>(),
-                                                    bout.as<uint32_t>(), blocks, nullptr) != BL_OK)
-                        return BL_UNEXPECTED;
-                      BL_HIP_CHECK(hipStreamSynchronize(nullptr));
-                      if (!out.down(h_songs_out + b) || (h_blocks_out && blocks && !bout.down(h_blocks_out)))
-                        return BL_UNEXPECTED;
-                      if (h_blocks_out) h_blocks_out += 2 * blocks;
-                      return BL_OK;
-                    });
+  return host_form(h_pcm, n_samples, channels, n_songs, h_songs_out && tpeak_args_ok(ceiling, block), tpeak_song_ok,
+                   [&](const int16_t *d_pcm, const bl_amd_song_desc *desc, int b, int e) {
+                     long long blocks = 0;
+                     for (int i = b; i < e; ++i) blocks += tpeak_blocks(n_samples[i], channels[i], block);
+                     WaveOut<bl_amd_song_tpeak> out(h_songs_out, e - b);
+                     WaveOut<uint32_t> bout(h_blocks_out, 2 * blocks); /* a block is a pair: 8 bytes */
+                     if (!out.ok() || !bout.ok() ||
+                         bl_amd_tpeak_batch_device(d_pcm, desc, e - b, ceiling, block, out.dev(), bout.dev(), blocks,
+                                                   nullptr) != BL_OK)
+                       return BL_UNEXPECTED;
+                     BL_HIP_CHECK(hipStreamSynchronize(nullptr));
+                     return out.fetch() && (!blocks || bout.fetch()) ? BL_OK : BL_UNEXPECTED;
+                   });
 }
 
 /* the kernel's two tiling constants */

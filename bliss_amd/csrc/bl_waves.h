@@ -1,7 +1,7 @@
 /*
- * bl_waves.h — how the host-fed entry points (bl_host_batch.hip) cut a list of songs into waves: songs in order, each at
- * a multiple of 8 samples, as many as fit a budget but at least one.  Plain C++, no HIP: tests/host/test_waves_host.cpp
- * compiles it alone.
+ * bl_waves.h — how the host-fed entry points (the host batch of bl_host_batch.hip, host_waves of bl_runtime.h under
+ * every *_batch_host form) cut a list of songs into waves: songs in order, each at a multiple of 8 samples, as many as
+ * fit a budget but at least one.  Plain C++, no HIP: tests/host/test_waves_host.cpp compiles it alone.
  */
 #ifndef BL_WAVES_H_
 #define BL_WAVES_H_
