@@ -132,6 +132,15 @@ class CoverMatch(C.Structure):  # include/bliss_amd.h bl_amd_cover_match
                 ("status", C.c_int32), ("reserved", C.c_int32)]
 
 
+class ChordsParams(C.Structure):  # include/bliss_amd.h bl_amd_chords_params
+    _fields_ = [("none", C.c_int32), ("reserved", C.c_int32), ("cost", C.c_uint16 * 625), ("pad", C.c_uint16 * 3)]
+
+
+class SongChords(C.Structure):  # include/bliss_amd.h bl_amd_song_chords
+    _fields_ = [("units", C.c_int32), ("status", C.c_int32), ("score", C.c_int32), ("changes", C.c_int32),
+                ("top", C.c_int32), ("top_units", C.c_int32), ("none_units", C.c_int32), ("reserved", C.c_int32)]
+
+
 class FrameChroma(C.Structure):  # include/bliss_amd.h bl_amd_frame_chroma
     _fields_ = [("x", C.c_uint64 * 12)]
 
@@ -389,6 +398,17 @@ SYMBOLS = {
     "bl_amd_cover_tempo_ratio": (C.c_double, [_P(CoverMatch)]),
     "bl_amd_cover_shape": (None, [_P(C.c_int), _P(C.c_int)]),
     "bl_amd_cover_profile_ms": (C.c_double, [C.c_char_p, _P(C.c_int)]),
+    "bl_amd_chords_device": (C.c_int, [C.c_void_p, _P(C.c_int32), C.c_int, C.c_longlong, _P(ChordsParams), C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bl_amd_ctx_chords_device": (C.c_int, [C.c_void_p, C.c_void_p, _P(C.c_int32), C.c_int, C.c_longlong,
+                                           _P(ChordsParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bl_amd_chords_host": (C.c_int, [C.c_void_p, _P(C.c_int32), C.c_int, _P(ChordsParams), C.c_void_p, C.c_void_p,
+                                     C.c_void_p]),
+    "bl_amd_chords_costs": (C.c_int, [C.c_int, C.c_int, _P(C.c_uint16)]),
+    "bl_amd_chords_name": (C.c_char_p, [C.c_int]),
+    "bl_amd_chords_segments": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
+    "bl_amd_chords_shape": (None, [_P(C.c_int), _P(C.c_int), _P(C.c_int)]),
+    "bl_amd_chords_profile_ms": (C.c_double, [C.c_char_p, _P(C.c_int)]),
     "bl_amd_chroma_frames": (C.c_int, [C.c_int, C.c_int]),
     "bl_amd_chroma_batch_device": (C.c_int, [C.c_void_p, _P(SongDesc), C.c_int, C.c_void_p, C.c_void_p, C.c_longlong,
                                              C.c_void_p]),

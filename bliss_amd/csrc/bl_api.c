@@ -471,6 +471,51 @@ double bl_amd_cover_tempo_ratio(const bl_amd_cover_match *m) {
   return (double)(m->b_end - m->b_start + 1) / (double)(m->a_end - m->a_start + 1);
 }
 
+/* ---- chords: the host arithmetic of bl_amd_chords_* (include/bliss_amd.h) ---- */
+
+/* the pitch classes of a triad label (0 .. 23) as a 12-bit set */
+static unsigned chords_classes(int label) {
+  const int r = label % 12;
+  return (1u << r) | (1u << ((r + (label < 12 ? 4 : 3)) % 12)) | (1u << ((r + 7) % 12));
+}
+
+int bl_amd_chords_costs(int change, int related, uint16_t *cost_out) {
+  if (!cost_out || related < 0 || 2 * (long long)related > change || change > BL_AMD_CHORDS_COST_MAX) return BL_UNEXPECTED;
+  for (int a = 0; a < BL_AMD_CHORDS_LABELS; ++a)
+    for (int b = 0; b < BL_AMD_CHORDS_LABELS; ++b) {
+      int v = change;
+      if (a == b) {
+        v = 0;
+      } else if (a != BL_AMD_CHORDS_NONE && b != BL_AMD_CHORDS_NONE) {
+        const unsigned both = chords_classes(a) & chords_classes(b);
+        for (int k = 0; k < 12; ++k) v -= ((both >> k) & 1u) ? related : 0;
+      }
+      cost_out[a * BL_AMD_CHORDS_LABELS + b] = (uint16_t)v;
+    }
+  return BL_OK;
+}
+
+const char *bl_amd_chords_name(int label) {
+  static const char *const names[BL_AMD_CHORDS_LABELS] = {
+      "C",  "C#",  "D",  "D#",  "E",  "F",  "F#",  "G",  "G#",  "A",  "A#",  "B", "Cm",
+      "C#m", "Dm", "D#m", "Em", "Fm", "F#m", "Gm", "G#m", "Am", "A#m", "Bm", "N"};
+  return label >= 0 && label < BL_AMD_CHORDS_LABELS ? names[label] : "";
+}
+
+int bl_amd_chords_segments(const uint8_t *labels, int units, int32_t *starts_out, uint8_t *chords_out, int cap) {
+  if (units < 0 || cap < 0 || (!labels && units > 0)) return -1;
+  int runs = 0;
+  for (int t = 0; t < units; ++t) {
+    if (t > 0 && labels[t] == labels[t - 1]) continue;
+    if (runs < cap) {
+      if (starts_out) starts_out[runs] = t;
+      if (chords_out) chords_out[runs] = labels[t];
+    }
+    ++runs;
+  }
+  return runs;
+}
+
 /* ---- harmonic mixes: the host arithmetic of bl_amd_hmix_* (include/bliss_amd.h) ---- */
 
 static int hmix_rule_args_ok(int tempo_tol, int flags) {

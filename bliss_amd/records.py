@@ -30,6 +30,7 @@ TPEAK_DTYPE = np.dtype(_lib.SongTpeak)
 FPRINT_MATCH_DTYPE = np.dtype(_lib.FprintMatch)
 FORM_DTYPE = np.dtype(_lib.SongForm)
 COVER_MATCH_DTYPE = np.dtype(_lib.CoverMatch)
+CHORDS_DTYPE = np.dtype(_lib.SongChords)
 CHROMA_DTYPE = np.dtype(_lib.SongChroma)
 FRAME_CHROMA_DTYPE = np.dtype(_lib.FrameChroma)
 MEL_DTYPE = np.dtype(_lib.SongMel)

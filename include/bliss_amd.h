@@ -1201,6 +1201,93 @@ double bl_amd_cover_tempo_ratio(const bl_amd_cover_match *m);
 void bl_amd_cover_shape(int *strip_columns, int *row_block);
 double bl_amd_cover_profile_ms(const char *name, int *launches);
 
+/* Chords: which chord sounds when, which is what none of the calls above can say.  The key is one label for a whole
+ * song and the structure call's boundaries are novelty peaks without a name.  This block labels every unit of a song
+ * with one of 24 triads or "no chord": triad templates over the unit's twelve chroma values, decoded by Viterbi with a
+ * caller-given table of transition costs, so that a label holds until the evidence against it outweighs a change.
+ * Every quantity is an exact integer and ties are part of the definition; no result depends on launch shape, batch
+ * composition, the context, or which optional outputs are asked for.  The defaults (none 150, change 60, related 15)
+ * label synthetic triad progressions, silence and noise correctly; there is no annotated music here,
+ * so they have not been tuned on recorded music.
+ *   units    As set a of bl_amd_cover_match_device: d_units is n_songs songs' units concatenated, 16 bytes each (the
+ *            twelve q in 0 .. 127 and four zero bytes), 16-byte aligned; h_count[i] = U_i units, 0 <= U_i < 2^20;
+ *            n_units is the sum of all U_i and may be 0.  There is no TOO_LONG: nothing of a song has to fit LDS.
+ *   labels   0 .. 11 the major triads on C .. B, 12 .. 23 the minor triads (the numbering of bl_amd_song_chroma.key),
+ *            24 "no chord" (N).
+ *   emission Of unit t, with q its twelve values:
+ *              E_t[r]      = q[r] + q[(r + 4) mod 12] + q[(r + 7) mod 12]   (major, r = 0 .. 11)
+ *              E_t[12 + r] = q[r] + q[(r + 3) mod 12] + q[(r + 7) mod 12]   (minor)
+ *              E_t[24]     = none
+ *            in 0 .. 381.  A silent unit goes to N for any none > 0.
+ *   costs    cost[a][b], 25 x 25 uint16 in 0 .. 1024: what going from label a to label b costs.  It is used as given,
+ *            the diagonal included.
+ *   scores   V_0[c] = E_0[c];  for t >= 1: V_t[c] = E_t[c] + max over a of (V_{t-1}[a] - cost[a][c]), and B_t[c] is the
+ *            smallest a that attains the maximum.  Taking a = argmax V_{t-1} shows max V_t >= max V_{t-1} - 1024 and the
+ *            emission max V_t <= max V_{t-1} + 381, so with t < 2^20: -2^30 < V < 381 x 2^20 < 2^29, |V| < 2^31.
+ *   trace    L_{U-1} is the smallest c with the largest V_{U-1}[c], and that value the record's score;
+ *            L_{t-1} = B_t[L_t]. */
+#define BL_AMD_CHORDS_LABELS 25
+#define BL_AMD_CHORDS_NONE 24
+#define BL_AMD_CHORDS_EMPTY 1
+#define BL_AMD_CHORDS_COST_MAX 1024
+#define BL_AMD_CHORDS_EMISSION_MAX 381
+typedef struct bl_amd_chords_params { /* 1264 bytes */
+  int32_t none;       /* E[24], in 0 .. 381 */
+  int32_t reserved;   /* must be 0 */
+  uint16_t cost[625]; /* [a][b], row-major, each in 0 .. 1024 */
+  uint16_t pad[3];    /* must be 0 */
+} bl_amd_chords_params;
+typedef struct bl_amd_song_chords { /* 32 bytes, every byte written for every song */
+  int32_t units;      /* U */
+  int32_t status;     /* 0, or BL_AMD_CHORDS_EMPTY for U = 0 */
+  int32_t score;      /* V_{U-1}[L_{U-1}] */
+  int32_t changes;    /* the number of t >= 1 with L_t != L_{t-1} */
+  int32_t top;        /* the label with the most units, the smaller label of equals; -1 for an empty song */
+  int32_t top_units;
+  int32_t none_units; /* the units labelled 24 */
+  int32_t reserved;   /* 0 */
+} bl_amd_song_chords; /* an empty song has every field but status and top equal to 0 */
+/* bl_amd_chords_device: one record per song in d_out.  The optional outputs may each be NULL, and every element is
+ *   written where given: d_labels_out (uint8 per unit, concatenated at the sum of U_j over j < i) and d_hist_out (25
+ *   uint32 per song: the units per label).  A song's record and outputs depend on its own units and the parameters
+ *   only; no unit of another song is read.  Asynchronous on `stream`; the host array and the parameters are copied
+ *   before the call returns.  bl_amd_ctx_chords_device: the same on an explicit context.  bl_amd_chords_host:
+ *   everything in host memory, blocking.
+ * A rejected call returns BL_UNEXPECTED and writes nothing: a NULL required pointer (units, counts, parameters,
+ * records), a misaligned pointer (units 16 bytes, records and hist 4), n_songs < 1, a count outside [0, 2^20), a wrong
+ * n_units, none or a cost out of range, a reserved or pad word that is not 0.  These checks come before any context or
+ * device is touched.  The workspace is kept per context (1264 bytes, 32 bytes per song, and the backpointers: 32 bytes
+ * per unit, one byte per label, a song's units rounded up to a multiple of 4); bl_amd_ctx_destroy frees it with the
+ * context.
+ * Host arithmetic, no device:
+ *   bl_amd_chords_costs: the table with 0 on the diagonal, `change` to and from N, and between two chords
+ *     change - related x (the pitch classes the two triads share: 0, 1 or 2).  BL_UNEXPECTED, and nothing written,
+ *     unless cost_out is given and 0 <= 2 related <= change <= 1024.
+ *   bl_amd_chords_name: "C" .. "B", "Cm" .. "Bm", "N", and "" for any other label.  The strings are static.
+ *   bl_amd_chords_segments: the runs of equal labels among `units` labels.  Returns their number (-1 for NULL labels
+ *     with units > 0, units < 0 or cap < 0) and writes the first unit and the label of the first `cap` of them
+ *     (either array may be NULL).  A unit's time is bl_amd_form_seconds.
+ *   bl_amd_chords_shape: the lengths at which the kernels change path, for tests: the units the forward kernel takes
+ *     at a time, the units the back-trace takes at a time, and the songs that share a wavefront of the forward kernel.
+ *     Any pointer may be NULL.
+ *   bl_amd_chords_profile_ms: as bl_amd_form_profile_ms, for "chords_forward" and "chords_trace".
+ * Out of scope: sevenths, inversions and other chord types; beat-synchronous units (a caller pools as usual); learning
+ * the costs from annotated music. */
+int bl_amd_chords_device(const void *d_units, const int32_t *h_count, int n_songs, long long n_units,
+                         const bl_amd_chords_params *params, bl_amd_song_chords *d_out, uint8_t *d_labels_out,
+                         uint32_t *d_hist_out, void *stream);
+int bl_amd_ctx_chords_device(bl_amd_ctx *ctx, const void *d_units, const int32_t *h_count, int n_songs,
+                             long long n_units, const bl_amd_chords_params *params, bl_amd_song_chords *d_out,
+                             uint8_t *d_labels_out, uint32_t *d_hist_out, void *stream);
+int bl_amd_chords_host(const void *h_units, const int32_t *h_count, int n_songs,
+                       const bl_amd_chords_params *params, bl_amd_song_chords *h_out, uint8_t *h_labels_out,
+                       uint32_t *h_hist_out);
+int bl_amd_chords_costs(int change, int related, uint16_t *cost_out);
+const char *bl_amd_chords_name(int label);
+int bl_amd_chords_segments(const uint8_t *labels, int units, int32_t *starts_out, uint8_t *chords_out, int cap);
+void bl_amd_chords_shape(int *forward_units, int *trace_units, int *songs_per_wave);
+double bl_amd_chords_profile_ms(const char *name, int *launches);
+
 /* Mel bands, cepstrum and flatness: the shape of every frame's spectrum.  The centroid and the rolloff of the timbre
  * block say where a frame's power sits and where it stops; the 32 log-mel band levels say how it is spread, the 13
  * cepstral coefficients (MFCC) are the usual compact description of that spread, and the flatness tells noise from
