@@ -141,6 +141,23 @@ class SongChords(C.Structure):  # include/bliss_amd.h bl_amd_song_chords
                 ("top", C.c_int32), ("top_units", C.c_int32), ("none_units", C.c_int32), ("reserved", C.c_int32)]
 
 
+class TgramParams(C.Structure):  # include/bliss_amd.h bl_amd_tgram_params
+    _fields_ = [("stride", C.c_int32), ("blocks", C.c_int32), ("lag_min", C.c_int32), ("lag_max", C.c_int32),
+                ("tol", C.c_int32), ("octaves", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class TgramFrame(C.Structure):  # include/bliss_amd.h bl_amd_tgram_frame
+    _fields_ = [("r0", C.c_uint64), ("r_prev", C.c_uint64), ("r_lag", C.c_uint64), ("r_next", C.c_uint64),
+                ("lag", C.c_int32), ("lag_peak", C.c_int32)]
+
+
+class SongTgram(C.Structure):  # include/bliss_amd.h bl_amd_song_tgram
+    _fields_ = [("hops", C.c_int32), ("frames", C.c_int32), ("n_tempo", C.c_int32), ("status", C.c_int32),
+                ("frame_first", C.c_int32), ("frame_last", C.c_int32), ("lag_first", C.c_int32),
+                ("lag_last", C.c_int32), ("lag_low", C.c_int32), ("lag_high", C.c_int32), ("lag_median", C.c_int32),
+                ("n_near", C.c_int32), ("n_jumps", C.c_int32), ("reserved", C.c_int32)]
+
+
 class FrameChroma(C.Structure):  # include/bliss_amd.h bl_amd_frame_chroma
     _fields_ = [("x", C.c_uint64 * 12)]
 
@@ -409,6 +426,18 @@ SYMBOLS = {
     "bl_amd_chords_segments": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
     "bl_amd_chords_shape": (None, [_P(C.c_int), _P(C.c_int), _P(C.c_int)]),
     "bl_amd_chords_profile_ms": (C.c_double, [C.c_char_p, _P(C.c_int)]),
+    "bl_amd_tgram_frames": (C.c_int, [C.c_int, _P(TgramParams)]),
+    "bl_amd_tgram_device": (C.c_int, [C.c_void_p, _P(C.c_int32), C.c_int, _P(TgramParams), C.c_void_p, C.c_void_p,
+                                      C.c_longlong, C.c_void_p, C.c_void_p]),
+    "bl_amd_ctx_tgram_device": (C.c_int, [C.c_void_p, C.c_void_p, _P(C.c_int32), C.c_int, _P(TgramParams), C.c_void_p,
+                                          C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]),
+    "bl_amd_tgram_host": (C.c_int, [C.c_void_p, _P(C.c_int32), C.c_int, _P(TgramParams), C.c_void_p, C.c_void_p,
+                                    C.c_void_p]),
+    "bl_amd_tgram_bpm": (C.c_double, [_P(TgramFrame), C.c_int]),
+    "bl_amd_tgram_seconds": (C.c_double, [C.c_int, _P(TgramParams), C.c_int]),
+    "bl_amd_tgram_steadiness": (C.c_double, [_P(SongTgram)]),
+    "bl_amd_tgram_shape": (None, [_P(C.c_int), _P(C.c_int)]),
+    "bl_amd_tgram_profile_ms": (C.c_double, [C.c_char_p, _P(C.c_int)]),
     "bl_amd_chroma_frames": (C.c_int, [C.c_int, C.c_int]),
     "bl_amd_chroma_batch_device": (C.c_int, [C.c_void_p, _P(SongDesc), C.c_int, C.c_void_p, C.c_void_p, C.c_longlong,
                                              C.c_void_p]),

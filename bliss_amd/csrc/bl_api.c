@@ -330,6 +330,45 @@ double bl_amd_beats_bpm(const bl_amd_song_beats *b, int rate) {
          ((double)BL_AMD_RHYTHM_HOP * (double)(b->last - b->first));
 }
 
+/* ---- tempo over time: the host arithmetic of bl_amd_tgram_* (include/bliss_amd.h) ---- */
+
+static int tgram_params_bad(const bl_amd_tgram_params *p) {
+  return !p || p->stride < 16 || p->stride > 1024 || p->stride % 16 || p->blocks < 1 || p->blocks > 16 ||
+         p->lag_min < 1 || p->lag_min > p->lag_max || p->lag_max > BL_AMD_RHYTHM_LAGS - 2 || p->tol < 0 ||
+         p->tol > 1000 || (p->octaves != 0 && p->octaves != 1) || p->reserved[0] || p->reserved[1];
+}
+
+/* F = (T - W) / S + 1 with T = H - 511 and W = m S, 0 when T < W */
+int bl_amd_tgram_frames(int hops, const bl_amd_tgram_params *p) {
+  if (tgram_params_bad(p) || hops < 1 || hops >= (1 << 24)) return -1;
+  const int T = hops - (BL_AMD_RHYTHM_LAGS - 1), W = p->blocks * p->stride;
+  return T >= W ? (T - W) / p->stride + 1 : 0;
+}
+
+/* bl_amd_rhythm_bpm on a frame's four values */
+double bl_amd_tgram_bpm(const bl_amd_tgram_frame *f, int rate) {
+  if (!f) return NAN;
+  bl_amd_song_rhythm r;
+  memset(&r, 0, sizeof(r));
+  r.r_prev = f->r_prev;
+  r.r_lag = f->r_lag;
+  r.r_next = f->r_next;
+  r.lag = f->lag;
+  return bl_amd_rhythm_bpm(&r, rate);
+}
+
+/* the centre of the window of frame `frame`: hop frame S + W / 2 */
+double bl_amd_tgram_seconds(int frame, const bl_amd_tgram_params *p, int rate) {
+  if (frame < 0 || rate < 1 || tgram_params_bad(p)) return NAN;
+  const double hop = (double)frame * (double)p->stride + 0.5 * (double)(p->blocks * p->stride);
+  return (double)BL_AMD_RHYTHM_HOP * hop / (double)rate;
+}
+
+double bl_amd_tgram_steadiness(const bl_amd_song_tgram *t) {
+  if (!t) return NAN;
+  return t->n_tempo > 0 ? (double)t->n_near / (double)t->n_tempo : 0.0;
+}
+
 /* ---- loudness: the host arithmetic over bl_amd_loud_params and bl_amd_song_loud (include/bliss_amd.h) ---- */
 
 /* The bilinear design of the two K-weighting sections.  The constants are the analogue prototype that gives

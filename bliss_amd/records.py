@@ -31,6 +31,8 @@ FPRINT_MATCH_DTYPE = np.dtype(_lib.FprintMatch)
 FORM_DTYPE = np.dtype(_lib.SongForm)
 COVER_MATCH_DTYPE = np.dtype(_lib.CoverMatch)
 CHORDS_DTYPE = np.dtype(_lib.SongChords)
+TGRAM_DTYPE = np.dtype(_lib.SongTgram)
+TGRAM_FRAME_DTYPE = np.dtype(_lib.TgramFrame)
 CHROMA_DTYPE = np.dtype(_lib.SongChroma)
 FRAME_CHROMA_DTYPE = np.dtype(_lib.FrameChroma)
 MEL_DTYPE = np.dtype(_lib.SongMel)

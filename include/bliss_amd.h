@@ -692,6 +692,96 @@ int bl_amd_beats_host(const uint32_t *h_onsets, const int32_t *h_hops, int n_son
 int bl_amd_beats_list(const uint8_t *h_flags, int hops, int rate, int32_t *h_hop_out, double *h_sec_out, int cap);
 double bl_amd_beats_bpm(const bl_amd_song_beats *b, int rate);
 
+/* Tempo over time (the tempogram): the lag products of stage 7 of the tempo call over a sliding window of the onset
+ * curve, and the pick of stage 8 on every window.  The tempo call gives one lag per song; this tells whether that lag
+ * holds for the whole song and what the tempo is at the song's two ends, where a beat-matched transition joins it to
+ * its neighbours.  Every field is an exact integer: all arithmetic below is integer arithmetic and fits an unsigned
+ * 64-bit value.
+ * Per song: a curve o[0 .. H-1] with values < 2^18 and 1 <= H < 2^24 (the layout of d_onsets_out of
+ * bl_amd_rhythm_batch_device), and one bl_amd_tgram_params per call: stride S, a multiple of 16 in [16, 1024];
+ * blocks m in [1, 16], the window is W = m S terms; 1 <= lag_min <= lag_max <= 510; tol per mille in [0, 1000];
+ * octaves 0 | 1; the reserved words 0.  T = H - 511 as in the tempo call.
+ *   1 frames      F = (T - W) / S + 1 by floor division if T >= W, else F = 0.  Frame f owns the terms h in
+ *                 [f S, f S + W).
+ *   2 lags        R_f[tau] = sum over the frame's terms of o_h o_{h+tau}, tau = 0 .. 511: every lag has the same
+ *                 number of terms, and no hop outside [0, H) is read
+ *   3 pick        stage 8 of the tempo call, word for word, on R_f: r_peak, lag_peak and lag; both lags are 0 when
+ *                 r_peak == 0.  A frame with lag != 0 "has a tempo".
+ *   4 frame       bl_amd_tgram_frame; r_prev, r_lag, r_next are 0 when lag == 0
+ *   5 near        near(L, M) is true if 1000 |L - M| <= tol M; with `octaves` set also if 1000 |2 L - M| <= tol M or
+ *                 1000 |L - 2 M| <= tol 2 M
+ *   6 song        bl_amd_song_tgram, over the frames that have a tempo, in frame order: n_tempo their number;
+ *                 frame_first, frame_last and their lags lag_first, lag_last (the frames -1 and the lags 0 when
+ *                 n_tempo == 0); lag_low, lag_high the smallest and largest lag; lag_median the lower median, the
+ *                 element at index (n_tempo - 1) >> 1 of the sorted lags; n_near the number of frames with
+ *                 near(lag, lag_median); n_jumps the number of consecutive pairs (earlier, later) with
+ *                 !near(later, earlier), where frames without a tempo are skipped and do not break a pair.
+ * Bounds: a product is < 2^36 and W <= 2^14, so R < 2^50 and 16 R fits.
+ * A song with F == 0 is no error of the call: its record has status = BL_UNEXPECTED, hops = H and every other field 0. */
+typedef struct bl_amd_tgram_params { /* 32 bytes */
+  int32_t stride, blocks;            /* S, m */
+  int32_t lag_min, lag_max;
+  int32_t tol, octaves;
+  int32_t reserved[2];               /* 0 */
+} bl_amd_tgram_params;
+typedef struct bl_amd_tgram_frame { /* 40 bytes */
+  uint64_t r0, r_prev, r_lag, r_next; /* R_f[0], R_f[lag-1], R_f[lag], R_f[lag+1]; the last three are 0 when lag == 0 */
+  int32_t lag, lag_peak;
+} bl_amd_tgram_frame;
+typedef struct bl_amd_song_tgram { /* 56 bytes */
+  int32_t hops, frames;              /* H, F */
+  int32_t n_tempo;
+  int32_t status;                    /* BL_OK; BL_UNEXPECTED for a song with F == 0 */
+  int32_t frame_first, frame_last, lag_first, lag_last;
+  int32_t lag_low, lag_high, lag_median;
+  int32_t n_near, n_jumps;
+  int32_t reserved;                  /* 0 */
+} bl_amd_song_tgram;
+/* bl_amd_tgram_frames: F of a song of `hops` hops, plain host arithmetic; -1 for NULL or bad parameters or hops outside
+ *   [1, 2^24).
+ * bl_amd_tgram_device: the tempograms of n_songs songs whose onset curves sit in device memory, songs concatenated in
+ *   the caller's order, song i at the sum of h_hops[j] over j < i.  d_songs_out: n_songs records.  d_frames_out: the
+ *   frame records, songs concatenated in the same order, song i at the sum of F_j over j < i; n_frames must equal the
+ *   sum of all F_j, and d_frames_out may be NULL when that sum is 0.  d_gram_out may be NULL; otherwise it receives
+ *   R_f[0 .. 511] of every frame, 512 uint64 per frame in the order of the frame records.  No output needs zeroing and
+ *   every byte of every record is written.  A rejected call returns BL_UNEXPECTED and writes nothing: a NULL required
+ *   pointer, a misaligned pointer (the curves 4 bytes, the song records 4, the frame records and the rows 8),
+ *   n_songs < 1, an h_hops[i] outside [1, 2^24), a wrong n_frames, bad parameters.  These checks come before any
+ *   context or device is touched.  An onset value >= 2^18 is the caller's error and is not checked on the device.
+ *   Asynchronous on `stream`; h_hops and params are copied before the call returns.  A song's outputs are a pure
+ *   function of its curve and the parameters: they depend neither on the other songs, their order, the launch shape
+ *   nor on which optional outputs are asked for.  The workspace is kept per context (32 bytes and 24 bytes per song);
+ *   bl_amd_ctx_destroy frees it with the context.
+ * bl_amd_tgram_host: the same from host memory, blocking; an onset value >= 2^18 rejects the call; h_frames_out may be
+ *   NULL when no song has a frame, h_gram_out may be NULL.
+ * Host arithmetic, no device:
+ *   bl_amd_tgram_bpm: the interpolation of bl_amd_rhythm_bpm on a frame's r_prev, r_lag, r_next and lag.  NaN for
+ *     lag == 0, a NULL record or rate < 1.
+ *   bl_amd_tgram_seconds: the time of the centre of frame `frame`'s window, 128 (frame S + W / 2) / rate.  NaN for
+ *     frame < 0, NULL or bad parameters or rate < 1.
+ *   bl_amd_tgram_steadiness: n_near / n_tempo, 0 when n_tempo == 0 (NaN for a NULL record): the share of the frames
+ *     whose tempo is the song's median tempo.
+ *   bl_amd_tgram_shape: the lengths at which the kernels change path, for tests: the terms of the curve the block
+ *     kernel stages at a time (it stages whole blocks of S terms: max(1, tile_terms / S) of them) and the frames of one
+ *     run of the block kernel when a song is cut into runs (a call of few songs cuts every song into runs of exactly
+ *     this many frames).  Any pointer may be NULL.
+ *   bl_amd_tgram_profile_ms: as bl_amd_chords_profile_ms, for "tgram_blocks" and "tgram_songs".
+ * tol, S and m have not been tuned on recorded music. */
+int bl_amd_tgram_frames(int hops, const bl_amd_tgram_params *params);
+int bl_amd_tgram_device(const uint32_t *d_onsets, const int32_t *h_hops, int n_songs, const bl_amd_tgram_params *params,
+                        bl_amd_song_tgram *d_songs_out, bl_amd_tgram_frame *d_frames_out, long long n_frames,
+                        uint64_t *d_gram_out, void *stream);
+int bl_amd_ctx_tgram_device(bl_amd_ctx *ctx, const uint32_t *d_onsets, const int32_t *h_hops, int n_songs,
+                            const bl_amd_tgram_params *params, bl_amd_song_tgram *d_songs_out,
+                            bl_amd_tgram_frame *d_frames_out, long long n_frames, uint64_t *d_gram_out, void *stream);
+int bl_amd_tgram_host(const uint32_t *h_onsets, const int32_t *h_hops, int n_songs, const bl_amd_tgram_params *params,
+                      bl_amd_song_tgram *h_songs_out, bl_amd_tgram_frame *h_frames_out, uint64_t *h_gram_out);
+double bl_amd_tgram_bpm(const bl_amd_tgram_frame *f, int rate);
+double bl_amd_tgram_seconds(int frame, const bl_amd_tgram_params *params, int rate);
+double bl_amd_tgram_steadiness(const bl_amd_song_tgram *t);
+void bl_amd_tgram_shape(int *tile_terms, int *run_frames);
+double bl_amd_tgram_profile_ms(const char *name, int *launches);
+
 /* Loudness: the K-weighted, gated programme loudness of ITU-R BS.1770-4 / EBU R128 and the loudness range of EBU Tech
  * 3342, the figure a player needs to level "B after A" (the reference's author lists "Loudness features" in ROADMAP.md;
  * bl_amd_levels_* gives peak and plain RMS, which is not loudness).  The filter is f64 in a fixed operation order;
