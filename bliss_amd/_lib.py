@@ -158,6 +158,18 @@ class SongTgram(C.Structure):  # include/bliss_amd.h bl_amd_song_tgram
                 ("n_near", C.c_int32), ("n_jumps", C.c_int32), ("reserved", C.c_int32)]
 
 
+class TbeatsParams(C.Structure):  # include/bliss_amd.h bl_amd_tbeats_params
+    _fields_ = [("seg", C.c_int32), ("origin", C.c_int32), ("tight", C.c_int32), ("fold", C.c_int32),
+                ("reserved", C.c_int32 * 4)]
+
+
+class SongTbeats(C.Structure):  # include/bliss_amd.h bl_amd_song_tbeats
+    _fields_ = [("score", C.c_int64), ("pen_scale", C.c_uint64), ("hops", C.c_int32), ("frames", C.c_int32),
+                ("n_beats", C.c_int32), ("first", C.c_int32), ("last", C.c_int32), ("status", C.c_int32),
+                ("period_first", C.c_int32), ("period_last", C.c_int32), ("n_runs", C.c_int32),
+                ("n_filled", C.c_int32), ("n_folded", C.c_int32), ("reserved", C.c_int32)]
+
+
 class FrameChroma(C.Structure):  # include/bliss_amd.h bl_amd_frame_chroma
     _fields_ = [("x", C.c_uint64 * 12)]
 
@@ -438,6 +450,18 @@ SYMBOLS = {
     "bl_amd_tgram_steadiness": (C.c_double, [_P(SongTgram)]),
     "bl_amd_tgram_shape": (None, [_P(C.c_int), _P(C.c_int)]),
     "bl_amd_tgram_profile_ms": (C.c_double, [C.c_char_p, _P(C.c_int)]),
+    "bl_amd_tbeats_device": (C.c_int, [C.c_void_p, _P(C.c_int32), _P(C.c_int32), C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                       C.c_int, _P(TbeatsParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
+    "bl_amd_ctx_tbeats_device": (C.c_int, [C.c_void_p, C.c_void_p, _P(C.c_int32), _P(C.c_int32), C.c_int, C.c_void_p,
+                                           C.c_int, C.c_void_p, C.c_int, _P(TbeatsParams), C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bl_amd_tbeats_host": (C.c_int, [C.c_void_p, _P(C.c_int32), _P(C.c_int32), C.c_int, C.c_void_p, C.c_void_p,
+                                     _P(TbeatsParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bl_amd_tbeats_params_from_tgram": (C.c_int, [_P(TgramParams), C.c_int, C.c_int, _P(TbeatsParams)]),
+    "bl_amd_tbeats_edge_bpm": (C.c_double, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "bl_amd_tbeats_shape": (None, [_P(C.c_int), _P(C.c_int)]),
+    "bl_amd_tbeats_profile_ms": (C.c_double, [C.c_char_p, _P(C.c_int)]),
     "bl_amd_chroma_frames": (C.c_int, [C.c_int, C.c_int]),
     "bl_amd_chroma_batch_device": (C.c_int, [C.c_void_p, _P(SongDesc), C.c_int, C.c_void_p, C.c_void_p, C.c_longlong,
                                              C.c_void_p]),

@@ -369,6 +369,35 @@ double bl_amd_tgram_steadiness(const bl_amd_song_tgram *t) {
   return t->n_tempo > 0 ? (double)t->n_near / (double)t->n_tempo : 0.0;
 }
 
+/* ---- beats that follow the tempo over time: the host arithmetic of bl_amd_tbeats_* (include/bliss_amd.h) ---- */
+
+/* frame f's window is centred on hop f S + m S / 2 and a frame speaks for the S hops around its centre: frame f owns
+ * [origin + f S, origin + (f + 1) S) with origin = (m - 1) S / 2 */
+int bl_amd_tbeats_params_from_tgram(const bl_amd_tgram_params *tgram, int tight, int fold, bl_amd_tbeats_params *out) {
+  if (!out || tgram_params_bad(tgram) || tight < 0 || tight > BL_AMD_BEATS_TIGHT_MAX || (fold != 0 && fold != 1))
+    return -1;
+  memset(out, 0, sizeof(*out));
+  out->seg = tgram->stride;
+  out->origin = (tgram->blocks - 1) * tgram->stride / 2;
+  out->tight = tight;
+  out->fold = fold;
+  return 0;
+}
+
+double bl_amd_tbeats_edge_bpm(const uint8_t *h_flags, int hops, int rate, int n, int at_end) {
+  if (!h_flags || hops < 0 || rate < 1 || n < 2) return NAN;
+  int k = 0, a = -1, b = -1; /* the k <= n beats taken so far, from hop a to hop b */
+  for (int i = 0; i < hops && k < n; ++i) {
+    const int h = at_end ? hops - 1 - i : i;
+    if (!h_flags[h]) continue;
+    if (k == 0) a = h;
+    b = h;
+    k += 1;
+  }
+  if (k < 2) return NAN;
+  return 60.0 * (double)rate * (double)(k - 1) / ((double)BL_AMD_RHYTHM_HOP * (double)(at_end ? a - b : b - a));
+}
+
 /* ---- loudness: the host arithmetic over bl_amd_loud_params and bl_amd_song_loud (include/bliss_amd.h) ---- */
 
 /* The bilinear design of the two K-weighting sections.  The constants are the analogue prototype that gives

@@ -1,8 +1,8 @@
 /*
  * bl_side_ws.h — the workspace that the loudness, the true peak, the fingerprints, the song structure, the version
- * matching, the chords and the tempogram each keep beside the context's own, and the one call path over it
- * (bl_loud_api.hip, bl_tpeak_api.hip, bl_fprint_api.hip, bl_form_api.hip, bl_cover_api.hip, bl_chords_api.hip,
- * bl_tgram_api.hip).  Host code only; the bodies that are no templates are bl_side_ws.hip's.
+ * matching, the chords, the tempogram and the beats that follow it each keep beside the context's own, and the one call
+ * path over it (bl_loud_api.hip, bl_tpeak_api.hip, bl_fprint_api.hip, bl_form_api.hip, bl_cover_api.hip,
+ * bl_chords_api.hip, bl_tgram_api.hip, bl_tbeats_api.hip).  Host code only; the bodies that are no templates are bl_side_ws.hip's.
  *
  * A feature (its `kind`) has one workspace per context it has been called on, made by the first call: the records of a
  * call, a few further blocks of the feature's own, a ring of pinned blocks the records are staged in.  The layout of
@@ -24,8 +24,8 @@
 
 #include "bl_runtime.h"
 
-enum { SIDE_LOUD, SIDE_TPEAK, SIDE_FPRINT, SIDE_FORM, SIDE_COVER, SIDE_CHORDS, SIDE_TGRAM, SIDE_COUNT };
-#define BL_SIDE_EXTRA 2 /* blocks besides the records: loudness, structure and chords two, true peak and matching one, fingerprints and tempogram none */
+enum { SIDE_LOUD, SIDE_TPEAK, SIDE_FPRINT, SIDE_FORM, SIDE_COVER, SIDE_CHORDS, SIDE_TGRAM, SIDE_TBEATS, SIDE_COUNT };
+#define BL_SIDE_EXTRA 2 /* blocks besides the records: loudness, structure, chords and the following beats two, true peak and matching one, fingerprints and tempogram none */
 
 struct bl_side_ws {
   bl_buf recs, extra[BL_SIDE_EXTRA];

@@ -33,6 +33,7 @@ COVER_MATCH_DTYPE = np.dtype(_lib.CoverMatch)
 CHORDS_DTYPE = np.dtype(_lib.SongChords)
 TGRAM_DTYPE = np.dtype(_lib.SongTgram)
 TGRAM_FRAME_DTYPE = np.dtype(_lib.TgramFrame)
+TBEATS_DTYPE = np.dtype(_lib.SongTbeats)
 CHROMA_DTYPE = np.dtype(_lib.SongChroma)
 FRAME_CHROMA_DTYPE = np.dtype(_lib.FrameChroma)
 MEL_DTYPE = np.dtype(_lib.SongMel)

@@ -14,7 +14,7 @@ import numpy as np
 from . import _lib
 from ._args import int_in
 from ._lib import check
-from .records import TGRAM_DTYPE, TGRAM_FRAME_DTYPE
+from .records import TBEATS_DTYPE, TGRAM_DTYPE, TGRAM_FRAME_DTYPE
 from .rhythm import HOP, LAGS, _curves_check, _hops_check, _lags_check
 
 STRIDE_MAX, BLOCKS_MAX, TOL_MAX = 1024, 16, 1000
@@ -173,3 +173,152 @@ def steadiness(songs):
     lib = _lib.load()
     ptr = st.ctypes.data_as(C.POINTER(_lib.SongTgram))
     return np.array([lib.bl_amd_tgram_steadiness(C.byref(ptr[i])) for i in range(st.size)], dtype=np.float64)
+
+
+# ---- beats that follow the tempo over time (bl_amd_tbeats_*) --------------------------------------------------------
+
+SEG_MAX, TIGHT_MAX, FRAMES_MAX = 16384, 4096, 1 << 20
+
+
+def beats_params(p=None, tight=128, fold=False, seg=None, origin=None):
+    """A bl_amd_tbeats_params.  From a tempogram's parameters (bl_amd_tbeats_params_from_tgram): a frame speaks for the
+    `stride` hops around the centre of its window, so seg = stride and origin = (blocks - 1) stride / 2.  With `seg`
+    (16 .. 16 384) and `origin` (0 .. 2^24 - 1) given, those instead.  tight (0 .. 4096) is that of
+    bliss_amd.rhythm.beats_device; with `fold`, a frame whose lag is near half or twice the song's anchor lag is moved
+    by an octave towards it."""
+    tight = int_in("tight", tight, 0, TIGHT_MAX)
+    bp = _lib.TbeatsParams()
+    if seg is None and origin is None:
+        check(_lib.load().bl_amd_tbeats_params_from_tgram(C.byref(_params(p)), tight, 1 if fold else 0, C.byref(bp)),
+              "bl_amd_tbeats_params_from_tgram")
+        return bp
+    bp.seg, bp.origin = int_in("seg", seg, 16, SEG_MAX), int_in("origin", 0 if origin is None else origin, 0, (1 << 24) - 1)
+    bp.tight, bp.fold = tight, 1 if fold else 0
+    return bp
+
+
+def _beats_params(bp):
+    if bp is None:
+        return beats_params()
+    if not isinstance(bp, _lib.TbeatsParams):
+        raise ValueError("params must come from bliss_amd.tempogram.beats_params()")
+    return bp
+
+
+def beats_shape():
+    """(scores the grid kernel keeps on the chip, frames the track kernel scans at a time) (bl_amd_tbeats_shape)."""
+    v = [C.c_int() for _ in range(2)]
+    _lib.load().bl_amd_tbeats_shape(*[C.byref(x) for x in v])
+    return tuple(x.value for x in v)
+
+
+def beats_to_numpy(raw_songs):
+    """bytes / a uint8 array of bl_amd_song_tbeats records -> a structured numpy array with the header's field names."""
+    return np.frombuffer(bytes(raw_songs), dtype=TBEATS_DTYPE).copy()
+
+
+def beats_device(onsets, hops, tgram, bp=None, anchor=True, links=False, scores=False, track=False, ctx=None):
+    """Enqueue the beat grids of n songs (bl_amd_tbeats_device) on torch's current stream, the periods read in place
+    from what tgram_device() returned for the same curves: the frames' lags at a stride of 40 bytes and, with `anchor`,
+    the songs' median lags at a stride of 56.  Returns a dict of CUDA tensors: "songs" (uint8, 64 bytes per song),
+    "flags" (uint8 per hop) and, where asked for, "links" (int16 holding uint16), "scores" (int64) and "track" (int32 per
+    frame); beats_to_numpy() reads the records once the stream has been waited for."""
+    import torch
+    from .queries import _on_device_of
+    bp = _beats_params(bp)
+    hops = _hops_check(hops)
+    n, total = len(hops), sum(hops)
+    if onsets.dtype != torch.int32 or not onsets.is_cuda or not onsets.is_contiguous() or onsets.dim() != 1 or \
+            onsets.numel() != total:
+        raise ValueError(f"onsets must be a contiguous 1-D int32 CUDA tensor of sum(hops) = {total} values")
+    counts = [int(x) for x in tgram["counts"]]
+    nf = sum(counts)
+    for k in ("songs", "frames"):
+        t = tgram[k]
+        if t.dtype != torch.uint8 or not t.is_cuda or t.device != onsets.device or not t.is_contiguous() or t.dim() != 1:
+            raise ValueError(f'tgram["{k}"] must be a contiguous 1-D uint8 CUDA tensor on the device of onsets')
+    if len(counts) != n or tgram["songs"].numel() != n * TGRAM_DTYPE.itemsize or \
+            tgram["frames"].numel() != nf * TGRAM_FRAME_DTYPE.itemsize:
+        raise ValueError("tgram must be what tgram_device() returned for these songs")
+    lib = _lib.load()
+    dev = onsets.device
+    out = {"songs": torch.empty(n * TBEATS_DTYPE.itemsize, dtype=torch.uint8, device=dev),
+           "flags": torch.empty(total, dtype=torch.uint8, device=dev)}
+    if links:
+        out["links"] = torch.empty(total, dtype=torch.int16, device=dev)
+    if scores:
+        out["scores"] = torch.empty(total, dtype=torch.int64, device=dev)
+    if track:
+        out["track"] = torch.empty(nf, dtype=torch.int32, device=dev)
+    opt = lambda k: C.c_void_p(out[k].data_ptr()) if k in out and out[k].numel() else None
+    with _on_device_of(lib, onsets, None) as cur:
+        args = (C.c_void_p(onsets.data_ptr()), (C.c_int32 * n)(*hops), (C.c_int32 * n)(*counts), n,
+                C.c_void_p(tgram["frames"].data_ptr() + TGRAM_FRAME_DTYPE.fields["lag"][1]) if nf else None,
+                TGRAM_FRAME_DTYPE.itemsize,
+                C.c_void_p(tgram["songs"].data_ptr() + TGRAM_DTYPE.fields["lag_median"][1]) if anchor else None,
+                TGRAM_DTYPE.itemsize, C.byref(bp), C.c_void_p(out["songs"].data_ptr()),
+                C.c_void_p(out["flags"].data_ptr()), opt("links"), opt("scores"), opt("track"),
+                C.c_void_p(cur.cuda_stream))
+        if ctx is None:
+            check(lib.bl_amd_tbeats_device(*args), "bl_amd_tbeats_device")
+        else:
+            check(lib.bl_amd_ctx_tbeats_device(ctx.handle, *args), "bl_amd_ctx_tbeats_device")
+    return out
+
+
+def beats_host(onsets_list, lags_list, anchors=None, bp=None, links=False, scores=False, track=False):
+    """Beat grids of onset curves and frame lags in host memory (bl_amd_tbeats_host), blocking.  lags_list: per song a
+    sequence of int32 lags (it may be empty); anchors: None or one lag per song.  Returns (songs, flags, links or None,
+    scores or None, track or None), the arrays of all songs one behind the other."""
+    bp = _beats_params(bp)
+    curves = _curves_check(onsets_list)
+    n = len(curves)
+    if len(lags_list) != n or (anchors is not None and len(anchors) != n):
+        raise ValueError("one sequence of lags, and one anchor if any, per song")
+    lags = [np.ascontiguousarray(x, dtype=np.int32).reshape(-1) for x in lags_list]
+    if any(x.size > FRAMES_MAX for x in lags):
+        raise ValueError(f"at most {FRAMES_MAX} frames per song")
+    flat = np.ascontiguousarray(np.concatenate(curves), dtype=np.uint32)
+    lag = np.ascontiguousarray(np.concatenate(lags + [np.zeros(1, np.int32)]), dtype=np.int32)
+    anc = None if anchors is None else np.ascontiguousarray(anchors, dtype=np.int32)
+    nh, nf = flat.size, lag.size - 1
+    songs = (_lib.SongTbeats * n)()
+    flags = np.zeros(nh, np.uint8)
+    outs = [np.zeros(k, dt) if want else None for want, k, dt in ((links, nh, np.uint16), (scores, nh, np.int64),
+                                                                  (track, max(nf, 1), np.int32))]
+    ptr = lambda a: None if a is None else C.c_void_p(a.ctypes.data)
+    check(_lib.load().bl_amd_tbeats_host(ptr(flat), (C.c_int32 * n)(*[o.size for o in curves]),
+                                         (C.c_int32 * n)(*[x.size for x in lags]), n, ptr(lag), ptr(anc), C.byref(bp),
+                                         songs, ptr(flags), *[ptr(a) for a in outs]), "bl_amd_tbeats_host")
+    return (beats_to_numpy(bytes(songs)), flags, outs[0], outs[1], None if outs[2] is None else outs[2][:nf])
+
+
+def beats_from_pcm(pcm_list, channels, p=None, tight=128, fold=False):
+    """(beat records, flags of all songs one behind the other, tempogram song records, frame records, per-song hop
+    counts) of songs in host memory: the tempo call with its onset curves, the tempogram on them and the grid that
+    follows it, all on the device with nothing copied in between."""
+    import torch
+    import bliss_amd
+    from .rhythm import rhythm_device
+    p = _params(p)
+    arrs = [np.ascontiguousarray(a, dtype=np.int16).reshape(-1) for a in pcm_list]
+    corpus = bliss_amd.DeviceCorpus([a.size for a in arrs], channels, 1)
+    for i, a in enumerate(arrs):
+        corpus.upload(i, a)
+    _, ons, _ = rhythm_device(corpus, p.lag_min, p.lag_max, onsets=True)
+    lengths, chs = corpus._songs()
+    hops = [int(ln) // ch // HOP for ln, ch in zip(lengths, chs)]
+    with torch.cuda.device(corpus.device):
+        tgram = tgram_device(ons, hops, p)
+        out = beats_device(ons, hops, tgram, beats_params(p, tight, fold))
+        torch.cuda.synchronize(corpus.device)
+    s, f = tgram_to_numpy(tgram["songs"].cpu().numpy().tobytes(), tgram["frames"].cpu().numpy().tobytes())
+    return beats_to_numpy(out["songs"].cpu().numpy().tobytes()), out["flags"].cpu().numpy(), s, f, hops
+
+
+def edge_bpm(flags, n=8, at_end=False, rate=22050):
+    """The tempo of one song's grid over its first (or, with at_end, last) min(n, beats) beats in beats per minute
+    (bl_amd_tbeats_edge_bpm): the tempo a transition into (out of) the song has to match.  NaN below two beats."""
+    fl = np.ascontiguousarray(flags, dtype=np.uint8).reshape(-1)
+    return _lib.load().bl_amd_tbeats_edge_bpm(C.c_void_p(fl.ctypes.data), fl.size, int_in("rate", rate, 1, 2 ** 31 - 1),
+                                              int_in("n", n, 0, 2 ** 31 - 1), 1 if at_end else 0)

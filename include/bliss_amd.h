@@ -782,6 +782,99 @@ double bl_amd_tgram_steadiness(const bl_amd_song_tgram *t);
 void bl_amd_tgram_shape(int *tile_terms, int *run_frames);
 double bl_amd_tgram_profile_ms(const char *name, int *launches);
 
+/* Beats that follow the tempo over time: the dynamic programme of bl_amd_beats_* with the period a function of the
+ * hop.  bl_amd_beats_* tracks at the tempo call's one lag; on a song whose tempo changes its grid is wrong for part of
+ * the song, and the ends, which a beat-matched transition joins, are where it is worst.  Here the period comes from
+ * per-frame lags such as bl_amd_tgram_frame.lag, read in place.  All arithmetic is integer arithmetic and fits a signed
+ * 64-bit value.
+ * Per song: a curve o[0 .. H-1] with values < 2^18 and 1 <= H < 2^24, F frame lags lag_f (int32), 0 <= F <= 2^20, and
+ * optionally an anchor lag A (int32).  Per call one bl_amd_tbeats_params: seg in [16, 16384], origin in [0, 2^24),
+ * tight in [0, 4096], fold 0 | 1, the reserved words 0.
+ *   1 valid       frame f is valid if 2 <= lag_f <= 510.  F == 0 or no valid frame: the song has no tempo
+ *   2 fill        q_f = lag_f for a valid frame; an invalid frame takes the lag of the valid frame nearest by |f - f'|,
+ *                 ties to the earlier frame; n_filled is the number of invalid frames
+ *   3 fold        only with `fold` set, an anchor given and 2 <= A <= 510: if 3 q <= 2 A then q' = 2 q, else if
+ *                 3 q > 4 A then q' = q >> 1; applied once, and q stays as it was if q' falls outside [2, 510];
+ *                 n_folded is the number of frames that changed.  (42 then 88 with A = 42 gives 42 then 44.)
+ *   4 track       g(t) = clamp(floor((t - origin) / seg), 0, F - 1) and L(t) = q_g(t); a tempogram of stride S and m
+ *                 blocks gives seg = S and origin = (m - 1) S / 2 (bl_amd_tbeats_params_from_tgram).  A run is a
+ *                 maximal stretch of hops with equal L(t); n_runs is their number
+ *   5 scale       W = tight max o_h over the whole song (pen_scale)
+ *   6 scores      stage 3 of bl_amd_beats_* with L = L(t), the period of the hop being scored, not of its source:
+ *                 lo = (L(t) + 1) >> 1, hi = 2 L(t), pen(d) = (W e^2) >> 28 with e = |Log2q12(d) - Log2q12(L(t))|;
+ *                 best(t) = max over d in [lo, min(hi, t)] of C[t-d] - pen(d), ties to the smallest d; a link is made
+ *                 only if best(t) > 0
+ *   7 end         t_end = the arg-max of C over [max(0, H - L(H-1)), H - 1], ties to the largest t; score = C[t_end]
+ *   8 back-trace  flags, first, last and n_beats as in bl_amd_beats_*; period_first = L(first) and
+ *                 period_last = L(last), both 0 when score == 0
+ * Bounds: those of bl_amd_beats_*: pen < 2^26, 0 <= C < 2^42, P <= 1020.
+ * Property: if every valid frame has the same lag L and no fold applies, flags, links, scores, score, pen_scale,
+ * n_beats, first and last equal those of bl_amd_beats_* at L byte for byte.
+ * A song without a tempo is no error of the call: its record has status = BL_UNEXPECTED, hops = H, frames = F and every
+ * other field 0, and its flags, links, scores and track are 0. */
+typedef struct bl_amd_tbeats_params { /* 32 bytes */
+  int32_t seg, origin;               /* hops per frame; the hop at which frame 0 would begin */
+  int32_t tight, fold;
+  int32_t reserved[4];               /* 0 */
+} bl_amd_tbeats_params;
+typedef struct bl_amd_song_tbeats { /* 64 bytes */
+  int64_t score;                    /* C[t_end] */
+  uint64_t pen_scale;               /* W */
+  int32_t hops, frames;             /* H, F */
+  int32_t n_beats, first, last;
+  int32_t status;                   /* BL_OK; BL_UNEXPECTED for a song without a tempo */
+  int32_t period_first, period_last;
+  int32_t n_runs, n_filled, n_folded;
+  int32_t reserved;                 /* 0 */
+} bl_amd_song_tbeats;
+/* bl_amd_tbeats_device: the grids of n_songs songs whose curves and frame lags sit in device memory.  d_onsets,
+ *   h_hops, d_flags_out, d_links_out and d_scores_out are those of bl_amd_beats_device.  h_frames[i] = F_i.  The lag of
+ *   frame f of song i is the int32 read at (char *)d_lag + (sum of F_j over j < i, plus f) * lag_stride: a stride of 4
+ *   takes a packed array, a stride of sizeof(bl_amd_tgram_frame) = 40 together with &d_frames->lag the tempogram's
+ *   frame records in place; d_lag may be NULL when every F_i is 0.  d_anchor may be NULL; otherwise the anchor of song
+ *   i is the int32 at (char *)d_anchor + i * anchor_stride: a stride of sizeof(bl_amd_song_tgram) = 56 together with
+ *   &d_songs->lag_median takes the tempogram's song records.  d_links_out, d_scores_out and d_track_out may be NULL;
+ *   d_track_out receives q of every frame after fill and fold, packed int32 in the order of the lags.  No output needs
+ *   zeroing and every byte of every output is written.  A rejected call returns BL_UNEXPECTED and writes nothing: a
+ *   NULL required pointer, a misaligned pointer (the curves, lags, anchors and track 4 bytes, the records and scores 8,
+ *   the links 2), n_songs < 1, an h_hops[i] outside [1, 2^24), an h_frames[i] outside [0, 2^20], a stride below 4 or
+ *   no multiple of 4, bad parameters or a reserved word that is not 0.  These checks come before any context or device
+ *   is touched.  An onset value >= 2^18 is the caller's error and is not checked on the device.  Asynchronous on
+ *   `stream`; h_hops, h_frames and params are copied before the call returns.  A song's outputs are a pure function of
+ *   its curve, its lags, its anchor and the parameters: they depend neither on the other songs, their order nor on
+ *   which optional outputs are asked for.  The workspace is kept per context (32 bytes and 40 bytes per song, 4 bytes
+ *   per frame without d_track_out, 2 bytes per hop of a launch group without d_links_out); bl_amd_ctx_destroy frees it.
+ * bl_amd_tbeats_host: the same from host memory, blocking; h_lag is a packed int32 array of all frames, h_anchor a
+ *   packed int32 array or NULL; an onset value >= 2^18 rejects the call.
+ * Host arithmetic, no device:
+ *   bl_amd_tbeats_params_from_tgram: seg = S and origin = (m - 1) S / 2 of a tempogram's parameters, with `tight` and
+ *     `fold`; -1 for a NULL pointer, bad tempogram parameters, tight outside [0, 4096] or fold outside 0 | 1, else 0.
+ *   bl_amd_tbeats_edge_bpm: the tempo of the grid over its first (at_end == 0) or last k = min(n, count) beats, where
+ *     count is the number of set flags among h_flags[0 .. hops): 60 rate (k - 1) / (128 span), span the hops from the
+ *     first to the last of those k beats: the in and out tempo a transition needs.  NaN for k < 2, a NULL pointer,
+ *     hops < 0 or rate < 1.
+ *   bl_amd_beats_list works on these flags as it does on those of bl_amd_beats_*.
+ *   bl_amd_tbeats_shape: the lengths at which the kernels change path, for tests: the scores kept on the chip and the
+ *     frames the track kernel scans at a time.  Any pointer may be NULL.
+ *   bl_amd_tbeats_profile_ms: as bl_amd_chords_profile_ms, for "tbeats_track" and "tbeats".
+ * tight, the fold and the tempogram's parameters have not been tuned on recorded music. */
+int bl_amd_tbeats_device(const uint32_t *d_onsets, const int32_t *h_hops, const int32_t *h_frames, int n_songs,
+                         const void *d_lag, int lag_stride, const void *d_anchor, int anchor_stride,
+                         const bl_amd_tbeats_params *params, bl_amd_song_tbeats *d_songs_out, uint8_t *d_flags_out,
+                         uint16_t *d_links_out, int64_t *d_scores_out, int32_t *d_track_out, void *stream);
+int bl_amd_ctx_tbeats_device(bl_amd_ctx *ctx, const uint32_t *d_onsets, const int32_t *h_hops, const int32_t *h_frames,
+                             int n_songs, const void *d_lag, int lag_stride, const void *d_anchor, int anchor_stride,
+                             const bl_amd_tbeats_params *params, bl_amd_song_tbeats *d_songs_out, uint8_t *d_flags_out,
+                             uint16_t *d_links_out, int64_t *d_scores_out, int32_t *d_track_out, void *stream);
+int bl_amd_tbeats_host(const uint32_t *h_onsets, const int32_t *h_hops, const int32_t *h_frames, int n_songs,
+                       const int32_t *h_lag, const int32_t *h_anchor, const bl_amd_tbeats_params *params,
+                       bl_amd_song_tbeats *h_songs_out, uint8_t *h_flags_out, uint16_t *h_links_out,
+                       int64_t *h_scores_out, int32_t *h_track_out);
+int bl_amd_tbeats_params_from_tgram(const bl_amd_tgram_params *tgram, int tight, int fold, bl_amd_tbeats_params *out);
+double bl_amd_tbeats_edge_bpm(const uint8_t *h_flags, int hops, int rate, int n, int at_end);
+void bl_amd_tbeats_shape(int *ring, int *track_tile);
+double bl_amd_tbeats_profile_ms(const char *name, int *launches);
+
 /* Loudness: the K-weighted, gated programme loudness of ITU-R BS.1770-4 / EBU R128 and the loudness range of EBU Tech
  * 3342, the figure a player needs to level "B after A" (the reference's author lists "Loudness features" in ROADMAP.md;
  * bl_amd_levels_* gives peak and plain RMS, which is not loudness).  The filter is f64 in a fixed operation order;
